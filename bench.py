@@ -29,9 +29,17 @@ Workloads (--workload):
                           likelihood (BASELINE config 4: "(Kalman kernel)"; estimation method ANOFOX_ARIMA_CSS_ML)
     autoarima_css_m5      the same with the library's default method (ANOFOX_ARIMA_CSS: the search's estimates, the reference's cost envelope)
 
-The JSON line also carries, on rank 0 at N = 1: `e2e` (the same workload through anofox_ts_forecast_batch: host
-buffers in, results on host -- pack + H2D + fit + D2H, SURVEY.md 8(d) metric (ii); never `value`) and
-`cpu_baseline` (the oracle on a bounded sample of the same batch, on this box's host cores).
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline, configuration, and the roofline
+figures derived from the library's counters of the last timed step).  With --full the line also carries, on rank 0 at
+N = 1: `e2e` (the same workload through anofox_ts_forecast_batch: host buffers in, results on host -- pack + H2D + fit
++ D2H, SURVEY.md 8(d) metric (ii); never `value`), `cpu_baseline` (the oracle on a bounded sample of the same batch, on
+the host's cores), `also` (short loops of the other BASELINE configurations, default workload only), the lane
+efficiency of the round kernels and the PMC figures of profiles/ stamped with this build.
+
+--dump-outputs DIR writes what the last timed step computed -- the result arrays a caller of the path receives (`yhat`,
+`lower`, `upper` [series, h]; `model_code`, `status` [series]), gathered on rank 0 -- as DIR/<name>.npy in float64.  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  Above 64 MB in all, a
+fixed seeded sample of series is written, and their indices as DIR/rows.npy.
 """
 from __future__ import annotations
 
@@ -62,16 +70,50 @@ def parse_args():
     ap.add_argument("--n-series", type=int, default=0, help="series per GPU (weak) / in total (strong); 0 = workload default")
     ap.add_argument("--t", type=int, default=0, help="observations per series (0 = workload default)")
     ap.add_argument("--horizon", type=int, default=28)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="series for the CPU baseline (-1 auto, 0 skip)")
-    ap.add_argument("--e2e-steps", type=int, default=-1, help="timed passes of the host-buffer entry (-1 auto, 0 skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: host-buffer (e2e) leg, CPU baseline, the other BASELINE "
+                         "configurations, lane efficiency, PMC figures of profiles/")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's result arrays to DIR/<name>.npy (float64; a seeded sample of series above 64 MB)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: series for the CPU baseline (-1 auto, 0 skip)")
+    ap.add_argument("--e2e-steps", type=int, default=-1, help="with --full: timed passes of the host-buffer entry (-1 auto, 0 skip)")
     ap.add_argument("--ets-model", default="", help="single-spec probes: override the workload's ETS spec (e.g. AMdA; implies model ETS on strictly positive series)")
     ap.add_argument("--also", type=int, default=-1,
-                    help="timed steps of each of the other BASELINE configurations, reported under \"also\" (-1 auto: 3 on the plain default "
-                         "single-GPU invocation -- no --workload / --n-series / --cpu-sample / --e2e-steps --, 0 otherwise; 0 skip)")
+                    help="with --full: timed steps of each of the other BASELINE configurations, reported under \"also\" (-1 auto: 3 on the "
+                         "default single-GPU invocation -- no --workload / --n-series / --cpu-sample / --e2e-steps --, 0 otherwise; 0 skip)")
     ap.add_argument("--simulate-world", type=int, default=0,
                     help="ONE process, ONE GPU: run rank 0's share of an N-GPU job (strong: shard 0 of N; weak: one full batch) and report the "
                          "per-GPU figure an N-GPU run would start from -- what can be known about 8 GPUs on a 1-GPU box (no collective runs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.cpu_sample > 0 or args.e2e_steps > 0 or args.also > 0):
+        ap.error("--cpu-sample, --e2e-steps and --also size legs that run only with --full")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SEED = 20260101
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Write per-series result arrays (numpy, first axis = series) as DIR/<name>.npy in float64.  When they would exceed `budget`,
+    a fixed seeded sample of series is written instead (the same rows for every array), with their indices as rows.npy.
+    Returns the sampled indices, or None when every series was written."""
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * int(np.prod(a.shape[1:])) for a in arrays.values())
+    rows = None
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=budget // (row_bytes + 8), replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a if rows is None else a[rows], dtype=np.float64))
+    rows_path = os.path.join(path, "rows.npy")
+    if rows is not None:
+        np.save(rows_path, rows.astype(np.float64))
+    elif os.path.exists(rows_path):
+        os.remove(rows_path)           # a sample index of an earlier dump would not describe these files
+    return rows
 
 
 CPU_TARGET_S = 12.0      # CPU work of the baseline leg (the contract asks for 10-30 s)
@@ -272,10 +314,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    gathered = {}
+
     def step():
         batch.run()                                   # async on torch's current stream
         if world > 1:
-            gather_forecasts(batch.results(), n_total, rank, world)     # the only exchange: forecast chunks -> rank 0
+            gathered["last"] = gather_forecasts(batch.results(), n_total, rank, world)     # the only exchange: forecast chunks -> rank 0
 
     for _ in range(args.warmup):
         step()
@@ -312,6 +356,9 @@ def main():
 
     res = batch.results()
     n_ok = int((res["status"] == 0).sum().item())
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step: this rank's results at N = 1, the gathered ones at N > 1
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in (gathered["last"] if world > 1 else res).items()})
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -383,8 +430,8 @@ def main():
                          "fp64_unit": {"achieved": round(achieved_fp64_unit, 1), "frac": round(achieved_fp64_unit / HBM_PEAK_GBS, 4),
                                        "algorithmic_bytes": int(alg_fp64_unit)}},
         }
-        if model != "AutoARIMA" and not wl["fixed"]:
-            # lane-level efficiency of the round kernels (device counters of the LAST timed step): the share of issued lanes that
+        if args.full and model != "AutoARIMA" and not wl["fixed"]:
+            # (--full) lane-level efficiency of the round kernels (device counters of the LAST timed step): the share of issued lanes that
             # evaluated a trial point of a running problem -- `valu.frac` counts a wave with three live lanes as fully useful, this does not
             try:
                 ls = batch.lane_stats()
@@ -399,109 +446,110 @@ def main():
             out["roofline"]["final_pass"] = {"kernel": "ets_final_kernel<spec,period> alone", "kernel_ms": round(final_pass_ms, 4),
                                              "achieved": round(float(np.mean(alg_bytes)) / (final_pass_ms * 1e-3) / 1e9, 1),
                                              "frac": round(float(np.mean(alg_bytes)) / (final_pass_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        # HBM traffic and VALU issue of the fit kernels come from separate rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE corrected
-        # as MI355X_MICROARCH.md prescribes; SQ_INSTS_VALU): tools/profile_round.sh writes profiles/rNN_pmc_traffic*.json STAMPED with
-        # the sha256 of the library they were taken on.  The figures are quoted only when the stamp is the library that just ran
-        # and the workload / shape agree -- anything else leaves the fields null and says why.
-        import glob
-        import hashlib
-        lib_sha = hashlib.sha256(open(lib.LIB_PATH, "rb").read()).hexdigest()
-        out["roofline"]["lib_sha256"] = lib_sha[:16]
-        stale = None
-        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic*.json")), reverse=True):
-            try:
-                tr = json.load(open(path))
-            except (OSError, ValueError):
-                continue
-            if not (tr.get("workload") == args.workload and n == wl["n"] and T == wl["T"]):
-                continue
-            fn = os.path.basename(path)
-            if tr.get("lib_sha256", "")[:16] != lib_sha[:16]:
-                stale = stale or f"profiles/{fn} was taken on another build of the library ({tr.get('lib_sha256', 'unstamped')[:16]}): not quoted"
-                continue
-            try:
-                out["roofline"]["traffic"] = int(tr["fit_kernel_traffic_bytes_per_step"])
-                out["roofline"]["traffic_source"] = f"profiles/{fn} (PMC passes on this build, per step)"
-                if "valu_insts_per_step" in tr:
-                    issued = float(tr["valu_insts_per_step"])
-                    rate = issued / (fit_ms_avg * 1e-3)
-                    out["roofline"]["valu"] = {"issued_insts": int(issued), "peak_issue": FP64_VALU_PEAK_WAVE_INSTS,
-                                               "frac": round(rate / FP64_VALU_PEAK_WAVE_INSTS, 4),
-                                               "unit": "wave-level VALU instructions per second against one fp64 issue per SIMD per 4 cycles",
-                                               "source": f"profiles/{fn} (SQ_INSTS_VALU per step, this build) / this run's kernel_ms"}
-            except (KeyError, ValueError):
-                pass
-            break
-        if out["roofline"]["traffic"] is None and stale:
-            out["roofline"]["traffic_source"] = stale
         if sim:
             # rank 0's shard alone: `value` is what THIS GPU did; the N-GPU job cannot be faster than its slowest rank, so the
             # projection is N x value at best (shards are equal sized up to one series; the gather adds < 1 ms)
             out["projection"] = {"world": sim, "scaling": args.scaling, "per_gpu_series": n, "per_gpu_ms_per_step": round(ms_per_step, 3),
                                  "job_series_per_s_upper_bound": round(sim * value, 1),
                                  "note": "one rank of the job measured alone on one GPU; no RCCL gather in the timed region"}
-        yhat_host = res["yhat"].cpu().numpy().copy()
-        batch.close()       # the host-buffer entry below is what a binding calls on its own: no second resident batch (and its streams) beside it
-        del res, y_dev, len_dev       # ... and the headline block goes back to torch's allocator before the other workloads allocate theirs
-        torch.cuda.empty_cache()
-        # ---- end to end: host buffers in, results on host (never `value`) -----------------------------
-        e2e_steps = args.e2e_steps if args.e2e_steps >= 0 else (0 if world > 1 else (1 if ms_per_step > 400 else 2))
-        if wl["fixed"]:
-            out["e2e"] = None        # the fixed-parameter entry exists on the device-resident API only
-        elif e2e_steps > 0 and world == 1:
-            times, e_ok = e2e_pass(lib, Y, opts, e2e_steps + 1)          # first pass untimed (allocations)
-            if True:
-                best = float(np.mean(times[1:]))
-                out["e2e"] = {"value": round(n / best, 1), "unit": "series/s", "ms_per_step": round(best * 1e3, 3), "steps": e2e_steps,
-                              "series_ok": e_ok,
-                              "what": "anofox_ts_forecast_batch: NULL fill + pack to the pinned time-major block (all host threads) + H2D + "
-                                      "fit + D2H + per-series malloc'd result arrays; PCIe-inclusive, never the headline value"}
-        # ---- the other BASELINE configurations, short loops (never `value`) ----------------------------
-        # (auto: only the PLAIN default invocation -- the driver's line; a run that switches the CPU or host-buffer leg off is a
-        #  measurement script, whose kernel trace or counters must hold the headline workload alone)
-        also_steps = args.also if args.also >= 0 else (3 if (world == 1 and not sim and args.workload == "autoets_m5_positive"
-                                                             and not args.n_series and not args.t and not args.ets_model
-                                                             and args.cpu_sample < 0 and args.e2e_steps < 0) else 0)
-        if also_steps > 0 and world == 1:
-            out["also"] = also_pass(ALSO_WORKLOADS, also_steps, h, dev, lib, synth, DeviceBatch, pack_time_major, torch)
-        # ---- CPU baseline: the oracle ("port") on a bounded sample of the same workload -------------
-        sample = wl["cpu_sample"] if args.cpu_sample < 0 else args.cpu_sample
-        if sample > 0 and world == 1:                  # (the contract: rank 0 at N = 1 only -- an N-GPU line carries no CPU leg)
-            from oracle import oracle as O
+        if args.full:
+            # HBM traffic and VALU issue of the fit kernels come from separate rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE corrected
+            # as MI355X_MICROARCH.md prescribes; SQ_INSTS_VALU): tools/profile_round.sh writes profiles/rNN_pmc_traffic*.json STAMPED with
+            # the sha256 of the library they were taken on.  The figures are quoted only when the stamp is the library that just ran
+            # and the workload / shape agree -- anything else leaves the fields null and says why.
+            import glob
+            import hashlib
+            lib_sha = hashlib.sha256(open(lib.LIB_PATH, "rb").read()).hexdigest()
+            out["roofline"]["lib_sha256"] = lib_sha[:16]
+            stale = None
+            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic*.json")), reverse=True):
+                try:
+                    tr = json.load(open(path))
+                except (OSError, ValueError):
+                    continue
+                if not (tr.get("workload") == args.workload and n == wl["n"] and T == wl["T"]):
+                    continue
+                fn = os.path.basename(path)
+                if tr.get("lib_sha256", "")[:16] != lib_sha[:16]:
+                    stale = stale or f"profiles/{fn} was taken on another build of the library ({tr.get('lib_sha256', 'unstamped')[:16]}): not quoted"
+                    continue
+                try:
+                    out["roofline"]["traffic"] = int(tr["fit_kernel_traffic_bytes_per_step"])
+                    out["roofline"]["traffic_source"] = f"profiles/{fn} (PMC passes on this build, per step)"
+                    if "valu_insts_per_step" in tr:
+                        issued = float(tr["valu_insts_per_step"])
+                        rate = issued / (fit_ms_avg * 1e-3)
+                        out["roofline"]["valu"] = {"issued_insts": int(issued), "peak_issue": FP64_VALU_PEAK_WAVE_INSTS,
+                                                   "frac": round(rate / FP64_VALU_PEAK_WAVE_INSTS, 4),
+                                                   "unit": "wave-level VALU instructions per second against one fp64 issue per SIMD per 4 cycles",
+                                                   "source": f"profiles/{fn} (SQ_INSTS_VALU per step, this build) / this run's kernel_ms"}
+                except (KeyError, ValueError):
+                    pass
+                break
+            if out["roofline"]["traffic"] is None and stale:
+                out["roofline"]["traffic_source"] = stale
+            yhat_host = res["yhat"].cpu().numpy().copy()
+            batch.close()       # the host-buffer entry below is what a binding calls on its own: no second resident batch (and its streams) beside it
+            del res, y_dev, len_dev       # ... and the headline block goes back to torch's allocator before the other workloads allocate theirs
+            torch.cuda.empty_cache()
+            # ---- end to end: host buffers in, results on host (never `value`) -----------------------------
+            e2e_steps = args.e2e_steps if args.e2e_steps >= 0 else (0 if world > 1 else (1 if ms_per_step > 400 else 2))
+            if wl["fixed"]:
+                out["e2e"] = None        # the fixed-parameter entry exists on the device-resident API only
+            elif e2e_steps > 0 and world == 1:
+                times, e_ok = e2e_pass(lib, Y, opts, e2e_steps + 1)          # first pass untimed (allocations)
+                if True:
+                    best = float(np.mean(times[1:]))
+                    out["e2e"] = {"value": round(n / best, 1), "unit": "series/s", "ms_per_step": round(best * 1e3, 3), "steps": e2e_steps,
+                                  "series_ok": e_ok,
+                                  "what": "anofox_ts_forecast_batch: NULL fill + pack to the pinned time-major block (all host threads) + H2D + "
+                                          "fit + D2H + per-series malloc'd result arrays; PCIe-inclusive, never the headline value"}
+            # ---- the other BASELINE configurations, short loops (never `value`) ----------------------------
+            # (auto: only the default workload and shape; a run that switches the CPU or host-buffer leg off is a measurement
+            #  script, whose kernel trace or counters must hold the headline workload alone)
+            also_steps = args.also if args.also >= 0 else (3 if (world == 1 and not sim and args.workload == "autoets_m5_positive"
+                                                                 and not args.n_series and not args.t and not args.ets_model
+                                                                 and args.cpu_sample < 0 and args.e2e_steps < 0) else 0)
+            if also_steps > 0 and world == 1:
+                out["also"] = also_pass(ALSO_WORKLOADS, also_steps, h, dev, lib, synth, DeviceBatch, pack_time_major, torch)
+            # ---- CPU baseline: the oracle ("port") on a bounded sample of the same workload -------------
+            sample = wl["cpu_sample"] if args.cpu_sample < 0 else args.cpu_sample
+            if sample > 0 and world == 1:                  # (the contract: rank 0 at N = 1 only -- an N-GPU line carries no CPU leg)
+                from oracle import oracle as O
 
-            def cpu_run(k):
-                vals = np.ascontiguousarray(Y[:k]).reshape(-1)
-                offs = np.arange(k + 1, dtype=np.int64) * T
-                t0 = time.perf_counter()
-                if wl["fixed"]:
-                    r = O.ets_fixed_batch(vals, offs, ets_model, m, *wl["fixed"], h)
-                else:
-                    C.c_int.in_dll(O.lib(), "oracle_arima_ml_refit").value = wl["arima_method"]     # the checker runs the same estimation method
-                    r = O.forecast_batch(vals, offs, O.make_options(model, h, ets_model=ets_model, seasonal_period=m), 0)
-                return r, time.perf_counter() - t0
+                def cpu_run(k):
+                    vals = np.ascontiguousarray(Y[:k]).reshape(-1)
+                    offs = np.arange(k + 1, dtype=np.int64) * T
+                    t0 = time.perf_counter()
+                    if wl["fixed"]:
+                        r = O.ets_fixed_batch(vals, offs, ets_model, m, *wl["fixed"], h)
+                    else:
+                        C.c_int.in_dll(O.lib(), "oracle_arima_ml_refit").value = wl["arima_method"]     # the checker runs the same estimation method
+                        r = O.forecast_batch(vals, offs, O.make_options(model, h, ets_model=ets_model, seasonal_period=m), 0)
+                    return r, time.perf_counter() - t0
 
-            # bounded sample: a pilot (the table's figure, ~1 s on 128 cores) sizes the timed run to ~CPU_TARGET_S of work on
-            # THIS host -- more series first, whole repetitions of the batch once it is exhausted
-            sample = min(sample, n)
-            reps = 1
-            if args.cpu_sample < 0:
-                _, pdt = cpu_run(sample)
-                want = CPU_TARGET_S / max(pdt, 1e-3) * sample
-                if want > n:
-                    sample, reps = n, int(min(64, max(1, round(want / n))))
-                else:
-                    sample = int(max(sample, want))
-            cdt = 0.0
-            for _ in range(reps):
-                cres, dt1 = cpu_run(sample)
-                cdt += dt1
-            cdt /= reps
-            got = yhat_host[:sample]
-            okm = cres["status"] == 0
-            rel = np.abs(got[okm] - cres["yhat"][okm]) / np.maximum(1.0, np.abs(cres["yhat"][okm]))
-            out["cpu_baseline"] = {"value": round(sample / cdt, 2), "unit": "series/s", "cores": int(cres["threads"]),
-                                   "kind": "port", "sample": f"first {sample} series of the same batch, oracle (C, OpenMP), {reps} x {cdt:.1f} s",
-                                   "max_rel_diff_vs_gpu": float(np.max(rel)) if rel.size else 0.0}
+                # bounded sample: a pilot (the table's figure, ~1 s on 128 cores) sizes the timed run to ~CPU_TARGET_S of work on
+                # THIS host -- more series first, whole repetitions of the batch once it is exhausted
+                sample = min(sample, n)
+                reps = 1
+                if args.cpu_sample < 0:
+                    _, pdt = cpu_run(sample)
+                    want = CPU_TARGET_S / max(pdt, 1e-3) * sample
+                    if want > n:
+                        sample, reps = n, int(min(64, max(1, round(want / n))))
+                    else:
+                        sample = int(max(sample, want))
+                cdt = 0.0
+                for _ in range(reps):
+                    cres, dt1 = cpu_run(sample)
+                    cdt += dt1
+                cdt /= reps
+                got = yhat_host[:sample]
+                okm = cres["status"] == 0
+                rel = np.abs(got[okm] - cres["yhat"][okm]) / np.maximum(1.0, np.abs(cres["yhat"][okm]))
+                out["cpu_baseline"] = {"value": round(sample / cdt, 2), "unit": "series/s", "cores": int(cres["threads"]),
+                                       "kind": "port", "sample": f"first {sample} series of the same batch, oracle (C, OpenMP), {reps} x {cdt:.1f} s",
+                                       "max_rel_diff_vs_gpu": float(np.max(rel)) if rel.size else 0.0}
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

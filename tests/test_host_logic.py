@@ -212,6 +212,35 @@ def test_bench_gpus_n_starts_its_own_ranks():
     assert '"n_gpus"' not in out.stdout
 
 
+def test_bench_dump_outputs_float64_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: every result array goes out as float64 .npy (int32 codes exactly), all series while they fit the
+    budget; above it the same fixed seeded sample of series for every array and every run, its indices in rows.npy -- which a later
+    dump that fits removes again."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    n, h = 1000, 28
+    arrays = {"yhat": rng.normal(size=(n, h)), "status": rng.integers(0, 7, n).astype(np.int32)}
+    d = tmp_path / "dump"
+    assert bench.dump_outputs(str(d), arrays) is None
+    for name, a in arrays.items():
+        got = np.load(d / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert not (d / "rows.npy").exists()
+    budget = 100 * (8 * h + 8 + 8)                              # 100 series: both arrays and their index
+    rows = bench.dump_outputs(str(d), arrays, budget=budget)
+    again = bench.dump_outputs(str(tmp_path / "again"), arrays, budget=budget)
+    assert len(rows) == 100 and np.array_equal(rows, again) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(d / "rows.npy"), rows)
+    assert sum(os.path.getsize(d / f) - 128 for f in os.listdir(d)) <= budget     # (128: the .npy header)
+    for name, a in arrays.items():
+        assert np.array_equal(np.load(d / f"{name}.npy"), a[rows])
+    bench.dump_outputs(str(d), arrays)
+    assert not (d / "rows.npy").exists()
+
+
 def test_scalar_chunk_groups_rows_by_option_block(monkeypatch):
     """Route A, round 6 (binding/ts_forecast_scalar_hip.cpp, mirrored by api.ts_forecast_scalar): a chunk's rows are grouped by their
     option block and every distinct block is ONE batch call with per-row horizons; NULL / empty lists are NULL rows and never reach

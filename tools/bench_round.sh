@@ -1,6 +1,6 @@
 #!/bin/bash
 # The round's bench lines on the GPU box -> gpurun_out/bench_round/*.json (copy to profiles/<round>_bench_*.json).
-# Every line is the plain `python bench.py --workload W` (default steps, CPU baseline and host-buffer leg included); the strong-scaling
+# Every line is `python bench.py --workload W --full` (default steps, CPU baseline and host-buffer leg included); the strong-scaling
 # shards are rank 0 of an 8-rank job measured alone (--scaling strong --simulate-world 8).
 OUT=/root/repo/gpurun_out/bench_round
 rm -rf $OUT; mkdir -p $OUT
@@ -8,7 +8,7 @@ cd /root/repo
 for w in autoets_m5_positive autoets_m5 ets_aaa_fixed_m5 ets_aaa_m5 autoets_stress autoarima_m5 autoarima_css_m5 autoets_m24 autoets_hourly168; do
   extra=""
   [ $w = ets_aaa_fixed_m5 ] && extra="--steps 20"
-  timeout 600 python bench.py --workload $w $extra 2>$OUT/$w.err | tail -1 > $OUT/bench_$w.json
+  timeout 600 python bench.py --workload $w --full $extra 2>$OUT/$w.err | tail -1 > $OUT/bench_$w.json
 done
 for w in autoets_m5_positive autoets_m5 autoarima_css_m5; do
   timeout 300 python bench.py --workload $w --scaling strong --simulate-world 8 --steps 5 --cpu-sample 0 --e2e-steps 0 2>>$OUT/strong.err | tail -1 > $OUT/bench_strong8_shard0_$w.json
