@@ -176,6 +176,11 @@ struct AnofoxHipBatch {
     // BASELINE config 2: ETS(spec) with GIVEN smoothing parameters -- no optimiser, one streamed pass per series
     bool fixed_params = false;
     double fixed_x[4] = {0.0, 0.0, 0.0, 0.0};   // optimiser coordinates (alpha, beta*, gamma*, phi) of the given parameters
+    // intermittent-demand models (fit_intermittent.hip): aggregation level of every series, largest level per group of 64 series
+    // (+ the batch's), and IMAPA's per-(level, series) terms, grown on demand to the largest level a run meets
+    int32_t *d_im_level = nullptr, *d_im_gmax = nullptr;
+    double *d_im_fc = nullptr;
+    size_t im_fc_elems = 0;
 };
 
 namespace {
@@ -205,6 +210,7 @@ bool make_plan(const ForecastOptions *o, Plan &p, AnofoxError *err)
     switch (p.model) {
     case M_Naive: case M_SeasonalNaive: case M_SMA: case M_RandomWalkDrift: case M_ARIMA:
     case M_SES: case M_SESOptimized: case M_Holt: case M_HoltWinters: case M_SeasonalES: case M_SeasonalESOptimized:
+    case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA:
         break;
     case M_ETS: {
         p.ets_notation = cstr_field(o->ets_model, sizeof o->ets_model);
@@ -316,6 +322,7 @@ void free_batch_buffers(AnofoxHipBatch *b)
     for (void *p : b->retired) F(p);
     b->retired.clear();
     F(b->d_m_col); F(b->d_ring); F(b->d_prep_scratch);
+    F(b->d_im_level); F(b->d_im_gmax); F(b->d_im_fc);
     F(b->d_passes_total); F(b->d_evals_total); F(b->d_mask); F(b->d_len_group); F(b->d_count); F(b->d_pos_map); F(b->d_pos_cnt); F(b->d_notpos); F(b->d_ypos);
     F(b->ar_w); F(b->ar_wmean); F(b->ar_wsd); F(b->ar_l0); F(b->ar_l1); F(b->ar_x); F(b->ar_aicc); F(b->ar_wlen); F(b->ar_d); F(b->ar_D);
     F(b->ar_order); F(b->ar_status); F(b->ar_evals); F(b->ar_passes); F(b->ar_models);
@@ -353,6 +360,10 @@ void alloc_common(AnofoxHipBatch *b)
     b->d_count = dalloc<int32_t>(2);
     if (b->plan.model == M_AutoETS) {
         b->d_pos_map = dalloc<int32_t>(ld); b->d_pos_cnt = dalloc<int32_t>(2); b->d_notpos = dalloc<int32_t>(ld);
+    }
+    if (is_intermittent_model(b->plan.model)) {
+        b->d_im_level = dalloc<int32_t>(ld);
+        b->d_im_gmax = dalloc<int32_t>((size_t)intermittent_groups((int)n) + 1);
     }
     if (b->plan.model == M_AutoARIMA) {
         const size_t T = std::max<size_t>(b->t_max, 1);
@@ -1247,6 +1258,39 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
     b->insp_ok = true;
 }
 
+// CrostonClassic / CrostonSBA / TSB: one streamed pass (croston_kernel).  ADIDA / IMAPA: that pass gives every series' aggregation
+// level K, then SESopt on the level sums (agg_ses_kernel).  IMAPA sizes its per-(level, series) terms by the batch's largest K, read
+// back once: the one host wait of these models (include/anofox_fcst_hip.h, anofox_hip_batch_run).
+void run_intermittent(AnofoxHipBatch *b, const int32_t *d_len, hipStream_t st)
+{
+    const ModelType m = b->plan.model;
+    IntermittentArgs a{};
+    a.y = b->d_y; a.ld = b->ld; a.len = d_len; a.n_series = (int)b->n;
+    a.kind = m == M_CrostonClassic ? IK_CROSTON : m == M_CrostonSBA ? IK_SBA : m == M_TSB ? IK_TSB : m == M_ADIDA ? IK_ADIDA : IK_IMAPA;
+    a.h = b->h;
+    a.n_groups = intermittent_groups((int)b->n);
+    a.yhat = b->d_yhat; a.detail = b->d_detail; a.level = b->d_im_level; a.group_max = b->d_im_gmax;
+    HIPCHECK(hipMemsetAsync(b->d_im_gmax, 0, ((size_t)a.n_groups + 1) * sizeof(int32_t), st));
+    launch_croston(a, st);
+    if (a.kind == IK_ADIDA) launch_agg_ses(a, st);
+    if (a.kind == IK_IMAPA) {
+        int32_t k_max = 0;
+        HIPCHECK(hipMemcpyAsync(&k_max, b->d_im_gmax + a.n_groups, sizeof k_max, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        const size_t need = (size_t)std::max(k_max, 0) * b->ld;
+        if (b->im_fc_elems < need) {
+            if (b->d_im_fc) b->retired.push_back(b->d_im_fc);
+            b->d_im_fc = nullptr; b->im_fc_elems = 0;
+            b->d_im_fc = dalloc<double>(need);
+            b->im_fc_elems = need;
+        }
+        a.level_fc = b->d_im_fc; a.n_levels = k_max;
+        try { launch_agg_ses(a, st); }
+        catch (const std::exception &e) { throw HipFail{e.what()}; }
+    }
+    b->n_problems += b->n;
+}
+
 void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t st)
 {
     const Plan &p = b->plan;
@@ -1445,6 +1489,12 @@ void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t 
         finish();
         break;
     }
+    case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: {
+        prep(1, false);
+        run_intermittent(b, d_len, st);
+        finish();
+        break;
+    }
     default: throw HipFail{"model not implemented"};
     }
     LAUNCHCHECK(model_name(p.model));
@@ -1482,6 +1532,7 @@ void run_batch(AnofoxHipBatch *b, hipStream_t st)
     auto used_period = [&](int period) {
         switch (b->plan.model) {
         case M_Naive: case M_RandomWalkDrift: case M_ARIMA: case M_SES: case M_SESOptimized: case M_Holt: return 1;
+        case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: return 1;
         case M_AutoARIMA:
             // a DETECTED period goes to the seasonal search exactly like an explicit one (forecast.rs:528-537 hands it to
             // forecast_auto_arima, :1448-1452 passes any period > 1 to with_seasonal_period): used up to 2,048 (rings in LDS up to
@@ -2339,6 +2390,7 @@ static bool forecast_batch_one_device(const double *const *values, const uint64_
         auto used_period = [&](int period) {
             switch (plan.model) {
             case M_Naive: case M_RandomWalkDrift: case M_ARIMA: case M_SES: case M_SESOptimized: case M_Holt: return 1;
+            case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: return 1;
             case M_AutoARIMA: return period > ETS_MAX_PERIOD ? ETS_MAX_PERIOD + 1 : (period > 1 ? period : 1);      // (forecast.rs:528-537, 1448-1452: any detected period is seasonal)
             default: return period;
             }

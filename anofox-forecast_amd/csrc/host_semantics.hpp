@@ -79,6 +79,12 @@ inline bool is_non_seasonal_model(ModelType m)
     }
 }
 
+// the intermittent-demand models the HIP backend runs (fit_intermittent.hip); CrostonOptimized is not one of them
+inline bool is_intermittent_model(ModelType m)
+{
+    return m == M_CrostonClassic || m == M_CrostonSBA || m == M_TSB || m == M_ADIDA || m == M_IMAPA;
+}
+
 inline bool valid_ets_notation(const std::string &s)
 {
     auto am = [](char c) { return c == 'A' || c == 'M'; };

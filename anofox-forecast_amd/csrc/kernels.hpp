@@ -153,6 +153,23 @@ struct SimpleArgs {
     double *yhat; int32_t *status;
 };
 
+// intermittent-demand models (fit_intermittent.hip)
+enum IntermittentKind { IK_CROSTON = 0, IK_SBA = 1, IK_TSB = 2, IK_ADIDA = 3, IK_IMAPA = 4 };
+struct IntermittentArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    int kind, h;
+    int n_groups;                // intermittent_groups(n_series): workgroups of 64 consecutive series
+    double *yhat;                // [n_series x h]
+    int32_t *detail;             // [ld] FIT_OK for every series with len > 0
+    int32_t *level;              // [ld] aggregation level K of every series (0: no demand)
+    int32_t *group_max;          // [n_groups + 1] largest K of each group, [n_groups]: of the batch (atomicMax: zeroed before croston)
+    double *level_fc;            // IMAPA: [n_levels x ld], SESopt of level k / k at row k - 1
+    int n_levels;                // IMAPA: rows of level_fc = largest K of the batch (read back after launch_croston)
+};
+int intermittent_groups(int n_series);
+void launch_croston(const IntermittentArgs &, hipStream_t);   // every kind: sizes / intervals / demand SES, K, group maxima
+void launch_agg_ses(const IntermittentArgs &, hipStream_t);   // ADIDA / IMAPA, after launch_croston
+
 struct IntervalArgs {
     int n_series, h;
     const double *yhat, *sd;

@@ -288,7 +288,8 @@ bool anofox_hip_selftest_recip(uint64_t n_operands, uint64_t seed, uint64_t *out
 /* Lane-level efficiency counters of the last run (waits for it); false before a run. */
 bool anofox_hip_batch_lane_stats(AnofoxHipBatch *batch, AnofoxHipLaneStats *out, size_t struct_size);
 
-/* Asynchronous fit + forecast, ordered on `stream` (a hipStream_t).  NULL is NOT the null stream: it means the batch's own non-blocking stream, which the null stream does not wait for -- wait for the batch (anofox_hip_batch_stats / _fetch, or a device-wide wait) before reading its results from another stream. */
+/* Asynchronous fit + forecast, ordered on `stream` (a hipStream_t).  NULL is NOT the null stream: it means the batch's own non-blocking stream, which the null stream does not wait for -- wait for the batch (anofox_hip_batch_stats / _fetch, or a device-wide wait) before reading its results from another stream.
+ * Host wait: with model IMAPA the call waits once on `stream`, after the first of its kernels, to read back the batch's largest aggregation level (it sizes the per-(level, series) buffer); the rest of the run stays asynchronous. */
 bool anofox_hip_batch_run(AnofoxHipBatch *batch, void *stream,
                           struct AnofoxError *out_error);
 
