@@ -80,13 +80,13 @@ template <class Cfg, int MS, class YT> struct RoundModelOf<Cfg, MS, YT, true> { 
 //           ARE the cost and four times the arithmetic is free; in a mix with the general-class specs (VALU bound) it is not,
 //           and the sequential driver stays.  Same iterates, same evaluation counts (the speculative driver's bookkeeping).
 // YT: storage type of the block the round streams (ets_device.hpp: double, or float / uint16_t for a compact copy of a batch of counts)
+// The round body: one virtual one-wave workgroup `vblock` of `vgrid` (`wave`: its index inside the real workgroup, `lds_all`: the
+// workgroup's dynamic LDS).  ets_round_kernel runs it for one spec per launch; ets_group_round_kernel (below) for the spec of its slot.
 template <class Cfg, int MS, int SPEC, bool K4 = false, class YT = double>
-__global__ __launch_bounds__(NM_BLOCK * RoundTraits<Cfg>::WPB, ((ANOFOX_SEQ_WAVES_COMPACT > 0 && SPEC == 0 && !K4 && !std::is_same_v<YT, double> && !Cfg::CLASSIC ? ANOFOX_SEQ_WAVES_COMPACT : RoundTraits<Cfg, YT>::WAVES) + RoundTraits<Cfg>::WPB - 1) / RoundTraits<Cfg>::WPB) void ets_round_kernel(const FitArgs a)
+__device__ __forceinline__ void ets_round_body(const FitArgs &a, const int vblock, const int vgrid, const int wave, double *const lds_all)
 {
-    extern __shared__ double lds_all[];
     constexpr int D = Cfg::DIM;
     constexpr bool PARK = RoundTraits<Cfg>::PARK;
-    constexpr int WPB = RoundTraits<Cfg>::WPB;
     if constexpr (ANOFOX_SETPRIO >= 1 && RoundTraits<Cfg>::DAMPED_MUL) __builtin_amdgcn_s_setprio(3);
     else if constexpr (ANOFOX_SETPRIO >= 2 && !Cfg::CLASSIC && !Cfg::ADDITIVE) __builtin_amdgcn_s_setprio(ANOFOX_SETPRIO == 2 ? 1 : 2);
     // per chain (host_api.hip launch_fit_slots, tune prio_top): the instruction takes an immediate
@@ -95,8 +95,6 @@ __global__ __launch_bounds__(NM_BLOCK * RoundTraits<Cfg>::WPB, ((ANOFOX_SEQ_WAVE
     else if (a.wave_prio == 1) __builtin_amdgcn_s_setprio(1);
     if constexpr (Cfg::T == C_MUL && Cfg::D) dm_pow_tab_init();     // b^phi tables -> LDS, by every thread of the workgroup, before any wave leaves
     const int lane = threadIdx.x & (NM_BLOCK - 1);
-    const int wave = WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    const int vblock = (int)blockIdx.x * WPB + wave, vgrid = (int)gridDim.x * WPB;      // the wave's virtual one-wave workgroup
     // this wave's slice of the dynamic LDS: [simplex store unless it rests in global scratch][seasonal ring of a run-time period]
     const int lds_per_wave = (PARK ? 0 : nm_lds_doubles<D>()) + ((MS == -1 || MS == -3) ? a.m * NM_BLOCK : 0);
     double *const lds = lds_all + (size_t)wave * (size_t)lds_per_wave;
@@ -245,6 +243,16 @@ __global__ __launch_bounds__(NM_BLOCK * RoundTraits<Cfg>::WPB, ((ANOFOX_SEQ_WAVE
         a.st.passes[s] = r.passes;
         a.st.done[s] = r.done ? 1 : 0;
     }
+}
+
+template <class Cfg, int MS, int SPEC, bool K4 = false, class YT = double>
+__global__ __launch_bounds__(NM_BLOCK * RoundTraits<Cfg>::WPB, ((ANOFOX_SEQ_WAVES_COMPACT > 0 && SPEC == 0 && !K4 && !std::is_same_v<YT, double> && !Cfg::CLASSIC ? ANOFOX_SEQ_WAVES_COMPACT : RoundTraits<Cfg, YT>::WAVES) + RoundTraits<Cfg>::WPB - 1) / RoundTraits<Cfg>::WPB) void ets_round_kernel(const FitArgs a)
+{
+    extern __shared__ double lds_all[];
+    constexpr int WPB = RoundTraits<Cfg>::WPB;
+    const int wave = WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    // the wave's virtual one-wave workgroup
+    ets_round_body<Cfg, MS, SPEC, K4, YT>(a, (int)blockIdx.x * WPB + wave, (int)gridDim.x * WPB, wave, lds_all);
 }
 
 template <class Cfg, int MS, class YT = double>

@@ -142,6 +142,10 @@ struct AnofoxHipBatch {
         double *nm_scratch = nullptr;    // where the lanes' simplices rest between passes (kernels that keep them out of LDS: RoundTraits::PARK)
         size_t nm_scratch_doubles = 0;
     } lanes[N_AUX_STREAMS];
+    // group rounds (launch_fit_slots): the [round][slot] arguments of a run's group launches, uploaded once per run from the pinned copy
+    anofox::FitArgs *d_group_tab = nullptr, *h_group_tab = nullptr;
+    size_t group_tab_cap = 0;
+    hipEvent_t ev_group_tab = nullptr;     // recorded behind the upload: the pinned copy is rewritten only once it has been read
     hipStream_t last_stream = nullptr;
     bool ran = false, timed_fit = false;
     uint32_t fit_launches = 0;
@@ -322,6 +326,8 @@ void free_batch_buffers(AnofoxHipBatch *b)
     for (void *p : b->retired) F(p);
     b->retired.clear();
     F(b->d_m_col); F(b->d_ring); F(b->d_prep_scratch);
+    F(b->d_group_tab); pin_free(b->h_group_tab); b->d_group_tab = b->h_group_tab = nullptr; b->group_tab_cap = 0;
+    if (b->ev_group_tab) { (void)hipEventDestroy(b->ev_group_tab); b->ev_group_tab = nullptr; }
     F(b->d_im_level); F(b->d_im_gmax); F(b->d_im_fc);
     F(b->d_passes_total); F(b->d_evals_total); F(b->d_mask); F(b->d_len_group); F(b->d_count); F(b->d_pos_map); F(b->d_pos_cnt); F(b->d_notpos); F(b->d_ypos);
     F(b->ar_w); F(b->ar_wmean); F(b->ar_wsd); F(b->ar_l0); F(b->ar_l1); F(b->ar_x); F(b->ar_aicc); F(b->ar_wlen); F(b->ar_d); F(b->ar_D);
@@ -881,7 +887,6 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
     const bool inline_stream = specs.size() == 1;
     const int n_fork = inline_stream ? 0 : n_lanes;      // streams that carry work: one per spec
     auto spec_stream = [&](int idx) -> hipStream_t { return inline_stream ? st : b->aux[idx]; };
-    for (int i = 0; i < n_fork; i++) HIPCHECK(hipStreamWaitEvent(b->aux[i], b->ev_fit0, 0));
     // enqueue order: most expensive specs first, dealt round-robin over the streams, so the long
     // multiplicative / damped / seasonal fits start together instead of queueing behind each other
     std::vector<size_t> order(specs.size());
@@ -988,12 +993,7 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
     std::vector<char> dead(order.size(), 0);
     if (b->none_pos && !b->fixed_params)
         for (size_t oi = 0; oi < order.size(); oi++)
-            if (args[oi].need_positive) {
-                dead[oi] = 1;
-                const FitArgs &a = args[oi];
-                hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, spec_stream(stream_of[oi]), (int)n, d_len,
-                                   b->d_notpos, a.status, a.st.done, a.st.passes, a.st.evals, a.st.iters, a.aicc, a.passes, a.evals, a.iters);
-            }
+            if (args[oi].need_positive) dead[oi] = 1;         // (their outputs: below, once the streams have forked)
     // additive-class specs, one lane per problem: four trial points per pass (K4).  Their pass is memory bound (6-10 instructions per
     // 8-byte load): against the sequential driver K4 is one pass per iteration instead of ~1.7, against four lanes per problem it is
     // the same bytes through a quarter of the load instructions (512 instead of 128 bytes each)
@@ -1089,6 +1089,252 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
             }
         }
     }
+    // a handful of series: one launch per spec, every problem on a wave of its own (two iterations per pass) to completion -- one
+    // series through AutoETS was 12 rounds x 3 launches x 25 specs
+    const bool tiny = (uint64_t)n * order.size() <= (uint64_t)TINY_BATCH_PROBLEMS;
+    const int total_rounds = b->fixed_params ? 0 : (tiny ? 1 : n_rounds);
+    // Group schedule (tune group_launch, the default): the live specs are dealt by class into at most four groups -- the damped
+    // multiplicative-trend specs (the step's critical path: two groups of similar expected work, on the priority streams), the other
+    // general-class specs and the additive class -- and round r of a group is ONE launch of its class's group kernel
+    // (ets_group_kernel.hpp) on the group's stream, behind one compaction and one gather launch for all its slots.  So the fit needs
+    // four streams whatever GPU_MAX_HW_QUEUES the host exports: with one stream per spec, 25 chains shared the runtime's default of
+    // four hardware queues (453 ms per step on the M5 batch, 372 ms with 16 queues; the group schedule: 377 and 376 ms,
+    // profiles/group_schedule_ab.txt).  Every argument of every round is known here, so the [round][slot] table goes to the device
+    // in one copy at the start of the run.  The per-spec schedule stays for one spec, a tiny batch (one launch per spec), given
+    // parameters and merged batches of several periods (per-lane period variants, which have no group kernels).
+    enum { RK_SEQ, RK_SPEC, RK_SPEC2, RK_AUTO, RK_K4, RK_AUTO_K4 };
+    std::vector<int> group_of(order.size(), -1);
+    std::vector<std::vector<size_t>> groups;         // slots (order indices) of each group, heaviest first
+    std::vector<int> group_stream;                   // the aux stream of each group
+    std::vector<GroupLaunchFn> group_fn;
+    std::vector<size_t> slot_of(order.size(), 0);    // column of the slot in a round's row of the table
+    size_t n_slots = 0;
+    bool grouped = b->tun.group_launch > 0 && !inline_stream && !tiny && !merged && !b->fixed_params && total_rounds > 0;
+    if (grouped) {
+        GroupLaunchFn fn[N_GROUP_CLASSES];
+        for (int c = 0; c < N_GROUP_CLASSES; c++) fn[c] = ets_group_launcher(c, m, yt);
+        std::vector<size_t> of_class[N_GROUP_CLASSES];
+        for (size_t oi = 0; oi < order.size() && grouped; oi++) {
+            if (dead[oi]) continue;
+            const int c = ets_group_class(specs[order[oi]]);
+            if (c < 0 || !fn[c] || fns[oi].nm_scratch_per_wg != 0) grouped = false;
+            else of_class[c].push_back(oi);
+        }
+        if (grouped) {
+            auto add = [&](const std::vector<size_t> &sl, int c) {
+                if (sl.empty()) return;
+                if (sl.size() > (size_t)GROUP_MAX_SLOTS) throw HipFail{"launch_fit_slots: more specs in one group than GROUP_MAX_SLOTS"};
+                groups.push_back(sl); group_fn.push_back(fn[c]);
+            };
+            // one class in two groups (tune group_split: 1 the damped-M class, 2 the other general-class specs), each spec (heaviest
+            // first) to the half with less expected work so far
+            auto add_split = [&](const std::vector<size_t> &sl, int c) {
+                std::vector<size_t> half[2];
+                double w[2] = {0.0, 0.0};
+                for (size_t oi : sl) {
+                    const int j = w[1] < w[0] ? 1 : 0;
+                    half[j].push_back(oi); w[j] += work(specs[order[oi]]);
+                }
+                add(half[0], c); add(half[1], c);
+            };
+            if (b->tun.group_split == 1) add_split(of_class[GROUP_DAMPED_MUL], GROUP_DAMPED_MUL);
+            else add(of_class[GROUP_DAMPED_MUL], GROUP_DAMPED_MUL);
+            if (b->tun.group_split == 2) add_split(of_class[GROUP_GENERAL], GROUP_GENERAL);
+            else add(of_class[GROUP_GENERAL], GROUP_GENERAL);
+            add(of_class[GROUP_ADDITIVE], GROUP_ADDITIVE);
+            grouped = !groups.empty();
+        }
+        if (grouped) {
+            // streams: the damped-M group (when there is one) on the first, which is the priority stream where the set has one; the
+            // others from the far end of the set, which never is
+            for (size_t g = 0; g < groups.size(); g++) {
+                const bool dm = spec_trend_idx(specs[order[groups[g][0]]]) == 4;
+                group_stream.push_back(dm ? (int)g : N_AUX_STREAMS - 1 - (int)g);      // (the damped-M groups come first)
+                for (size_t oi : groups[g]) { group_of[oi] = (int)g; stream_of[oi] = group_stream[g]; slot_of[oi] = n_slots++; }
+            }
+            // the specs with nothing to fit only get their outputs written: on the first group's stream
+            for (size_t oi = 0; oi < order.size(); oi++) if (dead[oi]) stream_of[oi] = group_stream[0];
+        }
+    }
+    // the table: pass 1 (emit = false) of the round loop below fills h_group_tab[r * n_slots + slot] and the slots' workgroup counts
+    bool emit = true;
+    std::vector<int> slot_blocks, slot_k4;
+    GroupCompactArgs gc{};          // pass 2: what enqueue_round collects of a group's slots for the group's compaction and gather
+    GroupGatherArgs gg{};
+    int gg_cols = 0;
+    auto run_round = [&](const size_t oi, const int kind, const FitArgs &a, hipStream_t sq, const int r) {
+        if (!grouped) {
+            const FitLaunchFn f = kind == RK_SEQ ? fns[oi].round_seq : kind == RK_SPEC ? fns[oi].round_spec : kind == RK_SPEC2 ? fns[oi].round_spec2 :
+                                  kind == RK_AUTO ? fns[oi].round_auto : kind == RK_K4 ? fns[oi].round_k4 : fns[oi].round_auto_k4;
+            f(a, sq);
+            return;
+        }
+        if (emit) return;                         // (the group launch carries it)
+        // the slot runs the device-side choice (SPEC 3) with the thresholds set so that it lands on the driver the host picked
+        FitArgs t = a;
+        if (kind == RK_SEQ || kind == RK_K4) { t.spec_below = -1; t.spec2_below = -1; t.budget_seq = t.budget; }
+        else if (kind == RK_SPEC) { t.spec_below = 0x7fffffff; t.spec2_below = -1; }
+        else if (kind == RK_SPEC2) throw HipFail{"launch_fit_slots: the one-wave-per-problem round of a tiny batch has no group form"};
+        // workgroups: those of the spec's own round_auto launch (ets_round_launch, SPEC 3) -- the same as its sequential (n / 64) or
+        // speculative (n / 16) launch under the thresholds above
+        const int g_seq = (int)((n + NM_BLOCK - 1) / NM_BLOCK);
+        const int g_spec = (int)((std::min<int64_t>((int64_t)n, std::max(t.spec_below, 0)) + NM_BLOCK / NM_K - 1) / (NM_BLOCK / NM_K));
+        const int g_spec2 = (int)std::min<int64_t>((int64_t)n, std::max(t.spec2_below, 0));
+        const int blocks = std::max(g_seq, std::max(g_spec, g_spec2));
+        if (t.ring_scratch != nullptr && (size_t)blocks * (size_t)t.m * NM_BLOCK > t.ring_scratch_doubles)
+            throw HipFail{"launch_fit_slots: the seasonal-ring scratch does not cover a group slot"};
+        const size_t cell = (size_t)r * n_slots + slot_of[oi];
+        b->h_group_tab[cell] = t;
+        slot_blocks[cell] = blocks;
+        slot_k4[cell] = (kind == RK_K4 || kind == RK_AUTO_K4) ? 1 : 0;
+    };
+    auto enqueue_round = [&](const int r, const size_t oi) {
+            if (dead[oi]) return;
+            const int q = (int)(oi % (size_t)n_lanes);
+            auto &lane = b->lanes[q];
+            hipStream_t sq = spec_stream(stream_of[oi]);
+            FitArgs &a = args[oi];
+            const bool spec_mode = r >= b->seq_rounds;
+            a.first_round = (r == 0);
+            a.wave_trace_tag = ((unsigned long long)specs[order[oi]] << 32) | ((unsigned long long)r << 16);
+            a.wave_prio = (int)oi < b->tun.prio_top ? std::max(1, 3 - (int)oi) : 0;
+            a.spec_below = -1; a.spec2_below = -1;
+            a.gathered = 0;
+            if (tiny) {
+                a.y_round = b->d_y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr;
+                a.budget = 1 << 30; a.budget_seq = a.budget;
+                run_round(oi, RK_SPEC2, a, sq, r);
+                b->fit_launches++;
+                return;
+            }
+            if (r == 0 && b->use_pos && a.need_positive) {
+                // mixed batch: this spec is admissible for the strictly positive series only -- its first round runs on
+                // their dense list (built once per group) instead of sweeping every wave for a few live lanes
+                if (emit)
+                    hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sq, (int)n, d_len, b->d_notpos,
+                                       a.status, lane.st.done, lane.st.passes, lane.st.evals, lane.st.iters);
+                a.series_of = b->d_pos_map; a.n_active = b->d_pos_cnt;
+                if (b->d_ypos) { a.y_round = b->d_ypos; a.ld_round = ld; a.gathered = 1; a.gather_cap = (int)ld; }
+                else { a.y_round = b->d_y; a.ld_round = ld; }
+            } else if (r == 0) {
+                a.y_round = a.y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr;
+            } else {
+                const int32_t *prev_map = (r == 1) ? nullptr : lane.map[(r - 1) & 1];
+                const int32_t *prev_cnt = (r == 1) ? nullptr : lane.cnt + ((r - 1) % 3);
+                if (emit && !grouped && r == 1) HIPCHECK(hipMemsetAsync(lane.cnt, 0, 3 * sizeof(int32_t), sq));      // then the counters rotate: no more memsets
+                if (emit && !grouped) launch_compact(prev_map, prev_cnt, (int)n, lane.st.done, lane.map[r & 1], lane.cnt + (r % 3), sq, lane.cnt + ((r + 1) % 3));
+                if (emit && grouped) {          // (the group's one compaction launch: enqueue_group_round)
+                    const int k = gc.n_slots++;
+                    gc.prev[k] = prev_map; gc.n_prev[k] = prev_cnt; gc.done[k] = lane.st.done;
+                    gc.next[k] = lane.map[r & 1]; gc.n_next[k] = lane.cnt + (r % 3); gc.n_clear[k] = lane.cnt + ((r + 1) % 3);
+                }
+                a.series_of = lane.map[r & 1]; a.n_active = lane.cnt + (r % 3);
+                if (b->use_gather && lane.ybuf) {
+                    if (emit && !grouped)
+                        launch_gather_columns(a.y, ld, lane.map[r & 1], lane.cnt + (r % 3), (int)n, (int)b->t_max, lane.ybuf, lane.ybuf_cols, sq,
+                                              (int)lane.ybuf_cols, ybytes);
+                    if (emit && grouped) {      // (and its one gather launch)
+                        const int k = gg.n_slots++;
+                        gg.series_of[k] = lane.map[r & 1]; gg.n_active[k] = lane.cnt + (r % 3);
+                        gg.out[k] = lane.ybuf; gg.ld_out[k] = lane.ybuf_cols; gg.cap[k] = (int)lane.ybuf_cols;
+                        gg_cols = std::max(gg_cols, (int)std::min<size_t>(n, lane.ybuf_cols));
+                    }
+                    a.y_round = lane.ybuf; a.ld_round = lane.ybuf_cols; a.gathered = 1; a.gather_cap = (int)lane.ybuf_cols;
+                } else {
+                    a.y_round = a.y; a.ld_round = ld;
+                }
+            }
+            const int s2 = (spec_trend_idx(specs[order[oi]]) == 4) ? b->spec2_below_md : b->spec2_below;
+            if (fill_mode && !k4[oi]) {
+                const int64_t live_i = (spec_has_mult(specs[order[oi]]) && b->live_pos >= 0) ? (int64_t)b->live_pos : (b->live_all >= 0 ? (int64_t)b->live_all : (int64_t)n);
+                const int s2v = (int)std::max<int64_t>(32, std::min<int64_t>(s2 > 0 ? s2 : 32, live_i / std::max(1, b->tun.fill_s2_div)));
+                a.budget = BUDGET[r]; a.budget_seq = (BUDGET[r] * 7) / 4;
+                if (r == 0) {
+                    if (fill_spec4[oi]) run_round(oi, RK_SPEC, a, sq, r);
+                    else { a.budget = a.budget_seq; run_round(oi, RK_SEQ, a, sq, r); }
+                } else {
+                    a.spec_below = fill_spec4[oi] ? 0x7fffffff : (int)std::max<int64_t>(64, live_i / std::max(1, b->tun.fill_late_div));
+                    a.spec2_below = s2v;
+                    run_round(oi, RK_AUTO, a, sq, r);
+                }
+                if (!grouped) b->fit_launches++;
+                return;
+            }
+            if (k4[oi]) {
+                // additive spec of a memory-bound run: one lane per problem with four trial points per pass wherever four LANES per
+                // problem would otherwise run -- the same bytes per iteration through a quarter of the load instructions (a wave of
+                // four-lane groups moves 128 bytes per load, and it is the CU's address pipeline that such a run saturates) -- as
+                // long as the spec still has more problems than `spec_below`; fewer are a latency problem again: four lanes, then
+                // one wave per problem
+                a.budget = BUDGET[r]; a.budget_seq = BUDGET[r];
+                const int64_t live = b->live_all >= 0 ? b->live_all : (int64_t)n;
+                // The most expensive spec (`k4_top` of them) switches to four lanes per problem EARLIER, at `k4_top_below` live problems
+                // (20,480; every other spec at spec_below = 8,192): its chain ends the step, alone on the chip for the last 10-25 ms of
+                // the intermittent M5 batch with 477 one-lane waves on 1,024 SIMDs -- four lanes per problem are the same arithmetic on
+                // four times the waves.  70.6-71.7 -> 66.1-68.1 ms on that batch (thresholds 14,336-24,576: the same; 12,288 and 32,768:
+                // no gain -- at 32,768 the first round already runs four lanes while all six chains still fill the chip), 125k x 1,024:
+                // 138-142 -> 132-139 ms, batches with general-class specs: unchanged (profiles/r04_ab_experiments.txt).
+                const int sb = ((int)oi < b->tun.k4_top && b->tun.k4_top_below > 0) ? b->tun.k4_top_below : b->spec_below;
+                if (r == 0) run_round(oi, live > sb ? RK_K4 : RK_SPEC, a, sq, r);
+                else {
+                    a.spec_below = sb; a.spec2_below = s2 > 0 ? s2 : -1;
+                    run_round(oi, RK_AUTO_K4, a, sq, r);
+                }
+            } else if (r == 0 || b->seq_rounds_env >= 0 || b->seq_rounds == 0) {
+                // first round (no device count yet) or a forced schedule: the host picks the driver
+                a.budget = spec_mode ? BUDGET[r] : (BUDGET[r] * 7) / 4;     // ~1.7 passes per iteration when sequential
+                if (spec_mode && r > 0 && s2 > 0) {
+                    // ... but the last s2 problems still go one per wave (device-side count), in the same launch
+                    a.spec_below = 0x7fffffff; a.spec2_below = s2; a.budget_seq = a.budget;
+                    run_round(oi, RK_AUTO, a, sq, r);
+                } else
+                    run_round(oi, spec_mode ? RK_SPEC : RK_SEQ, a, sq, r);
+            } else {
+                // later rounds: the device-side count of running problems picks the driver -- sequential (least arithmetic)
+                // while this spec still fills >= 1/8 of the chip, then speculative (one pass per iteration), then two-level
+                // speculative (one problem per wave, two iterations per pass)
+                a.spec_below = (spec_trend_idx(specs[order[oi]]) == 4) ? b->spec_below_md : b->spec_below;
+                a.spec2_below = s2 > 0 ? s2 : -1;
+                if ((int)oi < b->tun.top_boost_n) {         // (experiment: the chains that end the step get their parallelism earlier)
+                    a.spec_below = (int)std::min<int64_t>(0x7fffffff, (int64_t)a.spec_below * b->tun.top_boost_pct / 100);
+                    if (a.spec2_below > 0) a.spec2_below = (int)std::min<int64_t>(0x7fffffff, (int64_t)a.spec2_below * b->tun.top_boost_pct / 100);
+                }
+                // ONE launch: a launch whose workgroups only find out that another driver owns the round still has to be dispatched
+                a.budget_seq = (BUDGET[r] * 7) / 4;
+                a.budget = BUDGET[r];
+                run_round(oi, RK_AUTO, a, sq, r);
+            }
+            if (!grouped) b->fit_launches++;
+    };
+    if (grouped) {
+        // pass 1: the table, then one copy of it ahead of everything the group streams run
+        const size_t cells = (size_t)total_rounds * n_slots;
+        if (b->ev_group_tab) HIPCHECK(hipEventSynchronize(b->ev_group_tab));      // (the previous run's copy has been read)
+        else HIPCHECK(hipEventCreateWithFlags(&b->ev_group_tab, hipEventDisableTiming));
+        if (b->group_tab_cap < cells) {
+            if (b->d_group_tab) b->retired.push_back(b->d_group_tab);            // (an earlier run's launches may still read it)
+            pin_free(b->h_group_tab);
+            b->d_group_tab = nullptr; b->h_group_tab = nullptr; b->group_tab_cap = 0;
+            b->d_group_tab = dalloc<FitArgs>(cells);
+            b->h_group_tab = (FitArgs *)pin_alloc_bytes(cells * sizeof(FitArgs));
+            b->group_tab_cap = cells;
+        }
+        slot_blocks.assign(cells, 0); slot_k4.assign(cells, 0);
+        emit = false;
+        for (int r = 0; r < total_rounds; r++) for (size_t oi = 0; oi < order.size(); oi++) enqueue_round(r, oi);
+        emit = true;
+        HIPCHECK(hipMemcpyAsync(b->d_group_tab, b->h_group_tab, cells * sizeof(FitArgs), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipEventRecord(b->ev_group_tab, st));
+        HIPCHECK(hipEventRecord(b->ev_fork, st));
+        for (int q : group_stream) HIPCHECK(hipStreamWaitEvent(b->aux[q], b->ev_fork, 0));
+    } else
+        for (int i = 0; i < n_fork; i++) HIPCHECK(hipStreamWaitEvent(b->aux[i], b->ev_fit0, 0));
+    for (size_t oi = 0; oi < order.size(); oi++)
+        if (dead[oi]) {
+            const FitArgs &a = args[oi];
+            hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, spec_stream(stream_of[oi]), (int)n, d_len,
+                               b->d_notpos, a.status, a.st.done, a.st.passes, a.st.evals, a.st.iters, a.aicc, a.passes, a.evals, a.iters);
+        }
     if (b->fixed_params) {
         // given smoothing parameters: no rounds at all -- admissibility + parameters, then the final pass below
         for (size_t oi = 0; oi < order.size(); oi++) {
@@ -1107,121 +1353,46 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
         }
         LAUNCHCHECK("ETS fixed-parameter setup");
     }
-    // a handful of series: one launch per spec, every problem on a wave of its own (two iterations per pass) to completion -- one
-    // series through AutoETS was 12 rounds x 3 launches x 25 specs
-    const bool tiny = (uint64_t)n * order.size() <= (uint64_t)TINY_BATCH_PROBLEMS;
-    auto enqueue_round = [&](const int r, const size_t oi) {
-            if (dead[oi]) return;
-            const int q = (int)(oi % (size_t)n_lanes);
-            auto &lane = b->lanes[q];
-            hipStream_t sq = spec_stream(stream_of[oi]);
-            FitArgs &a = args[oi];
-            const bool spec_mode = r >= b->seq_rounds;
-            a.first_round = (r == 0);
-            a.wave_trace_tag = ((unsigned long long)specs[order[oi]] << 32) | ((unsigned long long)r << 16);
-            a.wave_prio = (int)oi < b->tun.prio_top ? std::max(1, 3 - (int)oi) : 0;
-            a.spec_below = -1; a.spec2_below = -1;
-            a.gathered = 0;
-            if (tiny) {
-                a.y_round = b->d_y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr;
-                a.budget = 1 << 30; a.budget_seq = a.budget;
-                fns[oi].round_spec2(a, sq);
-                b->fit_launches++;
-                return;
-            }
-            if (r == 0 && b->use_pos && a.need_positive) {
-                // mixed batch: this spec is admissible for the strictly positive series only -- its first round runs on
-                // their dense list (built once per group) instead of sweeping every wave for a few live lanes
-                hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sq, (int)n, d_len, b->d_notpos,
-                                   a.status, lane.st.done, lane.st.passes, lane.st.evals, lane.st.iters);
-                a.series_of = b->d_pos_map; a.n_active = b->d_pos_cnt;
-                if (b->d_ypos) { a.y_round = b->d_ypos; a.ld_round = ld; a.gathered = 1; a.gather_cap = (int)ld; }
-                else { a.y_round = b->d_y; a.ld_round = ld; }
-            } else if (r == 0) {
-                a.y_round = a.y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr;
-            } else {
-                const int32_t *prev_map = (r == 1) ? nullptr : lane.map[(r - 1) & 1];
-                const int32_t *prev_cnt = (r == 1) ? nullptr : lane.cnt + ((r - 1) % 3);
-                if (r == 1) HIPCHECK(hipMemsetAsync(lane.cnt, 0, 3 * sizeof(int32_t), sq));      // then the counters rotate: no more memsets
-                launch_compact(prev_map, prev_cnt, (int)n, lane.st.done, lane.map[r & 1], lane.cnt + (r % 3), sq, lane.cnt + ((r + 1) % 3));
-                a.series_of = lane.map[r & 1]; a.n_active = lane.cnt + (r % 3);
-                if (b->use_gather && lane.ybuf) {
-                    launch_gather_columns(a.y, ld, lane.map[r & 1], lane.cnt + (r % 3), (int)n, (int)b->t_max, lane.ybuf, lane.ybuf_cols, sq,
-                                          (int)lane.ybuf_cols, ybytes);
-                    a.y_round = lane.ybuf; a.ld_round = lane.ybuf_cols; a.gathered = 1; a.gather_cap = (int)lane.ybuf_cols;
-                } else {
-                    a.y_round = a.y; a.ld_round = ld;
-                }
-            }
-            const int s2 = (spec_trend_idx(specs[order[oi]]) == 4) ? b->spec2_below_md : b->spec2_below;
-            if (fill_mode && !k4[oi]) {
-                const int64_t live_i = (spec_has_mult(specs[order[oi]]) && b->live_pos >= 0) ? (int64_t)b->live_pos : (b->live_all >= 0 ? (int64_t)b->live_all : (int64_t)n);
-                const int s2v = (int)std::max<int64_t>(32, std::min<int64_t>(s2 > 0 ? s2 : 32, live_i / std::max(1, b->tun.fill_s2_div)));
-                a.budget = BUDGET[r]; a.budget_seq = (BUDGET[r] * 7) / 4;
-                if (r == 0) {
-                    if (fill_spec4[oi]) fns[oi].round_spec(a, sq);
-                    else { a.budget = a.budget_seq; fns[oi].round_seq(a, sq); }
-                } else {
-                    a.spec_below = fill_spec4[oi] ? 0x7fffffff : (int)std::max<int64_t>(64, live_i / std::max(1, b->tun.fill_late_div));
-                    a.spec2_below = s2v;
-                    fns[oi].round_auto(a, sq);
-                }
-                b->fit_launches++;
-                return;
-            }
-            if (k4[oi]) {
-                // additive spec of a memory-bound run: one lane per problem with four trial points per pass wherever four LANES per
-                // problem would otherwise run -- the same bytes per iteration through a quarter of the load instructions (a wave of
-                // four-lane groups moves 128 bytes per load, and it is the CU's address pipeline that such a run saturates) -- as
-                // long as the spec still has more problems than `spec_below`; fewer are a latency problem again: four lanes, then
-                // one wave per problem
-                a.budget = BUDGET[r]; a.budget_seq = BUDGET[r];
-                const int64_t live = b->live_all >= 0 ? b->live_all : (int64_t)n;
-                // The most expensive spec (`k4_top` of them) switches to four lanes per problem EARLIER, at `k4_top_below` live problems
-                // (20,480; every other spec at spec_below = 8,192): its chain ends the step, alone on the chip for the last 10-25 ms of
-                // the intermittent M5 batch with 477 one-lane waves on 1,024 SIMDs -- four lanes per problem are the same arithmetic on
-                // four times the waves.  70.6-71.7 -> 66.1-68.1 ms on that batch (thresholds 14,336-24,576: the same; 12,288 and 32,768:
-                // no gain -- at 32,768 the first round already runs four lanes while all six chains still fill the chip), 125k x 1,024:
-                // 138-142 -> 132-139 ms, batches with general-class specs: unchanged (profiles/r04_ab_experiments.txt).
-                const int sb = ((int)oi < b->tun.k4_top && b->tun.k4_top_below > 0) ? b->tun.k4_top_below : b->spec_below;
-                if (r == 0) (live > sb ? fns[oi].round_k4 : fns[oi].round_spec)(a, sq);
-                else {
-                    a.spec_below = sb; a.spec2_below = s2 > 0 ? s2 : -1;
-                    fns[oi].round_auto_k4(a, sq);
-                }
-            } else if (r == 0 || b->seq_rounds_env >= 0 || b->seq_rounds == 0) {
-                // first round (no device count yet) or a forced schedule: the host picks the driver
-                a.budget = spec_mode ? BUDGET[r] : (BUDGET[r] * 7) / 4;     // ~1.7 passes per iteration when sequential
-                if (spec_mode && r > 0 && s2 > 0) {
-                    // ... but the last s2 problems still go one per wave (device-side count), in the same launch
-                    a.spec_below = 0x7fffffff; a.spec2_below = s2; a.budget_seq = a.budget;
-                    fns[oi].round_auto(a, sq);
-                } else
-                    (spec_mode ? fns[oi].round_spec : fns[oi].round_seq)(a, sq);
-            } else {
-                // later rounds: the device-side count of running problems picks the driver -- sequential (least arithmetic)
-                // while this spec still fills >= 1/8 of the chip, then speculative (one pass per iteration), then two-level
-                // speculative (one problem per wave, two iterations per pass)
-                a.spec_below = (spec_trend_idx(specs[order[oi]]) == 4) ? b->spec_below_md : b->spec_below;
-                a.spec2_below = s2 > 0 ? s2 : -1;
-                if ((int)oi < b->tun.top_boost_n) {         // (experiment: the chains that end the step get their parallelism earlier)
-                    a.spec_below = (int)std::min<int64_t>(0x7fffffff, (int64_t)a.spec_below * b->tun.top_boost_pct / 100);
-                    if (a.spec2_below > 0) a.spec2_below = (int)std::min<int64_t>(0x7fffffff, (int64_t)a.spec2_below * b->tun.top_boost_pct / 100);
-                }
-                // ONE launch: a launch whose workgroups only find out that another driver owns the round still has to be dispatched
-                a.budget_seq = (BUDGET[r] * 7) / 4;
-                a.budget = BUDGET[r];
-                fns[oi].round_auto(a, sq);
-            }
-            b->fit_launches++;
+    // round r of group g: the slots' compaction and gather (enqueue_round) on the group's stream, then the one group launch
+    auto enqueue_group_round = [&](const int r, const size_t g) {
+        hipStream_t sg = b->aux[group_stream[g]];
+        if (r == 0) {
+            // the slots' rotating counters, cleared once before the first compaction (the per-spec chains' memsets)
+            int32_t *zero[GROUP_MAX_SLOTS] = {};
+            for (size_t k = 0; k < groups[g].size(); k++) zero[k] = b->lanes[groups[g][k] % (size_t)n_lanes].cnt;
+            launch_group_zero3((int)groups[g].size(), zero, sg);
+        }
+        gc = GroupCompactArgs{}; gc.n_series = (int)n;
+        gg = GroupGatherArgs{}; gg.t_max = (int)b->t_max; gg.elem_bytes = ybytes; gg.y = ybase; gg.ld = ld; gg_cols = 0;
+        for (size_t oi : groups[g]) enqueue_round(r, oi);
+        if (gc.n_slots > 0) launch_group_compact(gc, sg);
+        if (gg.n_slots > 0) launch_group_gather(gg, gg_cols, sg);
+        GroupRoundArgs ga{};
+        ga.n_slots = (int)groups[g].size();
+        const size_t row = (size_t)r * n_slots + slot_of[groups[g][0]];
+        for (int k = 0; k < ga.n_slots; k++) {
+            const size_t oi = groups[g][(size_t)k];
+            ga.spec[k] = specs[order[oi]];
+            ga.k4[k] = slot_k4[(size_t)r * n_slots + slot_of[oi]];
+            ga.start[k + 1] = ga.start[k] + slot_blocks[(size_t)r * n_slots + slot_of[oi]];
+        }
+        group_fn[g](b->d_group_tab + row, ga, m, sg);
+        b->fit_launches++;
     };
-    const int total_rounds = b->fixed_params ? 0 : (tiny ? 1 : n_rounds);
     // Head start of the damped multiplicative-trend chains (tune dm_head_rounds, round 5): their fits are the step's critical path -- alone
     // on the chip one of them takes 185-280 ms of a 450 ms step (profiles/r05_step_anatomy.txt) -- and while all 25 chains start together
     // their early, full rounds share every SIMD with the cheap specs' waves.  With a head start their first rounds are enqueued alone,
     // the other specs' streams wait for an event recorded behind them, and fill the chip once those chains thin out.
     int head = 0;
-    if (!tiny && !inline_stream && total_rounds > 0 && b->tun.dm_head_rounds > 0) {
+    if (grouped && total_rounds > 0 && b->tun.dm_head_rounds > 0 && groups.size() > 1 && group_stream[0] == 0 &&
+        spec_trend_idx(specs[order[groups[0][0]]]) == 4) {
+        // (the same head start for the damped-M group: its first rounds alone, the other groups' streams wait behind them)
+        head = std::min(b->tun.dm_head_rounds, total_rounds);
+        for (int r = 0; r < head; r++) enqueue_group_round(r, 0);
+        LAUNCHCHECK("ETS fit head rounds");
+        HIPCHECK(hipEventRecord(b->ev_join[0], b->aux[0]));
+        for (size_t g = 1; g < groups.size(); g++) HIPCHECK(hipStreamWaitEvent(b->aux[group_stream[g]], b->ev_join[0], 0));
+    } else if (!grouped && !tiny && !inline_stream && total_rounds > 0 && b->tun.dm_head_rounds > 0) {
         std::vector<size_t> dm, rest;
         for (size_t oi = 0; oi < order.size(); oi++)
             if (!dead[oi]) (spec_trend_idx(specs[order[oi]]) == 4 ? dm : rest).push_back(oi);
@@ -1234,10 +1405,13 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
         }
     }
     for (int r = 0; r < total_rounds; r++) {
-        for (size_t oi = 0; oi < order.size(); oi++) {
-            if (r < head && spec_trend_idx(specs[order[oi]]) == 4) continue;      // (already enqueued)
-            enqueue_round(r, oi);
-        }
+        if (grouped) {
+            for (size_t g = 0; g < groups.size(); g++) if (!(r < head && g == 0)) enqueue_group_round(r, g);
+        } else
+            for (size_t oi = 0; oi < order.size(); oi++) {
+                if (r < head && spec_trend_idx(specs[order[oi]]) == 4) continue;      // (already enqueued)
+                enqueue_round(r, oi);
+            }
         LAUNCHCHECK("ETS fit round");
     }
     // fixed parameters: the one streamed pass IS the workload -- the fit events bracket exactly that launch, on its stream
@@ -1245,10 +1419,16 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
     for (size_t oi = 0; oi < order.size(); oi++) if (!dead[oi]) fns[oi].final(args[oi], spec_stream(stream_of[oi]));
     if (b->fixed_params && order.size() == 1) HIPCHECK(hipEventRecord(b->ev_fit1, spec_stream(stream_of[0])));
     LAUNCHCHECK("ETS final pass");
-    for (int i = 0; i < n_fork; i++) {
-        HIPCHECK(hipEventRecord(b->ev_join[i], b->aux[i]));
-        HIPCHECK(hipStreamWaitEvent(st, b->ev_join[i], 0));
-    }
+    if (grouped)
+        for (int q : group_stream) {
+            HIPCHECK(hipEventRecord(b->ev_join[q], b->aux[q]));
+            HIPCHECK(hipStreamWaitEvent(st, b->ev_join[q], 0));
+        }
+    else
+        for (int i = 0; i < n_fork; i++) {
+            HIPCHECK(hipEventRecord(b->ev_join[i], b->aux[i]));
+            HIPCHECK(hipStreamWaitEvent(st, b->ev_join[i], 0));
+        }
     if (!(b->fixed_params && order.size() == 1)) HIPCHECK(hipEventRecord(b->ev_fit1, st));
     b->timed_fit = true;
     b->n_problems += (uint64_t)specs.size() * n;
@@ -1613,9 +1793,8 @@ void fitted_values_host(const double *y, size_t n, ModelType model, size_t perio
     }
 }
 
-// The candidate specs of a batch run on concurrent streams; ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues
-// (default 4: the 25-spec grid then runs ~2x slower; 16 is the measured best).  The library does NOT touch the process
-// environment: the host sets the variable before its first HIP call (lib.py and bench.py do).
+// The candidate specs of a batch run on at most four concurrent streams (launch_fit_slots, group schedule): ROCm's default of
+// GPU_MAX_HW_QUEUES=4 hardware queues is enough.  The library does NOT touch the process environment (Environment).
 bool device_ready(AnofoxError *err)
 {
     int cnt = 0;

@@ -66,6 +66,11 @@ struct Tunables {
     int fill_s2_div = 16;       // tune fill_s2_div: ... and any spec to one wave per problem at 1 / this of its problems (at most spec2_below)
     int top_boost_n = 0, top_boost_pct = 200;   // tune top_boost_n / top_boost_pct: the N heaviest chains switch to four lanes / one wave per problem at pct % of the class thresholds
     int prio_top = 0;           // tune prio_top: the N chains with the most expected work run their waves at raised issue priority (3, 2, 1, 1, ...: launch_fit_slots)
+    int group_launch = 1;       // tune group_launch: 1 = the specs of a class run each round in ONE launch (at most 4 streams: launch_fit_slots);
+                                //   0 = one stream and one launch chain per spec (the earlier schedule, for A/B runs and tests)
+    int group_split = 1;        // tune group_split: the class dealt by expected work into two groups (four streams in all): 1 the damped
+                                //   multiplicative-trend specs (the step's critical path), 2 the other general-class specs, 0 none.  M5 batch,
+                                //   4 queues: 377 / 412 / 418 ms (profiles/group_schedule_ab.txt)
     int dm_head_rounds = 0;     // tune dm_head_rounds: rounds the damped multiplicative-trend chains run before the other specs' streams start (launch_fit_slots)
     bool merge_periods = true;  // tune merge_periods: auto-detected periods run as merged batches (0: one batch per period)
     int part_threads = 16;      // tune part_threads: host threads that run the small per-period parts of an auto-detected batch side by side
@@ -128,6 +133,7 @@ struct Tunables {
         if (kv.count("spec_below")) t.spec_below = t.spec_below_md = std::atoi(kv.at("spec_below").c_str());
         geti("spec_below_md", t.spec_below_md);
         geti("gather_cols", t.gather_cols);
+        geti("group_launch", t.group_launch); geti("group_split", t.group_split);
         geti("k4", t.k4); geti("dm_head_rounds", t.dm_head_rounds); geti("k4_top", t.k4_top); geti("k4_top_below", t.k4_top_below);
         if (kv.count("spec2_below")) t.spec2_below = t.spec2_below_md = std::atoi(kv.at("spec2_below").c_str());
         geti("spec2_below_md", t.spec2_below_md);
@@ -486,18 +492,16 @@ void stream_set_destroy(StreamSet *s)
     for (auto &e : s->ev_join) if (e) (void)hipEventDestroy(e);
     delete s;
 }
-// The candidate specs of a fit run on up to 25 streams side by side; the HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues
-// (default 4) and streams that share a queue serialise.  The variable is read when the runtime initialises, and the library does not
-// touch the process environment (a setenv at load time races with getenv in a multi-threaded host such as DuckDB and changes every
-// other HIP user of the process: INTEGRATION.md, Environment) -- the HOST exports it.  What the library does: the first stream set
-// looks at what the environment says and, when the value is missing or below 16, says so ONCE on stderr -- only when the host has
-// asked for the library's diagnostics (ANOFOX_HIP_TIMING; round 6: an embedding host such as DuckDB must not get library noise on its
-// stderr at every process start).  Results are unaffected, the 25-spec AutoETS batch is 1.3-2x slower on 4 queues;
-// INTEGRATION.md is the primary place that says so.
+// The group schedule (launch_fit_slots, the default) runs a fit on at most four streams, so it needs no more than the HIP runtime's
+// default of 4 hardware queues (GPU_MAX_HW_QUEUES).  The one-stream-per-spec schedule (tune group_launch=0, A/B runs only) puts up to 25
+// streams side by side, and streams that share a queue serialise: for it, the first stream set says ONCE on stderr when the variable
+// is missing or below 16 -- only when the host has asked for the library's diagnostics (ANOFOX_HIP_TIMING).  The library does not touch
+// the process environment (Environment).
 inline void warn_hw_queues_once()
 {
     static std::once_flag once;
     std::call_once(once, [] {
+        if (Tunables::from_env().group_launch > 0) return;
         const char *q = std::getenv("GPU_MAX_HW_QUEUES");
         const int v = q ? std::atoi(q) : 0;
         if (v < 16 && std::getenv("ANOFOX_HIP_TIMING") != nullptr)
@@ -512,9 +516,11 @@ StreamSet *stream_set_take()
     HIPCHECK(hipGetDevice(&dev));
     warn_hw_queues_once();
     StreamPool &p = stream_pool();
-    // The first streams of a device's FIRST set carry the most expensive specs of a fit (launch_fit_slots orders the specs by
-    // work) and get the highest priority: the command processor then dispatches their workgroups first whenever slots free up, the
-    // cheap specs fill in behind -- longest chains first: 571 -> 536-545 ms on the 30-spec M5 batch, neutral elsewhere.  Every
+    // The first streams of a device's FIRST set carry the most expensive specs of a fit (launch_fit_slots: the damped multiplicative-
+    // trend groups, or the specs ordered by work) and get the highest priority: the command processor then dispatches their workgroups
+    // first whenever slots free up, the cheap specs fill in behind.  The group schedule uses two of them, whatever GPU_MAX_HW_QUEUES
+    // says.  For the one-stream-per-spec schedule, longest chains first:
+    // 571 -> 536-545 ms on the 30-spec M5 batch, neutral elsewhere.  Every
     // priority level has its own hardware queues and the chip multiplexes well only up to ~23 of them in total (16 normal + 7
     // high: 541 ms, + 8: 747 ms; 13 + 10, 14 + 9, 15 + 8: 544 ms; 20 + 7: 785 ms), so the count follows GPU_MAX_HW_QUEUES (none
     // when the host has not set it: the runtime's default of 4 queues leaves no room) and later sets (concurrent batches of other
@@ -533,7 +539,8 @@ StreamSet *stream_set_take()
     int n_prio = 0;
     if (want_prio) {
         const char *q = std::getenv("GPU_MAX_HW_QUEUES");
-        n_prio = q ? std::max(0, std::min(7, 23 - std::atoi(q))) : 0;
+        if (Tunables::from_env().group_launch > 0) n_prio = 2;      // (the damped-M groups' streams)
+        else n_prio = q ? std::max(0, std::min(7, 23 - std::atoi(q))) : 0;
         const int forced = ProcessTunables::get().prio_streams;
         if (forced >= 0) n_prio = std::min(forced, N_AUX_STREAMS);
     }

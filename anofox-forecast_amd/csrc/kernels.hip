@@ -241,6 +241,17 @@ FitLaunchers ets_fit_launcher(int spec_id, int m, int yt)
     return f;
 }
 
+GroupLaunchFn fit_group_damped_mul(int m, int yt);
+GroupLaunchFn fit_group_general(int m, int yt);
+GroupLaunchFn fit_group_additive(int m, int yt);
+GroupLaunchFn ets_group_launcher(int group_class, int m, int yt)
+{
+    if (group_class == GROUP_DAMPED_MUL) return fit_group_damped_mul(m, yt);
+    if (group_class == GROUP_GENERAL) return fit_group_general(m, yt);
+    if (group_class == GROUP_ADDITIVE) return fit_group_additive(m, yt);
+    return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------
 // compaction of the running problems (ballot per wave + one atomic; order of survivors not preserved)
 // ------------------------------------------------------------------------------------------
@@ -311,6 +322,87 @@ void launch_gather_columns(const void *y, size_t ld, const int32_t *series_of, c
         hipLaunchKernelGGL(gather_columns_kernel<float>, grid, dim3(NM_BLOCK), 0, stream, (const float *)y, ld, series_of, n_active, t_max, (float *)out, ld_out, cap);
     else
         hipLaunchKernelGGL(gather_columns_kernel<unsigned short>, grid, dim3(NM_BLOCK), 0, stream, (const unsigned short *)y, ld, series_of, n_active, t_max, (unsigned short *)out, ld_out, cap);
+}
+
+// group forms (kernels.hpp GroupCompactArgs / GroupGatherArgs): the same per-wave compaction and copy, slot k of the group in
+// blockIdx.y / blockIdx.z, a grid-stride loop over the slot's candidates / columns (a late round's few survivors leave at once)
+constexpr int GROUP_COMPACT_BLOCKS = 256, GROUP_GATHER_COL_BLOCKS = 128, GROUP_GATHER_ROW_BLOCKS = 8;
+__global__ __launch_bounds__(NM_BLOCK) void group_compact_kernel(const GroupCompactArgs g)
+{
+    const int k = blockIdx.y;
+    if (g.n_clear[k] && blockIdx.x == 0 && threadIdx.x == 0) *g.n_clear[k] = 0;
+    const int n_prev = g.n_prev[k] ? *g.n_prev[k] : g.n_series;
+    const int32_t *prev = g.prev[k], *done = g.done[k];
+    const int lane = threadIdx.x;
+    for (int base0 = (int)blockIdx.x * NM_BLOCK; base0 < n_prev; base0 += (int)gridDim.x * NM_BLOCK) {
+        const int idx = base0 + lane;
+        int s = 0;
+        bool keep = false;
+        if (idx < n_prev) {
+            s = prev ? prev[idx] : idx;
+            keep = done[s] == 0;
+        }
+        const unsigned long long bal = __ballot(keep);
+        const int cnt = __popcll(bal);
+        if (cnt == 0) continue;
+        int base = 0;
+        if (lane == 0) base = atomicAdd(g.n_next[k], cnt);
+        base = __shfl(base, 0);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep) g.next[k][base + before] = s;
+    }
+}
+
+void launch_group_compact(const GroupCompactArgs &g, hipStream_t stream)
+{
+    if (g.n_slots <= 0 || g.n_series <= 0) return;
+    const int grid = std::min((g.n_series + NM_BLOCK - 1) / NM_BLOCK, GROUP_COMPACT_BLOCKS);
+    hipLaunchKernelGGL(group_compact_kernel, dim3(grid, g.n_slots), dim3(NM_BLOCK), 0, stream, g);
+}
+
+struct GroupZeroArgs { int32_t *p[GROUP_MAX_SLOTS]; };
+__global__ void group_zero3_kernel(const int n, const GroupZeroArgs z)
+{
+    const int i = threadIdx.x;
+    if (i < 3 * n) z.p[i / 3][i % 3] = 0;
+}
+
+void launch_group_zero3(int n, int32_t *const *zero, hipStream_t stream)
+{
+    if (n <= 0) return;
+    GroupZeroArgs z{};
+    for (int k = 0; k < n && k < GROUP_MAX_SLOTS; k++) z.p[k] = zero[k];
+    hipLaunchKernelGGL(group_zero3_kernel, dim3(1), dim3(64), 0, stream, std::min(n, GROUP_MAX_SLOTS), z);
+}
+
+template <class E>
+__global__ __launch_bounds__(NM_BLOCK) void group_gather_kernel(const GroupGatherArgs g)
+{
+    const int k = blockIdx.z;
+    const int n_act = *g.n_active[k];
+    if (n_act > g.cap[k]) return;       // (more running problems than the slot's block holds: its round indexes y by series)
+    const E *y = (const E *)g.y;
+    E *out = (E *)g.out[k];
+    const size_t ld_out = g.ld_out[k];
+    const int32_t *series_of = g.series_of[k];
+    for (int p0 = (int)blockIdx.x * NM_BLOCK; p0 < n_act; p0 += (int)gridDim.x * NM_BLOCK) {
+        const int p = p0 + (int)threadIdx.x;
+        const int s = series_of[p < n_act ? p : n_act - 1];
+        for (int t0 = (int)blockIdx.y * GATHER_TB; t0 < g.t_max; t0 += (int)gridDim.y * GATHER_TB) {
+            const int t1 = t0 + GATHER_TB < g.t_max ? t0 + GATHER_TB : g.t_max;
+            for (int t = t0; t < t1; t++) out[(size_t)t * ld_out + p] = y[(size_t)t * g.ld + s];
+        }
+    }
+}
+
+void launch_group_gather(const GroupGatherArgs &g, int n_cols_max, hipStream_t stream)
+{
+    if (g.n_slots <= 0 || g.t_max <= 0 || n_cols_max <= 0) return;
+    dim3 grid(std::min((n_cols_max + NM_BLOCK - 1) / NM_BLOCK, GROUP_GATHER_COL_BLOCKS),
+              std::min((g.t_max + GATHER_TB - 1) / GATHER_TB, GROUP_GATHER_ROW_BLOCKS), g.n_slots);
+    if (g.elem_bytes == 8) hipLaunchKernelGGL(group_gather_kernel<double>, grid, dim3(NM_BLOCK), 0, stream, g);
+    else if (g.elem_bytes == 4) hipLaunchKernelGGL(group_gather_kernel<float>, grid, dim3(NM_BLOCK), 0, stream, g);
+    else hipLaunchKernelGGL(group_gather_kernel<unsigned short>, grid, dim3(NM_BLOCK), 0, stream, g);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -188,10 +188,50 @@ constexpr int ETS_PERLANE_LDS = -3, ETS_PERLANE_HBM = -4;
 // `yt`: storage type of the block the kernels stream (ets_device.hpp YT_F64 / YT_F32 / YT_U16); every entry is NULL when the
 // combination is not instantiated (compact types x per-lane period variants)
 FitLaunchers ets_fit_launcher(int spec_id, int m, int yt = 0);
+// Group rounds (launch_fit_slots, tune group_launch): round r of several specs of one class in ONE launch.  Slot k owns the
+// workgroups [start[k], start[k + 1]) and runs the round of spec[k] on tab[k] -- the same body as that spec's own round kernel, with
+// the driver picked per slot on the device (SPEC 3; k4[k] != 0: its K4 form).  The classes: the damped multiplicative-trend specs,
+// the additive class (EtsCfg::ADDITIVE) and the rest of the general class.
+constexpr int GROUP_MAX_SLOTS = 16;
+enum { GROUP_DAMPED_MUL = 0, GROUP_GENERAL = 1, GROUP_ADDITIVE = 2, N_GROUP_CLASSES = 3 };
+struct GroupRoundArgs {
+    int n_slots;
+    int spec[GROUP_MAX_SLOTS];
+    int k4[GROUP_MAX_SLOTS];
+    int start[GROUP_MAX_SLOTS + 1];     // prefix of the slots' one-wave workgroups; start[n_slots] = the launch's grid
+};
+// tab: [n_slots] this round's FitArgs of the slots, in device memory; m: the batch's period (1: none).  NULL: the combination is not
+// instantiated (a merged batch of several periods, or an experiment build whose round kernels differ in residency or layout)
+typedef void (*GroupLaunchFn)(const FitArgs *tab, const GroupRoundArgs &g, int m, hipStream_t);
+GroupLaunchFn ets_group_launcher(int group_class, int m, int yt);
+inline int ets_group_class(int spec_id)
+{
+    if (spec_id < 0 || spec_id >= 30 || (spec_id >= 15 && spec_id % 3 == 1)) return -1;      // (M,*,A: not a model)
+    const int e = spec_id / 15, ti = (spec_id % 15) / 3, s = spec_id % 3;
+    if (ti == 4) return GROUP_DAMPED_MUL;
+    return (e == 0 && ti < 3 && s < 2) ? GROUP_ADDITIVE : GROUP_GENERAL;
+}
 FitLaunchers classic_fit_launcher(int kind, int m);          // fit_classic.hip: the SES / Holt / Holt-Winters / SeasonalES family on the round kernels (final = NULL)
 struct ClassicArgs;
 void launch_classic_final(int kind, const FitArgs &a, const ClassicArgs &c, hipStream_t stream);
 
+// ... of every slot of a group round (launch_fit_slots) in one launch each: slot k in blockIdx.y (compaction) / blockIdx.z (gather).
+// Each slot keeps its own map, counters and block; the launches are sized by the slots' largest counts and stride over the columns.
+struct GroupCompactArgs {
+    int n_slots, n_series;
+    const int32_t *prev[GROUP_MAX_SLOTS], *n_prev[GROUP_MAX_SLOTS], *done[GROUP_MAX_SLOTS];
+    int32_t *next[GROUP_MAX_SLOTS], *n_next[GROUP_MAX_SLOTS], *n_clear[GROUP_MAX_SLOTS];
+};
+void launch_group_compact(const GroupCompactArgs &g, hipStream_t);
+// zero[k][0..3): the rotating counters of every slot, before the run's first compaction
+void launch_group_zero3(int n, int32_t *const *zero, hipStream_t);
+struct GroupGatherArgs {
+    int n_slots, t_max, elem_bytes;
+    const void *y; size_t ld;
+    const int32_t *series_of[GROUP_MAX_SLOTS], *n_active[GROUP_MAX_SLOTS];
+    void *out[GROUP_MAX_SLOTS]; size_t ld_out[GROUP_MAX_SLOTS]; int cap[GROUP_MAX_SLOTS];
+};
+void launch_group_gather(const GroupGatherArgs &g, int n_cols_max, hipStream_t);
 // compaction of the unfinished problems: series_next[0..n_next) = the series of the previous map whose done flag
 // is 0 (one ballot + one atomic per wave; the order of the survivors is not preserved, results do not depend on it)
 void launch_compact(const int32_t *series_prev, const int32_t *n_prev, int n_series, const int32_t *done,
