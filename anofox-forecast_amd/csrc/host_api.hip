@@ -185,6 +185,11 @@ struct AnofoxHipBatch {
     int32_t *d_im_level = nullptr, *d_im_gmax = nullptr;
     double *d_im_fc = nullptr;
     size_t im_fc_elems = 0;
+    // dynamic Theta models (fit_theta.hip): seasonal indices [m x ld], grown on demand to the largest period a run meets, and the
+    // per-series "seasonally adjusted" flag
+    double *d_th_sidx = nullptr;
+    size_t th_sidx_elems = 0;
+    int32_t *d_th_adj = nullptr;
 };
 
 namespace {
@@ -215,6 +220,7 @@ bool make_plan(const ForecastOptions *o, Plan &p, AnofoxError *err)
     case M_Naive: case M_SeasonalNaive: case M_SMA: case M_RandomWalkDrift: case M_ARIMA:
     case M_SES: case M_SESOptimized: case M_Holt: case M_HoltWinters: case M_SeasonalES: case M_SeasonalESOptimized:
     case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA:
+    case M_DynamicTheta: case M_DynamicOptimizedTheta:
         break;
     case M_ETS: {
         p.ets_notation = cstr_field(o->ets_model, sizeof o->ets_model);
@@ -329,6 +335,7 @@ void free_batch_buffers(AnofoxHipBatch *b)
     F(b->d_group_tab); pin_free(b->h_group_tab); b->d_group_tab = b->h_group_tab = nullptr; b->group_tab_cap = 0;
     if (b->ev_group_tab) { (void)hipEventDestroy(b->ev_group_tab); b->ev_group_tab = nullptr; }
     F(b->d_im_level); F(b->d_im_gmax); F(b->d_im_fc);
+    F(b->d_th_sidx); F(b->d_th_adj);
     F(b->d_passes_total); F(b->d_evals_total); F(b->d_mask); F(b->d_len_group); F(b->d_count); F(b->d_pos_map); F(b->d_pos_cnt); F(b->d_notpos); F(b->d_ypos);
     F(b->ar_w); F(b->ar_wmean); F(b->ar_wsd); F(b->ar_l0); F(b->ar_l1); F(b->ar_x); F(b->ar_aicc); F(b->ar_wlen); F(b->ar_d); F(b->ar_D);
     F(b->ar_order); F(b->ar_status); F(b->ar_evals); F(b->ar_passes); F(b->ar_models);
@@ -371,6 +378,7 @@ void alloc_common(AnofoxHipBatch *b)
         b->d_im_level = dalloc<int32_t>(ld);
         b->d_im_gmax = dalloc<int32_t>((size_t)intermittent_groups((int)n) + 1);
     }
+    if (is_theta_model(b->plan.model)) b->d_th_adj = dalloc<int32_t>(ld);
     if (b->plan.model == M_AutoARIMA) {
         const size_t T = std::max<size_t>(b->t_max, 1);
         b->ar_ws_bytes = arima_workspace_bytes((int)b->n, (int)T);
@@ -1471,6 +1479,31 @@ void run_intermittent(AnofoxHipBatch *b, const int32_t *d_len, hipStream_t st)
     b->n_problems += b->n;
 }
 
+// DynamicTheta / DynamicOptimizedTheta: for a period m > 1 the season test and the indices first (theta_season_kernel, into a
+// [m x ld] buffer grown on demand, no host wait), then one fit per series (theta_fit_kernel).
+void run_theta(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t st)
+{
+    ThetaArgs a{};
+    a.y = b->d_y; a.ld = b->ld; a.len = d_len; a.n_series = (int)b->n;
+    a.kind = b->plan.model == M_DynamicOptimizedTheta ? TK_DOTM : TK_DSTM;
+    a.h = b->h;
+    a.m = period > 1 ? period : 1;                          // <= ETS_MAX_PERIOD here: longer periods failed loudly in run_group
+    a.m_col = (b->d_m_col && a.m > 1) ? b->d_m_col : nullptr;
+    if (a.m > 1) {
+        const size_t need = (size_t)a.m * b->ld;
+        if (b->th_sidx_elems < need) {
+            if (b->d_th_sidx) b->retired.push_back(b->d_th_sidx);      // (an earlier group's launches may still read it)
+            b->d_th_sidx = nullptr; b->th_sidx_elems = 0;
+            b->d_th_sidx = dalloc<double>(need);
+            b->th_sidx_elems = need;
+        }
+    }
+    a.sidx = b->d_th_sidx; a.adjusted = b->d_th_adj;
+    a.yhat = b->d_yhat; a.detail = b->d_detail; a.evals = b->d_evals_total;
+    launch_theta(a, st);
+    b->n_problems += b->n;
+}
+
 void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t st)
 {
     const Plan &p = b->plan;
@@ -1509,7 +1542,7 @@ void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t 
 
     // A period the kernels cannot hold fails the group's series loudly (COMPUTATION_ERROR naming the cap) -- never a silent
     // non-seasonal fit.  The reference takes any period (forecast.rs:528-537); 2,048 covers every calendar period.
-    const bool uses_period = p.model == M_AutoETS || p.model == M_HoltWinters || p.model == M_SeasonalES || p.model == M_SeasonalESOptimized ||
+    const bool uses_period = p.model == M_AutoETS || p.model == M_HoltWinters || p.model == M_SeasonalES || p.model == M_SeasonalESOptimized || is_theta_model(p.model) ||
                              (p.model == M_ETS && (p.ets_spec_id < 0 || spec_season(p.ets_spec_id) != 0));
     const bool arima_period = p.model == M_AutoARIMA && period > ETS_MAX_PERIOD;      // seasonal ARIMA terms: LDS rings up to m = 24, an HBM scratch ring up to 2,048
     if ((uses_period && period > ETS_MAX_PERIOD) || arima_period) {
@@ -1672,6 +1705,12 @@ void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t 
     case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: {
         prep(1, false);
         run_intermittent(b, d_len, st);
+        finish();
+        break;
+    }
+    case M_DynamicTheta: case M_DynamicOptimizedTheta: {
+        prep(1, false);
+        run_theta(b, period, d_len, st);
         finish();
         break;
     }

@@ -85,6 +85,12 @@ inline bool is_intermittent_model(ModelType m)
     return m == M_CrostonClassic || m == M_CrostonSBA || m == M_TSB || m == M_ADIDA || m == M_IMAPA;
 }
 
+// the Theta models the HIP backend runs (fit_theta.hip); Theta, OptimizedTheta and AutoTheta are not among them
+inline bool is_theta_model(ModelType m)
+{
+    return m == M_DynamicTheta || m == M_DynamicOptimizedTheta;
+}
+
 inline bool valid_ets_notation(const std::string &s)
 {
     auto am = [](char c) { return c == 'A' || c == 'M'; };

@@ -170,6 +170,21 @@ int intermittent_groups(int n_series);
 void launch_croston(const IntermittentArgs &, hipStream_t);   // every kind: sizes / intervals / demand SES, K, group maxima
 void launch_agg_ses(const IntermittentArgs &, hipStream_t);   // ADIDA / IMAPA, after launch_croston
 
+// dynamic Theta models (fit_theta.hip)
+enum ThetaKind { TK_DSTM = 0, TK_DOTM = 1 };
+struct ThetaArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    int kind, h;
+    int m;                       // seasonal period of the batch (<= 1: no season test); m_col: per column (merged batch), m its largest
+    const int32_t *m_col;
+    double *sidx;                // [m x ld] multiplicative seasonal indices of the adjusted series (m > 1)
+    int32_t *adjusted;           // [ld] 1: the series is seasonally adjusted (written by theta_season_kernel, m > 1)
+    double *yhat;                // [n_series x h]
+    int32_t *detail;             // [ld] FIT_OK, or FIT_NONFINITE when a forecast is not finite
+    int32_t *evals;              // [ld] objective evaluations (DOTM), or nullptr
+};
+void launch_theta(const ThetaArgs &, hipStream_t);
+
 struct IntervalArgs {
     int n_series, h;
     const double *yhat, *sd;
