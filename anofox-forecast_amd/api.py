@@ -654,6 +654,72 @@ def _collect_groups(group, date, target):
     return order, series, valids
 
 
+MSTL_MODES = {"fail": 0, "trend": 1, "none": 2}
+
+
+def mstl_decompose_batch(series, periods, insufficient_data_mode=0, valids=None):
+    """anofox_hip_mstl_decompose_batch over a list of 1-D arrays.  Per series a dict: ok, code, message, applied, trend,
+    seasonal (list of arrays, longest period first), periods, remainder (None where not applied)."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    total = int(lens.sum()) if n else 0
+    K = len(periods)
+    pers = np.ascontiguousarray(periods, dtype=np.int32)
+    dummy = np.zeros(1)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else dummy.ctypes.data for y in ys])
+    masks = None
+    if valids is not None:
+        ms = [validity_mask(v) for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data for m in ms])
+    trend = np.empty(max(total, 1)); rem = np.empty(max(total, 1)); seas = np.empty(max(K * total, 1))
+    out_p = np.zeros(max(n * K, 1), dtype=np.int32); applied = np.zeros(max(n, 1), dtype=np.int32)
+    errs = (_lib.AnofoxError * max(n, 1))()
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_mstl_decompose_batch(vals, masks, lens.ctypes.data, n, pers.ctypes.data if K else None, K,
+                                           int(insufficient_data_mode), trend.ctypes.data, seas.ctypes.data, rem.ctypes.data,
+                                           out_p.ctypes.data, applied.ctypes.data, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out, off = [], 0
+    for i in range(n):
+        m = int(lens[i])
+        r = {"ok": errs[i].code == _lib.SUCCESS, "code": int(errs[i].code), "message": errs[i].message.decode(errors="replace"),
+             "applied": bool(applied[i]), "trend": None, "seasonal": [], "periods": [], "remainder": None}
+        if r["ok"] and r["applied"]:
+            r["trend"] = trend[off:off + m].copy()
+            r["remainder"] = rem[off:off + m].copy()
+            for j in range(K):
+                if out_p[i * K + j] == 0:
+                    break
+                r["periods"].append(int(out_p[i * K + j]))
+                r["seasonal"].append(seas[j * total + off:j * total + off + m].copy())
+        out.append(r)
+        off += m
+    return out
+
+
+def ts_mstl_decomposition_by(group, date, target, periods=(), insufficient_data="fail"):
+    """ts_mstl_decomposition_by(source, group_col, date_col, value_col, ...): the reference's MSTL decomposition per group
+    (decomposition.rs mstl_decompose; the table function ts_mstl_decomposition_native.cpp sorts each group by date and passes
+    a NULL value as 0.0).  `periods`: the seasonal periods (at most 8); `insufficient_data`: 'fail' (the group's rows are
+    dropped), 'trend' or 'none' (unknown strings mean 'fail', as InsufficientDataMode::from_str).  Returns
+    {group: {"trend", "seasonal", "remainder", "periods"}}, lists empty where the decomposition was not applied."""
+    mode = MSTL_MODES.get(str(insufficient_data).lower(), 0)
+    order, series, _ = _collect_groups(group, date, target)
+    res = mstl_decompose_batch(series, list(periods), mode)
+    out = {}
+    for k, r in zip(order, res):
+        if not r["ok"]:
+            continue
+        if not r["applied"]:
+            out[k] = {"trend": [], "seasonal": [], "remainder": [], "periods": []}
+            continue
+        out[k] = {"trend": r["trend"], "seasonal": r["seasonal"], "remainder": r["remainder"], "periods": r["periods"]}
+    return out
+
+
 def ts_forecast_inspect_by(group, date, target, method, params=None):
     """ts_forecast_inspect_by(source, group_col, date_col, target_col, method, params := MAP{}) (ts_macros.cpp:596-672,
     forecast.rs:1739-1885).  Supported here: AutoETS (model_family 'Ets') and AutoARIMA ('Arima'); a method outside the

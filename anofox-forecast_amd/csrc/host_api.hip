@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -219,6 +220,7 @@ bool make_plan(const ForecastOptions *o, Plan &p, AnofoxError *err)
     switch (p.model) {
     case M_Naive: case M_SeasonalNaive: case M_SMA: case M_RandomWalkDrift: case M_ARIMA:
     case M_SES: case M_SESOptimized: case M_Holt: case M_HoltWinters: case M_SeasonalES: case M_SeasonalESOptimized:
+    case M_SeasonalWindowAverage:
     case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA:
     case M_DynamicTheta: case M_DynamicOptimizedTheta:
         break;
@@ -1560,6 +1562,15 @@ void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t 
     case M_SMA: prep(1, false); simple(SK_SMA, 1, b->opt.window > 0 ? b->opt.window : std::max(period, 3)); break;
     case M_RandomWalkDrift: prep(1, false); simple(SK_DRIFT, 1, 0); break;
     case M_ARIMA: prep(1, false); simple(SK_TOY_ARIMA, 1, 0); break;
+    case M_SeasonalWindowAverage: {
+        prep(1, false);
+        SimpleArgs a{};
+        a.y = b->d_y; a.ld = ld; a.len = d_len; a.n_series = (int)n;
+        a.h = b->h; a.period = period;
+        a.yhat = b->d_yhat; a.status = b->d_status;
+        launch_swa(a, st);
+        break;
+    }
     case M_SES: prep(1, false); run_classic(b, CK_SES, d_len, 1, 0, 0.3, 0, nullptr, 0, 0, false, st); finish(); break;
     case M_SESOptimized: prep(1, false); run_classic(b, CK_SES, d_len, 1, 1, 0.0, 0, nullptr, 0, 0, false, st); finish(); break;
     case M_Holt: prep(1, false); run_classic(b, CK_HOLT, d_len, 1, 1, 0.0, 0, nullptr, 0, 0, false, st); finish(); break;
@@ -1825,6 +1836,17 @@ void fitted_values_host(const double *y, size_t n, ModelType model, size_t perio
         size_t p = std::min(std::max<size_t>(period, 1), n);
         for (size_t i = 0; i < p; i++) f[i] = y[0];
         for (size_t i = p; i < n; i++) f[i] = y[i - p];
+    } else if (model == M_SeasonalWindowAverage) {
+        // the running mean of the earlier values at the same phase (the value itself where there is none yet)
+        size_t p = std::min(std::max<size_t>(period, 1), n);
+        std::vector<double> sum(p, 0.0);
+        std::vector<size_t> cnt(p, 0);
+        for (size_t i = 0; i < n; i++) {
+            const size_t pos = i % p;
+            f[i] = cnt[pos] > 0 ? sum[pos] / (double)cnt[pos] : y[i];
+            sum[pos] += y[i];
+            cnt[pos]++;
+        }
     } else {
         double level = y[0];
         f[0] = level;
@@ -3300,6 +3322,231 @@ bool anofox_ts_forecast(const double *values, const uint64_t *validity, size_t l
     if (!my_ok) { if (out_error) *out_error = req.err; return false; }
     *out_result = req.res;
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// MSTL decomposition (decomposition.rs mstl_decompose; fit_mstl.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+bool anofox_hip_mstl_decompose_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
+                                      const int *periods, size_t n_periods, int insufficient_data_mode, double *trend,
+                                      double *seasonal, double *remainder, int32_t *info, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !trend || !remainder || !info || (n_periods > 0 && (!periods || !seasonal))) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (n_periods > (size_t)MSTL_MAX_PERIODS) {
+        set_error(out_error, COMPUTATION_ERROR, "Computation error: MSTL takes at most " + std::to_string(MSTL_MAX_PERIODS) +
+                                                    " seasonal periods, got " + std::to_string(n_periods));
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (!device_ready(out_error)) return false;
+    MstlArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.mode = (insufficient_data_mode == 1 || insufficient_data_mode == 2) ? insufficient_data_mode : MSTL_MODE_FAIL;
+    std::vector<int> ps(periods, periods + n_periods);
+    std::sort(ps.begin(), ps.end(), std::greater<int>());          // longest first (decomposition.rs:235-236)
+    // A period above t_rows / 2 + 1 is lowered to it: no series of the block holds two of its seasons either way (n <= t_rows <
+    // 2 p), so every test the kernels make on it keeps its outcome, and 2 p stays far from the int range.
+    const long long p_cap = (long long)(t_rows / 2) + 1;
+    auto capped = [&](int p) { return (long long)p > p_cap ? (int)p_cap : p; };
+    a.n_periods = (int)n_periods;
+    a.min_period = 0;
+    size_t rows = 0;
+    for (size_t k = 0; k < n_periods; k++) {
+        a.periods[k] = capped(ps[k]);
+        if (ps[k] > 0 && (a.min_period == 0 || capped(ps[k]) < a.min_period)) a.min_period = capped(ps[k]);
+        a.tab_off[k] = (int)std::min<size_t>(rows, (size_t)INT32_MAX);
+        // a phase table only for a period some series can hold (p >= 2, 2 p <= t_rows); the kernels never run the others
+        if (ps[k] >= 2 && (size_t)ps[k] <= t_rows / 2) rows += (size_t)ps[k];
+    }
+    a.trend = trend; a.remainder = remainder; a.seasonal = seasonal; a.info = info;
+    hipStream_t st = (hipStream_t)stream;
+    try {
+        a.tab = rows ? dalloc<double>(rows * ld) : nullptr;
+        a.mean = dalloc<double>((size_t)MSTL_MAX_PERIODS * ld);
+        a.used = dalloc<int32_t>(ld);
+        (void)hipGetLastError();
+        launch_mstl(a, st);
+        LAUNCHCHECK("mstl");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(a.tab, true); dev_free(a.mean, true); dev_free(a.used, true);
+    } catch (const HipFail &f) {
+        dev_free(a.tab); dev_free(a.mean); dev_free(a.used);        // (not quiesced: waits for the device first)
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_mstl_decompose_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
+                                     const int *periods, size_t n_periods, int insufficient_data_mode, double *out_trend,
+                                     double *out_seasonal, double *out_remainder, int32_t *out_periods, int32_t *out_applied,
+                                     AnofoxError *out_errors, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if ((n_series > 0 && (!values || !lengths || !out_applied)) || (n_periods > 0 && !periods)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    size_t total = 0, t_max = 0;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        total += lengths[s];
+        t_max = std::max(t_max, lengths[s]);
+    }
+    if (total > 0 && (!out_trend || !out_remainder || (n_periods > 0 && !out_seasonal))) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (n_periods > (size_t)MSTL_MAX_PERIODS) {
+        set_error(out_batch_error, COMPUTATION_ERROR, "Computation error: MSTL takes at most " + std::to_string(MSTL_MAX_PERIODS) +
+                                                          " seasonal periods, got " + std::to_string(n_periods));
+        return false;
+    }
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1), K = n_periods;
+    std::vector<int> ps(periods, periods + n_periods);
+    std::sort(ps.begin(), ps.end(), std::greater<int>());
+    int min_period = 0;
+    for (int p : ps) if (p > 0 && (min_period == 0 || p < min_period)) min_period = p;
+    double *d_y = nullptr, *d_trend = nullptr, *d_seas = nullptr, *d_rem = nullptr;
+    int32_t *d_len = nullptr, *d_info = nullptr;
+    // quiesced: on the success path the device entry has waited for its stream and the copies are synchronous; after a failure
+    // the first free waits for the device
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_trend, (void *)d_seas, (void *)d_rem, (void *)d_len, (void *)d_info}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<int32_t> info(n_series);
+    std::vector<double> trend, seas, rem;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        // time-major block; a NULL counts as 0.0, as the reference's table function passes it (ts_mstl_decomposition_native.cpp:215)
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<int32_t> len(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            const uint64_t *m = validity ? validity[s] : nullptr;
+            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = (m && !((m[t >> 6] >> (t & 63)) & 1)) ? 0.0 : values[s][t];
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld); d_info = dalloc<int32_t>(ld);
+        d_trend = dalloc<double>(T * ld); d_rem = dalloc<double>(T * ld); d_seas = dalloc<double>(std::max<size_t>(K, 1) * T * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!anofox_hip_mstl_decompose_device(d_y, ld, d_len, n_series, T, ps.data(), K, insufficient_data_mode, d_trend, d_seas, d_rem,
+                                              d_info, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        trend.resize(T * ld); rem.resize(T * ld); seas.resize(K * T * ld);
+        HIPCHECK(hipMemcpy(info.data(), d_info, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(trend.data(), d_trend, T * ld * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(rem.data(), d_rem, T * ld * sizeof(double), hipMemcpyDeviceToHost));
+        if (K) HIPCHECK(hipMemcpy(seas.data(), d_seas, K * T * ld * sizeof(double), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    // series i owns [off_i, off_i + lengths[i]) of every output; seasonal slot j holds the j-th component the series got
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    size_t off = 0;
+    for (size_t s = 0; s < n_series; s++) {
+        const size_t n = lengths[s];
+        const int state = info[s] >> 8, used = info[s] & 0xff;
+        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        const bool applied = state == MSTL_APPLIED || state == MSTL_TREND_ONLY;
+        out_applied[s] = applied ? 1 : 0;
+        if (state == MSTL_FAILED && out_errors)
+            set_error(&out_errors[s], COMPUTATION_ERROR, "Insufficient data: need at least " + std::to_string(n == 0 ? 1LL : 2LL * min_period) +
+                                                             " observations, got " + std::to_string(n));
+        for (size_t t = 0; t < n; t++) {
+            out_trend[off + t] = applied ? trend[t * ld + s] : nan;
+            out_remainder[off + t] = applied ? rem[t * ld + s] : nan;
+        }
+        size_t j = 0;
+        for (size_t k = 0; k < K; k++) {
+            if (!(state == MSTL_APPLIED && ((used >> k) & 1))) continue;
+            for (size_t t = 0; t < n; t++) out_seasonal[j * total + off + t] = seas[(k * T + t) * ld + s];
+            if (out_periods) out_periods[s * K + j] = ps[k];
+            j++;
+        }
+        for (size_t jj = j; jj < K; jj++) {
+            for (size_t t = 0; t < n; t++) out_seasonal[jj * total + off + t] = nan;
+            if (out_periods) out_periods[s * K + jj] = 0;
+        }
+        off += n;
+    }
+    return true;
+}
+
+bool anofox_ts_mstl_decomposition(const double *values, size_t length, const int *periods, size_t n_periods, int insufficient_data_mode,
+                                  MstlResult *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const size_t K = (periods && n_periods) ? n_periods : 0;        // (lib.rs: a NULL list is no periods)
+    std::vector<double> tr(std::max<size_t>(length, 1)), rm(std::max<size_t>(length, 1)), se(std::max<size_t>(K * length, 1));
+    std::vector<int32_t> per(std::max<size_t>(K, 1), 0);
+    int32_t applied = 0;
+    AnofoxError serr, berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    if (!anofox_hip_mstl_decompose_batch(v, nullptr, len, 1, K ? periods : nullptr, K, insufficient_data_mode, tr.data(), se.data(), rm.data(),
+                                         per.data(), &applied, &serr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
+    std::memset(out_result, 0, sizeof *out_result);
+    out_result->decomposition_applied = applied != 0;
+    out_result->n_observations = length;
+    if (!applied) return true;
+    auto copy = [&](const double *src) -> double * {
+        double *p = (double *)std::malloc(std::max<size_t>(length, 1) * sizeof(double));
+        if (p && length) std::memcpy(p, src, length * sizeof(double));
+        return p;
+    };
+    size_t ns = 0;
+    while (ns < K && per[ns] != 0) ns++;
+    bool ok = (out_result->trend = copy(tr.data())) && (out_result->remainder = copy(rm.data()));
+    if (ok && ns) {
+        out_result->seasonal_periods = (int *)std::malloc(ns * sizeof(int));
+        out_result->seasonal_components = (double **)std::calloc(ns, sizeof(double *));
+        ok = out_result->seasonal_periods && out_result->seasonal_components;
+        for (size_t j = 0; ok && j < ns; j++) {
+            out_result->seasonal_periods[j] = per[j];
+            ok = (out_result->seasonal_components[j] = copy(se.data() + j * length)) != nullptr;
+        }
+        out_result->n_seasonal = ns;
+    }
+    if (!ok) {
+        anofox_free_mstl_result(out_result);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate MSTL result");
+        return false;
+    }
+    return true;
+}
+
+void anofox_free_mstl_result(MstlResult *result)
+{
+    if (!result) return;
+    std::free(result->trend);
+    std::free(result->remainder);
+    if (result->seasonal_components)
+        for (size_t j = 0; j < result->n_seasonal; j++) std::free(result->seasonal_components[j]);
+    std::free(result->seasonal_components);
+    std::free(result->seasonal_periods);
+    result->trend = result->remainder = nullptr;
+    result->seasonal_components = nullptr;
+    result->seasonal_periods = nullptr;
+    result->n_seasonal = 0;
 }
 
 } // extern "C"

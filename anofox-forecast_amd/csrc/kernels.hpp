@@ -185,6 +185,27 @@ struct ThetaArgs {
 };
 void launch_theta(const ThetaArgs &, hipStream_t);
 
+// MSTL decomposition and SeasonalWindowAverage (fit_mstl.hip)
+constexpr int MSTL_MAX_PERIODS = 8;      // periods per call; more fail loudly (COMPUTATION_ERROR)
+enum MstlMode { MSTL_MODE_FAIL = 0, MSTL_MODE_TREND = 1, MSTL_MODE_NONE = 2 };     // decomposition.rs InsufficientDataMode::from_int
+enum MstlState { MSTL_APPLIED = 0, MSTL_TREND_ONLY = 1, MSTL_NOT_APPLIED = 2, MSTL_FAILED = 3 };
+struct MstlArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // rows of the output blocks
+    int mode, min_period;        // insufficient_data_mode; smallest period > 0 of the call (0: none)
+    int n_periods;               // <= MSTL_MAX_PERIODS, in descending order
+    int periods[MSTL_MAX_PERIODS];
+    int tab_off[MSTL_MAX_PERIODS];   // first row of period k's phase table in `tab`
+    double *tab;                 // [sum of periods x ld] phase means avg_k
+    double *mean;                // [MSTL_MAX_PERIODS x ld] mean of the periodic component of stage k
+    int32_t *used;               // [ld] bit k: stage k ran for the series
+    double *trend, *remainder;   // [t_rows x ld]
+    double *seasonal;            // [n_periods x t_rows x ld], slot k = stage k (NaN where it did not run)
+    int32_t *info;               // [ld] MstlState << 8 | used
+};
+void launch_mstl(const MstlArgs &, hipStream_t);      // one mstl_season_kernel per period, then mstl_final_kernel
+void launch_swa(const SimpleArgs &, hipStream_t);     // SeasonalWindowAverage point forecasts
+
 struct IntervalArgs {
     int n_series, h;
     const double *yhat, *sd;

@@ -91,6 +91,18 @@ class AnofoxHipLaneStats(C.Structure):
 
 assert C.sizeof(ForecastOptions) == 184 and C.sizeof(ForecastResult) == 144 and C.sizeof(AnofoxError) == 260
 
+class MstlResult(C.Structure):
+    _fields_ = [
+        ("trend", C.POINTER(C.c_double)),
+        ("seasonal_components", C.POINTER(C.POINTER(C.c_double))),
+        ("remainder", C.POINTER(C.c_double)),
+        ("n_observations", C.c_size_t),
+        ("n_seasonal", C.c_size_t),
+        ("seasonal_periods", C.POINTER(C.c_int)),
+        ("decomposition_applied", C.c_bool),
+    ]
+
+
 # every symbol include/anofox_fcst_hip.h declares
 class AnofoxHipInspection(C.Structure):
     _fields_ = [("model_code", C.c_int32), ("status", C.c_int32), ("seasonal_period", C.c_int32), ("reserved", C.c_int32),
@@ -111,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_set_devices", "anofox_hip_get_devices", "anofox_hip_set_min_series_per_device", "anofox_hip_shard_range",
     "anofox_hip_set_default_arima_method", "anofox_hip_batch_set_arima_method", "anofox_hip_release_caches",
     "anofox_hip_batch_run_many", "anofox_hip_batch_lane_stats", "anofox_hip_selftest_recip",
+    "anofox_ts_mstl_decomposition", "anofox_free_mstl_result", "anofox_hip_mstl_decompose_batch", "anofox_hip_mstl_decompose_device",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -189,6 +202,15 @@ def load():
     L.anofox_hip_release_caches.argtypes = []
     L.anofox_hip_batch_run_many.restype = C.c_bool
     L.anofox_hip_batch_run_many.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    L.anofox_ts_mstl_decomposition.restype = C.c_bool
+    L.anofox_ts_mstl_decomposition.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, P(MstlResult), P(AnofoxError)]
+    L.anofox_free_mstl_result.argtypes = [P(MstlResult)]
+    L.anofox_hip_mstl_decompose_batch.restype = C.c_bool
+    L.anofox_hip_mstl_decompose_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_mstl_decompose_device.restype = C.c_bool
+    L.anofox_hip_mstl_decompose_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

@@ -103,6 +103,35 @@ void anofox_free_forecast_result(struct ForecastResult *result);
 
 const char *anofox_fcst_version(void);
 
+/*
+ * MSTL decomposition result (layout of the reference's anofox_fcst_ffi.h).  The arrays are malloc()ed by the callee and
+ * released by anofox_free_mstl_result; they are NULL when the decomposition was not applied.
+ */
+typedef struct MstlResult {
+    double *trend;                 /* [n_observations] */
+    double **seasonal_components;  /* [n_seasonal] arrays of n_observations */
+    double *remainder;             /* [n_observations] */
+    size_t n_observations;
+    size_t n_seasonal;
+    int *seasonal_periods;         /* [n_seasonal], longest first */
+    bool decomposition_applied;
+} MstlResult;
+
+/*
+ * MSTL decomposition of ONE series (the reference's moving-average MSTL: periods handled longest first, a period p is used
+ * when p >= 2 and length >= 2p).  insufficient_data_mode: 0 = fail (COMPUTATION_ERROR when length < 2 * the smallest period),
+ * 1 = trend only, 2 = not applied.  At most 8 periods (more: COMPUTATION_ERROR).  Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_mstl_decomposition(const double *values,
+                                  size_t length,
+                                  const int *periods,
+                                  size_t n_periods,
+                                  int insufficient_data_mode,
+                                  struct MstlResult *out_result,
+                                  struct AnofoxError *out_error);
+
+void anofox_free_mstl_result(struct MstlResult *result);
+
 #endif /* ANOFOX_FCST_FFI_H */
 
 /* ------------------------------------------------------------------------- */
@@ -129,6 +158,53 @@ bool anofox_ts_forecast_batch(const double *const *values,
                               struct ForecastResult *out_results,
                               struct AnofoxError *out_errors,
                               struct AnofoxError *out_batch_error);
+
+/*
+ * MSTL decomposition of `n_series` series with one shared period list, in one GPU pass (same semantics as
+ * anofox_ts_mstl_decomposition per series).  `validity` may be NULL; a NULL value counts as 0.0, as the reference's
+ * ts_mstl_decomposition table function passes it.  With total = the sum of `lengths`, series i owns the range
+ * [off_i, off_i + lengths[i]) of out_trend[total], out_remainder[total] and of each slot j of out_seasonal[n_periods * total]
+ * (slot j = the j-th component the series got, longest period first); out_periods[i * n_periods + j] names the period of slot j
+ * (0: unused slot, filled with NaN).  out_applied[i] = 1 when the decomposition was applied (trend and remainder written,
+ * NaN otherwise).  Per-series failures (mode 0 and too short) land in out_errors[i] (may be NULL); the return value is false
+ * only for batch-level failures (NULL pointers, more than 8 periods, no GPU), also reported through `out_batch_error`.
+ */
+bool anofox_hip_mstl_decompose_batch(const double *const *values,
+                                     const uint64_t *const *validity,
+                                     const size_t *lengths,
+                                     size_t n_series,
+                                     const int *periods,
+                                     size_t n_periods,
+                                     int insufficient_data_mode,
+                                     double *out_trend,
+                                     double *out_seasonal,
+                                     double *out_remainder,
+                                     int32_t *out_periods,
+                                     int32_t *out_applied,
+                                     struct AnofoxError *out_errors,
+                                     struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows), lengths[n_series] (int32) and the outputs
+ * are device pointers.  trend / remainder are [t_rows x ld], seasonal is [n_periods x t_rows x ld] with slot k = the k-th
+ * period of the list sorted longest first (NaN where the series did not use it); info[s] = state << 8 | used, state 0 =
+ * decomposed, 1 = trend only, 2 = not applied, 3 = failed (mode 0, too short), bit k of `used` = period k was used.  Rows
+ * t >= lengths[s] are left untouched.  Runs on `stream` (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_mstl_decompose_device(const double *y,
+                                      size_t ld,
+                                      const int32_t *lengths,
+                                      size_t n_series,
+                                      size_t t_rows,
+                                      const int *periods,
+                                      size_t n_periods,
+                                      int insufficient_data_mode,
+                                      double *trend,
+                                      double *seasonal,
+                                      double *remainder,
+                                      int32_t *info,
+                                      void *stream,
+                                      struct AnofoxError *out_error);
 
 /*
  * Multi-device execution of the batch entry.  The reference's finalize loop is ONE process walking all groups
