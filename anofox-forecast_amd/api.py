@@ -720,6 +720,218 @@ def ts_mstl_decomposition_by(group, date, target, periods=(), insufficient_data=
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# exogenous regressors (ARIMAX): anofox_ts_forecast_exog_batch and the mirrors of _ts_forecast_exog / ts_forecast_exog_by
+# --------------------------------------------------------------------------------------------
+def forecast_exog_batch(series, xregs, futures, opts, valids=None):
+    """anofox_ts_forecast_exog_batch over host buffers: xregs[s] / futures[s] are the K historical / future regressor arrays of
+    series s (K shared by the batch; lengths len(series[s]) and opts.horizon).  Returns (results, batch_error); a result that
+    took the ARIMAX path also carries "intercept", "beta" [K] (0.0 where a regressor was left out) and "used" [K]."""
+    L = _lib.load()
+    n = len(series)
+    h = int(opts.horizon)
+    K = len(xregs[0]) if n else 0
+    arrs = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    xs, fs = [], []
+    for s in range(n):
+        if len(xregs[s]) != K or len(futures[s]) != K:
+            raise InvalidInputException("every series of an exogenous batch takes the same number of regressors")
+        for j in range(K):
+            x = np.ascontiguousarray(xregs[s][j], dtype=np.float64)
+            f = np.ascontiguousarray(futures[s][j], dtype=np.float64)
+            if len(x) != len(arrs[s]):
+                raise InvalidInputException(f"Exogenous regressor {j} has {len(x)} values but y has {len(arrs[s])} values")
+            if len(f) != h:
+                raise InvalidInputException(f"Exogenous regressor {j} has {len(f)} future values but horizon is {h}")
+            xs.append(x)
+            fs.append(f)
+    masks = [validity_mask(v) if v is not None else None for v in valids] if valids is not None else None
+    vptr = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else _EMPTY_SERIES_ADDR for a in arrs])
+    mptr = None
+    if masks is not None:
+        mptr = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in masks])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+    xptr = (C.c_void_p * max(n * K, 1))(*[x.ctypes.data if len(x) else _EMPTY_SERIES_ADDR for x in xs])
+    fptr = (C.c_void_p * max(n * K, 1))(*[f.ctypes.data if len(f) else _EMPTY_SERIES_ADDR for f in fs])
+    results = (_lib.ForecastResult * max(n, 1))()
+    errors = (_lib.AnofoxError * max(n, 1))()
+    berr = _lib.AnofoxError()
+    coef = np.full((max(n, 1), K + 1), np.nan)
+    used = np.zeros(max(n, 1), dtype=np.uint32)
+    ok = L.anofox_ts_forecast_exog_batch(vptr, mptr, lens, n, C.byref(opts), K, xptr, fptr, results, errors, C.byref(berr),
+                                         coef.ctypes.data, used.ctypes.data)
+    out = []
+    for i in range(n):
+        failed = errors[i].code != 0 or not ok
+        e = errors[i] if errors[i].code != 0 or ok else berr
+        d = {"ok": not failed, "code": int(e.code), "message": e.message.decode(errors="replace")}
+        if d["ok"]:
+            d.update(_result_dict(results[i], len(arrs[i])))
+            if d["model_name"] == "ARIMAX":
+                d["intercept"] = float(coef[i, 0])
+                d["beta"] = coef[i, 1:].copy()
+                d["used"] = ((int(used[i]) >> np.arange(K)) & 1).astype(bool)
+        L.anofox_free_forecast_result(C.byref(results[i]))
+        out.append(d)
+    return out, {"ok": bool(ok), "code": int(berr.code), "message": berr.message.decode(errors="replace")}
+
+
+def forecast_series_exog(values, xreg, future_xreg, opts, valid=None) -> dict:
+    """anofox_ts_forecast_exog: one series with its regressors (lists of arrays); lengths are passed as they are, so the entry's own
+    length checks answer.  `opts` is a ForecastOptions block."""
+    L = _lib.load()
+    y = np.ascontiguousarray(values, dtype=np.float64)
+    K = min(len(xreg), len(future_xreg))
+    xs = [np.ascontiguousarray(c, dtype=np.float64) for c in xreg[:K]]
+    fs = [np.ascontiguousarray(c, dtype=np.float64) for c in future_xreg[:K]]
+    regs = (_lib.ExogenousRegressor * max(K, 1))()
+    for j in range(K):
+        regs[j].values = C.cast(C.c_void_p(xs[j].ctypes.data if len(xs[j]) else _EMPTY_SERIES_ADDR), C.POINTER(C.c_double))
+        regs[j].n_values = len(xs[j])
+        regs[j].future_values = C.cast(C.c_void_p(fs[j].ctypes.data if len(fs[j]) else _EMPTY_SERIES_ADDR), C.POINTER(C.c_double))
+        regs[j].n_future = len(fs[j])
+    data = _lib.ExogenousData()
+    data.regressors = C.cast(regs, C.POINTER(_lib.ExogenousRegressor))
+    data.n_regressors = K
+    eo = _lib.make_options_exog(opts, data if K else None)     # (ts_forecast.cpp:306: no regressors -> a NULL exog pointer)
+    res = _lib.ForecastResult()
+    C.memset(C.byref(res), 0, C.sizeof(res))
+    err = _lib.AnofoxError()
+    mask = validity_mask(valid) if valid is not None else None
+    ok = L.anofox_ts_forecast_exog(y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR, mask.ctypes.data if mask is not None else None, len(y),
+                                   C.byref(eo), C.byref(res), C.byref(err))
+    out = {"ok": bool(ok), "code": int(err.code), "message": err.message.decode(errors="replace")}
+    if ok:
+        out.update(_result_dict(res, len(y)))
+        L.anofox_free_forecast_result(C.byref(res))
+    return out
+
+
+def _exog_cells(col):
+    """A regressor list as _ts_forecast_exog reads it: NULL (None / masked) cells become 0.0 (ts_forecast.cpp:219)."""
+    if np.ma.isMaskedArray(col):
+        return np.where(np.ma.getmaskarray(col), 0.0, np.ma.getdata(col).astype(np.float64))
+    return np.array([0.0 if v is None else float(v) for v in col], dtype=np.float64)
+
+
+def _exog_scalar_options(model, horizon):
+    # ts_forecast.cpp:294-306: confidence 0.95, no period and no detection, fitted values and residuals on
+    return _lib.make_options(str(model), int(horizon), confidence_level=0.95, seasonal_period=0, auto_detect=False,
+                             include_fitted=True, include_residuals=True)
+
+
+def ts_forecast_exog(values, xreg, future_xreg, horizon=12, model="AutoARIMA"):
+    """_ts_forecast_exog(values, xreg, future_xreg, horizon, model) (src/table_functions/ts_forecast.cpp:226-338): the regressors
+    are the first min(len(xreg), len(future_xreg)) pairs, NULL cells of a regressor are 0.0, NULL values of the series are
+    interpolated.  Returns the struct as a dict (point, lower, upper, fitted, residuals, model, aic, bic, mse), or None where the
+    scalar returns NULL (a NULL list, or any failure)."""
+    if values is None:
+        return None
+    vals = list(values)
+    valid = np.array([v is not None for v in vals], dtype=bool)
+    y = np.array([0.0 if v is None else float(v) for v in vals], dtype=np.float64)
+    xs = [_exog_cells(c) for c in (xreg or [])]
+    fs = [_exog_cells(c) for c in (future_xreg or [])]
+    r = forecast_series_exog(y, xs, fs, _exog_scalar_options(model, horizon), None if valid.all() else valid)
+    if not r["ok"]:
+        return None
+    return {"point": r["point"], "lower": r["lower"], "upper": r["upper"], "fitted": r.get("fitted", np.empty(0)),
+            "residuals": r.get("residuals", np.empty(0)), "model": r["model_name"], "aic": r["aic"], "bic": r["bic"], "mse": r["mse"]}
+
+
+def ts_forecast_exog_by(group, date, target, xregs, future_group, future_date, future_xregs, frequency, method="AutoARIMA",
+                        horizon=12, params=None):
+    """ts_forecast_exog_by(source, group_col, date_col, target_col, xreg_cols, future_source, future_date_col, future_xreg_cols,
+    frequency, method, horizon, params) (src/macros/ts_macros.cpp:827-935).  `xregs` / `future_xregs` map column names to columns
+    of the source / future table.  Per group the target and every regressor are listed in date order; the regressor lists are
+    ordered BY COLUMN NAME on each side and paired by position (the first min(len, len) pairs); a group absent from the future
+    table has no regressors and runs the ordinary model.  The groups with regressors go to ONE anofox_ts_forecast_exog_batch call,
+    the others to one anofox_ts_forecast_batch call.  A group whose call fails (a future list that is not `horizon` long, a model
+    that is not implemented, ...) yields no rows, as the NULL struct of the scalar does.  `params` is accepted and ignored, as
+    in the macro.  Dates: the group's last date as a TIMESTAMP truncated to seconds, plus step x the interval; frequencies of
+    fixed length only ('30m', '1h', '1d', '1w', '1 day', ..., a bare integer counts days).  Calendar frequencies ('1mo', '1q',
+    '1y') raise: the macro's series ends at last + n x EXTRACT(EPOCH FROM interval) seconds, which counts a month as 30 days, so it
+    produces fewer dates than forecasts for most months -- not a behaviour to reproduce silently.
+    Returns the macro's columns id, forecast_step, date, yhat, yhat_lower, yhat_upper, model_name, ordered by id, forecast_step."""
+    f = parse_frequency(frequency)
+    if f.type != "FIXED":
+        raise InvalidInputException(
+            f"ts_forecast_exog_by: calendar frequency '{frequency}' is not supported: the reference macro ends its date series at "
+            "last_date + n * EXTRACT(EPOCH FROM interval) seconds (a month counts 30 days), which yields fewer dates than forecasts")
+    step_us = (f.seconds * 86400 if f.is_raw else f.seconds) * 1000000
+    dates = np.asarray(date)
+    kind = _date_kind(dates)
+    if kind not in ("DATE", "TIMESTAMP"):
+        raise InvalidInputException("ts_forecast_exog_by: the date column must be DATE or TIMESTAMP (the macro casts it to TIMESTAMP)")
+    us = _to_micros(dates, kind)
+    grp = np.asarray(group, dtype=object)
+    tgt = np.asarray(target, dtype=object)
+    h = int(horizon)
+    xnames = sorted(xregs)                          # LIST(values ORDER BY col_name)
+    fnames = sorted(future_xregs)
+    xcols = {k: np.asarray(xregs[k], dtype=object) for k in xnames}
+    fcols = {k: np.asarray(future_xregs[k], dtype=object) for k in fnames}
+    rows = {}
+    for i in range(len(grp)):
+        rows.setdefault(grp[i], []).append(i)
+    fgrp = np.asarray(future_group, dtype=object)
+    fdates = np.asarray(future_date)
+    fus = _to_micros(fdates, _date_kind(fdates)) if len(fdates) else np.zeros(0, dtype=np.int64)
+    frows = {}
+    for i in range(len(fgrp)):
+        frows.setdefault(fgrp[i], []).append(i)
+    keys = sorted((k for k in rows if k is not None), key=lambda k: (str(type(k)), k)) + ([None] if None in rows else [])
+    n_pairs = min(len(xnames), len(fnames))
+    with_x, without_x = [], []
+    for k in keys:
+        idx = np.array(rows[k])
+        idx = idx[np.argsort(us[idx], kind="stable")]
+        ok = np.array([tgt[i] is not None and not (isinstance(tgt[i], float) and tgt[i] != tgt[i]) for i in idx])
+        y = np.array([float(tgt[i]) if o else 0.0 for i, o in zip(idx, ok)])
+        last = int(us[idx].max()) // 1000000 * 1000000                # date_trunc('second', MAX(date)::TIMESTAMP)
+        rec = {"key": k, "y": y, "valid": None if ok.all() else ok, "last": last}
+        if k is not None and k in frows and n_pairs > 0:               # (a NULL group never joins)
+            fidx = np.array(frows[k])
+            fidx = fidx[np.argsort(fus[fidx], kind="stable")]
+            rec["x"] = [_exog_cells(xcols[c][idx]) for c in xnames[:n_pairs]]
+            rec["f"] = [_exog_cells(fcols[c][fidx]) for c in fnames[:n_pairs]]
+            if any(len(c) != h for c in rec["f"]):
+                continue                                                # INVALID_INPUT in the scalar: a NULL struct, no rows
+            with_x.append(rec)
+        else:
+            without_x.append(rec)
+    opts = _exog_scalar_options(method, h)
+    if with_x:
+        res, _ = forecast_exog_batch([r["y"] for r in with_x], [r["x"] for r in with_x], [r["f"] for r in with_x], opts,
+                                     [r["valid"] for r in with_x])
+        for r, q in zip(with_x, res):
+            r["res"] = q
+    if without_x:
+        res, _ = forecast_batch([r["y"] for r in without_x], opts, [r["valid"] for r in without_x])
+        for r, q in zip(without_x, res):
+            r["res"] = q
+    by_key = {r["key"]: r for r in with_x + without_x}
+    out = {"id": [], "forecast_step": [], "date": [], "yhat": [], "yhat_lower": [], "yhat_upper": [], "model_name": []}
+    for k in keys:
+        r = by_key.get(k)
+        if r is None or not r["res"]["ok"]:
+            continue
+        q = r["res"]
+        for i in range(len(q["point"])):
+            out["id"].append(k)
+            out["forecast_step"].append(i + 1)
+            out["date"].append(r["last"] + (i + 1) * step_us)
+            out["yhat"].append(q["point"][i])
+            out["yhat_lower"].append(q["lower"][i])
+            out["yhat_upper"].append(q["upper"][i])
+            out["model_name"].append(q["model_name"])
+    out["forecast_step"] = np.array(out["forecast_step"], dtype=np.int32)
+    out["date"] = np.array(out["date"], dtype=np.int64).astype("datetime64[us]")
+    for c in ("yhat", "yhat_lower", "yhat_upper"):
+        out[c] = np.array(out[c], dtype=np.float64)
+    return out
+
+
 def ts_forecast_inspect_by(group, date, target, method, params=None):
     """ts_forecast_inspect_by(source, group_col, date_col, target_col, method, params := MAP{}) (ts_macros.cpp:596-672,
     forecast.rs:1739-1885).  Supported here: AutoETS (model_family 'Ets') and AutoARIMA ('Arima'); a method outside the

@@ -191,6 +191,13 @@ struct AnofoxHipBatch {
     double *d_th_sidx = nullptr;
     size_t th_sidx_elems = 0;
     int32_t *d_th_adj = nullptr;
+    // exogenous regressors (fit_exog.hip): the historical block [k x t_max x ld] and the future block [k x h x ld], adopted from the
+    // caller (anofox_hip_batch_set_exog_device) or owned (the host batch entry), and the per-series intercept, coefficients and used mask
+    int exog_k = 0;
+    const double *d_exog_x = nullptr, *d_exog_f = nullptr;
+    bool owns_exog = false;
+    double *d_exog_b0 = nullptr, *d_exog_beta = nullptr;
+    uint32_t *d_exog_used = nullptr;
 };
 
 namespace {
@@ -338,6 +345,9 @@ void free_batch_buffers(AnofoxHipBatch *b)
     if (b->ev_group_tab) { (void)hipEventDestroy(b->ev_group_tab); b->ev_group_tab = nullptr; }
     F(b->d_im_level); F(b->d_im_gmax); F(b->d_im_fc);
     F(b->d_th_sidx); F(b->d_th_adj);
+    if (b->owns_exog) { F((void *)b->d_exog_x); F((void *)b->d_exog_f); }
+    b->d_exog_x = b->d_exog_f = nullptr; b->owns_exog = false; b->exog_k = 0;
+    F(b->d_exog_b0); F(b->d_exog_beta); F(b->d_exog_used);
     F(b->d_passes_total); F(b->d_evals_total); F(b->d_mask); F(b->d_len_group); F(b->d_count); F(b->d_pos_map); F(b->d_pos_cnt); F(b->d_notpos); F(b->d_ypos);
     F(b->ar_w); F(b->ar_wmean); F(b->ar_wsd); F(b->ar_l0); F(b->ar_l1); F(b->ar_x); F(b->ar_aicc); F(b->ar_wlen); F(b->ar_d); F(b->ar_D);
     F(b->ar_order); F(b->ar_status); F(b->ar_evals); F(b->ar_passes); F(b->ar_models);
@@ -1506,6 +1516,28 @@ void run_theta(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t 
     b->n_problems += b->n;
 }
 
+// the regressors take part for ARIMA / AutoARIMA only (forecast.rs forecast_with_exog: every other model ignores them)
+bool exog_in_force(const AnofoxHipBatch *b) { return b->exog_k > 0 && (b->plan.model == M_ARIMA || b->plan.model == M_AutoARIMA); }
+
+// ARIMAX: one kernel per batch (three sweeps per series); the per-series coefficient buffers are allocated by the first run
+void run_exog(AnofoxHipBatch *b, const int32_t *d_len, hipStream_t st)
+{
+    if (!b->d_exog_b0) {
+        b->d_exog_b0 = dalloc<double>(b->ld);
+        b->d_exog_beta = dalloc<double>((size_t)EXOG_MAX_REGRESSORS * b->ld);
+        b->d_exog_used = dalloc<uint32_t>(b->ld);
+    }
+    ExogArgs a{};
+    a.y = b->d_y; a.ld = b->ld; a.len = d_len; a.n_series = (int)b->n;
+    a.k = b->exog_k; a.h = b->h; a.t_rows = std::max<size_t>(b->t_max, 1);
+    a.x = b->d_exog_x; a.f = b->d_exog_f;
+    a.yhat = b->d_yhat; a.status = b->d_status; a.model_code = b->d_model_code;
+    a.b0 = b->d_exog_b0; a.beta = b->d_exog_beta; a.used = b->d_exog_used;
+    try { launch_exog_arimax(a, st); }
+    catch (const std::exception &e) { throw HipFail{e.what()}; }
+    b->n_problems += b->n;
+}
+
 void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t st)
 {
     const Plan &p = b->plan;
@@ -1544,6 +1576,12 @@ void run_group(AnofoxHipBatch *b, int period, const int32_t *d_len, hipStream_t 
 
     // A period the kernels cannot hold fails the group's series loudly (COMPUTATION_ERROR naming the cap) -- never a silent
     // non-seasonal fit.  The reference takes any period (forecast.rs:528-537); 2,048 covers every calendar period.
+    if (exog_in_force(b)) {              // ARIMAX: the intervals' mean / sd come from y, as for every model
+        prep(1, false);
+        run_exog(b, d_len, st);
+        LAUNCHCHECK("ARIMAX");
+        return;
+    }
     const bool uses_period = p.model == M_AutoETS || p.model == M_HoltWinters || p.model == M_SeasonalES || p.model == M_SeasonalESOptimized || is_theta_model(p.model) ||
                              (p.model == M_ETS && (p.ets_spec_id < 0 || spec_season(p.ets_spec_id) != 0));
     const bool arima_period = p.model == M_AutoARIMA && period > ETS_MAX_PERIOD;      // seasonal ARIMA terms: LDS rings up to m = 24, an HBM scratch ring up to 2,048
@@ -1764,6 +1802,7 @@ void run_batch(AnofoxHipBatch *b, hipStream_t st)
         case M_Naive: case M_RandomWalkDrift: case M_ARIMA: case M_SES: case M_SESOptimized: case M_Holt: return 1;
         case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: return 1;
         case M_AutoARIMA:
+            if (exog_in_force(b)) return 1;      // ARIMAX is not the seasonal search
             // a DETECTED period goes to the seasonal search exactly like an explicit one (forecast.rs:528-537 hands it to
             // forecast_auto_arima, :1448-1452 passes any period > 1 to with_seasonal_period): used up to 2,048 (rings in LDS up to
             // 24, in HBM scratch above), failing loudly beyond.  Rounds 2-3 made detected periods above 24 non-seasonal -- a
@@ -2352,6 +2391,7 @@ void anofox_hip_model_name(const ForecastOptions *options, int32_t model_code, c
     out_name[0] = 0;
     if (model_code >= 1000000) { auto_arima_name(model_code, options ? options->seasonal_period : 1, out_name); return; }
     if (model_code >= 100 && model_code < 130) { auto_ets_name(model_code - 100, out_name); return; }
+    if (model_code == MODEL_CODE_ARIMAX) { std::snprintf(out_name, 64, "ARIMAX"); return; }
     Plan p;
     AnofoxError e;
     if (options && make_plan(options, p, &e)) {
@@ -2428,6 +2468,7 @@ bool anofox_hip_batch_fetch(AnofoxHipBatch *b, ForecastResult *out_results, Anof
         }
         if (code[s] >= 1000000) auto_arima_name(code[s], b->h_period[s], r.model_name);
         else if (code[s] >= 100) auto_ets_name(code[s] - 100, r.model_name);
+        else if (code[s] == MODEL_CODE_ARIMAX) std::snprintf(r.model_name, 64, "ARIMAX");
         else std::snprintf(r.model_name, 64, "%s", b->plan.static_name.c_str());
         r.aic = std::nan(""); r.bic = std::nan(""); r.mse = std::nan("");
         if ((b->opt.include_fitted || b->opt.include_residuals) && !b->h_clean_off.empty()) {
@@ -3547,6 +3588,303 @@ void anofox_free_mstl_result(MstlResult *result)
     result->seasonal_components = nullptr;
     result->seasonal_periods = nullptr;
     result->n_seasonal = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Exogenous regressors: ARIMAX (forecast.rs forecast_with_exog; fit_exog.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+} // extern "C"
+
+namespace {
+
+// what forecast_with_exog does with a model when regressors are present (forecast.rs:803-840)
+enum ExogRoute { EXOG_IGNORED = 0, EXOG_ARIMAX = 1, EXOG_NOT_IMPLEMENTED = 2 };
+ExogRoute exog_route(ModelType m)
+{
+    switch (m) {
+    case M_ARIMA: case M_AutoARIMA: return EXOG_ARIMAX;
+    case M_OptimizedTheta: case M_DynamicTheta: case M_MFLES: case M_AutoMFLES: return EXOG_NOT_IMPLEMENTED;     // ThetaX / MFLESX: DESIGN section 7
+    default: return EXOG_IGNORED;
+    }
+}
+
+std::string exog_not_implemented_message(ModelType m)
+{
+    return std::string("Internal error: model '") + model_name(m) + "' with exogenous regressors (" +
+           ((m == M_MFLES || m == M_AutoMFLES) ? "MFLESX" : "ThetaX") + ") is not implemented by the HIP backend";
+}
+
+std::string exog_cap_message(size_t k)
+{
+    return "Computation error: ARIMAX takes at most " + std::to_string(EXOG_MAX_REGRESSORS) + " exogenous regressors, got " + std::to_string(k);
+}
+
+void clear_error(AnofoxError *e) { if (e) { e->code = SUCCESS; std::memset(e->message, 0, sizeof e->message); } }
+
+// host regressors -> the batch's own device blocks, through one pinned staging block per regressor slice (cells past a series' end: 0.0)
+void batch_pack_exog_host(AnofoxHipBatch *b, const double *const *xreg, const double *const *future_xreg, const size_t *lengths, size_t k)
+{
+    const size_t n = b->n, ld = b->ld, T = std::max<size_t>(b->t_max, 1), h = (size_t)std::max(b->h, 0);
+    double *d_x = dalloc<double>(k * T * ld), *d_f = nullptr;
+    void *stage = nullptr;
+    try {
+        d_f = dalloc<double>(k * h * ld);
+        stage = pin_alloc_bytes(std::max(T, k * h) * ld * sizeof(double));
+        double *st = (double *)stage;
+        batch_attach_streams(b);
+        unsigned n_thr = std::max(1u, std::min(std::thread::hardware_concurrency(), 16u));
+        if (tl_host_thread_share > 1) n_thr = std::max(1u, n_thr / tl_host_thread_share);
+        if (T * ld < (1u << 20)) n_thr = 1;
+        const size_t n_tiles = ld / 64;
+        for (size_t j = 0; j < k; j++) {
+            auto fill = [&](size_t tile0, size_t tile1) {
+                for (size_t tile = tile0; tile < tile1; tile++)
+                    for (size_t t = 0; t < T; t++) {
+                        double *row = st + t * ld + tile * 64;
+                        for (size_t c = 0; c < 64; c++) {
+                            const size_t s = tile * 64 + c;
+                            row[c] = (s < n && t < lengths[s]) ? xreg[s * k + j][t] : 0.0;
+                        }
+                    }
+            };
+            if (n_thr <= 1) fill(0, n_tiles);
+            else parallel_shares(n_thr, [&](unsigned q) { fill(n_tiles * q / n_thr, n_tiles * (q + 1) / n_thr); });
+            HIPCHECK(hipMemcpyAsync(d_x + j * T * ld, st, T * ld * sizeof(double), hipMemcpyHostToDevice, b->own_stream));
+            HIPCHECK(hipStreamSynchronize(b->own_stream));         // the staging block is refilled for the next regressor
+        }
+        if (h) {
+            for (size_t j = 0; j < k; j++)
+                for (size_t i = 0; i < h; i++)
+                    for (size_t s = 0; s < ld; s++) st[(j * h + i) * ld + s] = s < n ? future_xreg[s * k + j][i] : 0.0;
+            HIPCHECK(hipMemcpyAsync(d_f, st, k * h * ld * sizeof(double), hipMemcpyHostToDevice, b->own_stream));
+            HIPCHECK(hipStreamSynchronize(b->own_stream));
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(b->own_stream);
+        pin_free(stage);
+        dev_free(d_x); dev_free(d_f);
+        throw;
+    }
+    pin_free(stage);
+    if (b->owns_exog) { dev_free((void *)b->d_exog_x); dev_free((void *)b->d_exog_f); }
+    b->d_exog_x = d_x; b->d_exog_f = d_f; b->owns_exog = true; b->exog_k = (int)k;
+}
+
+} // namespace
+
+extern "C" {
+
+bool anofox_hip_batch_set_exog_device(AnofoxHipBatch *b, const void *d_x, const void *d_future, size_t k, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!b) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (k > 0 && (!d_x || (!d_future && b->h > 0))) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (k > (size_t)EXOG_MAX_REGRESSORS) { set_error(out_error, COMPUTATION_ERROR, exog_cap_message(k)); return false; }
+    DeviceGuard guard(b->dev);
+    if (b->owns_exog) {
+        // (a run that reads the owned blocks may still be in flight)
+        if (!b->quiesced && b->last_stream) (void)hipStreamSynchronize(b->last_stream);
+        dev_free((void *)b->d_exog_x); dev_free((void *)b->d_exog_f);
+        b->owns_exog = false;
+    }
+    b->d_exog_x = k ? (const double *)d_x : nullptr;
+    b->d_exog_f = k ? (const double *)d_future : nullptr;
+    b->exog_k = (int)k;
+    return true;
+}
+
+bool anofox_hip_batch_exog_coefficients(AnofoxHipBatch *b, double *out_intercept, double *out_beta, uint32_t *out_used, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!b) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!b->ran || !exog_in_force(b) || !b->d_exog_b0) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the batch's last run did not take the ARIMAX path");
+        return false;
+    }
+    DeviceGuard guard(b->dev);
+    try {
+        const size_t n = b->n, ld = b->ld, k = (size_t)b->exog_k;
+        HIPCHECK(hipStreamSynchronize(b->last_stream));
+        std::vector<int32_t> status(n);
+        HIPCHECK(hipMemcpy(status.data(), b->d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        if (out_intercept) {
+            HIPCHECK(hipMemcpy(out_intercept, b->d_exog_b0, n * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t s = 0; s < n; s++) if (status[s] != 0) out_intercept[s] = nan;
+        }
+        if (out_beta) {
+            std::vector<double> beta(k * ld);
+            HIPCHECK(hipMemcpy(beta.data(), b->d_exog_beta, k * ld * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t s = 0; s < n; s++)
+                for (size_t j = 0; j < k; j++) out_beta[s * k + j] = status[s] != 0 ? nan : beta[j * ld + s];
+        }
+        if (out_used) {
+            HIPCHECK(hipMemcpy(out_used, b->d_exog_used, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t s = 0; s < n; s++) if (status[s] != 0) out_used[s] = 0u;
+        }
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_ts_forecast_exog_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
+                                   const ForecastOptions *options, size_t n_regressors, const double *const *xreg,
+                                   const double *const *future_xreg, ForecastResult *out_results, AnofoxError *out_errors,
+                                   AnofoxError *out_batch_error, double *out_coefficients, uint32_t *out_used)
+{
+    clear_error(out_batch_error);
+    if (!values || !lengths || !options || !out_results) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+    ModelType mt = M_Naive;
+    {
+        const std::string mname = cstr_field(options->model, sizeof options->model);
+        if (!parse_model(mname, mt)) {
+            AnofoxError me;
+            set_error(&me, INVALID_MODEL, "Invalid model: Unknown model: '" + mname + "'");
+            if (out_batch_error) *out_batch_error = me;
+            for (size_t s = 0; s < n_series; s++) { std::memset(&out_results[s], 0, sizeof(ForecastResult)); if (out_errors) out_errors[s] = me; }
+            return false;
+        }
+    }
+    const size_t K = n_regressors;
+    const ExogRoute route = K == 0 ? EXOG_IGNORED : exog_route(mt);
+    // no regressors, or a model that ignores them: the ordinary batch path (forecast.rs:840-855)
+    if (route == EXOG_IGNORED) {
+        if (out_coefficients) for (size_t i = 0; i < n_series * (K + 1); i++) out_coefficients[i] = std::numeric_limits<double>::quiet_NaN();
+        if (out_used) for (size_t s = 0; s < n_series; s++) out_used[s] = 0u;
+        return anofox_ts_forecast_batch(values, validity, lengths, n_series, options, nullptr, out_results, out_errors, out_batch_error);
+    }
+    for (size_t s = 0; s < n_series; s++) {
+        std::memset(&out_results[s], 0, sizeof(ForecastResult));
+        clear_error(out_errors ? &out_errors[s] : nullptr);
+    }
+    auto fail_all = [&](int code, const std::string &msg) {
+        set_error(out_batch_error, code, msg);
+        if (out_errors)
+            for (size_t s = 0; s < n_series; s++) {
+                // the length checks come before the model's own (forecast.rs:780-789)
+                if (lengths[s] == 0) set_error(&out_errors[s], INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0");
+                else if (lengths[s] < 3) set_error(&out_errors[s], INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(lengths[s]));
+                else set_error(&out_errors[s], code, msg);
+            }
+        return false;
+    };
+    if (options->horizon < 0) return fail_all(PANIC_CAUGHT, "Panic in Rust code");
+    if (!xreg || (!future_xreg && options->horizon > 0)) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+    for (size_t s = 0; s < n_series; s++) {
+        if (!values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        for (size_t j = 0; j < K; j++)
+            if ((!xreg[s * K + j] && lengths[s] > 0) || (options->horizon > 0 && !future_xreg[s * K + j])) {
+                set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+                return false;
+            }
+    }
+    if (route == EXOG_NOT_IMPLEMENTED) return fail_all(INTERNAL_ERROR, exog_not_implemented_message(mt));
+    if (K > (size_t)EXOG_MAX_REGRESSORS) return fail_all(COMPUTATION_ERROR, exog_cap_message(K));
+    if (n_series == 0) return true;
+    // ARIMAX is the same for ARIMA and AutoARIMA (no search, no period), and so are their fitted values (forecast.rs:2593-2643): the
+    // batch is planned as ARIMA, which spares AutoARIMA's search workspace; forecast_with_model takes no seasonal_period check
+    ForecastOptions opt = *options;
+    std::memset(opt.model, 0, sizeof opt.model);
+    std::snprintf(opt.model, sizeof opt.model, "%s", "ARIMA");
+    opt.seasonal_period = 0;
+    opt.auto_detect_seasonality = false;
+    size_t t_max = 0;
+    for (size_t s = 0; s < n_series; s++) t_max = std::max(t_max, lengths[s]);
+    AnofoxHipBatch *b = nullptr;
+    AnofoxError e;
+    clear_error(&e);
+    if (!anofox_hip_batch_create(n_series, t_max, &opt, &b, &e)) return fail_all(e.code, e.message);
+    bool ok = anofox_hip_batch_pack_host(b, values, validity, lengths, &e);
+    if (ok) {
+        DeviceGuard guard(b->dev);
+        try { batch_pack_exog_host(b, xreg, future_xreg, lengths, K); }
+        catch (const HipFail &f) { report_hip_failure(&e, f); ok = false; }
+        catch (const std::exception &x) { set_error(&e, INTERNAL_ERROR, std::string("Internal error: ") + x.what()); ok = false; }
+    }
+    ok = ok && anofox_hip_batch_run(b, nullptr, &e);
+    ok = ok && anofox_hip_batch_fetch(b, out_results, out_errors);
+    if (ok && (out_coefficients || out_used)) {
+        std::vector<double> b0(n_series), beta(n_series * K);
+        ok = anofox_hip_batch_exog_coefficients(b, b0.data(), beta.data(), out_used, &e);
+        if (ok && out_coefficients)
+            for (size_t s = 0; s < n_series; s++) {
+                out_coefficients[s * (K + 1)] = b0[s];
+                for (size_t j = 0; j < K; j++) out_coefficients[s * (K + 1) + 1 + j] = beta[s * K + j];
+            }
+    }
+    anofox_hip_batch_destroy(b);
+    if (!ok) {
+        if (e.code == SUCCESS) set_error(&e, INTERNAL_ERROR, "Internal error: device batch failed");
+        if (out_batch_error) *out_batch_error = e;
+        return false;
+    }
+    return true;
+}
+
+bool anofox_ts_forecast_exog(const double *values, const uint64_t *validity, size_t length, const ForecastOptionsExog *options,
+                             ForecastResult *out_result, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!values || !options || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    // the order of the reference (lib.rs:3603-3668, forecast.rs:772-789): model name, regressor lengths, series length
+    const std::string mname = cstr_field(options->model, sizeof options->model);
+    ModelType mt;
+    if (!parse_model(mname, mt)) { set_error(out_error, INVALID_MODEL, "Invalid model: Unknown model: '" + mname + "'"); return false; }
+    if (options->horizon < 0) { set_error(out_error, PANIC_CAUGHT, "Panic in Rust code"); return false; }
+    size_t K = 0;
+    if (options->exog && options->exog->n_regressors > 0) {
+        K = options->exog->n_regressors;
+        if (!options->exog->regressors) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        for (size_t i = 0; i < K; i++) {
+            const ExogenousRegressor &r = options->exog->regressors[i];
+            if (r.n_values != length) {
+                set_error(out_error, INVALID_INPUT, "Invalid input: Exogenous regressor " + std::to_string(i) + " has " + std::to_string(r.n_values) +
+                                                        " values but y has " + std::to_string(length) + " values");
+                return false;
+            }
+            if (r.n_future != (size_t)options->horizon) {
+                set_error(out_error, INVALID_INPUT, "Invalid input: Exogenous regressor " + std::to_string(i) + " has " + std::to_string(r.n_future) +
+                                                        " future values but horizon is " + std::to_string(options->horizon));
+                return false;
+            }
+            if ((!r.values && r.n_values > 0) || (!r.future_values && r.n_future > 0)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        }
+    }
+    if (length == 0) { set_error(out_error, INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0"); return false; }
+    if (length < 3) { set_error(out_error, INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(length)); return false; }
+    ForecastOptions opt;
+    std::memset(&opt, 0, sizeof opt);
+    std::memcpy(opt.model, options->model, sizeof opt.model);
+    std::memcpy(opt.ets_model, options->ets_model, sizeof opt.ets_model);
+    opt.horizon = options->horizon; opt.confidence_level = options->confidence_level; opt.seasonal_period = options->seasonal_period;
+    opt.auto_detect_seasonality = options->auto_detect_seasonality; opt.include_fitted = options->include_fitted;
+    opt.include_residuals = options->include_residuals; opt.window = options->window;
+    std::memcpy(opt.seasonal_periods_str, options->seasonal_periods_str, sizeof opt.seasonal_periods_str);
+    std::memcpy(opt.model_pool, options->model_pool, sizeof opt.model_pool);
+    std::memcpy(opt.laplace_variant, options->laplace_variant, sizeof opt.laplace_variant);
+    opt.laplace_seasonal_batch_init = options->laplace_seasonal_batch_init;
+    const ExogRoute route = K == 0 ? EXOG_IGNORED : exog_route(mt);
+    if (route == EXOG_IGNORED) return anofox_ts_forecast(values, validity, length, &opt, out_result, out_error);
+    if (route == EXOG_NOT_IMPLEMENTED) { set_error(out_error, INTERNAL_ERROR, exog_not_implemented_message(mt)); return false; }
+    if (K > (size_t)EXOG_MAX_REGRESSORS) { set_error(out_error, COMPUTATION_ERROR, exog_cap_message(K)); return false; }
+    std::vector<const double *> xr(K), fx(K);
+    for (size_t i = 0; i < K; i++) { xr[i] = options->exog->regressors[i].values; fx[i] = options->exog->regressors[i].future_values; }
+    // (a horizon of 0 has no future values to point at: the batch entry does not read them)
+    const double *vals[1] = {values};
+    const uint64_t *valid[1] = {validity};
+    const size_t lens[1] = {length};
+    ForecastResult r;
+    AnofoxError se, be;
+    clear_error(&se); clear_error(&be);
+    if (!anofox_ts_forecast_exog_batch(vals, validity ? valid : nullptr, lens, 1, &opt, K, xr.data(), fx.data(), &r, &se, &be, nullptr, nullptr)) {
+        if (out_error) *out_error = be.code != SUCCESS ? be : se;
+        return false;
+    }
+    if (se.code != SUCCESS) { anofox_free_forecast_result(&r); if (out_error) *out_error = se; return false; }
+    *out_result = r;
+    return true;
 }
 
 } // extern "C"

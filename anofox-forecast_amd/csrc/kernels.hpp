@@ -206,6 +206,23 @@ struct MstlArgs {
 void launch_mstl(const MstlArgs &, hipStream_t);      // one mstl_season_kernel per period, then mstl_final_kernel
 void launch_swa(const SimpleArgs &, hipStream_t);     // SeasonalWindowAverage point forecasts
 
+// ARIMAX: exogenous regressors (fit_exog.hip)
+constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
+constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")
+struct ExogArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    int k, h;                    // regressors (1 .. EXOG_MAX_REGRESSORS), horizon
+    size_t t_rows;               // rows of every regressor's slice of x (>= the longest series)
+    const double *x;             // [k x t_rows x ld] historical values, x[(j * t_rows + t) * ld + s]
+    const double *f;             // [k x h x ld] future values, f[(j * h + i) * ld + s]
+    double *yhat;                // [n_series x h]
+    int32_t *status;             // [n_series] 0 for every series forecast here
+    int32_t *model_code;         // [n_series] MODEL_CODE_ARIMAX
+    double *b0, *beta;           // [ld] intercept, [k x ld] coefficients (0.0 where the regressor is not used)
+    uint32_t *used;              // [ld] bit j: regressor j is used (not aliased)
+};
+void launch_exog_arimax(const ExogArgs &, hipStream_t);
+
 struct IntervalArgs {
     int n_series, h;
     const double *yhat, *sd;

@@ -67,6 +67,36 @@ class DeviceBatch:
         if not self.L.anofox_hip_batch_set_arima_method(self.handle, int(method), C.byref(err)):
             raise RuntimeError(f"set_arima_method failed: [{err.code}] {err.message.decode()}")
 
+    def set_exog(self, x: torch.Tensor | None, future: torch.Tensor | None = None):
+        """Adopt the regressor blocks (no copy; kept alive by this object): x [k, t_max, ld] and future [k, horizon, ld], fp64 on the
+        batch's device, regressor j of series s at x[j, t, s] / future[j, i, s].  ARIMA and AutoARIMA batches then run ARIMAX; every
+        other model ignores the blocks.  set_exog(None) clears them."""
+        err = _lib.AnofoxError()
+        if x is None:
+            ok = self.L.anofox_hip_batch_set_exog_device(self.handle, None, None, 0, C.byref(err))
+            self._x = self._f = None
+        else:
+            k = int(x.shape[0])
+            assert x.dtype == torch.float64 and x.is_cuda and x.is_contiguous() and tuple(x.shape) == (k, self.t_max, self.ld), tuple(x.shape)
+            assert future is not None and future.dtype == torch.float64 and future.is_cuda and future.is_contiguous()
+            assert tuple(future.shape) == (k, self.h, self.ld), tuple(future.shape)
+            ok = self.L.anofox_hip_batch_set_exog_device(self.handle, x.data_ptr(), future.data_ptr(), k, C.byref(err))
+            if ok:
+                self._x, self._f = x, future
+        if not ok:
+            raise RuntimeError(f"set_exog_device failed: [{err.code}] {err.message.decode()}")
+
+    def exog_coefficients(self) -> dict:
+        """Intercept [n], beta [n, k] (0.0 where a regressor was left out) and used [n, k] of the last ARIMAX run (waits for it)."""
+        k = int(self._x.shape[0]) if getattr(self, "_x", None) is not None else 0
+        b0 = np.zeros(self.n)
+        beta = np.zeros((self.n, k))
+        used = np.zeros(self.n, dtype=np.uint32)
+        err = _lib.AnofoxError()
+        if not self.L.anofox_hip_batch_exog_coefficients(self.handle, b0.ctypes.data, beta.ctypes.data, used.ctypes.data, C.byref(err)):
+            raise RuntimeError(f"exog_coefficients failed: [{err.code}] {err.message.decode()}")
+        return {"intercept": b0, "beta": beta, "used": ((used[:, None] >> np.arange(k, dtype=np.uint32)[None, :]) & 1).astype(bool)}
+
     def periods(self) -> np.ndarray:
         """The seasonal period every series runs with (auto-detected on the device when the options ask for it)."""
         out = np.zeros(self.n, dtype=np.int32)

@@ -103,6 +103,38 @@ class MstlResult(C.Structure):
     ]
 
 
+class ExogenousRegressor(C.Structure):
+    _fields_ = [("values", C.POINTER(C.c_double)), ("n_values", C.c_size_t),
+                ("future_values", C.POINTER(C.c_double)), ("n_future", C.c_size_t)]
+
+
+class ExogenousData(C.Structure):
+    _fields_ = [("regressors", C.POINTER(ExogenousRegressor)), ("n_regressors", C.c_size_t)]
+
+
+class ForecastOptionsExog(C.Structure):
+    _fields_ = [
+        ("model", C.c_char * 32),
+        ("ets_model", C.c_char * 8),
+        ("horizon", C.c_int),
+        ("confidence_level", C.c_double),
+        ("seasonal_period", C.c_int),
+        ("auto_detect_seasonality", C.c_bool),
+        ("include_fitted", C.c_bool),
+        ("include_residuals", C.c_bool),
+        ("exog", C.POINTER(ExogenousData)),
+        ("window", C.c_int),
+        ("seasonal_periods_str", C.c_char * 64),
+        ("model_pool", C.c_char * 32),
+        ("laplace_variant", C.c_char * 16),
+        ("laplace_seasonal_batch_init", C.c_bool),
+    ]
+
+
+assert C.sizeof(ExogenousRegressor) == 32 and C.sizeof(ExogenousData) == 16 and C.sizeof(ForecastOptionsExog) == 192
+MODEL_CODE_ARIMAX = 50             # include/anofox_fcst_hip.h: model_code of a series the ARIMAX path forecast
+
+
 # every symbol include/anofox_fcst_hip.h declares
 class AnofoxHipInspection(C.Structure):
     _fields_ = [("model_code", C.c_int32), ("status", C.c_int32), ("seasonal_period", C.c_int32), ("reserved", C.c_int32),
@@ -124,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_set_default_arima_method", "anofox_hip_batch_set_arima_method", "anofox_hip_release_caches",
     "anofox_hip_batch_run_many", "anofox_hip_batch_lane_stats", "anofox_hip_selftest_recip",
     "anofox_ts_mstl_decomposition", "anofox_free_mstl_result", "anofox_hip_mstl_decompose_batch", "anofox_hip_mstl_decompose_device",
+    "anofox_ts_forecast_exog", "anofox_ts_forecast_exog_batch", "anofox_hip_batch_set_exog_device", "anofox_hip_batch_exog_coefficients",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -211,6 +244,15 @@ def load():
     L.anofox_hip_mstl_decompose_device.restype = C.c_bool
     L.anofox_hip_mstl_decompose_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_forecast_exog.restype = C.c_bool
+    L.anofox_ts_forecast_exog.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(ForecastOptionsExog), P(ForecastResult), P(AnofoxError)]
+    L.anofox_ts_forecast_exog_batch.restype = C.c_bool
+    L.anofox_ts_forecast_exog_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(ForecastOptions), C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError), C.c_void_p, C.c_void_p]
+    L.anofox_hip_batch_set_exog_device.restype = C.c_bool
+    L.anofox_hip_batch_set_exog_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(AnofoxError)]
+    L.anofox_hip_batch_exog_coefficients.restype = C.c_bool
+    L.anofox_hip_batch_exog_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -249,6 +291,17 @@ def make_options(model, horizon, *, ets_model="", seasonal_period=0, confidence_
     o.window = int(window)
     o.seasonal_periods_str = seasonal_periods_str.encode()[:63]
     o.model_pool = model_pool.encode()[:31]
+    return o
+
+
+def make_options_exog(opts, exog=None):
+    """ForecastOptionsExog with the fields of a ForecastOptions block and `exog` (a ctypes ExogenousData, kept alive by the caller)."""
+    o = ForecastOptionsExog()
+    C.memset(C.byref(o), 0, C.sizeof(o))
+    for f, _ in ForecastOptions._fields_:
+        setattr(o, f, getattr(opts, f))
+    if exog is not None:
+        o.exog = C.pointer(exog)
     return o
 
 

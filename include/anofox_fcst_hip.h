@@ -15,6 +15,8 @@
  *                        (Rust body crates/anofox-fcst-ffi/src/lib.rs:3344-3550)
  *   anofox_free_forecast_result  anofox_fcst_ffi.h:2886 (lib.rs:5900-5930)
  *   anofox_fcst_version  anofox_fcst_ffi.h:3058
+ *   ExogenousRegressor / ExogenousData / ForecastOptionsExog   anofox_fcst_ffi.h:1152-1249   (32 / 16 / 192 bytes)
+ *   anofox_ts_forecast_exog      (Rust body crates/anofox-fcst-ffi/src/lib.rs:3580-3780)
  *
  * Plain C, SysV x86-64, no torch / HIP types in any signature: a device stream
  * is passed as an opaque `void *` (a hipStream_t), device buffers as `void *`.
@@ -132,6 +134,55 @@ bool anofox_ts_mstl_decomposition(const double *values,
 
 void anofox_free_mstl_result(struct MstlResult *result);
 
+/* One exogenous regressor: `values[n_values]` aligned with the series, `future_values[n_future]` with the horizon. */
+typedef struct ExogenousRegressor {
+    const double *values;
+    size_t n_values;                /* must equal the series' length          */
+    const double *future_values;
+    size_t n_future;                /* must equal the horizon                 */
+} ExogenousRegressor;
+
+typedef struct ExogenousData {
+    const struct ExogenousRegressor *regressors;
+    size_t n_regressors;            /* 0 = none                               */
+} ExogenousData;
+
+/* ForecastOptions with the regressors behind the three flags (the other fields as above). */
+typedef struct ForecastOptionsExog {
+    char model[32];
+    char ets_model[8];
+    int horizon;
+    double confidence_level;
+    int seasonal_period;
+    bool auto_detect_seasonality;
+    bool include_fitted;
+    bool include_residuals;
+    const struct ExogenousData *exog; /* NULL = no regressors                 */
+    int window;
+    char seasonal_periods_str[64];
+    char model_pool[32];
+    char laplace_variant[16];
+    bool laplace_seasonal_batch_init;
+} ForecastOptionsExog;
+
+/*
+ * Fit + forecast ONE series with exogenous regressors (forecast.rs forecast_with_exog).  Checks in the reference's order: NULL
+ * pointers, the model name, every regressor's n_values against `length` and n_future against the horizon (INVALID_INPUT), then
+ * the series' length.  With regressors, ARIMA and AutoARIMA run ARIMAX (model_name "ARIMAX"): least squares of y on the
+ * regressors with an intercept, the ARIMA model's forecast of the residuals, plus intercept + sum beta_j future_j; an aliased
+ * regressor (constant, duplicated, linearly dependent, or holding a non-finite value) is left out.  At most 8 regressors
+ * (more: COMPUTATION_ERROR).  OptimizedTheta, DynamicTheta, MFLES and AutoMFLES with regressors (ThetaX, MFLESX) are
+ * INTERNAL_ERROR: not implemented.  Without regressors, or with any other model, the call is anofox_ts_forecast on the series
+ * (the regressors are ignored, as in the reference).  Intervals, fitted values, residuals and mse follow anofox_ts_forecast.
+ * Runs on the GPU as a batch of one; results are released by anofox_free_forecast_result.
+ */
+bool anofox_ts_forecast_exog(const double *values,
+                             const uint64_t *validity,
+                             size_t length,
+                             const struct ForecastOptionsExog *options,
+                             struct ForecastResult *out_result,
+                             struct AnofoxError *out_error);
+
 #endif /* ANOFOX_FCST_FFI_H */
 
 /* ------------------------------------------------------------------------- */
@@ -158,6 +209,32 @@ bool anofox_ts_forecast_batch(const double *const *values,
                               struct ForecastResult *out_results,
                               struct AnofoxError *out_errors,
                               struct AnofoxError *out_batch_error);
+
+/*
+ * The batch form of anofox_ts_forecast_exog: `n_series` series, one shared option block and horizon, one shared number of
+ * regressors K = n_regressors.  xreg[s * K + j] points at regressor j of series s (lengths[s] values), future_xreg[s * K + j] at
+ * its options->horizon future values; regressors have no NULL masks (the reference has none: its callers pass 0.0).  Replaces the
+ * per-group loop of the reference binding (src/table_functions/ts_forecast.cpp:245-337, one FFI call per group of
+ * ts_forecast_exog_by).  K = 0, or a model that ignores regressors, forwards to anofox_ts_forecast_batch.  Per-series results
+ * and errors and the batch error are those of anofox_ts_forecast_batch; more than 8 regressors, ThetaX and MFLESX fail the
+ * whole call (false; the error is also written to every series that is long enough to be forecast).
+ * out_coefficients (may be NULL): [n_series x (K + 1)] intercept, then beta_j (0.0 for a regressor that was left out; NaN for a
+ * series that failed or did not take the ARIMAX path); out_used (may be NULL): [n_series] bit j = regressor j was used.
+ * The ARIMAX path runs on the calling thread's current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_ts_forecast_exog_batch(const double *const *values,
+                                   const uint64_t *const *validity,
+                                   const size_t *lengths,
+                                   size_t n_series,
+                                   const struct ForecastOptions *options,
+                                   size_t n_regressors,
+                                   const double *const *xreg,
+                                   const double *const *future_xreg,
+                                   struct ForecastResult *out_results,
+                                   struct AnofoxError *out_errors,
+                                   struct AnofoxError *out_batch_error,
+                                   double *out_coefficients,
+                                   uint32_t *out_used);
 
 /*
  * MSTL decomposition of `n_series` series with one shared period list, in one GPU pass (same semantics as
@@ -345,6 +422,26 @@ bool anofox_hip_batch_set_device_block(AnofoxHipBatch *batch,
                                        const void *d_y, size_t ld,
                                        const void *d_len,
                                        struct AnofoxError *out_error);
+
+/*
+ * Adopt exogenous regressor blocks that are already in HBM, without a copy: `d_x` is [k x t_max x ld] fp64 with regressor j of
+ * series s at d_x[(j * t_max + t) * ld + s] (the layout of the series block, once per regressor; rows t >= the series' length are
+ * not read), `d_future` is [k x horizon x ld] with d_future[(j * horizon + i) * ld + s].  t_max, ld and horizon are the batch's
+ * (anofox_hip_batch_create, anofox_hip_batch_ld); the pointers are 8-byte aligned device pointers, and both blocks must stay
+ * alive and unchanged until every run that uses them has finished.  From then on anofox_hip_batch_run takes the ARIMAX path when
+ * the batch's model is ARIMA or AutoARIMA (model_code 50 = "ARIMAX") and ignores the blocks for every other model, like the
+ * reference.  k = 0 clears them: the batch runs its ordinary model again.  k > 8: COMPUTATION_ERROR.
+ */
+bool anofox_hip_batch_set_exog_device(AnofoxHipBatch *batch, const void *d_x, const void *d_future, size_t k,
+                                      struct AnofoxError *out_error);
+
+/*
+ * The least-squares fit of the last ARIMAX run (waits for it): out_intercept[n_series], out_beta[n_series x k] (0.0 for a
+ * regressor that was left out), out_used[n_series] (bit j = regressor j was used); each may be NULL.  Series that failed report
+ * NaN / 0.  False when the last run did not take the ARIMAX path.
+ */
+bool anofox_hip_batch_exog_coefficients(AnofoxHipBatch *batch, double *out_intercept, double *out_beta, uint32_t *out_used,
+                                        struct AnofoxError *out_error);
 
 /*
  * The seasonal period every series of the packed / adopted block runs with: the caller's, or -- auto_detect_seasonality with
