@@ -721,6 +721,275 @@ def ts_mstl_decomposition_by(group, date, target, periods=(), insufficient_data=
 
 
 # --------------------------------------------------------------------------------------------
+# changepoint detection (BOCPD): anofox_hip_changepoints_batch and the mirrors of _ts_detect_changepoints_bocpd,
+# ts_detect_changepoints, ts_detect_changepoints_agg and ts_detect_changepoints_by
+# --------------------------------------------------------------------------------------------
+def changepoints_batch(series, hazard_lambda=250.0, valids=None):
+    """anofox_hip_changepoints_batch over a list of 1-D arrays, one hazard_lambda for the call (<= 0 means 250).  Per series a
+    dict: ok, code, message, probability, is_changepoint (arrays; None where the series failed) and n_changepoints (-1 there)."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    total = int(lens.sum()) if n else 0
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks = None
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+    prob = np.empty(max(total, 1))
+    flag = np.zeros(max(total, 1), dtype=np.uint8)
+    cnt = np.zeros(max(n, 1), dtype=np.int32)
+    errs = (_lib.AnofoxError * max(n, 1))()
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_changepoints_batch(vals, masks, lens.ctypes.data, n, float(hazard_lambda), prob.ctypes.data, flag.ctypes.data,
+                                         cnt.ctypes.data, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out, off = [], 0
+    for i in range(n):
+        m = int(lens[i])
+        r = {"ok": errs[i].code == _lib.SUCCESS, "code": int(errs[i].code), "message": errs[i].message.decode(errors="replace"),
+             "probability": None, "is_changepoint": None, "n_changepoints": int(cnt[i])}
+        if r["ok"]:
+            r["probability"] = prob[off:off + m].copy()
+            r["is_changepoint"] = flag[off:off + m].astype(bool)
+        out.append(r)
+        off += m
+    return out
+
+
+def _is_null(v):
+    return v is None or v is np.ma.masked or (isinstance(v, float) and v != v)
+
+
+def _ts_detect_changepoints_bocpd(values, hazard_lambda=250.0, include_probabilities=False):
+    """The scalar _ts_detect_changepoints_bocpd(values, hazard_lambda, include_probabilities) (ts_changepoints.cpp:233-360): None for
+    a NULL list, for fewer than 2 non-NULL values (NULL elements are dropped, ExtractListAsDouble) and when the call fails (2
+    values); a NULL hazard_lambda is 250, a NULL include_probabilities false.  Else the STRUCT as a dict of three lists."""
+    if values is None:
+        return None
+    vals = np.array([float(v) for v in values if v is not None and v is not np.ma.masked], dtype=np.float64)
+    if len(vals) < 2:
+        return None
+    lam = 250.0 if hazard_lambda is None else float(hazard_lambda)
+    inc = False if include_probabilities is None else bool(include_probabilities)
+    L = _lib.load()
+    res = _lib.BocpdResult()
+    C.memset(C.byref(res), 0, C.sizeof(res))
+    err = _lib.AnofoxError()
+    if not L.anofox_ts_detect_changepoints_bocpd(vals.ctypes.data, len(vals), lam, inc, C.byref(res), C.byref(err)):
+        return None
+    n, k = res.n_points, res.n_changepoints
+    out = {"is_changepoint": [bool(res.is_changepoint[i]) for i in range(n)],
+           "changepoint_probability": [float(res.changepoint_probability[i]) for i in range(n)],
+           "changepoint_indices": [int(res.changepoint_indices[i]) for i in range(k)] if res.changepoint_indices else []}
+    L.anofox_free_bocpd_result(C.byref(res))
+    return out
+
+
+def _stod(text):
+    """std::stod: leading whitespace, the longest numeric prefix, trailing text ignored; None where it throws (no conversion, or a
+    decimal out of the double range)."""
+    m = re.match(r"\s*([+-]?(?:inf(?:inity)?|nan(?:\([0-9a-z_]*\))?|0x(?:[0-9a-f]+\.?[0-9a-f]*|\.[0-9a-f]+)(?:p[+-]?[0-9]+)?|"
+                 r"(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:e[+-]?[0-9]+)?))", text, re.IGNORECASE)
+    if not m:
+        return None
+    tok = m.group(1).lower()
+    body = tok.lstrip("+-")
+    if body.startswith("nan"):
+        return float("nan")
+    if body.startswith("inf"):
+        return float("-inf") if tok.startswith("-") else float("inf")
+    try:
+        v = float.fromhex(tok) if body.startswith("0x") else float(tok)
+    except (OverflowError, ValueError):
+        return None
+    return None if v in (float("inf"), float("-inf")) else v
+
+
+def parse_hazard_lambda(params_str) -> float:
+    """ParseHazardLambda (ts_changepoints.cpp:451-473): the trimmed string as a number, else the number after `hazard_lambda` in a
+    JSON-like string, else 250."""
+    s = str(params_str)
+    v = _stod(s.strip(" \t"))
+    if v is not None:
+        return v
+    m = re.search(r"hazard_lambda['\"]?\s*[:=]\s*['\"]?([0-9.]+)", s, re.IGNORECASE)
+    if m:
+        v = _stod(m.group(1))
+        if v is None:
+            raise InvalidInputException(f"Invalid hazard_lambda: '{m.group(1)}'")      # (std::stod throws out of the bind)
+        return v
+    return 250.0
+
+
+def _param(params, key):
+    if not params:
+        return None
+    v = params.get(key)
+    return None if v is None else str(v)
+
+
+def _try_double(text):
+    """TRY_CAST(text AS DOUBLE): the whole trimmed string must be a number."""
+    if text is None:
+        return None
+    try:
+        return float(text.strip())
+    except ValueError:
+        return None
+
+
+def _try_bool(text):
+    """TRY_CAST(text AS BOOLEAN)."""
+    if text is None:
+        return None
+    t = text.strip().lower()
+    if t in ("true", "t", "1", "yes", "y"):
+        return True
+    if t in ("false", "f", "0", "no", "n"):
+        return False
+    return None
+
+
+def _changepoint_dates(date):
+    """(dates, 'DATE' | 'TIMESTAMP', microseconds, NULL mask) of the date column of ts_detect_changepoints_by (ts_changepoints.cpp:504-516)."""
+    dates = np.asarray(date)
+    if not np.issubdtype(dates.dtype, np.datetime64):
+        names = {"int32": "INTEGER", "int64": "BIGINT", "float64": "DOUBLE", "object": "VARCHAR"}
+        raise InvalidInputException(f"Date column must be DATE or TIMESTAMP, got: {names.get(str(dates.dtype), str(dates.dtype))}")
+    kind = "DATE" if np.datetime_data(dates.dtype)[0] == "D" else "TIMESTAMP"
+    null_date = np.isnat(dates)
+    us = _to_micros(np.where(null_date, np.datetime64(0, np.datetime_data(dates.dtype)[0]), dates), kind)
+    return dates, kind, us, null_date
+
+
+def _changepoint_values(value):
+    """(values with 0.0 at the NULLs, NULL mask) of a value column: None / masked entries are NULL."""
+    if np.ma.isMaskedArray(value):
+        mask = np.ma.getmaskarray(value).copy()
+        return np.where(mask, 0.0, np.ma.getdata(value).astype(np.float64)), mask
+    col = np.asarray(value)
+    if col.dtype == object:
+        mask = np.array([v is None or v is np.ma.masked for v in col], dtype=bool)
+        return np.array([0.0 if m else float(v) for v, m in zip(col, mask)], dtype=np.float64), mask
+    return col.astype(np.float64), np.zeros(len(col), dtype=bool)
+
+
+def ts_detect_changepoints_by(group, date, value, params=None, group_name="id", date_name="date"):
+    """ts_detect_changepoints_by(source, group_col, date_col, value_col, params) (macro ts_macros.cpp:526-532 over
+    _ts_detect_changepoints_by_native, ts_changepoints.cpp:475-800).  `date` must be a datetime64 column (DATE or TIMESTAMP; NaT is
+    NULL); params['hazard_lambda'] goes through its string form and ParseHazardLambda (default '250.0').  Groups come in
+    first-appearance order, a group's rows sorted by (timestamp, value); a NULL value counts as 0.0.  A group of fewer than 2 rows,
+    and a group the detection fails for (2 rows), keeps its rows with is_changepoint False and a NULL probability; rows with a NULL
+    date come last with a NULL date, False and NULL.  Every group goes to the GPU in ONE anofox_hip_changepoints_batch call (the
+    reference walks the groups in one thread).  Returns a dict of columns: <group_name>, <date_name>, is_changepoint (bool),
+    changepoint_probability (float64 masked array, masked = NULL); <date_name> holds NaT for a NULL date."""
+    text = _param(params, "hazard_lambda")
+    lam = parse_hazard_lambda("250.0" if text is None else text)
+    dates, kind, us, null_date = _changepoint_dates(date)
+    vals, _ = _changepoint_values(value)
+    grp = np.asarray(group, dtype=object)
+    order, members = [], {}
+    for i in range(len(grp)):
+        if null_date[i]:
+            continue
+        k = "__NULL__" if grp[i] is None else grp[i]
+        if k not in members:
+            members[k] = []
+            order.append(k)
+        members[k].append(i)
+    sorted_us, series, run = {}, [], []
+    for k in order:
+        idx = np.array(members[k])
+        if len(idx) < 2:
+            sorted_us[k] = us[idx]
+            continue
+        o = np.lexsort((vals[idx], us[idx]))          # std::sort of (timestamp, value) pairs
+        sorted_us[k] = us[idx][o]
+        series.append(vals[idx][o])
+        run.append(k)
+    res = dict(zip(run, changepoints_batch(series, lam))) if series else {}
+    g_out, d_out, f_out, p_out, p_null = [], [], [], [], []
+    for k in order:
+        r = res.get(k)
+        good = r is not None and r["ok"]
+        for i, t in enumerate(sorted_us[k]):
+            g_out.append(None if k == "__NULL__" else k)
+            d_out.append(int(t))
+            f_out.append(bool(r["is_changepoint"][i]) if good else False)
+            p_out.append(float(r["probability"][i]) if good else 0.0)
+            p_null.append(not good)
+    n_dated = len(d_out)
+    for i in np.nonzero(null_date)[0]:
+        g_out.append(grp[i])
+        f_out.append(False)
+        p_out.append(0.0)
+        p_null.append(True)
+    unit = "D" if kind == "DATE" else "us"
+    d_col = np.full(len(g_out), np.datetime64("NaT"), dtype=f"datetime64[{unit}]")
+    if n_dated:
+        d_col[:n_dated] = _from_micros(np.array(d_out, dtype=np.int64), kind, dates.dtype)
+    return {group_name: g_out, date_name: d_col, "is_changepoint": np.array(f_out, dtype=bool),
+            "changepoint_probability": np.ma.array(np.array(p_out, dtype=np.float64), mask=np.array(p_null, dtype=bool))}
+
+
+def ts_detect_changepoints(date, value, params=None):
+    """ts_detect_changepoints(source, date_col, value_col, params) (macro ts_macros.cpp:489-513): ONE series.  hazard_lambda is
+    TRY_CAST to DOUBLE (default 250), include_probabilities to BOOLEAN (default FALSE: the probabilities are then all 0.0).  The
+    rows are ordered by date (NULLs last); the scalar gets the values in that order with the NULL values dropped, and row i takes
+    element i of its lists, so rows past the list's end -- and every row when the scalar returns NULL -- get NULLs.  Returns a
+    dict of columns: date_col, value_col, is_changepoint, changepoint_probability (lists; None = NULL)."""
+    lam = _try_double(_param(params, "hazard_lambda"))
+    inc = _try_bool(_param(params, "include_probabilities"))
+    dates = np.asarray(date)
+    vals, vnull = _changepoint_values(value)
+    if np.issubdtype(dates.dtype, np.datetime64):
+        null_date = np.isnat(dates)
+        key = np.where(null_date, 0, dates.astype(np.int64))
+    else:
+        null_date = np.zeros(len(dates), dtype=bool)
+        key = dates
+    o = np.lexsort((key, null_date))                  # ORDER BY date_col: ascending, NULLS LAST, stable
+    ordered = [None if vnull[i] else float(vals[i]) for i in o]
+    cp = _ts_detect_changepoints_bocpd(ordered, 250.0 if lam is None else lam, False if inc is None else inc) if len(o) else None
+    flags = cp["is_changepoint"] if cp else []
+    probs = cp["changepoint_probability"] if cp else []
+    return {"date_col": [None if null_date[i] else dates[i] for i in o], "value_col": ordered,
+            "is_changepoint": [flags[j] if j < len(flags) else None for j in range(len(o))],
+            "changepoint_probability": [probs[j] if j < len(probs) else None for j in range(len(o))]}
+
+
+def ts_detect_changepoints_agg(ts, value, params=None):
+    """The aggregate ts_detect_changepoints_agg(ts, value, params) over ONE group (src/aggregate_functions/ts_changepoints_agg.cpp):
+    rows with a NULL timestamp or value are skipped, the rest sorted by (timestamp, value); the hazard is ALWAYS 250 -- the
+    aggregate never reads its params MAP (ts_changepoints_agg.cpp:104-108) -- and the probabilities are always included.  None
+    when no row is left or the detection fails (fewer than 3 rows); else a list of dicts timestamp, value, is_changepoint,
+    changepoint_probability."""
+    dates = np.asarray(ts)
+    if not np.issubdtype(dates.dtype, np.datetime64):
+        raise InvalidInputException("ts_detect_changepoints_agg: the timestamp column must be TIMESTAMP")
+    vals, vnull = _changepoint_values(value)
+    keep = np.nonzero(~(np.isnat(dates) | vnull))[0]
+    if len(keep) == 0:
+        return None
+    us = dates[keep].astype("datetime64[us]").astype(np.int64)
+    v = vals[keep]
+    o = np.lexsort((v, us))
+    r = changepoints_batch([v[o]], 250.0)[0]
+    if not r["ok"]:
+        return None
+    return [{"timestamp": np.datetime64(int(t), "us"), "value": float(x), "is_changepoint": bool(f), "changepoint_probability": float(p)}
+            for t, x, f, p in zip(us[o], v[o], r["is_changepoint"], r["probability"])]
+
+
+anofox_fcst_ts_detect_changepoints = ts_detect_changepoints
+anofox_fcst_ts_detect_changepoints_by = ts_detect_changepoints_by
+anofox_fcst_ts_detect_changepoints_agg = ts_detect_changepoints_agg      # ts_changepoints_agg.cpp:274-288
+
+
+# --------------------------------------------------------------------------------------------
 # exogenous regressors (ARIMAX): anofox_ts_forecast_exog_batch and the mirrors of _ts_forecast_exog / ts_forecast_exog_by
 # --------------------------------------------------------------------------------------------
 def forecast_exog_batch(series, xregs, futures, opts, valids=None):

@@ -3591,6 +3591,172 @@ void anofox_free_mstl_result(MstlResult *result)
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Bayesian online changepoint detection (changepoint.rs detect_changepoints_bocpd; changepoint.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+bool anofox_hip_changepoints_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, double hazard_lambda,
+                                    double *probability, uint8_t *flags, int32_t *counts, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !probability || !flags || !counts) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if (!device_ready(out_error)) return false;
+    const double lambda = hazard_lambda > 0.0 ? hazard_lambda : 250.0;       // the FFI wrapper (lib.rs:3077-3081)
+    ChangepointArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.hazard = 1.0 / std::fmax(lambda, 1.0);                                 // changepoint.rs:210
+    a.prob = probability; a.flag = flags; a.count = counts;
+    hipStream_t st = (hipStream_t)stream;
+    try {
+        (void)hipGetLastError();
+        launch_bocpd(a, st);
+        LAUNCHCHECK("bocpd");
+        HIPCHECK(hipStreamSynchronize(st));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_changepoints_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
+                                   double hazard_lambda, double *out_probability, uint8_t *out_is_changepoint, int32_t *out_n_changepoints,
+                                   AnofoxError *out_errors, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_series > 0 && (!values || !lengths || !out_n_changepoints)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    size_t total = 0, t_max = 0;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)INT32_MAX) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        total += lengths[s];
+        t_max = std::max(t_max, lengths[s]);
+    }
+    if (total > 0 && (!out_probability || !out_is_changepoint)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    double *d_y = nullptr, *d_prob = nullptr;
+    uint8_t *d_flag = nullptr;
+    int32_t *d_len = nullptr, *d_cnt = nullptr;
+    // quiesced: on the success path the device entry has waited for its stream and the copies are synchronous; after a failure
+    // the first free waits for the device
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_prob, (void *)d_flag, (void *)d_len, (void *)d_cnt}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<int32_t> cnt(n_series);
+    std::vector<double> prob;
+    std::vector<uint8_t> flag;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        // time-major block; a NULL counts as 0.0, as the reference's table function passes it (ts_changepoints.cpp:599)
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<int32_t> len(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            const uint64_t *m = validity ? validity[s] : nullptr;
+            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = (m && !((m[t >> 6] >> (t & 63)) & 1)) ? 0.0 : values[s][t];
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld); d_cnt = dalloc<int32_t>(ld);
+        d_prob = dalloc<double>(T * ld); d_flag = dalloc<uint8_t>(T * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!anofox_hip_changepoints_device(d_y, ld, d_len, n_series, T, hazard_lambda, d_prob, d_flag, d_cnt, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        prob.resize(T * ld); flag.resize(T * ld);
+        HIPCHECK(hipMemcpy(cnt.data(), d_cnt, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(prob.data(), d_prob, T * ld * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(flag.data(), d_flag, T * ld * sizeof(uint8_t), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    size_t off = 0;
+    for (size_t s = 0; s < n_series; s++) {
+        const size_t n = lengths[s];
+        const bool ok = cnt[s] >= 0;
+        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        if (!ok && out_errors)      // ForecastError::InsufficientData { needed: 3, got: n } (changepoint.rs:205-207)
+            set_error(&out_errors[s], COMPUTATION_ERROR, "Insufficient data: need at least 3 observations, got " + std::to_string(n));
+        out_n_changepoints[s] = ok ? cnt[s] : -1;
+        for (size_t t = 0; t < n; t++) {
+            out_probability[off + t] = ok ? prob[t * ld + s] : nan;
+            out_is_changepoint[off + t] = ok ? flag[t * ld + s] : 0;
+        }
+        off += n;
+    }
+    return true;
+}
+
+bool anofox_ts_detect_changepoints_bocpd(const double *values, size_t length, double hazard_lambda, bool include_probabilities,
+                                         BocpdResult *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    std::vector<double> pr(std::max<size_t>(length, 1));
+    std::vector<uint8_t> fl(std::max<size_t>(length, 1));
+    int32_t n_cp = 0;
+    AnofoxError serr, berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    if (!anofox_hip_changepoints_batch(v, nullptr, len, 1, hazard_lambda, pr.data(), fl.data(), &n_cp, &serr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
+    std::memset(out_result, 0, sizeof *out_result);
+    out_result->n_points = length;
+    out_result->n_changepoints = (size_t)n_cp;
+    out_result->is_changepoint = (bool *)std::malloc(length * sizeof(bool));
+    out_result->changepoint_probability = (double *)std::calloc(length, sizeof(double));     // zeros unless asked for (changepoint.rs:347-349)
+    if (n_cp > 0) out_result->changepoint_indices = (size_t *)std::malloc((size_t)n_cp * sizeof(size_t));
+    if (!out_result->is_changepoint || !out_result->changepoint_probability || (n_cp > 0 && !out_result->changepoint_indices)) {
+        anofox_free_bocpd_result(out_result);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate BOCPD result");
+        return false;
+    }
+    size_t k = 0;
+    for (size_t t = 0; t < length; t++) {
+        out_result->is_changepoint[t] = fl[t] != 0;
+        if (include_probabilities) out_result->changepoint_probability[t] = pr[t];
+        if (fl[t] && k < (size_t)n_cp) out_result->changepoint_indices[k++] = t;
+    }
+    return true;
+}
+
+void anofox_free_bocpd_result(BocpdResult *result)
+{
+    if (!result) return;
+    std::free(result->is_changepoint);
+    std::free(result->changepoint_probability);
+    std::free(result->changepoint_indices);
+    result->is_changepoint = nullptr;
+    result->changepoint_probability = nullptr;
+    result->changepoint_indices = nullptr;
+    result->n_points = 0;
+    result->n_changepoints = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Exogenous regressors: ARIMAX (forecast.rs forecast_with_exog; fit_exog.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 } // extern "C"

@@ -206,6 +206,18 @@ struct MstlArgs {
 void launch_mstl(const MstlArgs &, hipStream_t);      // one mstl_season_kernel per period, then mstl_final_kernel
 void launch_swa(const SimpleArgs &, hipStream_t);     // SeasonalWindowAverage point forecasts
 
+// Bayesian online changepoint detection (changepoint.rs detect_changepoints_bocpd; changepoint.hip)
+constexpr int BOCPD_MAX_RUN = 500;       // run lengths tracked per series (changepoint.rs: max_keep)
+struct ChangepointArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // rows of the output blocks; a longer series is cut to it
+    double hazard;               // 1 / max(hazard_lambda, 1)
+    double *prob;                // [t_rows x ld] P(run length = 1) after step t; rows t >= len stay untouched
+    uint8_t *flag;               // [t_rows x ld] prob > 0.5 && t > 0
+    int32_t *count;              // [n_series] flagged points, -1 for a series of fewer than 3 observations (nothing else written)
+};
+void launch_bocpd(const ChangepointArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

@@ -103,6 +103,16 @@ class MstlResult(C.Structure):
     ]
 
 
+class BocpdResult(C.Structure):
+    _fields_ = [
+        ("is_changepoint", C.POINTER(C.c_bool)),
+        ("changepoint_probability", C.POINTER(C.c_double)),
+        ("n_points", C.c_size_t),
+        ("changepoint_indices", C.POINTER(C.c_size_t)),
+        ("n_changepoints", C.c_size_t),
+    ]
+
+
 class ExogenousRegressor(C.Structure):
     _fields_ = [("values", C.POINTER(C.c_double)), ("n_values", C.c_size_t),
                 ("future_values", C.POINTER(C.c_double)), ("n_future", C.c_size_t)]
@@ -157,6 +167,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_batch_run_many", "anofox_hip_batch_lane_stats", "anofox_hip_selftest_recip",
     "anofox_ts_mstl_decomposition", "anofox_free_mstl_result", "anofox_hip_mstl_decompose_batch", "anofox_hip_mstl_decompose_device",
     "anofox_ts_forecast_exog", "anofox_ts_forecast_exog_batch", "anofox_hip_batch_set_exog_device", "anofox_hip_batch_exog_coefficients",
+    "anofox_ts_detect_changepoints_bocpd", "anofox_free_bocpd_result", "anofox_hip_changepoints_batch", "anofox_hip_changepoints_device",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -253,6 +264,15 @@ def load():
     L.anofox_hip_batch_set_exog_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(AnofoxError)]
     L.anofox_hip_batch_exog_coefficients.restype = C.c_bool
     L.anofox_hip_batch_exog_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_detect_changepoints_bocpd.restype = C.c_bool
+    L.anofox_ts_detect_changepoints_bocpd.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_bool, P(BocpdResult), P(AnofoxError)]
+    L.anofox_free_bocpd_result.argtypes = [P(BocpdResult)]
+    L.anofox_hip_changepoints_batch.restype = C.c_bool
+    L.anofox_hip_changepoints_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_changepoints_device.restype = C.c_bool
+    L.anofox_hip_changepoints_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

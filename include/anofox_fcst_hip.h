@@ -134,6 +134,36 @@ bool anofox_ts_mstl_decomposition(const double *values,
 
 void anofox_free_mstl_result(struct MstlResult *result);
 
+/*
+ * Result of the Bayesian online changepoint detection (layout of the reference's anofox_fcst_ffi.h).  The arrays are malloc()ed
+ * by the callee and released by anofox_free_bocpd_result; changepoint_indices is NULL when no point is flagged.
+ */
+typedef struct BocpdResult {
+    bool *is_changepoint;            /* [n_points] */
+    double *changepoint_probability; /* [n_points]; all zeros when include_probabilities is false */
+    size_t n_points;
+    size_t *changepoint_indices;     /* [n_changepoints] ascending, or NULL */
+    size_t n_changepoints;
+} BocpdResult;
+
+/*
+ * Bayesian online changepoint detection (BOCPD) of ONE series, the reference's detect_changepoints_bocpd: Normal-Gamma prior
+ * mu0 = 0, kappa0 = alpha0 = beta0 = 0.01, constant hazard 1 / max(hazard_lambda, 1), Student-t predictive weights without their
+ * normalising constant, at most 500 tracked run lengths.  changepoint_probability[t] is the normalised P(run length = 1) after
+ * step t, is_changepoint[t] = probability > 0.5 && t > 0.  hazard_lambda <= 0 (or NaN) means 250.  NULL `values` or `out_result`:
+ * NULL_POINTER; length < 3: COMPUTATION_ERROR "Insufficient data: need at least 3 observations, got N".  Non-finite values are
+ * not special-cased, as in the reference: a NaN reaches the sums, the step's sum fails the `> 1e-300` test and the step stays
+ * unnormalised, the probabilities from there on are NaN and a NaN is never flagged.  Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_detect_changepoints_bocpd(const double *values,
+                                         size_t length,
+                                         double hazard_lambda,
+                                         bool include_probabilities,
+                                         struct BocpdResult *out_result,
+                                         struct AnofoxError *out_error);
+
+void anofox_free_bocpd_result(struct BocpdResult *result);
+
 /* One exogenous regressor: `values[n_values]` aligned with the series, `future_values[n_future]` with the horizon. */
 typedef struct ExogenousRegressor {
     const double *values;
@@ -282,6 +312,46 @@ bool anofox_hip_mstl_decompose_device(const double *y,
                                       int32_t *info,
                                       void *stream,
                                       struct AnofoxError *out_error);
+
+/*
+ * BOCPD of `n_series` series with one hazard_lambda, in one GPU pass (same semantics as anofox_ts_detect_changepoints_bocpd per
+ * series, probabilities always included).  Replaces the single-threaded per-group loop of the reference's
+ * _ts_detect_changepoints_by_native finalize.  `validity` may be NULL; a NULL value counts as 0.0, as that table function passes
+ * it.  With total = the sum of `lengths`, series i owns [off_i, off_i + lengths[i]) of out_probability[total] and
+ * out_is_changepoint[total] (0 / 1); out_n_changepoints[i] is its number of flagged points.  A series of fewer than 3 values
+ * fails alone: out_errors[i] (may be NULL) gets the single entry's COMPUTATION_ERROR, out_n_changepoints[i] = -1, its
+ * probabilities are NaN and its flags 0.  The return value is false only for batch-level failures (NULL pointers, no GPU), also
+ * reported through `out_batch_error`.  Runs on the calling thread's current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_changepoints_batch(const double *const *values,
+                                   const uint64_t *const *validity,
+                                   const size_t *lengths,
+                                   size_t n_series,
+                                   double hazard_lambda,
+                                   double *out_probability,
+                                   uint8_t *out_is_changepoint,
+                                   int32_t *out_n_changepoints,
+                                   struct AnofoxError *out_errors,
+                                   struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows), lengths[n_series] (int32) and the outputs
+ * are device pointers.  probability (fp64) and flags (uint8) are [t_rows x ld], counts is [n_series] (int32).  Rows
+ * t >= lengths[s] are left untouched; a series with lengths[s] < 3 gets counts[s] = -1 and is otherwise untouched; a length above
+ * t_rows is cut to t_rows.  One wavefront per series, the run-length state in registers; the same bits on every run and through
+ * every entry.  Runs on `stream` (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_changepoints_device(const double *y,
+                                    size_t ld,
+                                    const int32_t *lengths,
+                                    size_t n_series,
+                                    size_t t_rows,
+                                    double hazard_lambda,
+                                    double *probability,
+                                    uint8_t *flags,
+                                    int32_t *counts,
+                                    void *stream,
+                                    struct AnofoxError *out_error);
 
 /*
  * Multi-device execution of the batch entry.  The reference's finalize loop is ONE process walking all groups
