@@ -990,6 +990,196 @@ anofox_fcst_ts_detect_changepoints_agg = ts_detect_changepoints_agg      # ts_ch
 
 
 # --------------------------------------------------------------------------------------------
+# per-series statistics: anofox_hip_stats_batch and the mirrors of _ts_stats, _ts_stats_with_dates, ts_stats, ts_stats_by,
+# ts_stats_agg, ts_quality_report and ts_stats_summary
+# --------------------------------------------------------------------------------------------
+STATS_FIELDS = _lib.STATS_INT_FIELDS + _lib.STATS_FP_FIELDS + ("expected_length", "n_gaps")
+
+
+def _stats_dict(r: _lib.TsStatsResult) -> dict:
+    out = {f: int(getattr(r, f)) for f in _lib.STATS_INT_FIELDS}
+    out["is_constant"] = bool(r.is_constant)
+    for f in _lib.STATS_FP_FIELDS:
+        out[f] = float(getattr(r, f))
+    out["expected_length"] = int(r.expected_length) if r.has_date_metrics else None
+    out["n_gaps"] = int(r.n_gaps) if r.has_date_metrics else None
+    return out
+
+
+def stats_batch(series, valids=None, dates=None, frequency_micros=0, frequency_type="FIXED"):
+    """anofox_hip_stats_batch over a list of 1-D arrays: one GPU pass for all series.  `valids[i]` (booleans, False = NULL) and
+    `dates[i]` (int64 microseconds) may be None per series, as may both lists.  Per series a dict keyed by the 36 field names
+    (STATS_FIELDS); expected_length / n_gaps are None without date figures."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks = ds = None
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+    if dates is not None:
+        dl = [np.ascontiguousarray(d, dtype=np.int64) if d is not None else None for d in dates]
+        for y, d in zip(ys, dl):
+            if d is not None and len(d) != len(y):
+                raise InvalidInputException("stats_batch: a series and its dates differ in length")
+        ds = (C.c_void_p * max(n, 1))(*[(d.ctypes.data if len(d) else _EMPTY_SERIES_ADDR) if d is not None else None for d in dl])
+    res = (_lib.TsStatsResult * max(n, 1))()
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_stats_batch(vals, masks, ds, lens.ctypes.data, n, int(frequency_micros), _lib.FREQUENCY_TYPES[frequency_type],
+                                  res, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    return [_stats_dict(res[i]) for i in range(n)]
+
+
+def frequency_for_stats(frequency):
+    """ParseFrequencyForStats (ts_stats.cpp:22-45): (microseconds, type).  A calendar frequency also gets an approximate
+    duration: 30, 90 or 365 days per unit."""
+    f = parse_frequency(frequency)
+    days = {"FIXED": None, "MONTHLY": 30, "QUARTERLY": 90, "YEARLY": 365}[f.type]
+    micros = f.seconds * 1000000 if days is None else f.seconds * 86400 * days * 1000000
+    return micros, f.type
+
+
+def _stats_cells(values):
+    """(values with 0.0 at the NULLs, validity) of a list whose None / masked elements are NULL; a NaN stays a valid NaN."""
+    ok = np.array([v is not None and v is not np.ma.masked for v in values], dtype=bool)
+    return np.array([float(v) if o else 0.0 for v, o in zip(values, ok)], dtype=np.float64), ok
+
+
+def _ts_stats(values):
+    """The scalar _ts_stats(values) (ts_stats.cpp TsStatsFunction): None for a NULL list; NULL elements are invalid slots, a NaN
+    is a valid slot holding NaN.  An EMPTY list also gives None: the C++ hands the wrapper the data() of an empty vector, a null
+    pointer with libstdc++, and turns the wrapper's NULL_POINTER failure into SQL NULL (the C entry anofox_ts_stats itself keeps
+    the `length == 0` rule: counts 0, floats NaN).  Else the STRUCT as a dict; expected_length / n_gaps are None."""
+    if values is None or len(values) == 0:
+        return None
+    v, ok = _stats_cells(list(values))
+    return stats_batch([v], [ok])[0]
+
+
+def _ts_stats_with_dates(values, dates, frequency):
+    """The scalar _ts_stats_with_dates(values, dates, frequency) (ts_stats.cpp TsStatsWithDatesFunction): None when an argument is
+    NULL or the value list is empty (see _ts_stats).  The frequency goes through parse_frequency and frequency_for_stats and then
+    the FIXED rule -- this scalar never passes the calendar type, so '1mo' counts steps of 30 days.  `dates`: int64 microseconds or
+    datetime64; a NULL date element (None / NaT) counts as 0, as ExtractListTimestamps stores it."""
+    if values is None or dates is None or frequency is None or len(values) == 0:
+        return None
+    micros, _ = frequency_for_stats(frequency)
+    v, ok = _stats_cells(list(values))
+    return stats_batch([v], [ok], [_stats_dates(dates)], micros, "FIXED")[0]
+
+
+def _stats_dates(dates):
+    d = np.asarray(dates)
+    if np.issubdtype(d.dtype, np.datetime64):
+        us = d.astype("datetime64[us]").astype(np.int64)
+        return np.where(np.isnat(d), 0, us)
+    if d.dtype == object:
+        return np.array([0 if x is None else int(np.datetime64(x, "us").astype(np.int64)) if not isinstance(x, (int, np.integer)) else int(x)
+                         for x in d], dtype=np.int64)
+    return d.astype(np.int64)
+
+
+def _stats_groups(group, date, value, sort_by_date):
+    """Groups in first-arrival order with their rows; a NULL value is an invalid slot and a NaN stays a valid NaN (unlike
+    _collect_groups, which is for the forecasting macros)."""
+    dates = np.asarray(date)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), dtype=bool)
+    us = _to_micros(np.where(null_date, np.datetime64(0, np.datetime_data(dates.dtype)[0]), dates) if null_date.any() else dates,
+                    _date_kind(dates))
+    vals, vnull = _changepoint_values(value)
+    grp = np.asarray(group, dtype=object)
+    order, rows = [], {}
+    for i in range(len(grp)):
+        if not sort_by_date and null_date[i]:
+            continue                                     # ts_stats_by drops rows with a NULL date (ts_stats.cpp:565)
+        if grp[i] not in rows:
+            rows[grp[i]] = []
+            order.append(grp[i])
+        rows[grp[i]].append(i)
+    series, valids, stamps = [], [], []
+    for k in order:
+        idx = np.array(rows[k])
+        if sort_by_date:                                 # LIST(... ORDER BY date_col): ascending, NULLS LAST, stable
+            idx = idx[np.lexsort((us[idx], null_date[idx]))]
+        series.append(vals[idx])
+        valids.append(~vnull[idx])
+        stamps.append(np.where(null_date[idx], 0, us[idx]))
+    return order, series, valids, stamps
+
+
+def _stats_table(name, order, res):
+    out = {name: list(order)}
+    for f in STATS_FIELDS:
+        out[f] = [r[f] for r in res]
+    return out
+
+
+def ts_stats(group, date, value, frequency, group_name="id"):
+    """The macro ts_stats(source, group_col, date_col, value_col, frequency) (ts_macros.cpp:31-83): per group the values and the
+    dates ordered by date, then _ts_stats_with_dates -- so a calendar frequency is counted by the FIXED rule with 30 / 90 / 365
+    days.  All groups go to the GPU in one stats_batch call.  Returns a dict of columns: the group column and the 36 figures
+    (lists; None = NULL)."""
+    micros, _ = frequency_for_stats(frequency)
+    order, series, valids, stamps = _stats_groups(group, date, value, True)
+    return _stats_table(group_name, order, stats_batch(series, valids, stamps, micros, "FIXED") if order else [])
+
+
+def ts_stats_by(group, date, value, frequency, group_name="id"):
+    """ts_stats_by(source, group_col, date_col, value_col, frequency) (_ts_stats_by_native, ts_stats.cpp:337-800).  Rows with a
+    NULL date are dropped, a NULL value is an invalid slot, groups appear in first-arrival order and a group's rows STAY IN
+    ARRIVAL ORDER (the source sorts only the dates, inside the core), so the order-dependent figures differ from ts_stats on rows
+    that arrive out of date order.  The calendar type of the frequency is passed on; the group column keeps the caller's name.
+    One stats_batch call for all groups (the reference walks them in one thread).  Returns a dict of columns."""
+    micros, ftype = frequency_for_stats(frequency)
+    order, series, valids, stamps = _stats_groups(group, date, value, False)
+    return _stats_table(group_name, order, stats_batch(series, valids, stamps, micros, ftype) if order else [])
+
+
+def ts_stats_agg(ts, value):
+    """The aggregate ts_stats_agg(ts, value) over ONE group (ts_stats_agg.cpp): rows with a NULL timestamp or value are skipped,
+    the rest ordered by (timestamp, value), all valid, no date figures.  None when no row is left."""
+    dates = np.asarray(ts)
+    vals, vnull = _changepoint_values(value)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), dtype=bool)
+    keep = np.nonzero(~(null_date | vnull))[0]
+    if len(keep) == 0:
+        return None
+    us = _to_micros(dates[keep], _date_kind(dates))
+    v = vals[keep]
+    return stats_batch([v[np.lexsort((v, us))]])[0]
+
+
+def ts_quality_report(stats, min_length):
+    """The macro ts_quality_report(stats_table, min_length) (ts_macros.cpp:90-99) over a table of ts_stats / ts_stats_by columns.
+    Host only.  SUM over no rows is NULL (None), COUNT is 0."""
+    n = len(stats["length"])
+    if n == 0:
+        return {"n_passed": None, "n_nan_issues": None, "n_missing_issues": None, "n_constant": None, "n_total": 0}
+    return {"n_passed": sum(1 for l, c in zip(stats["length"], stats["is_constant"]) if l >= min_length and not c),
+            "n_nan_issues": sum(1 for x in stats["n_nan"] if x > 0),
+            "n_missing_issues": sum(1 for x in stats["n_nulls"] if x > 0),
+            "n_constant": sum(1 for c in stats["is_constant"] if c),
+            "n_total": n}
+
+
+def ts_stats_summary(stats):
+    """The macro ts_stats_summary(stats_table) (ts_macros.cpp:106-116).  Host only."""
+    ln = list(stats["length"])
+    n = len(ln)
+    if n == 0:
+        return {"n_series": 0, "avg_length": None, "min_length": None, "max_length": None, "total_nulls": None, "total_nans": None}
+    return {"n_series": n, "avg_length": sum(ln) / n, "min_length": min(ln), "max_length": max(ln),
+            "total_nulls": sum(stats["n_nulls"]), "total_nans": sum(stats["n_nan"])}
+
+
+anofox_fcst_ts_stats_agg = ts_stats_agg
+
+
+# --------------------------------------------------------------------------------------------
 # exogenous regressors (ARIMAX): anofox_ts_forecast_exog_batch and the mirrors of _ts_forecast_exog / ts_forecast_exog_by
 # --------------------------------------------------------------------------------------------
 def forecast_exog_batch(series, xregs, futures, opts, valids=None):

@@ -3757,6 +3757,180 @@ void anofox_free_bocpd_result(BocpdResult *result)
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Per-series statistics (stats.rs compute_ts_stats_with_dates_and_type; stats.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(TsStatsResult) == 296 && offsetof(TsStatsResult, n_zeros_start) == 64 && offsetof(TsStatsResult, mean) == 96 &&
+              offsetof(TsStatsResult, expected_length) == 272 && offsetof(TsStatsResult, has_date_metrics) == 288, "TsStatsResult layout");
+
+bool anofox_hip_stats_device(const double *y, const uint8_t *valid, const int64_t *dates, size_t ld, const int32_t *lengths, size_t n_series,
+                             size_t t_rows, int64_t frequency_micros, FrequencyType frequency_type, int64_t *out_int, double *out_fp,
+                             void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !out_int || !out_fp) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if ((int)frequency_type < STATS_FREQ_FIXED || (int)frequency_type > STATS_FREQ_YEARLY) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: unknown frequency type");
+        return false;
+    }
+    if (!device_ready(out_error)) return false;
+    StatsArgs a{};
+    a.y = y; a.valid = valid; a.dates = dates; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.freq_us = frequency_micros; a.freq_type = (int)frequency_type;
+    a.out_int = out_int; a.out_fp = out_fp;
+    a.work_stride = stats_work_stride(t_rows);
+    a.work_waves = a.work_stride ? stats_work_waves((int)n_series) : 0;
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *work = nullptr;
+    try {
+        (void)hipGetLastError();
+        if (a.work_stride && a.work_waves > 0) work = dalloc<uint64_t>(a.work_stride * (size_t)a.work_waves);
+        a.work = work;
+        launch_stats(a, st);
+        LAUNCHCHECK("stats");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(work, true);
+    } catch (const HipFail &f) {
+        dev_free(work, false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_stats_batch(const double *const *values, const uint64_t *const *validity, const int64_t *const *dates, const size_t *lengths,
+                            size_t n_series, int64_t frequency_micros, FrequencyType frequency_type, TsStatsResult *out_results,
+                            AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_series > 0 && (!values || !lengths || !out_results)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    size_t t_max = 0;
+    bool any_mask = false, any_dates = false;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        t_max = std::max(t_max, lengths[s]);
+        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
+        any_dates = any_dates || (dates && dates[s] && lengths[s] > 0);
+    }
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    double *d_y = nullptr, *d_fp = nullptr;
+    uint8_t *d_valid = nullptr;
+    int64_t *d_dates = nullptr, *d_int = nullptr;
+    int32_t *d_len = nullptr;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_valid, (void *)d_dates, (void *)d_int, (void *)d_len}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<int64_t> oi(STATS_N_INT * ld);
+    std::vector<double> of(STATS_N_FP * ld);
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
+        std::vector<int64_t> db(any_dates ? T * ld : 0, 0);
+        std::vector<int32_t> len(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            const uint64_t *m = validity ? validity[s] : nullptr;
+            const int64_t *d = dates ? dates[s] : nullptr;
+            for (size_t t = 0; t < lengths[s]; t++) {
+                yb[t * ld + s] = values[s][t];
+                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
+                if (d) db[t * ld + s] = d[t];
+            }
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
+        d_int = dalloc<int64_t>(STATS_N_INT * ld); d_fp = dalloc<double>(STATS_N_FP * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (any_mask) {
+            d_valid = dalloc<uint8_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+        }
+        if (any_dates) {
+            d_dates = dalloc<int64_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_dates, db.data(), T * ld * sizeof(int64_t), hipMemcpyHostToDevice));
+        }
+        if (!anofox_hip_stats_device(d_y, d_valid, d_dates, ld, d_len, n_series, T, frequency_micros, frequency_type, d_int, d_fp, nullptr,
+                                     out_batch_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++) {
+        TsStatsResult &r = out_results[s];
+        std::memset(&r, 0, sizeof r);
+        size_t *cnt[12] = {&r.length, &r.n_nulls, &r.n_nan, &r.n_zeros, &r.n_positive, &r.n_negative, &r.n_unique_values, nullptr,
+                           &r.n_zeros_start, &r.n_zeros_end, &r.plateau_size, &r.plateau_size_nonzero};
+        for (int i = 0; i < 12; i++)
+            if (cnt[i]) *cnt[i] = (size_t)oi[i * ld + s];
+        r.is_constant = oi[7 * ld + s] != 0;
+        double *fp = &r.mean;                                     // 22 consecutive doubles, mean .. stability
+        for (int i = 0; i < STATS_N_FP; i++) fp[i] = of[i * ld + s];
+        // has_date_metrics as the source sets it (stats.rs:322-359): dates given, and not the FIXED rule with a frequency <= 0 on
+        // two or more dates
+        const size_t n = lengths[s];
+        const bool dated = dates && dates[s] && n > 0 && (n < 2 || frequency_type != FIXED || frequency_micros > 0);
+        r.has_date_metrics = dated;
+        r.expected_length = dated ? (size_t)oi[12 * ld + s] : 0;
+        r.n_gaps = dated ? (size_t)oi[13 * ld + s] : 0;
+    }
+    return true;
+}
+
+bool anofox_ts_stats_with_dates_and_type(const double *values, const uint64_t *validity, const int64_t *dates, size_t length,
+                                         int64_t frequency_micros, FrequencyType frequency_type, TsStatsResult *out_result,
+                                         AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !dates || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const double *v[1] = {values};
+    const uint64_t *m[1] = {validity};
+    const int64_t *d[1] = {dates};
+    const size_t len[1] = {length};
+    return anofox_hip_stats_batch(v, m, d, len, 1, frequency_micros, frequency_type, out_result, out_error);
+}
+
+bool anofox_ts_stats_with_dates(const double *values, const uint64_t *validity, const int64_t *dates, size_t length, int64_t frequency_micros,
+                                TsStatsResult *out_result, AnofoxError *out_error)
+{
+    return anofox_ts_stats_with_dates_and_type(values, validity, dates, length, frequency_micros, FIXED, out_result, out_error);
+}
+
+bool anofox_ts_stats(const double *values, const uint64_t *validity, size_t length, TsStatsResult *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const double *v[1] = {values};
+    const uint64_t *m[1] = {validity};
+    const size_t len[1] = {length};
+    return anofox_hip_stats_batch(v, m, nullptr, len, 1, 0, FIXED, out_result, out_error);
+}
+
+void anofox_free_ts_stats_result(TsStatsResult *result) { (void)result; }      // the struct owns no memory (as the reference's)
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Exogenous regressors: ARIMAX (forecast.rs forecast_with_exog; fit_exog.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 } // extern "C"

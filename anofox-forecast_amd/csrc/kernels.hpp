@@ -218,6 +218,25 @@ struct ChangepointArgs {
 };
 void launch_bocpd(const ChangepointArgs &, hipStream_t);
 
+// Per-series statistics (stats.rs compute_ts_stats_with_dates_and_type; stats.hip)
+constexpr int STATS_RESIDENT = 2048;     // rows of the longest series that is sorted in LDS; longer ones use the global workspace
+constexpr int STATS_WORK_WAVES = 1024;   // waves (and workspace slices) that walk the longer series
+constexpr int STATS_N_INT = 14, STATS_N_FP = 22;
+constexpr int STATS_FREQ_FIXED = 0, STATS_FREQ_MONTHLY = 1, STATS_FREQ_QUARTERLY = 2, STATS_FREQ_YEARLY = 3;
+struct StatsArgs {
+    const double *y; const uint8_t *valid; const int64_t *dates;      // [t_rows x ld]; valid and dates may be null
+    size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    int64_t freq_us; int freq_type;
+    int64_t *out_int;            // [STATS_N_INT x ld] the 12 counts in struct order, expected_length, n_gaps (-1: no date figures)
+    double *out_fp;              // [STATS_N_FP x ld] mean .. stability in struct order
+    uint64_t *work;              // [work_waves x work_stride] or null when t_rows <= STATS_RESIDENT
+    size_t work_stride; int work_waves;
+};
+size_t stats_work_stride(size_t t_rows);  // words per workspace slice (0: no workspace needed)
+int stats_work_waves(int n_series);
+void launch_stats(const StatsArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

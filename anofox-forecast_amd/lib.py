@@ -113,6 +113,22 @@ class BocpdResult(C.Structure):
     ]
 
 
+class TsStatsResult(C.Structure):
+    """include/anofox_fcst_hip.h TsStatsResult: 36 figures and has_date_metrics (296 bytes)."""
+    _fields_ = ([(n, C.c_size_t) for n in ("length", "n_nulls", "n_nan", "n_zeros", "n_positive", "n_negative", "n_unique_values")]
+                + [("is_constant", C.c_bool)]
+                + [(n, C.c_size_t) for n in ("n_zeros_start", "n_zeros_end", "plateau_size", "plateau_size_nonzero")]
+                + [(n, C.c_double) for n in ("mean", "median", "std_dev", "variance", "min", "max", "range", "sum", "skewness",
+                                             "kurtosis", "tail_index", "bimodality_coef", "trimmed_mean", "coef_variation", "q1", "q3",
+                                             "iqr", "autocorr_lag1", "trend_strength", "seasonality_strength", "entropy", "stability")]
+                + [("expected_length", C.c_size_t), ("n_gaps", C.c_size_t), ("has_date_metrics", C.c_bool)])
+
+
+FREQUENCY_TYPES = {"FIXED": 0, "MONTHLY": 1, "QUARTERLY": 2, "YEARLY": 3}      # include/anofox_fcst_hip.h FrequencyType
+STATS_INT_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[:12])
+STATS_FP_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[12:34])
+
+
 class ExogenousRegressor(C.Structure):
     _fields_ = [("values", C.POINTER(C.c_double)), ("n_values", C.c_size_t),
                 ("future_values", C.POINTER(C.c_double)), ("n_future", C.c_size_t)]
@@ -168,6 +184,8 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_mstl_decomposition", "anofox_free_mstl_result", "anofox_hip_mstl_decompose_batch", "anofox_hip_mstl_decompose_device",
     "anofox_ts_forecast_exog", "anofox_ts_forecast_exog_batch", "anofox_hip_batch_set_exog_device", "anofox_hip_batch_exog_coefficients",
     "anofox_ts_detect_changepoints_bocpd", "anofox_free_bocpd_result", "anofox_hip_changepoints_batch", "anofox_hip_changepoints_device",
+    "anofox_ts_stats", "anofox_ts_stats_with_dates", "anofox_ts_stats_with_dates_and_type", "anofox_free_ts_stats_result",
+    "anofox_hip_stats_batch", "anofox_hip_stats_device",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -273,6 +291,20 @@ def load():
     L.anofox_hip_changepoints_device.restype = C.c_bool
     L.anofox_hip_changepoints_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_stats.restype = C.c_bool
+    L.anofox_ts_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(TsStatsResult), P(AnofoxError)]
+    L.anofox_ts_stats_with_dates.restype = C.c_bool
+    L.anofox_ts_stats_with_dates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, P(TsStatsResult), P(AnofoxError)]
+    L.anofox_ts_stats_with_dates_and_type.restype = C.c_bool
+    L.anofox_ts_stats_with_dates_and_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int, P(TsStatsResult),
+                                                      P(AnofoxError)]
+    L.anofox_free_ts_stats_result.argtypes = [P(TsStatsResult)]
+    L.anofox_hip_stats_batch.restype = C.c_bool
+    L.anofox_hip_stats_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int, C.c_void_p,
+                                         P(AnofoxError)]
+    L.anofox_hip_stats_device.restype = C.c_bool
+    L.anofox_hip_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

@@ -164,6 +164,65 @@ bool anofox_ts_detect_changepoints_bocpd(const double *values,
 
 void anofox_free_bocpd_result(struct BocpdResult *result);
 
+/* How a frequency is counted in the date figures of the statistics (the reference's FrequencyType). */
+typedef enum FrequencyType {
+    FIXED = 0,     /* a fixed number of microseconds */
+    MONTHLY = 1,   /* calendar months */
+    QUARTERLY = 2, /* calendar quarters */
+    YEARLY = 3     /* calendar years */
+} FrequencyType;
+
+/*
+ * The 36 per-series figures of ts_stats (layout of the reference's anofox_fcst_ffi.h: sizeof == 296, n_zeros_start at 64, mean
+ * at 96, expected_length at 272, has_date_metrics at 288).  Holds no pointer; anofox_free_ts_stats_result exists for symmetry.
+ */
+typedef struct TsStatsResult {
+    size_t length, n_nulls, n_nan, n_zeros, n_positive, n_negative, n_unique_values;
+    bool is_constant;
+    size_t n_zeros_start, n_zeros_end, plateau_size, plateau_size_nonzero;
+    double mean, median, std_dev, variance, min, max, range, sum, skewness, kurtosis, tail_index, bimodality_coef, trimmed_mean,
+           coef_variation, q1, q3, iqr, autocorr_lag1, trend_strength, seasonality_strength, entropy, stability;
+    size_t expected_length, n_gaps; /* 0 unless has_date_metrics */
+    bool has_date_metrics;
+} TsStatsResult;
+
+/*
+ * Statistics of ONE series, the reference's compute_ts_stats / compute_ts_stats_with_dates_and_type (stats.rs) behind its FFI
+ * wrappers.  `validity` (bit i of word i / 64; NULL = all valid) marks NULLs; NULLs and NaNs are counted and dropped, every
+ * other figure is computed on the remaining values in arrival order (infinities are ordinary values).  NULL `values`, `dates`
+ * or `out_result`: NULL_POINTER.  length == 0: every count 0, every floating figure NaN, no date figures, and true.  A series
+ * with no valid value: length, n_nulls, n_nan set, every other count 0 and every floating figure 0.0.  Date figures
+ * (has_date_metrics): the dates are sorted inside the call; FIXED counts (last - first) / frequency_micros + 1 and a gap is a
+ * step above (int64)(1.5 * frequency_micros), nothing is set when frequency_micros <= 0 and there are at least two dates; the
+ * calendar types count month, quarter or year numbers of the UTC date.  anofox_ts_stats_with_dates is the FIXED rule.  Counts,
+ * min, max, range, median, q1, q3, iqr are exact; the figures that are sums meet the reference within the data's own rounding
+ * noise.  Each runs on the GPU as a batch of one.
+ */
+bool anofox_ts_stats(const double *values,
+                     const uint64_t *validity,
+                     size_t length,
+                     struct TsStatsResult *out_result,
+                     struct AnofoxError *out_error);
+
+bool anofox_ts_stats_with_dates(const double *values,
+                                const uint64_t *validity,
+                                const int64_t *dates,
+                                size_t length,
+                                int64_t frequency_micros,
+                                struct TsStatsResult *out_result,
+                                struct AnofoxError *out_error);
+
+bool anofox_ts_stats_with_dates_and_type(const double *values,
+                                         const uint64_t *validity,
+                                         const int64_t *dates,
+                                         size_t length,
+                                         int64_t frequency_micros,
+                                         enum FrequencyType frequency_type,
+                                         struct TsStatsResult *out_result,
+                                         struct AnofoxError *out_error);
+
+void anofox_free_ts_stats_result(struct TsStatsResult *result);
+
 /* One exogenous regressor: `values[n_values]` aligned with the series, `future_values[n_future]` with the horizon. */
 typedef struct ExogenousRegressor {
     const double *values;
@@ -352,6 +411,46 @@ bool anofox_hip_changepoints_device(const double *y,
                                     int32_t *counts,
                                     void *stream,
                                     struct AnofoxError *out_error);
+
+/*
+ * Statistics of `n_series` series in one GPU pass (per series the semantics of anofox_ts_stats_with_dates_and_type).  Replaces
+ * the single-threaded per-group loop of the reference's _ts_stats_by_native finalize.  `validity` and `dates` may be NULL, and so
+ * may validity[i] (all valid) and dates[i] (no date figures for series i).  out_results is TsStatsResult[n_series].  No
+ * per-series failure exists; the return value is false only for batch-level failures (NULL pointers, no GPU), also reported
+ * through `out_batch_error`.  Runs on the calling thread's current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_stats_batch(const double *const *values,
+                            const uint64_t *const *validity,
+                            const int64_t *const *dates,
+                            const size_t *lengths,
+                            size_t n_series,
+                            int64_t frequency_micros,
+                            enum FrequencyType frequency_type,
+                            struct TsStatsResult *out_results,
+                            struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows), lengths[n_series] (int32; a length above
+ * t_rows is cut to it) and the outputs are device pointers.  `valid` (uint8 [t_rows x ld], 0 = NULL) and `dates` (int64
+ * [t_rows x ld], microseconds) may be NULL.  out_int is int64 [14 x ld]: the 12 counts in struct order (is_constant as 0 / 1), then
+ * expected_length and n_gaps (both -1 without date figures); out_fp is fp64 [22 x ld], mean to stability in struct order.
+ * Columns s >= n_series are left untouched.  One wavefront per series: a series of at most 2,048 rows is sorted in LDS, a longer
+ * one in a workspace in global memory that the call allocates (slower, the same figures).  The same bits on every run and
+ * through every entry.  Runs on `stream` (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_stats_device(const double *y,
+                             const uint8_t *valid,
+                             const int64_t *dates,
+                             size_t ld,
+                             const int32_t *lengths,
+                             size_t n_series,
+                             size_t t_rows,
+                             int64_t frequency_micros,
+                             enum FrequencyType frequency_type,
+                             int64_t *out_int,
+                             double *out_fp,
+                             void *stream,
+                             struct AnofoxError *out_error);
 
 /*
  * Multi-device execution of the batch entry.  The reference's finalize loop is ONE process walking all groups
