@@ -621,11 +621,12 @@ def inspect_batch(series, opts, valids=None):
             if d["ok"]:
                 d.update(_result_dict(results[i], len(arrs[i])))
                 L.anofox_free_forecast_result(C.byref(results[i]))
-                x = insp[i]
-                d.update({k: getattr(x, k) for k in ("model_code", "alpha", "beta", "gamma", "phi", "aic", "aicc", "bic", "sse", "level", "trend")})
-                d["has_constant"] = bool(x.reserved)
-                d["fitted_values"] = fitted[i, :len(arrs[i])].copy()
-                d["seasonal_states"] = seas[i].copy()
+            # the inspection record of a series that failed is the run's own code and status beside NaN fields
+            x = insp[i]
+            d.update({k: getattr(x, k) for k in ("model_code", "status", "alpha", "beta", "gamma", "phi", "aic", "aicc", "bic", "sse", "level", "trend")})
+            d["has_constant"] = bool(x.reserved)
+            d["fitted_values"] = fitted[i, :len(arrs[i])].copy()
+            d["seasonal_states"] = seas[i].copy()
             out.append(d)
         return out
     finally:

@@ -593,7 +593,8 @@ __device__ __forceinline__ void ets_pass(const SeriesView &v, const EtsInit &in,
     if constexpr (FINAL) {
         if (fin->sse_out && v.len > 0) *fin->sse_out = st[0].sse;
         if (fin->var_out) *fin->var_out = var_acc;
-        if (fin->states && v.len > 0) { fin->states[0] = st[0].l; fin->states[fin->states_ld] = st[0].b; }
+        // (a spec without a trend has no growth state: NaN, like its beta)
+        if (fin->states && v.len > 0) { fin->states[0] = st[0].l; fin->states[fin->states_ld] = Cfg::T != C_NONE ? st[0].b : __builtin_nan(""); }
     }
 }
 

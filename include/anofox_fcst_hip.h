@@ -664,8 +664,8 @@ bool anofox_hip_batch_fetch(AnofoxHipBatch *batch,
  * Fit-state snapshot of a batch that has been run (what ts_forecast_inspect_by /
  * ts_forecast_explain_by read out of a fitted model, forecast.rs:1739-1885, 1899-2017).  For AutoETS and ETS(spec):
  * the smoothing parameters in the model's own terms (beta = alpha beta*, gamma = gamma* (1 - alpha); NaN where the
- * spec has no such component), AIC / AICc / BIC, SSE, the final level and growth, optionally the final seasonal states
- * by phase (`seasonal`, row stride `seasonal_stride` >= period) and the one-step fitted values (`fitted`, [n_series x
+ * spec has no such component), AIC / AICc / BIC, SSE, the final level and growth (growth NaN without a trend), optionally the
+ * final seasonal states by phase (`seasonal`, row stride `seasonal_stride` >= period) and the one-step fitted values (`fitted`, [n_series x
  * t_max] row-major, NaN past a series' length).  A second streamed pass per candidate spec on the device produces
  * them; series that took the fallback chain, and every other model, report NaN (AutoARIMA reports its AICc; its orders
  * are in model_code).  The batch must have one seasonal period.

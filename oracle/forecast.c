@@ -840,7 +840,7 @@ int oracle_ets_inspect(const double *y, int n, int period, int pool, int spec_id
     par8[2] = sp.season != ETS_NONE ? fit.gamma_star * (1.0 - fit.alpha) : NAN;
     par8[3] = sp.damped ? fit.phi : NAN;
     par8[4] = fit.aic; par8[5] = fit.aicc; par8[6] = fit.bic; par8[7] = fit.sse;
-    states[0] = fit.l; states[1] = fit.b;
+    states[0] = fit.l; states[1] = sp.trend != ETS_NONE ? fit.b : NAN;     /* no growth state without a trend, like beta */
     if (sp.season != ETS_NONE) for (int j = 0; j < sp.m; j++) states[2 + j] = sfin[j];
     return best;
 }

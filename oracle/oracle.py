@@ -178,7 +178,7 @@ def ets_inspect(values, period, spec_id=-1, pool=0):
     L.oracle_ets_inspect.restype = C.c_int
     L.oracle_ets_inspect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     par = np.zeros(8)
-    states = np.full(2 + 64, np.nan)
+    states = np.full(2 + max(int(period), 1), np.nan)
     fitted = np.full(len(y), np.nan)
     sid = L.oracle_ets_inspect(y.ctypes.data, len(y), int(period), int(pool), int(spec_id), par.ctypes.data, states.ctypes.data, fitted.ctypes.data)
     if sid < 0:
