@@ -1183,6 +1183,229 @@ anofox_fcst_ts_stats_agg = ts_stats_agg
 # --------------------------------------------------------------------------------------------
 # exogenous regressors (ARIMAX): anofox_ts_forecast_exog_batch and the mirrors of _ts_forecast_exog / ts_forecast_exog_by
 # --------------------------------------------------------------------------------------------
+# ------------------------------------------------------------------------------------------------------------------------------
+# Period detection: Lomb-Scargle, AIC comparison, SAZED (the other ten methods of the reference are errors here)
+# ------------------------------------------------------------------------------------------------------------------------------
+_PERIOD_ALIASES = {  # PeriodMethod::from_str (periods.rs:47-68); everything else, unknown strings included, is one of the other ten
+    "lombscargle": "lomb_scargle", "lomb_scargle": "lomb_scargle", "lomb-scargle": "lomb_scargle", "ls": "lomb_scargle",
+    "aic": "aic", "aic_comparison": "aic", "sazed": "sazed", "zero_padded": "sazed", "enhanced_dft": "sazed"}
+_PERIOD_OTHERS = {
+    "fft": "fft", "periodogram": "fft", "acf": "acf", "autocorrelation": "acf", "regression": "regression", "fourier": "regression",
+    "multi": "multi", "multiple": "multi", "auto": "auto", "autoperiod": "autoperiod", "ap": "autoperiod", "cfd": "cfd_autoperiod",
+    "cfdautoperiod": "cfd_autoperiod", "cfd_autoperiod": "cfd_autoperiod", "ssa": "ssa", "singular_spectrum": "ssa", "stl": "stl",
+    "stl_period": "stl", "seasonal_trend": "stl", "matrix_profile": "matrix_profile", "matrixprofile": "matrix_profile",
+    "mp": "matrix_profile"}
+
+
+def period_method(method) -> str:
+    """The canonical name of one of the three methods of this backend; every other method of the reference -- the default 'fft' and
+    the unknown-string fallback to it included -- raises the not-implemented error instead of falling back."""
+    m = "fft" if method is None else str(method).lower()
+    if m in _PERIOD_ALIASES:
+        return _PERIOD_ALIASES[m]
+    raise InvalidInputException(f"Internal error: period detection method '{_PERIOD_OTHERS.get(m, 'fft')}' is not implemented by the HIP backend")
+
+
+def _size_t(v):
+    """static_cast<size_t> of a BIGINT argument (a negative one wraps, as in ts_periods.cpp); None is 0, the default."""
+    return 0 if v is None else int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+def periods_batch(series, method, min_period=None, max_period=None, n_frequencies=None, n_candidates=None, zero_pad_factor=None):
+    """anofox_hip_periods_batch over a list of 1-D arrays: ONE method ('lomb_scargle' | 'aic' | 'sazed' or an alias) and one
+    parameter set for the call; None, zero or below means the source's default.  The grid parameter is n_frequencies, n_candidates
+    or zero_pad_factor according to the method.  Per series a dict: ok, code, message, index (the selected frequency, candidate or
+    DFT bin; -1: none) and the method's figures (lib.PERIOD_FIGURES; NaN where the series failed)."""
+    name = period_method(method)
+    grid = {"lomb_scargle": n_frequencies, "aic": n_candidates, "sazed": zero_pad_factor}[name]
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    fig = np.full((_lib.PERIODS_N_FP, max(n, 1)), np.nan)
+    idx = np.full(max(n, 1), -1, dtype=np.int32)
+    errs = (_lib.AnofoxError * max(n, 1))()
+    berr = _lib.AnofoxError()
+    lo = 0.0 if min_period is None else float(min_period)
+    hi = 0.0 if max_period is None else float(max_period)
+    if name == "sazed":      # size_t arguments of the single entry, carried as doubles
+        lo, hi = float(_size_t(min_period)), float(_size_t(max_period))
+    ok = L.anofox_hip_periods_batch(vals, lens.ctypes.data, n, _lib.PERIOD_METHODS[name], lo, hi, _size_t(grid), fig.ctypes.data,
+                                    idx.ctypes.data, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    for i in range(n):
+        r = {"ok": errs[i].code == _lib.SUCCESS, "code": int(errs[i].code), "message": errs[i].message.decode(errors="replace"),
+             "index": int(idx[i]), "method": name}
+        for j, f in enumerate(_lib.PERIOD_FIGURES[name]):
+            r[f] = float(fig[j, i])
+        out.append(r)
+    return out
+
+
+def _list_values(values):
+    """ExtractListAsDouble (ts_periods.cpp:22-48): the list's non-NULL elements, in order."""
+    return np.array([float(v) for v in values if v is not None and v is not np.ma.masked], dtype=np.float64)
+
+
+def _period_scalar(values, name, needed, lo, hi, grid):
+    if values is None:
+        return None
+    vals = _list_values(values)
+    if len(vals) < needed:
+        return None
+    kw = {"lomb_scargle": "n_frequencies", "aic": "n_candidates", "sazed": "zero_pad_factor"}[name]
+    r = periods_batch([vals], name, lo, hi, **{kw: grid})[0]
+    if not r["ok"]:
+        return None
+    out = {f: r[f] for f in _lib.PERIOD_FIGURES[name]}
+    out["method"] = name
+    return out
+
+
+def ts_lomb_scargle(values, min_period=None, max_period=None, n_frequencies=None):
+    """The scalar ts_lomb_scargle(values[, min_period[, max_period[, n_frequencies]]]) (ts_periods.cpp:1026-1123): None for a NULL
+    list and for fewer than 4 non-NULL values (NULL elements are dropped); a NULL or zero argument is the default.  Else the
+    STRUCT(period, frequency, power, false_alarm_prob, method) as a dict."""
+    return _period_scalar(values, "lomb_scargle", 4, min_period, max_period, n_frequencies)
+
+
+def ts_aic_period(values, min_period=None, max_period=None, n_candidates=None):
+    """The scalar ts_aic_period(values[, min_period[, max_period[, n_candidates]]]) (ts_periods.cpp:1151-1244): None for a NULL list
+    and for fewer than 8 non-NULL values.  Else STRUCT(period, aic, bic, rss, r_squared, method) as a dict."""
+    return _period_scalar(values, "aic", 8, min_period, max_period, n_candidates)
+
+
+def ts_sazed_period(values, min_period=None, max_period=None, zero_pad_factor=None):
+    """The scalar ts_sazed_period(values[, min_period[, max_period[, zero_pad_factor]]]) (ts_periods.cpp:1599-1690; BIGINT
+    arguments): None for a NULL list, for fewer than 8 non-NULL values (the function's own check) and when the call fails (fewer
+    than 16, or a padded length above the backend's limit).  Else STRUCT(period, power, snr, method) as a dict."""
+    return _period_scalar(values, "sazed", 8, min_period, max_period, zero_pad_factor)
+
+
+_PERIOD_NEEDED = {"lomb_scargle": 4, "aic": 8, "sazed": 16}
+
+
+def _detected_periods(r, min_confidence, expected_periods, tolerance):
+    """detect_periods_with_validation (periods.rs:1438-1520, 1651-1686, 1741-1758) on the figures of one series: the result STRUCT
+    of _ts_detect_periods as a dict."""
+    name = r["method"]
+    period = r["period"]
+    if name == "lomb_scargle":
+        confidence, strength = 1.0 - r["false_alarm_prob"], r["power"]
+    elif name == "aic":
+        confidence, strength = r["r_squared"], r["r_squared"]
+    else:
+        snr = r["snr"]
+        confidence, strength = (1.0 if snr != snr else min(snr, 1.0)), r["power"]      # f64::min returns the other operand for a NaN
+    mc = -1.0 if min_confidence is None else float(min_confidence)
+    threshold = 0.3 if (mc < 0.0 or mc != mc) else mc
+    if threshold > 0.0 and not confidence >= threshold:
+        return {"periods": [], "n_periods": 0, "primary_period": 0.0, "method": f"{name} (no seasonality)"}
+    matches, matched, deviation = False, None, None
+    if expected_periods:
+        tol = -1.0 if tolerance is None else float(tolerance)
+        tol = 0.1 if (tol < 0.0 or tol != tol) else tol
+        for e in expected_periods:
+            if e <= 0.0:
+                continue
+            dev = abs(period - e) / e
+            if dev <= tol and (not matches or dev < deviation):
+                matches, matched, deviation = True, float(e), dev
+    one = {"period": period, "confidence": confidence, "strength": strength, "amplitude": 0.0, "phase": 0.0, "iteration": 1,
+           "matches_expected": matches,
+           "matched_expected_period": matched if matches else float("nan"),       # the scalar copies the flat result's NaN
+           "match_deviation": deviation if matches else float("nan")}
+    return {"periods": [one], "n_periods": 1, "primary_period": period, "method": name}
+
+
+def _ts_detect_periods_many(lists, method, max_period, min_confidence, expected_periods, tolerance):
+    """_ts_detect_periods over many lists with one parameter set: every non-NULL list goes to the GPU in ONE batch call."""
+    name = period_method(method)
+    del max_period                      # accepted and, as in the source, not used by these three methods
+    exp = None if expected_periods is None else [float(e) for e in expected_periods if e is not None]
+    rows, series = [], []
+    for v in lists:
+        if v is None:
+            rows.append(None)
+            continue
+        rows.append(len(series))
+        series.append(_list_values(v))
+    res = periods_batch(series, name) if series else []
+    out = []
+    for k in rows:
+        r = None if k is None else res[k]
+        out.append(_detected_periods(r, min_confidence, exp, tolerance) if r is not None and r["ok"] else None)
+    return out
+
+
+def _ts_detect_periods(values, method="fft", max_period=0, min_confidence=-1.0, expected_periods=None, tolerance=-1.0):
+    """The scalar _ts_detect_periods(values[, method[, max_period[, min_confidence[, expected_periods[, tolerance]]]]])
+    (ts_periods.cpp:81-465 over anofox_ts_detect_periods_flat): None for a NULL list and when the detection fails (too few non-NULL
+    values); a NULL method is 'fft'.  Only 'lomb_scargle', 'aic', 'sazed' and their aliases run here: every other method -- the
+    default 'fft' included -- raises the not-implemented error.  Else STRUCT(periods[], n_periods, primary_period, method) as a
+    dict; a period below the confidence threshold (default 0.3, 0 disables) leaves "<method> (no seasonality)"."""
+    return _ts_detect_periods_many([values], method, max_period, min_confidence, expected_periods, tolerance)[0]
+
+
+def _period_params(params):
+    p = params or {}
+    return (p.get("method", "fft"), p.get("max_period", 0), p.get("min_confidence", -1.0), p.get("expected_periods"), p.get("tolerance", -1.0))
+
+
+def _ordered_lists(group, date, value):
+    """LIST(value_col::DOUBLE ORDER BY date_col) per group (first-appearance order of the groups; NULL dates last, stable)."""
+    dates = np.asarray(date)
+    vals, vnull = _changepoint_values(value)
+    if np.issubdtype(dates.dtype, np.datetime64):
+        null_date = np.isnat(dates)
+        key = np.where(null_date, 0, dates.astype(np.int64))
+    else:
+        null_date = np.zeros(len(dates), dtype=bool)
+        key = dates
+    grp = [None] * len(dates) if group is None else list(np.asarray(group, dtype=object))
+    order, members = [], {}
+    for i, g in enumerate(grp):
+        k = "__NULL__" if g is None else g
+        if k not in members:
+            members[k] = []
+            order.append(k)
+        members[k].append(i)
+    lists = []
+    for k in order:
+        idx = np.array(members[k])
+        o = idx[np.lexsort((key[idx], null_date[idx]))]
+        lists.append([None if vnull[i] else float(vals[i]) for i in o])
+    return [None if k == "__NULL__" else k for k in order], lists
+
+
+def ts_detect_periods_by(group, date, value, params=None, group_name="id"):
+    """ts_detect_periods_by(source, group_col, date_col, value_col, params) (macro ts_macros.cpp:1858-1884): per group the values
+    ordered by date go through _ts_detect_periods with params method (default 'fft', which this backend does not implement),
+    max_period, min_confidence, expected_periods and tolerance.  ALL groups go to the GPU in one anofox_hip_periods_batch call (the
+    reference calls its detector once per group).  Returns a dict of columns: <group_name>, periods, n_periods, primary_period,
+    method (lists; None = NULL, the row of a group whose detection failed)."""
+    method, max_period, min_conf, expected, tol = _period_params(params)
+    keys, lists = _ordered_lists(group, date, value)
+    res = _ts_detect_periods_many(lists, method, max_period, min_conf, expected, tol)
+    cols = {group_name: keys}
+    for f in ("periods", "n_periods", "primary_period", "method"):
+        cols[f] = [None if r is None else r[f] for r in res]
+    return cols
+
+
+def ts_detect_periods(date, value, params=None):
+    """ts_detect_periods(source, date_col, value_col, params) (macro ts_macros.cpp:1824-1844): ONE series, one row.  Returns a dict
+    of the columns periods, n_periods, primary_period, method (one-element lists; None = NULL)."""
+    method, max_period, min_conf, expected, tol = _period_params(params)
+    _, lists = _ordered_lists(None, date, value)
+    # an aggregate without GROUP BY over an empty table still gives one row: LIST() is NULL, and so is the result
+    res = _ts_detect_periods_many(lists if lists else [None], method, max_period, min_conf, expected, tol)
+    return {f: [None if r is None else r[f] for r in res] for f in ("periods", "n_periods", "primary_period", "method")}
+
+
 def forecast_exog_batch(series, xregs, futures, opts, valids=None):
     """anofox_ts_forecast_exog_batch over host buffers: xregs[s] / futures[s] are the K historical / future regressor arrays of
     series s (K shared by the batch; lengths len(series[s]) and opts.horizon).  Returns (results, batch_error); a result that

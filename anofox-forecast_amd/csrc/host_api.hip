@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cctype>
 #include <atomic>
 #include <memory>
 #include <unordered_map>
@@ -3929,6 +3930,320 @@ bool anofox_ts_stats(const double *values, const uint64_t *validity, size_t leng
 }
 
 void anofox_free_ts_stats_result(TsStatsResult *result) { (void)result; }      // the struct owns no memory (as the reference's)
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Period detection (periods.rs lomb_scargle, aic_comparison, sazed_period, detect_periods_with_validation; periods.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(LombScargleResultFFI) == 64 && offsetof(LombScargleResultFFI, false_alarm_prob) == 24 &&
+              offsetof(LombScargleResultFFI, method) == 32, "LombScargleResultFFI layout");
+static_assert(sizeof(AicPeriodResultFFI) == 72 && offsetof(AicPeriodResultFFI, r_squared) == 32 && offsetof(AicPeriodResultFFI, method) == 40,
+              "AicPeriodResultFFI layout");
+static_assert(sizeof(SazedPeriodResultFFI) == 56 && offsetof(SazedPeriodResultFFI, snr) == 16 && offsetof(SazedPeriodResultFFI, method) == 24,
+              "SazedPeriodResultFFI layout");
+static_assert(sizeof(FlatMultiPeriodResult) == 120 && offsetof(FlatMultiPeriodResult, iteration_values) == 40 &&
+              offsetof(FlatMultiPeriodResult, n_periods) == 72 && offsetof(FlatMultiPeriodResult, primary_period) == 80 &&
+              offsetof(FlatMultiPeriodResult, method) == 88, "FlatMultiPeriodResult layout");
+
+extern "C++" {
+namespace {
+
+const char *const PERIODS_METHOD_NAME[3] = {"lomb_scargle", "aic", "sazed"};
+constexpr size_t PERIODS_NEEDED[3] = {4, 8, 16};
+
+// PeriodMethod::from_str (periods.rs:47-68): 0 .. 2 the methods of this backend, -1 one of the other ten; `canonical` names it
+int parse_period_method(const char *method, std::string &canonical)
+{
+    std::string m = method ? method : "fft";
+    for (char &c : m) c = (char)std::tolower((unsigned char)c);
+    struct Alias { const char *name; const char *canonical; int id; };
+    static const Alias table[] = {
+        {"fft", "fft", -1}, {"periodogram", "fft", -1}, {"acf", "acf", -1}, {"autocorrelation", "acf", -1},
+        {"regression", "regression", -1}, {"fourier", "regression", -1}, {"multi", "multi", -1}, {"multiple", "multi", -1},
+        {"auto", "auto", -1}, {"autoperiod", "autoperiod", -1}, {"ap", "autoperiod", -1},
+        {"cfd", "cfd_autoperiod", -1}, {"cfdautoperiod", "cfd_autoperiod", -1}, {"cfd_autoperiod", "cfd_autoperiod", -1},
+        {"lombscargle", "lomb_scargle", PERIODS_LOMB_SCARGLE}, {"lomb_scargle", "lomb_scargle", PERIODS_LOMB_SCARGLE},
+        {"lomb-scargle", "lomb_scargle", PERIODS_LOMB_SCARGLE}, {"ls", "lomb_scargle", PERIODS_LOMB_SCARGLE},
+        {"aic", "aic", PERIODS_AIC}, {"aic_comparison", "aic", PERIODS_AIC},
+        {"ssa", "ssa", -1}, {"singular_spectrum", "ssa", -1}, {"stl", "stl", -1}, {"stl_period", "stl", -1}, {"seasonal_trend", "stl", -1},
+        {"matrix_profile", "matrix_profile", -1}, {"matrixprofile", "matrix_profile", -1}, {"mp", "matrix_profile", -1},
+        {"sazed", "sazed", PERIODS_SAZED}, {"zero_padded", "sazed", PERIODS_SAZED}, {"enhanced_dft", "sazed", PERIODS_SAZED},
+    };
+    for (const Alias &a : table)
+        if (m == a.name) { canonical = a.canonical; return a.id; }
+    canonical = "fft";                                             // the source's fallback for an unknown string
+    return -1;
+}
+
+void copy_method(char (&dst)[32], const std::string &src)
+{
+    std::memset(dst, 0, sizeof dst);
+    std::memcpy(dst, src.data(), std::min(src.size(), sizeof dst - 1));
+}
+
+std::string periods_series_error(int method, int32_t status, size_t n)
+{
+    if (status == PERIODS_TOO_SHORT)                               // ForecastError::InsufficientData { needed, got }
+        return "Insufficient data: need at least " + std::to_string(PERIODS_NEEDED[method]) + " observations, got " + std::to_string(n);
+    return "SAZED: the zero-padded length of a series of " + std::to_string(n) + " observations exceeds the limit of " +
+           std::to_string((long long)PERIODS_SAZED_MAX_PADDED) + " of the HIP backend";
+}
+
+// one series through the batch entry; false with out_error set on any failure
+bool periods_single(int method, const double *values, size_t length, double min_period, double max_period, size_t n_grid, double (&fig)[PERIODS_N_FP],
+                    AnofoxError *out_error)
+{
+    AnofoxError serr, berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    int32_t idx = -1;
+    if (!anofox_hip_periods_batch(v, len, 1, method, min_period, max_period, n_grid, fig, &idx, &serr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
+    return true;
+}
+
+} // namespace
+} // extern "C++"
+
+bool anofox_hip_periods_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, int method, double min_period,
+                               double max_period, size_t n_grid, double *figures, int32_t *index, int32_t *status, void *stream,
+                               AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !figures || !index || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (method < PERIODS_LOMB_SCARGLE || method > PERIODS_SAZED) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: unknown period detection method " + std::to_string(method));
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if (method != PERIODS_SAZED && n_grid > (size_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: more than 2147483647 frequencies or candidates");
+        return false;
+    }
+    if (!device_ready(out_error)) return false;
+    PeriodsArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows; a.method = method;
+    a.out_fp = figures; a.out_index = index; a.status = status;
+    if (method == PERIODS_SAZED) {
+        // the wrapper's size_t arguments (lib.rs:1967-1983): zero means the default; values beyond any length act like the largest
+        auto whole = [](double v) { return v > 0.0 ? (int64_t)std::fmin(v, 4e18) : (int64_t)0; };
+        a.s_min = whole(min_period); a.s_max = whole(max_period);
+        a.s_pad = (int64_t)std::min<size_t>(n_grid, (size_t)PERIODS_SAZED_MAX_PADDED + 1);
+        a.work_stride = periods_work_stride(t_rows, a.s_pad);
+        a.work_blocks = periods_work_blocks(a.work_stride, (int)n_series);
+    } else {
+        a.min_period = min_period; a.max_period = max_period;        // > 0.0 or the default (lib.rs:1635-1649, 1707-1721)
+        a.n_grid = n_grid > 0 ? (int64_t)n_grid : (method == PERIODS_LOMB_SCARGLE ? 1000 : 50);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double *work = nullptr;
+    try {
+        (void)hipGetLastError();
+        if (a.work_stride && a.work_blocks > 0) work = dalloc<double>(a.work_stride * (size_t)a.work_blocks);
+        a.work = work;
+        launch_periods(a, st);
+        LAUNCHCHECK("periods");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(work, true);
+    } catch (const HipFail &f) {
+        dev_free(work, false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_periods_batch(const double *const *values, const size_t *lengths, size_t n_series, int method, double min_period, double max_period,
+                              size_t n_grid, double *out_figures, int32_t *out_index, AnofoxError *out_errors, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_series > 0 && (!values || !lengths || !out_figures)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (method < PERIODS_LOMB_SCARGLE || method > PERIODS_SAZED) {
+        set_error(out_batch_error, INVALID_INPUT, "Invalid input: unknown period detection method " + std::to_string(method));
+        return false;
+    }
+    size_t t_max = 0;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)INT32_MAX) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        t_max = std::max(t_max, lengths[s]);
+    }
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    double *d_y = nullptr, *d_fp = nullptr;
+    int32_t *d_len = nullptr, *d_idx = nullptr, *d_st = nullptr;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_len, (void *)d_idx, (void *)d_st}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<double> fp(PERIODS_N_FP * ld);
+    std::vector<int32_t> idx(n_series), status(n_series);
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<int32_t> len(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = values[s][t];
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
+        d_fp = dalloc<double>(PERIODS_N_FP * ld); d_idx = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!anofox_hip_periods_device(d_y, ld, d_len, n_series, T, method, min_period, max_period, n_grid, d_fp, d_idx, d_st, nullptr,
+                                       out_batch_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(fp.data(), d_fp, fp.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(idx.data(), d_idx, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status.data(), d_st, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const int used = method == PERIODS_LOMB_SCARGLE ? 4 : (method == PERIODS_AIC ? 5 : 3);
+    for (size_t s = 0; s < n_series; s++) {
+        const bool ok = status[s] == PERIODS_OK;
+        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        if (!ok && out_errors) set_error(&out_errors[s], COMPUTATION_ERROR, periods_series_error(method, status[s], lengths[s]));
+        for (int j = 0; j < PERIODS_N_FP; j++) out_figures[(size_t)j * n_series + s] = (ok && j < used) ? fp[(size_t)j * ld + s] : nan;
+        if (out_index) out_index[s] = ok ? idx[s] : -1;
+    }
+    return true;
+}
+
+bool anofox_ts_lomb_scargle(const double *values, size_t length, double min_period, double max_period, size_t n_frequencies,
+                            LombScargleResultFFI *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    double fig[PERIODS_N_FP];
+    if (!periods_single(PERIODS_LOMB_SCARGLE, values, length, min_period, max_period, n_frequencies, fig, out_error)) return false;
+    out_result->period = fig[0]; out_result->frequency = fig[1]; out_result->power = fig[2]; out_result->false_alarm_prob = fig[3];
+    copy_method(out_result->method, PERIODS_METHOD_NAME[PERIODS_LOMB_SCARGLE]);
+    return true;
+}
+
+bool anofox_ts_aic_period(const double *values, size_t length, double min_period, double max_period, size_t n_candidates,
+                          AicPeriodResultFFI *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    double fig[PERIODS_N_FP];
+    if (!periods_single(PERIODS_AIC, values, length, min_period, max_period, n_candidates, fig, out_error)) return false;
+    out_result->period = fig[0]; out_result->aic = fig[1]; out_result->bic = fig[2]; out_result->rss = fig[3]; out_result->r_squared = fig[4];
+    copy_method(out_result->method, PERIODS_METHOD_NAME[PERIODS_AIC]);
+    return true;
+}
+
+bool anofox_ts_sazed_period(const double *values, size_t length, size_t min_period, size_t max_period, size_t zero_pad_factor,
+                            SazedPeriodResultFFI *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    double fig[PERIODS_N_FP];
+    // periods beyond 2^53 act like any period beyond the series' length, so the conversion to double loses nothing that matters
+    if (!periods_single(PERIODS_SAZED, values, length, (double)min_period, (double)max_period, zero_pad_factor, fig, out_error)) return false;
+    out_result->period = fig[0]; out_result->power = fig[1]; out_result->snr = fig[2];
+    copy_method(out_result->method, PERIODS_METHOD_NAME[PERIODS_SAZED]);
+    return true;
+}
+
+bool anofox_ts_detect_periods_flat(const double *values, size_t length, const char *method, size_t max_period, double min_confidence,
+                                   const double *expected_periods, size_t n_expected, double tolerance, FlatMultiPeriodResult *out_result,
+                                   AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    (void)max_period;                                              // detect_periods_internal passes it to fft / acf / auto only
+    std::string name;
+    const int m = parse_period_method(method, name);
+    if (m < 0) {
+        set_error(out_error, INTERNAL_ERROR, "Internal error: period detection method '" + name + "' is not implemented by the HIP backend");
+        return false;
+    }
+    double fig[PERIODS_N_FP];
+    if (!periods_single(m, values, length, 0.0, 0.0, 0, fig, out_error)) return false;
+    // one DetectedPeriod per method (periods.rs:1651-1686, 1741-1758)
+    const double period = fig[0];
+    double confidence, strength;
+    if (m == PERIODS_LOMB_SCARGLE) { confidence = 1.0 - fig[3]; strength = fig[2]; }
+    else if (m == PERIODS_AIC) { confidence = fig[4]; strength = fig[4]; }
+    else { confidence = std::fmin(fig[2], 1.0); strength = fig[1]; }
+    // detect_periods (periods.rs:1494-1517): these methods use the 0.3 threshold; 0 or below disables the filter
+    const double threshold = (min_confidence < 0.0 || std::isnan(min_confidence)) ? 0.3 : min_confidence;
+    const bool kept = !(threshold > 0.0) || confidence >= threshold;
+    std::memset(out_result, 0, sizeof *out_result);
+    if (!kept) {
+        out_result->primary_period = 0.0;
+        copy_method(out_result->method, name + " (no seasonality)");
+        return true;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    bool matches = false;
+    double matched = nan, deviation = nan;
+    if (expected_periods && n_expected > 0) {                      // validate_period (periods.rs:1385-1421)
+        const double tol = (tolerance < 0.0 || std::isnan(tolerance)) ? 0.1 : tolerance;
+        for (size_t i = 0; i < n_expected; i++) {
+            const double e = expected_periods[i];
+            if (e <= 0.0) continue;
+            const double dev = std::fabs(period - e) / e;
+            if (dev <= tol && (!matches || dev < deviation)) { matches = true; matched = e; deviation = dev; }
+        }
+    }
+    double *d[7];
+    for (double *&q : d) q = (double *)std::malloc(sizeof(double));
+    out_result->iteration_values = (size_t *)std::malloc(sizeof(size_t));
+    out_result->matches_expected_values = (bool *)std::malloc(sizeof(bool));
+    out_result->period_values = d[0]; out_result->confidence_values = d[1]; out_result->strength_values = d[2];
+    out_result->amplitude_values = d[3]; out_result->phase_values = d[4];
+    out_result->matched_expected_values = d[5]; out_result->match_deviation_values = d[6];
+    bool ok = out_result->iteration_values && out_result->matches_expected_values;
+    for (double *q : d) ok = ok && q;
+    if (!ok) {
+        anofox_free_flat_multi_period_result(out_result);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate period detection result");
+        return false;
+    }
+    *d[0] = period; *d[1] = confidence; *d[2] = strength; *d[3] = 0.0; *d[4] = 0.0; *d[5] = matched; *d[6] = deviation;
+    out_result->iteration_values[0] = 1;
+    out_result->matches_expected_values[0] = matches;
+    out_result->n_periods = 1;
+    out_result->primary_period = period;
+    copy_method(out_result->method, name);
+    return true;
+}
+
+void anofox_free_flat_multi_period_result(FlatMultiPeriodResult *result)
+{
+    if (!result) return;
+    std::free(result->period_values); std::free(result->confidence_values); std::free(result->strength_values);
+    std::free(result->amplitude_values); std::free(result->phase_values); std::free(result->iteration_values);
+    std::free(result->matches_expected_values); std::free(result->matched_expected_values); std::free(result->match_deviation_values);
+    result->period_values = result->confidence_values = result->strength_values = result->amplitude_values = result->phase_values = nullptr;
+    result->matched_expected_values = result->match_deviation_values = nullptr;
+    result->iteration_values = nullptr;
+    result->matches_expected_values = nullptr;
+    result->n_periods = 0;
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Exogenous regressors: ARIMAX (forecast.rs forecast_with_exog; fit_exog.hip)

@@ -237,6 +237,31 @@ size_t stats_work_stride(size_t t_rows);  // words per workspace slice (0: no wo
 int stats_work_waves(int n_series);
 void launch_stats(const StatsArgs &, hipStream_t);
 
+// Period detection (periods.rs lomb_scargle, aic_comparison, sazed_period; periods.hip)
+constexpr int PERIODS_LOMB_SCARGLE = 0, PERIODS_AIC = 1, PERIODS_SAZED = 2;
+constexpr int PERIODS_TILE = 2048;       // rows of a series staged in LDS at a time; a longer series is walked tile by tile
+constexpr int PERIODS_SPEC_LDS = 4096;   // SAZED power-spectrum bins kept in LDS; a longer spectrum lives in the global workspace
+constexpr int64_t PERIODS_SAZED_MAX_PADDED = (int64_t)1 << 24;       // largest padded length of SAZED; a longer one fails loudly
+constexpr size_t PERIODS_WORK_BYTES = (size_t)256 << 20;             // upper bound of the SAZED workspace, whatever n_series is
+constexpr int PERIODS_N_FP = 5;
+constexpr int32_t PERIODS_OK = 0, PERIODS_TOO_SHORT = 1, PERIODS_OVER_LIMIT = 2;
+struct PeriodsArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    int method;
+    double min_period, max_period;       // Lomb-Scargle / AIC: <= 0 means the source's default
+    int64_t n_grid;              // frequencies (Lomb-Scargle) or candidates (AIC), the default already applied
+    int64_t s_min, s_max, s_pad; // SAZED: min_period, max_period, zero_pad_factor; 0 means the source's default
+    double *out_fp;              // [PERIODS_N_FP x ld]  LS: period, frequency, power, false_alarm_prob;  AIC: period, aic, bic, rss,
+                                 //                      r_squared;  SAZED: period, power, snr
+    int32_t *out_index;          // [n_series] the selected grid index (frequency, candidate or DFT bin), -1: none
+    int32_t *status;             // [n_series] PERIODS_OK / _TOO_SHORT / _OVER_LIMIT (nothing else written unless OK)
+    double *work; size_t work_stride; int work_blocks;   // SAZED spectra above PERIODS_SPEC_LDS bins: [work_blocks x work_stride]
+};
+size_t periods_work_stride(size_t t_rows, int64_t s_pad);   // doubles per workspace slice (0: every spectrum fits in LDS)
+int periods_work_blocks(size_t work_stride, int n_series);
+void launch_periods(const PeriodsArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

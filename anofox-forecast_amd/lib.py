@@ -124,6 +124,45 @@ class TsStatsResult(C.Structure):
                 + [("expected_length", C.c_size_t), ("n_gaps", C.c_size_t), ("has_date_metrics", C.c_bool)])
 
 
+class LombScargleResultFFI(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("period", "frequency", "power", "false_alarm_prob")] + [("method", C.c_char * 32)]
+
+
+class AicPeriodResultFFI(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("period", "aic", "bic", "rss", "r_squared")] + [("method", C.c_char * 32)]
+
+
+class SazedPeriodResultFFI(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("period", "power", "snr")] + [("method", C.c_char * 32)]
+
+
+class FlatMultiPeriodResult(C.Structure):
+    _fields_ = [
+        ("period_values", C.POINTER(C.c_double)),
+        ("confidence_values", C.POINTER(C.c_double)),
+        ("strength_values", C.POINTER(C.c_double)),
+        ("amplitude_values", C.POINTER(C.c_double)),
+        ("phase_values", C.POINTER(C.c_double)),
+        ("iteration_values", C.POINTER(C.c_size_t)),
+        ("matches_expected_values", C.POINTER(C.c_bool)),
+        ("matched_expected_values", C.POINTER(C.c_double)),
+        ("match_deviation_values", C.POINTER(C.c_double)),
+        ("n_periods", C.c_size_t),
+        ("primary_period", C.c_double),
+        ("method", C.c_char * 32),
+    ]
+
+
+assert (C.sizeof(LombScargleResultFFI), C.sizeof(AicPeriodResultFFI), C.sizeof(SazedPeriodResultFFI), C.sizeof(FlatMultiPeriodResult)) \
+    == (64, 72, 56, 120)
+# include/anofox_fcst_hip.h: the `method` of anofox_hip_periods_batch / _device and the figures each one returns, in row order
+PERIOD_METHODS = {"lomb_scargle": 0, "aic": 1, "sazed": 2}
+PERIOD_FIGURES = {"lomb_scargle": ("period", "frequency", "power", "false_alarm_prob"),
+                  "aic": ("period", "aic", "bic", "rss", "r_squared"),
+                  "sazed": ("period", "power", "snr")}
+PERIODS_N_FP = 5
+
+
 FREQUENCY_TYPES = {"FIXED": 0, "MONTHLY": 1, "QUARTERLY": 2, "YEARLY": 3}      # include/anofox_fcst_hip.h FrequencyType
 STATS_INT_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[:12])
 STATS_FP_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[12:34])
@@ -186,6 +225,8 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_detect_changepoints_bocpd", "anofox_free_bocpd_result", "anofox_hip_changepoints_batch", "anofox_hip_changepoints_device",
     "anofox_ts_stats", "anofox_ts_stats_with_dates", "anofox_ts_stats_with_dates_and_type", "anofox_free_ts_stats_result",
     "anofox_hip_stats_batch", "anofox_hip_stats_device",
+    "anofox_ts_lomb_scargle", "anofox_ts_aic_period", "anofox_ts_sazed_period", "anofox_ts_detect_periods_flat",
+    "anofox_free_flat_multi_period_result", "anofox_hip_periods_batch", "anofox_hip_periods_device",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -305,6 +346,22 @@ def load():
     L.anofox_hip_stats_device.restype = C.c_bool
     L.anofox_hip_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_lomb_scargle.restype = C.c_bool
+    L.anofox_ts_lomb_scargle.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_size_t, P(LombScargleResultFFI), P(AnofoxError)]
+    L.anofox_ts_aic_period.restype = C.c_bool
+    L.anofox_ts_aic_period.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_size_t, P(AicPeriodResultFFI), P(AnofoxError)]
+    L.anofox_ts_sazed_period.restype = C.c_bool
+    L.anofox_ts_sazed_period.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, P(SazedPeriodResultFFI), P(AnofoxError)]
+    L.anofox_ts_detect_periods_flat.restype = C.c_bool
+    L.anofox_ts_detect_periods_flat.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t, C.c_double,
+                                                P(FlatMultiPeriodResult), P(AnofoxError)]
+    L.anofox_free_flat_multi_period_result.argtypes = [P(FlatMultiPeriodResult)]
+    L.anofox_hip_periods_batch.restype = C.c_bool
+    L.anofox_hip_periods_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_size_t, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_periods_device.restype = C.c_bool
+    L.anofox_hip_periods_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_double,
+                                            C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

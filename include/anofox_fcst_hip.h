@@ -135,6 +135,108 @@ bool anofox_ts_mstl_decomposition(const double *values,
 void anofox_free_mstl_result(struct MstlResult *result);
 
 /*
+ * Period detection (layouts of the reference's anofox_fcst_ffi.h: LombScargleResultFFI, AicPeriodResultFFI, SazedPeriodResultFFI and
+ * FlatMultiPeriodResult, 64 / 72 / 56 / 120 bytes).  Only the three methods that the reference writes out in its own tree run here:
+ * Lomb-Scargle, the AIC comparison of sinusoids, and SAZED.  The arrays of FlatMultiPeriodResult are malloc()ed by the callee
+ * and released by anofox_free_flat_multi_period_result; they are NULL when n_periods is 0.
+ */
+typedef struct LombScargleResultFFI {
+    double period;            /* 1 / frequency, NaN when no power exceeds zero */
+    double frequency;
+    double power;             /* normalised by the variance */
+    double false_alarm_prob;
+    char method[32];          /* "lomb_scargle" */
+} LombScargleResultFFI;
+
+typedef struct AicPeriodResultFFI {
+    double period;
+    double aic;
+    double bic;
+    double rss;
+    double r_squared;
+    char method[32];          /* "aic" */
+} AicPeriodResultFFI;
+
+typedef struct SazedPeriodResultFFI {
+    double period;            /* NaN when the spectrum has no peak inside the period range */
+    double power;
+    double snr;
+    char method[32];          /* "sazed" */
+} SazedPeriodResultFFI;
+
+typedef struct FlatMultiPeriodResult {
+    double *period_values;
+    double *confidence_values;
+    double *strength_values;
+    double *amplitude_values;
+    double *phase_values;
+    size_t *iteration_values;          /* 1-indexed */
+    bool *matches_expected_values;
+    double *matched_expected_values;   /* NaN: no match */
+    double *match_deviation_values;    /* NaN: no match */
+    size_t n_periods;
+    double primary_period;             /* 0.0: nothing passed the confidence threshold */
+    char method[32];
+} FlatMultiPeriodResult;
+
+/*
+ * Period detection of ONE series, the reference's lomb_scargle / aic_comparison / sazed_period (periods.rs) behind its FFI
+ * wrappers: an argument of zero (or below) means the source's default -- min_period 2, max_period (n - 1) / 2 (Lomb-Scargle),
+ * n / 2 (AIC, SAZED), 1,000 frequencies, 50 candidates, zero_pad_factor 4.  NULL `values` or `out_result`: NULL_POINTER.  Fewer
+ * than 4 / 8 / 16 observations: COMPUTATION_ERROR "Insufficient data: need at least 4 observations, got 3".  SAZED pads to the
+ * next power of two of length * zero_pad_factor; a padded length above 16,777,216 fails with COMPUTATION_ERROR naming the limit.
+ * Each runs on the GPU as a batch of one; the decisions (which frequency, candidate or bin) are the source's, the figures differ
+ * from it by the rounding of sin / cos / ln / exp only.
+ */
+bool anofox_ts_lomb_scargle(const double *values,
+                            size_t length,
+                            double min_period,
+                            double max_period,
+                            size_t n_frequencies,
+                            struct LombScargleResultFFI *out_result,
+                            struct AnofoxError *out_error);
+
+bool anofox_ts_aic_period(const double *values,
+                          size_t length,
+                          double min_period,
+                          double max_period,
+                          size_t n_candidates,
+                          struct AicPeriodResultFFI *out_result,
+                          struct AnofoxError *out_error);
+
+bool anofox_ts_sazed_period(const double *values,
+                            size_t length,
+                            size_t min_period,
+                            size_t max_period,
+                            size_t zero_pad_factor,
+                            struct SazedPeriodResultFFI *out_result,
+                            struct AnofoxError *out_error);
+
+/*
+ * The reference's detect_periods_with_validation for ONE series.  `method` is parsed as its PeriodMethod::from_str does
+ * (case-insensitive, aliases; NULL or an unknown string means "fft").  "lomb_scargle" / "lombscargle" / "lomb-scargle" / "ls",
+ * "aic" / "aic_comparison" and "sazed" / "zero_padded" / "enhanced_dft" run with the source's defaults and give one period:
+ * confidence = 1 - false_alarm_prob / r_squared / min(snr, 1), strength = power / r_squared / power, amplitude = phase = 0,
+ * iteration = 1.  Every other method -- "fft" included, hence the default -- fails with INTERNAL_ERROR "... is not implemented
+ * by the HIP backend".  max_period is accepted and, as in the source, ignored by these three methods.  min_confidence < 0 (or
+ * NaN) means 0.3; 0 disables the filter; a period whose confidence is below the threshold (or NaN) is dropped, and when none
+ * is left n_periods = 0, primary_period = 0.0 and the method reads "<method> (no seasonality)".  expected_periods (may be NULL)
+ * marks a period that lies within `tolerance` (< 0 or NaN: 0.1) of an expected one, relative to the expected one.
+ */
+bool anofox_ts_detect_periods_flat(const double *values,
+                                   size_t length,
+                                   const char *method,
+                                   size_t max_period,
+                                   double min_confidence,
+                                   const double *expected_periods,
+                                   size_t n_expected,
+                                   double tolerance,
+                                   struct FlatMultiPeriodResult *out_result,
+                                   struct AnofoxError *out_error);
+
+void anofox_free_flat_multi_period_result(struct FlatMultiPeriodResult *result);
+
+/*
  * Result of the Bayesian online changepoint detection (layout of the reference's anofox_fcst_ffi.h).  The arrays are malloc()ed
  * by the callee and released by anofox_free_bocpd_result; changepoint_indices is NULL when no point is flagged.
  */
@@ -451,6 +553,54 @@ bool anofox_hip_stats_device(const double *y,
                              double *out_fp,
                              void *stream,
                              struct AnofoxError *out_error);
+
+/*
+ * Period detection of `n_series` series with ONE method and one parameter set, in one GPU pass.  Replaces the per-group calls of
+ * the reference's ts_detect_periods_by.  method: 0 Lomb-Scargle, 1 AIC, 2 SAZED (anything else: INVALID_INPUT).  min_period /
+ * max_period are doubles for all three (SAZED's are truncated to integers); n_grid is n_frequencies, n_candidates or
+ * zero_pad_factor; zero or below means the source's default, as in the single entries.  out_figures is fp64 [5 x n_series],
+ * figure j of series i at out_figures[j * n_series + i]: Lomb-Scargle period, frequency, power, false_alarm_prob; AIC period,
+ * aic, bic, rss, r_squared; SAZED period, power, snr (unused rows are NaN).  out_index[i] (int32, may be NULL) is the selected
+ * frequency, candidate or DFT bin, -1 when none.  A series that is too short (4 / 8 / 16) or whose SAZED padding exceeds
+ * 16,777,216 fails alone: out_errors[i] (may be NULL) gets the single entry's COMPUTATION_ERROR and its figures are NaN.  The
+ * return value is false only for batch-level failures, also reported through `out_batch_error`.  Runs on the calling thread's
+ * current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_periods_batch(const double *const *values,
+                              const size_t *lengths,
+                              size_t n_series,
+                              int method,
+                              double min_period,
+                              double max_period,
+                              size_t n_grid,
+                              double *out_figures,
+                              int32_t *out_index,
+                              struct AnofoxError *out_errors,
+                              struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows), lengths[n_series] (int32; a length above
+ * t_rows is cut to it) and the outputs are device pointers.  figures is fp64 [5 x ld] (figure j of series s at j * ld + s), index
+ * and status are int32 [n_series]; status is 0 (done), 1 (too short) or 2 (SAZED padding above the limit), and nothing else is
+ * written for a series whose status is not 0.  One wavefront per series, the series staged in LDS 2,048 rows at a time.  SAZED
+ * keeps a spectrum of up to 4,096 bins in LDS; for longer ones the call allocates a workspace of at most 256 MiB, whatever
+ * n_series is, and walks the batch in chunks.  The same bits on every run and through every entry.  Runs on `stream` (NULL: the
+ * null stream) and returns after it has finished.
+ */
+bool anofox_hip_periods_device(const double *y,
+                               size_t ld,
+                               const int32_t *lengths,
+                               size_t n_series,
+                               size_t t_rows,
+                               int method,
+                               double min_period,
+                               double max_period,
+                               size_t n_grid,
+                               double *figures,
+                               int32_t *index,
+                               int32_t *status,
+                               void *stream,
+                               struct AnofoxError *out_error);
 
 /*
  * Multi-device execution of the batch entry.  The reference's finalize loop is ONE process walking all groups
