@@ -1406,6 +1406,298 @@ def ts_detect_periods(date, value, params=None):
     return {f: [None if r is None else r[f] for r in res] for f in ("periods", "n_periods", "primary_period", "method")}
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# Forecast accuracy metrics: the twelve scalars, the eleven table macros, and every requested figure of every group in ONE call
+# ------------------------------------------------------------------------------------------------------------------------------
+def _metric_columns(cols, n):
+    """An array of n pointers to the groups' arrays (kept alive by the caller), or None for a block that is not supplied."""
+    if cols is None:
+        return None, None
+    arrs = [np.ascontiguousarray(c, dtype=np.float64) for c in cols]
+    if len(arrs) != n:
+        raise InvalidInputException("Invalid input: every supplied block needs one array per group")
+    return arrs, (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else _EMPTY_SERIES_ADDR for a in arrs])
+
+
+def metrics_batch(actual, forecast=None, second=None, lower=None, upper=None, quantiles=None, levels=None, figures=("mae",), quantile=0.5,
+                  drop_nan=False):
+    """anofox_hip_metrics_batch: every figure of `figures` (names of lib.METRIC_FIGURES) for every group from ONE GPU pass.  actual,
+    forecast, second (baseline / pred2), lower, upper are lists with one 1-D array per group, all of a group's arrays of one length;
+    quantiles[k][i] holds level levels[k]'s forecasts of group i.  A block that no requested figure needs stays None; with drop_nan a
+    row with a NaN in any SUPPLIED block is skipped for every figure.  Returns a dict: figure name -> float64 array over the groups
+    (NaN where the figure failed), "code" (int array, 0 = SUCCESS) and "message" (list) per group."""
+    names = [str(f).lower() for f in figures]
+    for f in names:
+        if f not in _lib.METRIC_FIGURES:
+            raise InvalidInputException(f"Invalid input: unknown figure '{f}' (known: {', '.join(_lib.METRIC_FIGURES)})")
+    mask = 0
+    for f in names:
+        mask |= 1 << _lib.METRIC_FIGURES.index(f)
+    L = _lib.load()
+    n = len(actual)
+    keep = []
+    ptrs = []
+    for cols in (actual, forecast, second, lower, upper):
+        arrs, p = _metric_columns(cols, n)
+        keep.append(arrs)
+        ptrs.append(p)
+    for arrs in keep[1:]:
+        if arrs is not None and any(len(a) != len(b) for a, b in zip(arrs, keep[0])):
+            raise InvalidInputException("Invalid input: the arrays of a group must have the same length")
+    lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.float64)
+    n_levels = 0 if lv is None else len(lv)
+    qptr = None
+    if quantiles is not None:
+        if len(quantiles) != n_levels:
+            raise InvalidInputException("Invalid input: Number of forecasts must match number of quantiles")
+        qcols = []
+        for qk in quantiles:
+            arrs, p = _metric_columns(qk, n)
+            if any(len(a) != len(b) for a, b in zip(arrs, keep[0])):
+                raise InvalidInputException("Invalid input: the arrays of a group must have the same length")
+            keep.append(arrs)
+            qcols.append(p)
+        qptr = (C.c_void_p * max(n_levels, 1))(*[C.addressof(p) for p in qcols])
+        keep.append(qcols)
+    lens = np.array([len(a) for a in keep[0]], dtype=np.uint64)
+    fig = np.full((len(_lib.METRIC_FIGURES), max(n, 1)), np.nan)
+    errs = (_lib.AnofoxError * max(n, 1))()
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_metrics_batch(ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], qptr, None if lv is None else lv.ctypes.data, n_levels,
+                                    lens.ctypes.data, n, mask, float(quantile), bool(drop_nan), fig.ctypes.data, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = {f: fig[_lib.METRIC_FIGURES.index(f), :n].copy() for f in names}
+    out["code"] = np.array([errs[i].code for i in range(n)], dtype=np.int32)
+    out["message"] = [errs[i].message.decode(errors="replace") for i in range(n)]
+    return out
+
+
+def _metric_scalar(figure, actual, others, quantile=0.5):
+    """One of the list scalars of metrics.cpp: None for a NULL list; NULL cells are dropped from each list on its own
+    (ExtractListAsDouble), so the lengths may then differ -- that, an empty list and every other failure of the FFI call give None."""
+    if actual is None or any(o is None for o in others.values()) or quantile is None:
+        return None
+    a = _list_values(actual)
+    cols = {k: _list_values(v) for k, v in others.items()}
+    if len(a) == 0:                                                # an empty vector hands the FFI a null pointer
+        return None
+    if figure == "coverage":                                       # the bounds carry no length of their own: actual's is used
+        if any(len(c) < len(a) for c in cols.values()):
+            return None
+        cols = {k: c[:len(a)] for k, c in cols.items()}
+    elif any(len(c) != len(a) for c in cols.values()):
+        return None
+    r = metrics_batch([a], figures=(figure,), quantile=quantile, **{k: [c] for k, c in cols.items()})
+    if r["code"][0] != _lib.SUCCESS:
+        return None
+    return float(r[figure][0])
+
+
+def ts_mae(actual, forecast):
+    """The scalar ts_mae(actual[], forecast[]) (metrics.cpp:36-70)."""
+    return _metric_scalar("mae", actual, {"forecast": forecast})
+
+
+def ts_mse(actual, forecast):
+    return _metric_scalar("mse", actual, {"forecast": forecast})
+
+
+def ts_rmse(actual, forecast):
+    return _metric_scalar("rmse", actual, {"forecast": forecast})
+
+
+def ts_mape(actual, forecast):
+    return _metric_scalar("mape", actual, {"forecast": forecast})
+
+
+def ts_smape(actual, forecast):
+    return _metric_scalar("smape", actual, {"forecast": forecast})
+
+
+def ts_r2(actual, forecast):
+    return _metric_scalar("r2", actual, {"forecast": forecast})
+
+
+def ts_bias(actual, forecast):
+    return _metric_scalar("bias", actual, {"forecast": forecast})
+
+
+def ts_mase(actual, forecast, baseline):
+    """ts_mase(actual[], forecast[], baseline[]): MAE of the forecast over MAE of the baseline (metrics.cpp:426-466)."""
+    return _metric_scalar("mase", actual, {"forecast": forecast, "second": baseline})
+
+
+def ts_rmae(actual, pred1, pred2):
+    return _metric_scalar("rmae", actual, {"forecast": pred1, "second": pred2})
+
+
+def ts_quantile_loss(actual, forecast, quantile):
+    """ts_quantile_loss(actual[], forecast[], quantile) (metrics.cpp:748-795): a quantile outside [0, 1] gives None."""
+    return _metric_scalar("quantile_loss", actual, {"forecast": forecast}, quantile)
+
+
+def ts_coverage(actual, lower, upper):
+    return _metric_scalar("coverage", actual, {"lower": lower, "upper": upper})
+
+
+def ts_mqloss(actual, quantiles, levels):
+    """ts_mqloss(actual[], quantiles[][], levels[]) (metrics.cpp:871-920): quantiles[k] are the forecasts of level levels[k].  None
+    for a NULL argument, for a different number of forecasts and levels, and for every failure of the FFI call (no level, an empty
+    or NULL inner list, a level outside [0, 1]).  More than 16 levels raise: that is this backend's limit, not a NULL."""
+    if actual is None or quantiles is None or levels is None:
+        return None
+    a = _list_values(actual)
+    lv = _list_values(levels)
+    qs = [None if q is None else _list_values(q) for q in quantiles]
+    if len(qs) != len(lv) or len(lv) == 0 or len(a) == 0:
+        return None
+    if len(lv) > _lib.METRICS_MAX_LEVELS:
+        raise InvalidInputException(f"Invalid input: at most {_lib.METRICS_MAX_LEVELS} quantile levels per call, got {len(lv)}")
+    if any(q is None or len(q) < len(a) for q in qs):              # (the FFI reads actual's length from every inner list)
+        return None
+    r = metrics_batch([a], quantiles=[[q[:len(a)]] for q in qs], levels=lv, figures=("mqloss",))
+    if r["code"][0] != _lib.SUCCESS:
+        return None
+    return float(r["mqloss"][0])
+
+
+for _name in ("mae", "mse", "rmse", "mape", "smape", "mase", "r2", "bias", "rmae", "quantile_loss", "mqloss", "coverage"):
+    globals()["anofox_fcst_ts_" + _name] = globals()["ts_" + _name]            # the aliases metrics.cpp registers
+del _name
+
+
+def _metric_group_columns(group_columns, n_rows):
+    if group_columns is None:
+        return [], []
+    if isinstance(group_columns, dict):
+        names, cols = list(group_columns.keys()), list(group_columns.values())
+    else:
+        cols = list(group_columns)
+        names = [f"group_{i}" for i in range(len(cols))]
+    cols = [list(c.tolist()) if isinstance(c, np.ndarray) else list(c) for c in cols]
+    if any(len(c) != n_rows for c in cols):
+        raise InvalidInputException("Invalid input: every column needs one value per row")
+    return names, cols
+
+
+def _metric_dates(date):
+    """(sort keys, NULL mask) of a date column: datetime64 (NaT is NULL), numbers, or objects with None / masked for NULL."""
+    if np.ma.isMaskedArray(date):
+        null = np.ma.getmaskarray(date).copy()
+        d = np.ma.getdata(date)
+    else:
+        d = np.asarray(date)
+        null = np.zeros(len(d), dtype=bool)
+    if np.issubdtype(d.dtype, np.datetime64):
+        null = null | np.isnat(d)
+        return np.where(null, 0, d.astype(np.int64)), null
+    if d.dtype == object:
+        null = null | np.array([v is None or v is np.ma.masked for v in d], dtype=bool)
+        return np.array([0 if m else v for v, m in zip(d, null)]), null
+    return d, null
+
+
+def _metrics_table(group_columns, date, blocks, figure, column, quantile=0.5):
+    """The body shared by the five table functions of ts_metrics_native.cpp: rows with a NULL date are dropped before their group
+    exists, the group key is ALL group columns (none: one global group), groups come in order of first appearance, rows are ordered
+    by date within the group (a stable sort here; the source's std::sort leaves the order of equal dates open), NULL values become
+    NaN, and rows with a NaN in any of the statement's columns are filtered -- on the device, by drop_nan.  A group whose rows are
+    all filtered, and every group of a failed call (a quantile outside [0, 1]), gets NaN.  ALL groups go to the GPU in one call."""
+    key, null_date = _metric_dates(date)
+    n_rows = len(key)
+    names, gcols = _metric_group_columns(group_columns, n_rows)
+    vals = {}
+    for k, col in blocks.items():
+        v, vnull = _changepoint_values(col)
+        if len(v) != n_rows:
+            raise InvalidInputException("Invalid input: every column needs one value per row")
+        vals[k] = np.where(vnull, np.nan, v)
+    order, members = [], {}
+    for i in range(n_rows):
+        if null_date[i]:
+            continue
+        g = tuple(c[i] for c in gcols)
+        if g not in members:
+            members[g] = []
+            order.append(g)
+        members[g].append(i)
+    per_block = {k: [] for k in vals}
+    for g in order:
+        idx = np.array(members[g])
+        o = idx[np.argsort(key[idx], kind="stable")]
+        for k in vals:
+            per_block[k].append(vals[k][o])
+    out = {name: [g[j] for g in order] for j, name in enumerate(names)}
+    if not order:
+        out[column] = []
+        return out
+    r = metrics_batch(per_block.pop("actual"), figures=(figure,), quantile=quantile, drop_nan=True, **per_block)
+    out[column] = [float(v) for v in r[figure]]
+    return out
+
+
+_TS_METRIC_TYPES = ("mae", "mse", "rmse", "mape", "smape", "r2", "bias")
+
+
+def _ts_metrics_native(group_columns, date, actual, forecast, metric):
+    """_ts_metrics_native(source, date_col, actual_col, forecast_col, metric) (ts_metrics_native.cpp:232-507): `group_columns` are
+    the source's remaining columns (a dict name -> column, a list of columns, or None).  Returns a dict of columns: the group
+    columns, then the metric under its own name."""
+    m = str(metric).lower()
+    if m not in _TS_METRIC_TYPES:
+        raise InvalidInputException(f"Unknown metric type: {metric}. Supported: mae, mse, rmse, mape, smape, r2, bias")
+    return _metrics_table(group_columns, date, {"actual": actual, "forecast": forecast}, m, m)
+
+
+def ts_mae_by(group_columns, date, actual, forecast):
+    """ts_mae_by(source, date_col, actual_col, forecast_col) (ts_macros.cpp:2015-2023)."""
+    return _ts_metrics_native(group_columns, date, actual, forecast, "mae")
+
+
+def ts_mse_by(group_columns, date, actual, forecast):
+    return _ts_metrics_native(group_columns, date, actual, forecast, "mse")
+
+
+def ts_rmse_by(group_columns, date, actual, forecast):
+    return _ts_metrics_native(group_columns, date, actual, forecast, "rmse")
+
+
+def ts_mape_by(group_columns, date, actual, forecast):
+    return _ts_metrics_native(group_columns, date, actual, forecast, "mape")
+
+
+def ts_smape_by(group_columns, date, actual, forecast):
+    return _ts_metrics_native(group_columns, date, actual, forecast, "smape")
+
+
+def ts_r2_by(group_columns, date, actual, forecast):
+    return _ts_metrics_native(group_columns, date, actual, forecast, "r2")
+
+
+def ts_bias_by(group_columns, date, actual, forecast):
+    return _ts_metrics_native(group_columns, date, actual, forecast, "bias")
+
+
+def ts_mase_by(group_columns, date, actual, forecast, baseline):
+    """ts_mase_by(source, date_col, actual_col, forecast_col, baseline_col) over _ts_mase_native (ts_metrics_native.cpp:589-860)."""
+    return _metrics_table(group_columns, date, {"actual": actual, "forecast": forecast, "second": baseline}, "mase", "mase")
+
+
+def ts_rmae_by(group_columns, date, actual, pred1, pred2):
+    return _metrics_table(group_columns, date, {"actual": actual, "forecast": pred1, "second": pred2}, "rmae", "rmae")
+
+
+def ts_coverage_by(group_columns, date, actual, lower, upper):
+    return _metrics_table(group_columns, date, {"actual": actual, "lower": lower, "upper": upper}, "coverage", "coverage")
+
+
+def ts_quantile_loss_by(group_columns, date, actual, forecast, quantile):
+    """ts_quantile_loss_by(source, date_col, actual_col, forecast_col, quantile) over _ts_quantile_loss_native: a quantile outside
+    [0, 1] fails every group's FFI call, so every group reads NaN (ts_metrics_native.cpp:1660-1670)."""
+    return _metrics_table(group_columns, date, {"actual": actual, "forecast": forecast}, "quantile_loss", "quantile_loss", float(quantile))
+
+
 def forecast_exog_batch(series, xregs, futures, opts, valids=None):
     """anofox_ts_forecast_exog_batch over host buffers: xregs[s] / futures[s] are the K historical / future regressor arrays of
     series s (K shared by the batch; lengths len(series[s]) and opts.horizon).  Returns (results, batch_error); a result that

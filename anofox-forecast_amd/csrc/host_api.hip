@@ -4246,6 +4246,324 @@ void anofox_free_flat_multi_period_result(FlatMultiPeriodResult *result)
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Forecast accuracy metrics (metrics.rs mae .. coverage behind lib.rs:303-800; metrics.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+const char *const METRICS_FIGURE_NAME[METRICS_N_FIG] = {"mae", "mse", "rmse", "mape", "smape", "r2", "bias", "rmae", "mase", "quantile_loss",
+                                                        "mqloss", "coverage"};
+const char *const METRICS_EMPTY_TEXT = "Insufficient data: need at least 1 observations, got 0";       // ForecastError::InsufficientData
+const char *const METRICS_QUANTILE_TEXT = "Invalid input: Quantile must be between 0 and 1";            // metrics.rs:278-282
+constexpr uint32_t METRICS_ALL = (1u << METRICS_N_FIG) - 1;
+
+bool metrics_unit_interval(double q) { return q >= 0.0 && q <= 1.0; }       // (0.0..=1.0).contains: false for a NaN
+
+// what the batch and the device entry check alike: the mask, the level count, and that every requested figure has its blocks
+bool metrics_check_request(uint32_t mask, bool has_f, bool has_s, bool has_l, bool has_u, bool has_q, size_t n_levels, const double *levels,
+                           AnofoxError *err)
+{
+    if (mask == 0 || (mask & ~METRICS_ALL)) {
+        set_error(err, INVALID_INPUT, "Invalid input: the figure mask must name at least one of the 12 figures and nothing else");
+        return false;
+    }
+    if (n_levels > (size_t)METRICS_MAX_LEVELS) {
+        set_error(err, INVALID_INPUT, "Invalid input: at most " + std::to_string(METRICS_MAX_LEVELS) + " quantile levels per call, got " +
+                                          std::to_string(n_levels));
+        return false;
+    }
+    for (int k = 0; k < METRICS_N_FIG; k++) {
+        if (!(mask >> k & 1u)) continue;
+        const char *missing = nullptr;
+        if ((METRICS_NEED_FORECAST >> k & 1u) && !has_f) missing = "forecast";
+        else if ((METRICS_NEED_SECOND >> k & 1u) && !has_s) missing = "second";
+        else if (k == MF_COVERAGE && !(has_l && has_u)) missing = "lower and upper";
+        else if (k == MF_MQLOSS && n_levels > 0 && !(has_q && levels)) missing = "quantiles and levels";
+        if (missing) {
+            set_error(err, INVALID_INPUT, std::string("Invalid input: figure '") + METRICS_FIGURE_NAME[k] + "' needs " + missing);
+            return false;
+        }
+    }
+    if ((mask >> MF_MQLOSS & 1u) && n_levels == 0) {
+        set_error(err, INVALID_INPUT, "Must have at least one quantile level");        // lib.rs:700-708
+        return false;
+    }
+    return true;
+}
+
+// one group, one figure, through the batch entry (the argument checks of the single entries come before it and need no device)
+bool metrics_single(int figure, const double *actual, size_t n, const double *forecast, const double *second, const double *lower,
+                    const double *upper, const double *const *quantiles, const double *levels, size_t n_levels, double quantile,
+                    double *out_result, AnofoxError *out_error)
+{
+    AnofoxError gerr, berr;
+    const double *a[1] = {actual}, *f[1] = {forecast}, *s[1] = {second}, *l[1] = {lower}, *u[1] = {upper};
+    const double *qcol[METRICS_MAX_LEVELS];
+    const double *const *qq[METRICS_MAX_LEVELS];
+    for (size_t k = 0; k < n_levels && k < (size_t)METRICS_MAX_LEVELS; k++) { qcol[k] = quantiles[k]; qq[k] = &qcol[k]; }
+    const size_t len[1] = {n};
+    double fig[METRICS_N_FIG];
+    if (!anofox_hip_metrics_batch(a, forecast ? f : nullptr, second ? s : nullptr, lower ? l : nullptr, upper ? u : nullptr,
+                                  quantiles ? qq : nullptr, levels, n_levels, len, 1, 1u << figure, quantile, false, fig, &gerr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (gerr.code != SUCCESS) { if (out_error) *out_error = gerr; return false; }
+    *out_result = fig[figure];
+    return true;
+}
+
+// validate_inputs (metrics.rs:364-375) as the FFI wrappers report it
+bool metrics_validate(size_t n_actual, size_t n_forecast, AnofoxError *err)
+{
+    if (n_actual != n_forecast) {
+        set_error(err, COMPUTATION_ERROR, "Invalid input: Actual and forecast arrays must have the same length: " + std::to_string(n_actual) +
+                                              " vs " + std::to_string(n_forecast));
+        return false;
+    }
+    if (n_actual == 0) { set_error(err, COMPUTATION_ERROR, METRICS_EMPTY_TEXT); return false; }
+    return true;
+}
+
+bool metrics_two(int figure, const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result,
+                 AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !forecast || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!metrics_validate(actual_len, forecast_len, out_error)) return false;
+    return metrics_single(figure, actual, actual_len, forecast, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.5, out_result, out_error);
+}
+
+bool metrics_three(int figure, const char *third_name, const double *actual, size_t actual_len, const double *forecast, size_t forecast_len,
+                   const double *third, size_t third_len, double *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !forecast || !third || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!metrics_validate(actual_len, forecast_len, out_error)) return false;
+    if (actual_len != third_len) {                                 // metrics.rs:168-173, 238-243
+        set_error(out_error, COMPUTATION_ERROR, std::string("Invalid input: Actual and ") + third_name + " arrays must have the same length: " +
+                                                    std::to_string(actual_len) + " vs " + std::to_string(third_len));
+        return false;
+    }
+    return metrics_single(figure, actual, actual_len, forecast, third, nullptr, nullptr, nullptr, nullptr, 0, 0.5, out_result, out_error);
+}
+
+} // namespace
+} // extern "C++"
+
+bool anofox_hip_metrics_device(const double *actual, const double *forecast, const double *second, const double *lower, const double *upper,
+                               const double *quantiles, size_t stride_q, const double *levels, size_t n_levels, size_t stride_s,
+                               size_t stride_t, const int32_t *lengths, size_t n_groups, size_t t_rows, uint32_t figures_mask, double quantile,
+                               bool drop_nan, double *figures, size_t ld, int32_t *status, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !lengths || !figures || !status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!metrics_check_request(figures_mask, forecast, second, lower, upper, quantiles, n_levels, levels, out_error)) return false;
+    if ((figures_mask >> MF_QUANTILE_LOSS & 1u) && !metrics_unit_interval(quantile)) {
+        set_error(out_error, INVALID_INPUT, METRICS_QUANTILE_TEXT);
+        return false;
+    }
+    const bool use_q = quantiles && levels && n_levels > 0;
+    if (figures_mask >> MF_MQLOSS & 1u)
+        for (size_t k = 0; k < n_levels; k++)
+            if (!metrics_unit_interval(levels[k])) { set_error(out_error, INVALID_INPUT, METRICS_QUANTILE_TEXT); return false; }
+    if (ld < n_groups) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_groups"); return false; }
+    if (n_groups > (size_t)INT32_MAX || t_rows > (size_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if (n_groups == 0) return true;
+    if (!device_ready(out_error)) return false;
+    MetricsArgs a{};
+    a.actual = actual; a.forecast = forecast; a.second = second; a.lower = lower; a.upper = upper;
+    a.quant = use_q ? quantiles : nullptr; a.n_levels = use_q ? (int)n_levels : 0; a.stride_q = stride_q;
+    for (int k = 0; k < a.n_levels; k++) a.levels[k] = levels[k];
+    a.stride_s = stride_s; a.stride_t = stride_t; a.len = lengths; a.n_groups = (int)n_groups; a.t_rows = t_rows;
+    a.mask = figures_mask; a.drop_nan = drop_nan ? 1 : 0; a.quantile = quantile;
+    a.figures = figures; a.ld = ld; a.status = status;
+    a.staging = -1;
+    {                                                              // developer knob of tools/time_metrics.py: 0 strided reads, 1 LDS staging
+        const std::map<std::string, std::string> kv = Tunables::tune_map();
+        auto it = kv.find("metrics_staging");
+        if (it != kv.end()) a.staging = std::atoi(it->second.c_str());
+    }
+    hipStream_t st = (hipStream_t)stream;
+    try {
+        (void)hipGetLastError();
+        launch_metrics(a, st);
+        LAUNCHCHECK("metrics");
+        HIPCHECK(hipStreamSynchronize(st));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_metrics_batch(const double *const *actual, const double *const *forecast, const double *const *second, const double *const *lower,
+                              const double *const *upper, const double *const *const *quantiles, const double *levels, size_t n_levels,
+                              const size_t *lengths, size_t n_groups, uint32_t figures_mask, double quantile, bool drop_nan,
+                              double *out_figures, AnofoxError *out_errors, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_groups > 0 && (!actual || !lengths || !out_figures)) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!metrics_check_request(figures_mask, forecast, second, lower, upper, quantiles, n_levels, levels, out_batch_error)) return false;
+    const size_t nq = (quantiles && levels) ? n_levels : 0;
+    for (size_t k = 0; k < nq; k++)
+        if (!quantiles[k]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+    size_t t_max = 0;
+    std::vector<int> null_level(n_groups, -1);                     // a group whose level k forecasts are NULL fails alone (lib.rs:716-723)
+    for (size_t s = 0; s < n_groups; s++) {
+        if (lengths[s] == 0) continue;
+        if (!actual[s] || (forecast && !forecast[s]) || (second && !second[s]) || (lower && !lower[s]) || (upper && !upper[s])) {
+            set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+            return false;
+        }
+        if (lengths[s] > (size_t)INT32_MAX) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a group is too long"); return false; }
+        for (size_t k = 0; k < nq && null_level[s] < 0; k++)
+            if (!quantiles[k][s]) null_level[s] = (int)k;
+        if (null_level[s] < 0) t_max = std::max(t_max, lengths[s]);
+    }
+    if (n_groups == 0) return true;
+    // a quantile or level outside [0, 1] fails the figure that uses it, per group as the single entries do; the others are computed
+    uint32_t mask = figures_mask;
+    const bool ql_bad = (mask >> MF_QUANTILE_LOSS & 1u) && !metrics_unit_interval(quantile);
+    bool mql_bad = false;
+    if (mask >> MF_MQLOSS & 1u)
+        for (size_t k = 0; k < nq; k++) mql_bad = mql_bad || !metrics_unit_interval(levels[k]);
+    if (ql_bad) mask &= ~(1u << MF_QUANTILE_LOSS);
+    if (mql_bad) mask &= ~(1u << MF_MQLOSS);
+    const size_t ld = (n_groups + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    std::vector<double> fig((size_t)METRICS_N_FIG * ld, std::numeric_limits<double>::quiet_NaN());
+    std::vector<int32_t> status(n_groups, METRICS_OK), len(ld, 0);
+    for (size_t s = 0; s < n_groups; s++) {
+        len[s] = null_level[s] < 0 ? (int32_t)lengths[s] : 0;
+        status[s] = len[s] > 0 ? METRICS_OK : METRICS_EMPTY;
+    }
+    if (mask != 0) {
+        const double *const *src[5] = {actual, forecast, second, lower, upper};
+        const bool use_q = nq > 0 && (mask >> MF_MQLOSS & 1u);
+        const size_t n_blocks = 5 + (use_q ? nq : 0);
+        std::vector<double *> d_in(6, nullptr);                    // actual .. upper, and every level's block in one (level k at k * T * ld)
+        double *d_fig = nullptr;
+        int32_t *d_len = nullptr, *d_st = nullptr;
+        auto release = [&](bool quiesced) {
+            for (double *q : d_in) { dev_free(q, quiesced); quiesced = true; }
+            dev_free(d_fig, quiesced); dev_free(d_len, true); dev_free(d_st, true);
+        };
+        try {
+            if (!device_ready(out_batch_error)) return false;
+            std::vector<double> blk(T * ld);
+            if (use_q) d_in[5] = dalloc<double>(nq * T * ld);
+            for (size_t b = 0; b < n_blocks; b++) {
+                const double *const *col = b < 5 ? src[b] : quantiles[b - 5];
+                if (!col) continue;
+                std::fill(blk.begin(), blk.end(), 0.0);
+                for (size_t s = 0; s < n_groups; s++)
+                    for (size_t t = 0; t < (size_t)len[s]; t++) blk[t * ld + s] = col[s][t];
+                double *dst = b < 5 ? (d_in[b] = dalloc<double>(T * ld)) : d_in[5] + (b - 5) * T * ld;
+                HIPCHECK(hipMemcpy(dst, blk.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+            }
+            d_fig = dalloc<double>((size_t)METRICS_N_FIG * ld); d_len = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+            HIPCHECK(hipMemcpy(d_fig, fig.data(), fig.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (!anofox_hip_metrics_device(d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], use_q ? d_in[5] : nullptr, T * ld, levels, use_q ? nq : 0, 1,
+                                           ld, d_len, n_groups, T, mask, ql_bad ? 0.5 : quantile, drop_nan, d_fig, ld, d_st, nullptr,
+                                           out_batch_error)) {
+                release(false);
+                return false;
+            }
+            HIPCHECK(hipMemcpy(fig.data(), d_fig, fig.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHECK(hipMemcpy(status.data(), d_st, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
+            release(true);
+        } catch (const HipFail &f) {
+            release(false);
+            report_hip_failure(out_batch_error, f);
+            return false;
+        }
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t s = 0; s < n_groups; s++) {
+        const bool empty = status[s] != METRICS_OK;
+        for (int k = 0; k < METRICS_N_FIG; k++)
+            out_figures[(size_t)k * n_groups + s] = (!empty && (mask >> k & 1u)) ? fig[(size_t)k * ld + s] : nan;
+        if (!out_errors) continue;
+        out_errors[s].code = SUCCESS;
+        std::memset(out_errors[s].message, 0, sizeof out_errors[s].message);
+        if (null_level[s] >= 0) set_error(&out_errors[s], COMPUTATION_ERROR, "Invalid input: Null pointer at quantile index " + std::to_string(null_level[s]));
+        else if (empty && (figures_mask & ~(1u << MF_COVERAGE))) set_error(&out_errors[s], COMPUTATION_ERROR, METRICS_EMPTY_TEXT);   // coverage of nothing is NaN, no error
+        else if (!empty && (ql_bad || mql_bad)) set_error(&out_errors[s], COMPUTATION_ERROR, METRICS_QUANTILE_TEXT);
+    }
+    return true;
+}
+
+bool anofox_ts_mae(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_MAE, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+bool anofox_ts_mse(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_MSE, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+bool anofox_ts_rmse(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_RMSE, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+bool anofox_ts_mape(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_MAPE, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+bool anofox_ts_smape(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_SMAPE, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+bool anofox_ts_r2(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_R2, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+bool anofox_ts_bias(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result, AnofoxError *out_error)
+{ return metrics_two(MF_BIAS, actual, actual_len, forecast, forecast_len, out_result, out_error); }
+
+bool anofox_ts_rmae(const double *actual, size_t actual_len, const double *pred1, size_t pred1_len, const double *pred2, size_t pred2_len,
+                    double *out_result, AnofoxError *out_error)
+{ return metrics_three(MF_RMAE, "pred2", actual, actual_len, pred1, pred1_len, pred2, pred2_len, out_result, out_error); }
+
+bool anofox_ts_mase(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, const double *baseline, size_t baseline_len,
+                    double *out_result, AnofoxError *out_error)
+{ return metrics_three(MF_MASE, "baseline", actual, actual_len, forecast, forecast_len, baseline, baseline_len, out_result, out_error); }
+
+bool anofox_ts_quantile_loss(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double quantile,
+                             double *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !forecast || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!metrics_validate(actual_len, forecast_len, out_error)) return false;
+    if (!metrics_unit_interval(quantile)) { set_error(out_error, COMPUTATION_ERROR, METRICS_QUANTILE_TEXT); return false; }
+    return metrics_single(MF_QUANTILE_LOSS, actual, actual_len, forecast, nullptr, nullptr, nullptr, nullptr, nullptr, 0, quantile, out_result,
+                          out_error);
+}
+
+bool anofox_ts_mqloss(const double *actual, size_t actual_len, const double *const *quantiles, size_t n_levels, const double *levels,
+                      double *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !quantiles || !levels || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_levels == 0) { set_error(out_error, INVALID_INPUT, "Must have at least one quantile level"); return false; }
+    if (n_levels > (size_t)METRICS_MAX_LEVELS) {                   // the backend's limit
+        set_error(out_error, INVALID_INPUT, "Invalid input: at most " + std::to_string(METRICS_MAX_LEVELS) + " quantile levels per call, got " +
+                                                std::to_string(n_levels));
+        return false;
+    }
+    for (size_t k = 0; k < n_levels; k++)
+        if (!quantiles[k]) {
+            set_error(out_error, COMPUTATION_ERROR, "Invalid input: Null pointer at quantile index " + std::to_string(k));
+            return false;
+        }
+    // mqloss walks the levels in order (metrics.rs:319-322): quantile_loss validates its inputs, then its level
+    if (actual_len == 0) { set_error(out_error, COMPUTATION_ERROR, METRICS_EMPTY_TEXT); return false; }
+    for (size_t k = 0; k < n_levels; k++)
+        if (!metrics_unit_interval(levels[k])) { set_error(out_error, COMPUTATION_ERROR, METRICS_QUANTILE_TEXT); return false; }
+    return metrics_single(MF_MQLOSS, actual, actual_len, nullptr, nullptr, nullptr, nullptr, quantiles, levels, n_levels, 0.5, out_result, out_error);
+}
+
+bool anofox_ts_coverage(const double *actual, size_t actual_len, const double *lower, const double *upper, double *out_result,
+                        AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !lower || !upper || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (actual_len == 0) { *out_result = std::numeric_limits<double>::quiet_NaN(); return true; }       // metrics.rs:350-352
+    return metrics_single(MF_COVERAGE, actual, actual_len, nullptr, nullptr, lower, upper, nullptr, nullptr, 0, 0.5, out_result, out_error);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Exogenous regressors: ARIMAX (forecast.rs forecast_with_exog; fit_exog.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 } // extern "C"

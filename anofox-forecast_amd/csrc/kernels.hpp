@@ -262,6 +262,29 @@ size_t periods_work_stride(size_t t_rows, int64_t s_pad);   // doubles per works
 int periods_work_blocks(size_t work_stride, int n_series);
 void launch_periods(const PeriodsArgs &, hipStream_t);
 
+// Forecast accuracy metrics per group (metrics.rs mae .. coverage; metrics.hip)
+constexpr int METRICS_N_FIG = 12;        // rows of `figures`, in this order:
+enum { MF_MAE = 0, MF_MSE, MF_RMSE, MF_MAPE, MF_SMAPE, MF_R2, MF_BIAS, MF_RMAE, MF_MASE, MF_QUANTILE_LOSS, MF_MQLOSS, MF_COVERAGE };
+constexpr int METRICS_MAX_LEVELS = 16;   // quantile levels of mqloss per call; more fail loudly
+constexpr uint32_t METRICS_NEED_FORECAST = 0x3FFu, METRICS_NEED_SECOND = 0x180u;      // figures that read `forecast` / `second`
+constexpr int32_t METRICS_OK = 0, METRICS_EMPTY = 1;
+struct MetricsArgs {
+    // element (group s, row t) of every input block at s * stride_s + t * stride_t; a block that no requested figure reads may be
+    // null; with drop_nan every block that is NOT null takes part in the row filter
+    const double *actual, *forecast, *second, *lower, *upper;
+    const double *quant;         // level k's forecasts: the block at quant + k * stride_q
+    size_t stride_s, stride_t, stride_q;
+    const int32_t *len; int n_groups;
+    size_t t_rows;               // a longer group is cut to it
+    uint32_t mask;               // bit k: figure k is wanted
+    int drop_nan;                // 1: a row with a NaN in any block is skipped and does not count
+    int n_levels; double quantile; double levels[METRICS_MAX_LEVELS];
+    double *figures; size_t ld;  // [METRICS_N_FIG x ld]; only the rows of `mask` and the columns s < n_groups are written
+    int32_t *status;             // [n_groups] METRICS_OK, METRICS_EMPTY (no row left: every wanted figure is NaN)
+    int staging;                 // -1: LDS staging when stride_t == 1 and stride_s != 1; 0: never (strided reads); 1: whenever stride_t == 1
+};
+void launch_metrics(const MetricsArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

@@ -163,6 +163,11 @@ PERIOD_FIGURES = {"lomb_scargle": ("period", "frequency", "power", "false_alarm_
 PERIODS_N_FP = 5
 
 
+# include/anofox_fcst_hip.h: bit k of the figure mask of anofox_hip_metrics_batch / _device and row k of their output
+METRIC_FIGURES = ("mae", "mse", "rmse", "mape", "smape", "r2", "bias", "rmae", "mase", "quantile_loss", "mqloss", "coverage")
+METRICS_MAX_LEVELS = 16
+
+
 FREQUENCY_TYPES = {"FIXED": 0, "MONTHLY": 1, "QUARTERLY": 2, "YEARLY": 3}      # include/anofox_fcst_hip.h FrequencyType
 STATS_INT_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[:12])
 STATS_FP_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[12:34])
@@ -227,6 +232,9 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_stats_batch", "anofox_hip_stats_device",
     "anofox_ts_lomb_scargle", "anofox_ts_aic_period", "anofox_ts_sazed_period", "anofox_ts_detect_periods_flat",
     "anofox_free_flat_multi_period_result", "anofox_hip_periods_batch", "anofox_hip_periods_device",
+    "anofox_ts_mae", "anofox_ts_mse", "anofox_ts_rmse", "anofox_ts_mape", "anofox_ts_smape", "anofox_ts_r2", "anofox_ts_bias",
+    "anofox_ts_rmae", "anofox_ts_mase", "anofox_ts_quantile_loss", "anofox_ts_mqloss", "anofox_ts_coverage",
+    "anofox_hip_metrics_batch", "anofox_hip_metrics_device",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -362,6 +370,27 @@ def load():
     L.anofox_hip_periods_device.restype = C.c_bool
     L.anofox_hip_periods_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_double,
                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    for name in ("mae", "mse", "rmse", "mape", "smape", "r2", "bias"):
+        f = getattr(L, "anofox_ts_" + name)
+        f.restype = C.c_bool
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_double), P(AnofoxError)]
+    for name in ("rmae", "mase"):
+        f = getattr(L, "anofox_ts_" + name)
+        f.restype = C.c_bool
+        f.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_double), P(AnofoxError)]
+    L.anofox_ts_quantile_loss.restype = C.c_bool
+    L.anofox_ts_quantile_loss.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, P(C.c_double), P(AnofoxError)]
+    L.anofox_ts_mqloss.restype = C.c_bool
+    L.anofox_ts_mqloss.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_double), P(AnofoxError)]
+    L.anofox_ts_coverage.restype = C.c_bool
+    L.anofox_ts_coverage.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(C.c_double), P(AnofoxError)]
+    L.anofox_hip_metrics_batch.restype = C.c_bool
+    L.anofox_hip_metrics_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_uint32, C.c_double, C.c_bool, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_metrics_device.restype = C.c_bool
+    L.anofox_hip_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_double,
+                                            C.c_bool, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

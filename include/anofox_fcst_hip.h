@@ -603,6 +603,183 @@ bool anofox_hip_periods_device(const double *y,
                                struct AnofoxError *out_error);
 
 /*
+ * Forecast accuracy metrics, the reference's twelve functions of metrics.rs behind their FFI wrappers, with its signatures.  Each
+ * call runs on the GPU as a batch of one group; the argument checks come first and need no device.  Any NULL pointer: NULL_POINTER
+ * "Null pointer argument".  Different lengths, an empty input or a quantile outside [0, 1]: COMPUTATION_ERROR with the source's text
+ * ("Invalid input: Actual and forecast arrays must have the same length: 3 vs 2", "... Actual and baseline arrays ...", "... Actual
+ * and pred2 arrays ...", "Insufficient data: need at least 1 observations, got 0", "Invalid input: Quantile must be between 0 and
+ * 1").  mqloss: n_levels == 0 is INVALID_INPUT "Must have at least one quantile level", a NULL quantiles[k] is COMPUTATION_ERROR
+ * "Invalid input: Null pointer at quantile index k", and more than 16 levels is INVALID_INPUT naming that limit of this backend.
+ * coverage of an empty input returns true and NaN.  The results equal the source's arithmetic bit for bit (sequential sums in row
+ * order from 0.0), except for the sign of a zero result and NaN payloads.
+ */
+bool anofox_ts_mae(const double *actual,
+                   size_t actual_len,
+                   const double *forecast,
+                   size_t forecast_len,
+                   double *out_result,
+                   struct AnofoxError *out_error);
+
+bool anofox_ts_mse(const double *actual,
+                   size_t actual_len,
+                   const double *forecast,
+                   size_t forecast_len,
+                   double *out_result,
+                   struct AnofoxError *out_error);
+
+bool anofox_ts_rmse(const double *actual,
+                    size_t actual_len,
+                    const double *forecast,
+                    size_t forecast_len,
+                    double *out_result,
+                    struct AnofoxError *out_error);
+
+bool anofox_ts_mape(const double *actual,
+                    size_t actual_len,
+                    const double *forecast,
+                    size_t forecast_len,
+                    double *out_result,
+                    struct AnofoxError *out_error);
+
+bool anofox_ts_smape(const double *actual,
+                     size_t actual_len,
+                     const double *forecast,
+                     size_t forecast_len,
+                     double *out_result,
+                     struct AnofoxError *out_error);
+
+bool anofox_ts_r2(const double *actual,
+                  size_t actual_len,
+                  const double *forecast,
+                  size_t forecast_len,
+                  double *out_result,
+                  struct AnofoxError *out_error);
+
+bool anofox_ts_bias(const double *actual,
+                    size_t actual_len,
+                    const double *forecast,
+                    size_t forecast_len,
+                    double *out_result,
+                    struct AnofoxError *out_error);
+
+bool anofox_ts_rmae(const double *actual,
+                    size_t actual_len,
+                    const double *pred1,
+                    size_t pred1_len,
+                    const double *pred2,
+                    size_t pred2_len,
+                    double *out_result,
+                    struct AnofoxError *out_error);
+
+bool anofox_ts_mase(const double *actual,
+                    size_t actual_len,
+                    const double *forecast,
+                    size_t forecast_len,
+                    const double *baseline,
+                    size_t baseline_len,
+                    double *out_result,
+                    struct AnofoxError *out_error);
+
+bool anofox_ts_quantile_loss(const double *actual,
+                             size_t actual_len,
+                             const double *forecast,
+                             size_t forecast_len,
+                             double quantile,
+                             double *out_result,
+                             struct AnofoxError *out_error);
+
+bool anofox_ts_mqloss(const double *actual,
+                      size_t actual_len,
+                      const double *const *quantiles,
+                      size_t n_levels,
+                      const double *levels,
+                      double *out_result,
+                      struct AnofoxError *out_error);
+
+bool anofox_ts_coverage(const double *actual,
+                        size_t actual_len,
+                        const double *lower,
+                        const double *upper,
+                        double *out_result,
+                        struct AnofoxError *out_error);
+
+/*
+ * Every requested figure of `n_groups` groups from ONE GPU pass over their rows.  Replaces the per-group, per-metric FFI calls of
+ * the reference's _ts_metrics_native / _ts_mase_native / _ts_rmae_native / _ts_coverage_native / _ts_quantile_loss_native.
+ *
+ * Figure order (bit k of figures_mask, row k of the output) and the inputs each figure needs besides `actual`:
+ *    0 mae, 1 mse, 2 rmse, 3 mape, 4 smape, 5 r2, 6 bias   forecast
+ *    7 rmae, 8 mase                                        forecast and second (pred2 / baseline; both are forecast's MAE / second's MAE)
+ *    9 quantile_loss                                       forecast, `quantile`
+ *   10 mqloss                                              quantiles, levels, n_levels (1 .. 16)
+ *   11 coverage                                            lower and upper
+ * A requested figure whose input is NULL, an empty mask or a bit above 11: INVALID_INPUT; more than 16 levels: INVALID_INPUT naming
+ * the limit; mqloss with n_levels == 0: INVALID_INPUT "Must have at least one quantile level".
+ *
+ * actual[i], forecast[i], second[i], lower[i], upper[i] point to the lengths[i] values of group i (an array that no requested
+ * figure needs may be NULL as a whole); quantiles[k][i] points to level k's forecasts of group i.  drop_nan: a row in which any
+ * SUPPLIED array holds a NaN is skipped for every figure and does not count -- the row filter of the reference's table functions,
+ * which filter on exactly the columns their statement uses, so supply exactly those.  out_figures is fp64 [12 x n_groups], figure k
+ * of group i at out_figures[k * n_groups + i]; figures that were not requested, or failed, are NaN.  Per-group errors
+ * (out_errors[i], may be NULL) follow the single entries: a group with no row (left) is COMPUTATION_ERROR "Insufficient data: need
+ * at least 1 observations, got 0" unless coverage is the only figure requested (NaN, no error); a quantile or level outside [0, 1]
+ * fails quantile_loss / mqloss with COMPUTATION_ERROR "Invalid input: Quantile must be between 0 and 1" while the other figures are
+ * computed; a NULL quantiles[k][i] fails group i with "Invalid input: Null pointer at quantile index k".  The return value is false
+ * only for batch-level failures, also reported through `out_batch_error`.  Runs on the calling thread's current device
+ * (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_metrics_batch(const double *const *actual,
+                              const double *const *forecast,
+                              const double *const *second,
+                              const double *const *lower,
+                              const double *const *upper,
+                              const double *const *const *quantiles,
+                              const double *levels,
+                              size_t n_levels,
+                              const size_t *lengths,
+                              size_t n_groups,
+                              uint32_t figures_mask,
+                              double quantile,
+                              bool drop_nan,
+                              double *out_figures,
+                              struct AnofoxError *out_errors,
+                              struct AnofoxError *out_batch_error);
+
+/*
+ * The same on device-resident fp64 blocks.  Element (group s, row t) of every input block is at s * stride_s + t * stride_t:
+ * stride_s = 1, stride_t = ld_in is the project's time-major block; stride_s = horizon, stride_t = 1 is the series-major
+ * [n_series x horizon] layout of anofox_hip_batch_device_results, whose yhat / lower / upper can be scored where they lie.  Level
+ * k's forecasts are the block at quantiles + k * stride_q.  `levels` is a HOST array.  lengths is int32 [n_groups] on the device
+ * (a length above t_rows is cut to it).  figures is fp64 [12 x ld] (figure k of group s at k * ld + s; only the requested rows
+ * and the columns s < n_groups are written), status is int32 [n_groups]: 0 done, 1 no row (left) -- every requested figure NaN.
+ * Here a quantile or level outside [0, 1] fails the call (INVALID_INPUT).  One lane per group walks its rows in order; a
+ * series-major block goes through LDS tiles of 64 groups, a time-major one is read directly, and both give the same bits.  Runs
+ * on `stream` (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_metrics_device(const double *actual,
+                               const double *forecast,
+                               const double *second,
+                               const double *lower,
+                               const double *upper,
+                               const double *quantiles,
+                               size_t stride_q,
+                               const double *levels,
+                               size_t n_levels,
+                               size_t stride_s,
+                               size_t stride_t,
+                               const int32_t *lengths,
+                               size_t n_groups,
+                               size_t t_rows,
+                               uint32_t figures_mask,
+                               double quantile,
+                               bool drop_nan,
+                               double *figures,
+                               size_t ld,
+                               int32_t *status,
+                               void *stream,
+                               struct AnofoxError *out_error);
+
+/*
  * Multi-device execution of the batch entry.  The reference's finalize loop is ONE process walking all groups
  * (src/table_functions/ts_forecast_native.cpp:559-800); series are independent, so anofox_ts_forecast_batch shards
  * contiguous series-id ranges [g * ceil(N / G), (g + 1) * ceil(N / G)) over the G devices named here: one host thread,
