@@ -689,7 +689,7 @@ def test_two_level_speculation_counts(env, monkeypatch):
         np.testing.assert_array_equal(r0[k], r1[k])
 
 
-@pytest.mark.parametrize("model", ["AutoETS", "HoltWinters", "SeasonalESOptimized", "ETS:AAA", "ETS:MAdM"])
+@pytest.mark.parametrize("model", ["AutoETS", "HoltWinters", "SeasonalESOptimized", "ETS:AAA", "ETS:MAdM", "SeasonalES", "SESOptimized"])
 def test_auto_detected_periods_merge_into_one_batch(env, monkeypatch, model):
     """params := MAP{} (no seasonal_period): every series gets its own detected period.  The batch entry runs the series of all
     periods of a ring class as ONE batch whose 64-column blocks each have their own period (prep, fit, final pass and the
@@ -1366,7 +1366,10 @@ def test_release_caches_and_double_free_guard(env):
 
 @pytest.mark.parametrize("model,kw", [("AutoETS", dict(seasonal_period=7)), ("AutoETS", dict(seasonal_period=1)),
                                       ("AutoARIMA", dict(seasonal_period=7)), ("HoltWinters", dict(seasonal_period=7)),
-                                      ("ETS", dict(ets_model="MMdM", seasonal_period=7)), ("SESOptimized", dict())])
+                                      ("ETS", dict(ets_model="MMdM", seasonal_period=7)), ("SESOptimized", dict()),
+                                      ("Holt", dict()), ("SeasonalES", dict(seasonal_period=7)), ("SeasonalES", dict(seasonal_period=12)),
+                                      ("SeasonalESOptimized", dict(seasonal_period=7)), ("SeasonalESOptimized", dict(seasonal_period=12)),
+                                      ("SMA", dict()), ("RandomWalkDrift", dict()), ("ARIMA", dict())])
 def test_hostile_inputs_match_oracle(env, model, kw):
     """Non-finite, huge, tiny, negative, all-zero, step and alternating series, lengths around every admissibility
     threshold, horizons 0 / 5 / 200: the same error code or the same bits as the oracle, series by series."""
