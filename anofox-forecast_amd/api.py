@@ -1181,6 +1181,327 @@ anofox_fcst_ts_stats_agg = ts_stats_agg
 
 
 # --------------------------------------------------------------------------------------------
+# series preparation: anofox_hip_prepare_batch, the single entries of gaps.rs / imputation.rs, and the mirrors of ts_fill_gaps_by,
+# ts_fill_nulls_*_by, ts_drop_*_zeros_by and the four drop filters (ts_macros.cpp:172-413)
+# --------------------------------------------------------------------------------------------
+def _unpack_mask(words, n):
+    return [bool((int(words[i >> 6]) >> (i & 63)) & 1) for i in range(n)]
+
+
+def prepare_batch(series, valids=None, dates=None, gaps=False, frequency_micros=0, frequency_type="FIXED", trim="none", fill="none",
+                  fill_value=0.0):
+    """anofox_hip_prepare_batch over a list of 1-D arrays: gaps, trim and fill for all series in one GPU pass.  `valids[i]`
+    (booleans, False = NULL) may be None per series; `dates` (int64 microseconds per series) is given for every series or is None,
+    and each series is stable-sorted by date first.  Per series a dict: "values" (float64 array, NaN at a NULL), "valid" (bool
+    array), "dates" (int64 array or None), "figures" (lib.PREP_FIGURES -> int), "min", "max"."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks = ds = None
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+    if dates is not None:
+        dl = [np.ascontiguousarray(d, dtype=np.int64) for d in dates]
+        for y, d in zip(ys, dl):
+            if len(d) != len(y):
+                raise InvalidInputException("prepare_batch: a series and its dates differ in length")
+        ds = (C.c_void_p * max(n, 1))(*[d.ctypes.data if len(d) else _EMPTY_SERIES_ADDR for d in dl])
+    opts = _lib.make_prep_options(gaps, frequency_micros, frequency_type, trim, fill, fill_value)
+    res = (_lib.AnofoxHipPrepared * max(n, 1))()
+    berr = _lib.AnofoxError()
+    if not L.anofox_hip_prepare_batch(vals, masks, ds, lens.ctypes.data, n, C.byref(opts), C.sizeof(opts), res, C.byref(berr)):
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    try:
+        for i in range(n):
+            r = res[i]
+            m = int(r.length)
+            out.append({"values": np.array(r.values[:m], dtype=np.float64), "valid": np.array(_unpack_mask(r.validity, m), dtype=bool),
+                        "dates": np.array(r.dates[:m], dtype=np.int64) if dates is not None else None,
+                        "figures": {f: int(r.figures[k]) for k, f in enumerate(_lib.PREP_FIGURES)},
+                        "min": float(r.min), "max": float(r.max)})
+    finally:
+        L.anofox_hip_free_prepared(res, n)
+    return out
+
+
+def fill_nulls(values, valid=None, method="const", fill_value=0.0):
+    """The reference's single entries anofox_ts_fill_nulls_const / _mean / _interpolate / _forward / _backward on one series:
+    (values, valid) as arrays; const, mean and interpolate leave no NULL."""
+    L = _lib.load()
+    y = np.ascontiguousarray(values, dtype=np.float64)
+    n = len(y)
+    m = validity_mask(valid) if valid is not None else None
+    yp = y.ctypes.data if n else _EMPTY_SERIES_ADDR
+    mp = m.ctypes.data if m is not None and len(m) else None
+    err = _lib.AnofoxError()
+    if method in ("forward", "backward"):
+        r = _lib.FilledValuesResult()
+        if not getattr(L, "anofox_ts_fill_nulls_" + method)(yp, mp, n, C.byref(r), C.byref(err)):
+            raise InvalidInputException(err.message.decode(errors="replace"))
+        k = int(r.length)
+        out = np.array(r.values[:k], dtype=np.float64), np.array(_unpack_mask(r.validity, k), dtype=bool)
+        L.anofox_free_filled_values_result(C.byref(r))
+        return out
+    q = C.POINTER(C.c_double)()
+    if method == "const":
+        ok = L.anofox_ts_fill_nulls_const(yp, mp, n, float(fill_value), C.byref(q), C.byref(err))
+    else:
+        ok = getattr(L, "anofox_ts_fill_nulls_" + method)(yp, mp, n, C.byref(q), C.byref(err))
+    if not ok:
+        raise InvalidInputException(err.message.decode(errors="replace"))
+    out = np.array(q[:n], dtype=np.float64), np.ones(n, dtype=bool)
+    L.anofox_free_double_array(q)
+    return out
+
+
+def fill_gaps(dates, values, valid=None, frequency_micros=0, frequency_type="FIXED"):
+    """anofox_ts_fill_gaps on one series: (dates, values, valid); inserted rows are NaN and not valid."""
+    L = _lib.load()
+    y = np.ascontiguousarray(values, dtype=np.float64)
+    d = np.ascontiguousarray(dates, dtype=np.int64)
+    n = len(y)
+    m = validity_mask(valid) if valid is not None else None
+    r = _lib.GapFillResult()
+    err = _lib.AnofoxError()
+    ok = L.anofox_ts_fill_gaps(d.ctypes.data if n else _EMPTY_SERIES_ADDR, y.ctypes.data if n else _EMPTY_SERIES_ADDR,
+                               m.ctypes.data if m is not None and len(m) else None, n, int(frequency_micros),
+                               _lib.FREQUENCY_TYPES[frequency_type], C.byref(r), C.byref(err))
+    if not ok:
+        raise InvalidInputException(err.message.decode(errors="replace"))
+    k = int(r.length)
+    out = (np.array(r.dates[:k], dtype=np.int64), np.array(r.values[:k], dtype=np.float64),
+           np.array(_unpack_mask(r.validity, k), dtype=bool))
+    L.anofox_free_gap_fill_result(C.byref(r))
+    return out
+
+
+def _prep_rows(group, date, drop_null_dates):
+    """Groups in first-appearance order with the row numbers of each, ordered by date (ascending, NULLS LAST, stable), the
+    microseconds of every row, the NULL-date mask and the date kind."""
+    dates = np.asarray(date)
+    kind = _date_kind(dates)
+    is_dt = np.issubdtype(dates.dtype, np.datetime64)
+    null_date = np.isnat(dates) if is_dt else np.zeros(len(dates), dtype=bool)
+    us = _to_micros(np.where(null_date, np.datetime64(0, np.datetime_data(dates.dtype)[0]), dates) if null_date.any() else dates, kind)
+    grp = np.asarray(group, dtype=object)
+    order, rows = [], {}
+    for i in range(len(grp)):
+        if drop_null_dates and null_date[i]:
+            continue
+        if grp[i] not in rows:
+            rows[grp[i]] = []
+            order.append(grp[i])
+        rows[grp[i]].append(i)
+    idx = []
+    for k in order:
+        r = np.array(rows[k], dtype=np.int64)
+        idx.append(r[np.lexsort((us[r], null_date[r]))])
+    return order, idx, us, null_date, kind, dates.dtype
+
+
+def _gap_frequency(frequency, kind):
+    """(microseconds, type) as _ts_fill_gaps_native hands them to the core (ts_fill_gaps_native.cpp:450-461): the raw count for
+    integer date columns, days for a raw integer on a date column, else seconds."""
+    f = parse_frequency(frequency)
+    if kind in ("INTEGER", "BIGINT"):
+        return f.seconds, f.type
+    return (f.seconds * _US_PER_DAY if f.is_raw else f.seconds * 1000000), f.type
+
+
+def ts_fill_gaps_by(group, date, value, frequency, group_name="id", date_name="date", value_name="value"):
+    """ts_fill_gaps_by(source, group_col, date_col, value_col, frequency) (macro over _ts_fill_gaps_native).  The date column is
+    DATE, TIMESTAMP, INTEGER or BIGINT; rows with a NULL date are dropped; a repeated (group, date) pair fails as the source's
+    collector does; the frequency spellings are parse_frequency's.  Every group's rows are sorted by date and gap-filled in ONE
+    GPU pass (the reference finalises its groups in one thread, one FFI call each).  Groups come in first-appearance order (the
+    reference's order depends on its thread count).  Returns the three columns; an inserted row and a NULL value are None."""
+    order, idx, us, _, kind, dtype = _prep_rows(group, date, True)
+    micros, ftype = _gap_frequency(frequency, kind)
+    vals, vnull = _changepoint_values(value)
+    for k, r in zip(order, idx):
+        if len(np.unique(us[r])) != len(r):
+            raise InvalidInputException("ts_fill_gaps_by: Duplicate (group, date) pair detected. "
+                                        f"Group '{k}' has multiple rows for the same date. "
+                                        "Please deduplicate your input data before calling this function.")
+    if ftype == "FIXED" and micros <= 0 and order:
+        raise InvalidInputException("ts_fill_gaps failed: Frequency must be positive for fixed intervals")
+    res = prepare_batch([vals[r] for r in idx], [~vnull[r] for r in idx], [us[r] for r in idx], gaps=True, frequency_micros=micros,
+                        frequency_type=ftype) if order else []
+    g, d, v = [], [], []
+    for k, r in zip(order, res):
+        if r["figures"]["status"] != _lib.PREP_OK:
+            raise InvalidInputException("ts_fill_gaps failed: Computation error: the gap-filled series exceeds 16777216 rows")
+        g += [k] * len(r["values"])
+        d.append(_from_micros(r["dates"], kind, dtype))
+        v += [float(x) if ok else None for x, ok in zip(r["values"], r["valid"])]
+    return {group_name: g, date_name: np.concatenate(d) if d else np.asarray(date)[:0], value_name: v}
+
+
+def _by_output(order, idx, columns, sort_groups):
+    """The rows idx[k] of every group, groups ascending (ORDER BY group_col) or in first-appearance order."""
+    ks = list(range(len(order)))
+    if sort_groups:
+        ks.sort(key=lambda k: (order[k] is None, order[k] if order[k] is not None else 0))
+    rows = np.concatenate([idx[k] for k in ks]) if ks else np.zeros(0, dtype=np.int64)
+    return ks, rows, {n: _take(c, rows) for n, c in columns.items()}
+
+
+def _take(col, rows):
+    if isinstance(col, np.ndarray) or np.ma.isMaskedArray(col):
+        return col[rows]
+    return [col[i] for i in rows]
+
+
+def _ts_fill_nulls_by(group, date, value, fill, fill_value, names, extra):
+    order, idx, us, null_date, kind, _ = _prep_rows(group, date, False)
+    vals, vnull = _changepoint_values(value)
+    cols = {names[0]: group, names[1]: date, names[2]: value}
+    cols.update(extra or {})
+    ks, rows, out = _by_output(order, idx, cols, True)
+    res = prepare_batch([vals[idx[k]] for k in ks], [~vnull[idx[k]] for k in ks], fill=fill, fill_value=fill_value) if ks else []
+    filled = []
+    for r in res:
+        filled += [float(x) if ok else None for x, ok in zip(r["values"], r["valid"])]
+    out["filled_value"] = filled
+    return out
+
+
+def ts_fill_nulls_const_by(group, date, value, fill_value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_fill_nulls_const_by (ts_macros.cpp:261-269): every input column (`extra`: further columns by name) plus filled_value =
+    COALESCE(value, fill_value), ordered by group and date (NULLS LAST).  One GPU pass for all groups."""
+    return _ts_fill_nulls_by(group, date, value, "const", fill_value, (group_name, date_name, value_name), extra)
+
+
+def ts_fill_nulls_forward_by(group, date, value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_fill_nulls_forward_by (ts_macros.cpp:274-285): the last valid value in date order; leading NULLs stay NULL (None)."""
+    return _ts_fill_nulls_by(group, date, value, "forward", 0.0, (group_name, date_name, value_name), extra)
+
+
+def ts_fill_nulls_backward_by(group, date, value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_fill_nulls_backward_by (ts_macros.cpp:290-301): the next valid value in date order; trailing NULLs stay NULL (None)."""
+    return _ts_fill_nulls_by(group, date, value, "backward", 0.0, (group_name, date_name, value_name), extra)
+
+
+def ts_fill_nulls_mean_by(group, date, value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_fill_nulls_mean_by (ts_macros.cpp:306-319): the group's mean of the valid values -- the core's sum, in date order from
+    0.0, over their count (imputation.rs:49-59); a group without a valid value stays NULL as AVG over no row is (None), where the
+    core gives NaN."""
+    out = _ts_fill_nulls_by(group, date, value, "mean", 0.0, (group_name, date_name, value_name), extra)
+    _, vnull = _changepoint_values(out[value_name])
+    grp = out[group_name]
+    has_valid = {}
+    for g, nul in zip(grp, vnull):
+        has_valid[g] = has_valid.get(g, False) or not nul
+    out["filled_value"] = [f if has_valid[g] else None for f, g in zip(out["filled_value"], grp)]
+    return out
+
+
+def _ts_drop_zeros_edge(group, date, value, trim, names, extra):
+    order, idx, us, null_date, _, _ = _prep_rows(group, date, True)     # a NULL date compares as NULL: the row is dropped
+    vals, vnull = _changepoint_values(value)
+    res = prepare_batch([vals[r] for r in idx], [~vnull[r] for r in idx], trim=trim) if order else []
+    keep = []
+    for r, p in zip(idx, res):
+        lo, hi = p["figures"]["n_trim_front"], len(r) - p["figures"]["n_trim_back"]
+        # the macros compare DATES (date_col >= _first_nz): rows that share the bounding row's date stay with it
+        while 0 < lo < hi and us[r[lo - 1]] == us[r[lo]]:
+            lo -= 1
+        while lo < hi < len(r) and us[r[hi]] == us[r[hi - 1]]:
+            hi += 1
+        keep.append(r[lo:hi])
+    cols = {names[0]: group, names[1]: date, names[2]: value}
+    cols.update(extra or {})
+    return _by_output(order, keep, cols, False)[2]
+
+
+def ts_drop_leading_zeros_by(group, date, value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_drop_leading_zeros_by (ts_macros.cpp:208-218): the rows from the first non-zero row on (valid and != 0: -0.0 is a zero,
+    NaN is not); a group without one loses every row.  All input columns; groups in first-appearance order, rows by date."""
+    return _ts_drop_zeros_edge(group, date, value, "leading", (group_name, date_name, value_name), extra)
+
+
+def ts_drop_trailing_zeros_by(group, date, value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_drop_trailing_zeros_by (ts_macros.cpp:225-235): the rows up to the last non-zero row."""
+    return _ts_drop_zeros_edge(group, date, value, "trailing", (group_name, date_name, value_name), extra)
+
+
+def ts_drop_edge_zeros_by(group, date, value, group_name="id", date_name="date", value_name="value", extra=None):
+    """ts_drop_edge_zeros_by (ts_macros.cpp:242-253): both."""
+    return _ts_drop_zeros_edge(group, date, value, "edge", (group_name, date_name, value_name), extra)
+
+
+def _group_figures(group, value):
+    """The figures of anofox_hip_prepare_batch (no stage on) of every group, rows in arrival order; a NULL group key matches no
+    `group_col IN (...)` and is left out."""
+    vals, vnull = _changepoint_values(value)
+    grp = np.asarray(group, dtype=object)
+    order, rows = [], {}
+    for i in range(len(grp)):
+        if grp[i] is None:
+            continue
+        if grp[i] not in rows:
+            rows[grp[i]] = []
+            order.append(grp[i])
+        rows[grp[i]].append(i)
+    res = prepare_batch([vals[rows[k]] for k in order], [~vnull[rows[k]] for k in order]) if order else []
+    return grp, {k: r for k, r in zip(order, res)}
+
+
+def _drop_filter(group, value, keep_group, names, extra):
+    grp, fig = _group_figures(group, value)
+    rows = np.array([i for i in range(len(grp)) if grp[i] is not None and keep_group(fig[grp[i]])], dtype=np.int64)
+    cols = {names[0]: group, names[1]: value}
+    cols.update(extra or {})
+    return {n: _take(c, rows) for n, c in cols.items()}
+
+
+def ts_drop_constant_by(group, value, group_name="id", value_name="value", extra=None):
+    """ts_drop_constant_by (ts_macros.cpp:174-184): keeps the groups with MIN(value) != MAX(value) or no valid value (NaN ranks above
+    every number and equals itself).  From the min / max figures of one GPU pass; rows in input order."""
+    def keep(p):
+        f = p["figures"]
+        if f["n_input"] == f["n_null_input"]:
+            return True
+        lo, hi = p["min"], p["max"]
+        return not (lo == hi or (lo != lo and hi != hi))
+    return _drop_filter(group, value, keep, (group_name, value_name), extra)
+
+
+def ts_drop_short_by(group, min_length, value=None, group_name="id", value_name="value", extra=None):
+    """ts_drop_short_by (ts_macros.cpp:191-201): keeps the groups with COUNT(*) >= min_length, NULL rows counted."""
+    value = np.zeros(len(group)) if value is None else value
+    return _drop_filter(group, value, lambda p: p["figures"]["n_input"] >= min_length, (group_name, value_name), extra)
+
+
+def ts_drop_gappy_by(group, value, max_gap_ratio, group_name="id", value_name="value", extra=None):
+    """ts_drop_gappy_by (ts_macros.cpp:383-393): keeps the groups whose share of NULL values is at most max_gap_ratio."""
+    return _drop_filter(group, value, lambda p: float(p["figures"]["n_null_input"]) / float(p["figures"]["n_input"]) <= max_gap_ratio,
+                        (group_name, value_name), extra)
+
+
+def ts_drop_zeros_by(group, value, group_name="id", value_name="value", extra=None):
+    """ts_drop_zeros_by (ts_macros.cpp:400-410): keeps the groups with at least one row that is valid and != 0."""
+    return _drop_filter(group, value, lambda p: p["figures"]["n_nonzero_output"] > 0, (group_name, value_name), extra)
+
+
+anofox_fcst_ts_fill_gaps_by = ts_fill_gaps_by
+anofox_fcst_ts_fill_nulls_const_by = ts_fill_nulls_const_by
+anofox_fcst_ts_fill_nulls_forward_by = ts_fill_nulls_forward_by
+anofox_fcst_ts_fill_nulls_backward_by = ts_fill_nulls_backward_by
+anofox_fcst_ts_fill_nulls_mean_by = ts_fill_nulls_mean_by
+anofox_fcst_ts_drop_leading_zeros_by = ts_drop_leading_zeros_by
+anofox_fcst_ts_drop_trailing_zeros_by = ts_drop_trailing_zeros_by
+anofox_fcst_ts_drop_edge_zeros_by = ts_drop_edge_zeros_by
+anofox_fcst_ts_drop_constant_by = ts_drop_constant_by
+anofox_fcst_ts_drop_short_by = ts_drop_short_by
+anofox_fcst_ts_drop_gappy_by = ts_drop_gappy_by
+anofox_fcst_ts_drop_zeros_by = ts_drop_zeros_by
+
+
+# --------------------------------------------------------------------------------------------
 # exogenous regressors (ARIMAX): anofox_ts_forecast_exog_batch and the mirrors of _ts_forecast_exog / ts_forecast_exog_by
 # --------------------------------------------------------------------------------------------
 # ------------------------------------------------------------------------------------------------------------------------------

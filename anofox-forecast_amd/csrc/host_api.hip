@@ -3932,6 +3932,339 @@ bool anofox_ts_stats(const double *values, const uint64_t *validity, size_t leng
 void anofox_free_ts_stats_result(TsStatsResult *result) { (void)result; }      // the struct owns no memory (as the reference's)
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Series preparation: gaps, zero trimming, NULL fills (gaps.rs, ts_macros.cpp:208-256, imputation.rs; dataprep.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(GapFillResult) == 32 && offsetof(GapFillResult, values) == 8 && offsetof(GapFillResult, validity) == 16 &&
+              offsetof(GapFillResult, length) == 24, "GapFillResult layout");
+static_assert(sizeof(FilledValuesResult) == 24 && offsetof(FilledValuesResult, validity) == 8 && offsetof(FilledValuesResult, length) == 16,
+              "FilledValuesResult layout");
+static_assert(sizeof(AnofoxHipPrepOptions) == 32 && offsetof(AnofoxHipPrepOptions, frequency_micros) == 8 &&
+              offsetof(AnofoxHipPrepOptions, trim) == 16 && offsetof(AnofoxHipPrepOptions, fill_value) == 24, "AnofoxHipPrepOptions layout");
+
+static bool prep_options_ok(const AnofoxHipPrepOptions *o, size_t struct_size, AnofoxError *err)
+{
+    if (struct_size != sizeof(AnofoxHipPrepOptions)) {
+        set_error(err, INVALID_INPUT, "Invalid input: struct_size is not sizeof(AnofoxHipPrepOptions)");
+        return false;
+    }
+    if (o->frequency_type < STATS_FREQ_FIXED || o->frequency_type > STATS_FREQ_YEARLY) {
+        set_error(err, INVALID_INPUT, "Invalid input: unknown frequency type");
+        return false;
+    }
+    if (o->trim < PREP_TRIM_NONE || o->trim > PREP_TRIM_EDGE || o->fill < PREP_FILL_NONE || o->fill > PREP_FILL_INTERPOLATE ||
+        (o->gaps != 0 && o->gaps != 1)) {
+        set_error(err, INVALID_INPUT, "Invalid input: unknown gaps, trim or fill mode");
+        return false;
+    }
+    if (o->gaps && o->frequency_type == STATS_FREQ_FIXED && o->frequency_micros <= 0) {
+        set_error(err, INVALID_FREQUENCY, "Frequency must be positive for fixed intervals");
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_prepare_device(const double *y, const uint8_t *valid, const int64_t *dates, size_t ld, const int32_t *lengths, size_t n_series,
+                               size_t t_rows, const AnofoxHipPrepOptions *options, size_t struct_size, size_t t_out, double *y_out,
+                               uint8_t *valid_out, int64_t *dates_out, int32_t *len_out, int64_t *out_int, double *out_fp, void *stream,
+                               AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !options || !len_out || !out_int || !out_fp) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30) || t_out > (size_t)(1u << 30)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if (!prep_options_ok(options, struct_size, out_error)) return false;
+    if (options->gaps && !dates) { set_error(out_error, INVALID_INPUT, "Invalid input: the gaps stage needs dates"); return false; }
+    if (y_out) {
+        // byte ranges of the blocks: no output may overlap an input (a lane reads rows that another lane's shifted store would hit)
+        struct Range { const char *p; size_t bytes; };
+        const Range in[3] = {{(const char *)y, t_rows * ld * 8}, {(const char *)valid, t_rows * ld}, {(const char *)dates, t_rows * ld * 8}};
+        const Range out[3] = {{(const char *)y_out, t_out * ld * 8}, {(const char *)valid_out, t_out * ld}, {(const char *)dates_out, t_out * ld * 8}};
+        for (const Range &o : out)
+            for (const Range &i : in)
+                if (o.p && i.p && o.bytes && i.bytes && o.p < i.p + i.bytes && i.p < o.p + o.bytes) {
+                    set_error(out_error, INVALID_INPUT, "Invalid input: an output block overlaps an input block");
+                    return false;
+                }
+    }
+    if (!device_ready(out_error)) return false;
+    DataprepArgs a{};
+    a.y = y; a.valid = valid; a.dates = dates; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.gaps = options->gaps; a.freq_type = options->frequency_type; a.freq_us = options->frequency_micros;
+    a.trim = options->trim; a.fill = options->fill; a.fill_value = options->fill_value;
+    a.t_out = t_out; a.y_out = y_out; a.valid_out = y_out ? valid_out : nullptr; a.dates_out = y_out ? dates_out : nullptr;
+    a.len_out = len_out; a.out_int = out_int; a.out_fp = out_fp;
+    hipStream_t st = (hipStream_t)stream;
+    try {
+        (void)hipGetLastError();
+        launch_dataprep(a, st);
+        LAUNCHCHECK("dataprep");
+        HIPCHECK(hipStreamSynchronize(st));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+void anofox_hip_free_prepared(AnofoxHipPrepared *results, size_t n_series)
+{
+    if (!results) return;
+    for (size_t s = 0; s < n_series; s++) {
+        std::free(results[s].dates); std::free(results[s].values); std::free(results[s].validity);
+        results[s].dates = nullptr; results[s].values = nullptr; results[s].validity = nullptr;
+        results[s].length = 0;
+    }
+}
+
+bool anofox_hip_prepare_batch(const double *const *values, const uint64_t *const *validity, const int64_t *const *dates, const size_t *lengths,
+                              size_t n_series, const AnofoxHipPrepOptions *options, size_t struct_size, AnofoxHipPrepared *out_results,
+                              AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (!options || (n_series > 0 && (!values || !lengths || !out_results))) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!prep_options_ok(options, struct_size, out_batch_error)) return false;
+    size_t t_max = 0, n_dated = 0, n_nonempty = 0;
+    bool any_mask = false;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)PREP_MAX_ROWS) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        t_max = std::max(t_max, lengths[s]);
+        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
+        if (lengths[s] > 0) { n_nonempty++; if (dates && dates[s]) n_dated++; }
+    }
+    if (n_dated != 0 && n_dated != n_nonempty) {
+        set_error(out_batch_error, INVALID_INPUT, "Invalid input: dates must be given for every series or for none");
+        return false;
+    }
+    const bool dated = dates != nullptr && (n_dated > 0 || n_nonempty == 0);     // (only empty series: the block still has its date plane)
+    if (options->gaps && !dated && n_nonempty > 0) {
+        set_error(out_batch_error, INVALID_INPUT, "Invalid input: the gaps stage needs dates");
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++) std::memset(&out_results[s], 0, sizeof out_results[s]);
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    double *d_y = nullptr, *d_fp = nullptr, *d_yo = nullptr;
+    uint8_t *d_valid = nullptr, *d_vo = nullptr;
+    int64_t *d_dates = nullptr, *d_int = nullptr, *d_do = nullptr;
+    int32_t *d_len = nullptr, *d_lo = nullptr;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_yo, (void *)d_valid, (void *)d_vo, (void *)d_dates, (void *)d_int, (void *)d_do,
+                        (void *)d_len, (void *)d_lo}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<int64_t> oi(PREP_N_INT * ld);
+    std::vector<double> of(PREP_N_FP * ld), yo;
+    std::vector<uint8_t> vo;
+    std::vector<int64_t> dto;
+    std::vector<int32_t> lo(n_series, 0);
+    size_t t_out = 1;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
+        std::vector<int64_t> db(dated ? T * ld : 0, 0);
+        std::vector<int32_t> len(ld, 0);
+        std::vector<size_t> order;
+        for (size_t s = 0; s < n_series; s++) {
+            const size_t n = lengths[s];
+            len[s] = (int32_t)n;
+            const uint64_t *m = validity ? validity[s] : nullptr;
+            const int64_t *d = dated ? dates[s] : nullptr;
+            order.resize(n);
+            for (size_t t = 0; t < n; t++) order[t] = t;
+            if (d) std::stable_sort(order.begin(), order.end(), [d](size_t i, size_t j) { return d[i] < d[j]; });     // gaps.rs:98-101
+            for (size_t t = 0; t < n; t++) {
+                const size_t i = order[t];
+                yb[t * ld + s] = values[s][i];
+                if (m) vb[t * ld + s] = (uint8_t)((m[i >> 6] >> (i & 63)) & 1);
+                if (d) db[t * ld + s] = d[i];
+            }
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld); d_lo = dalloc<int32_t>(ld);
+        d_int = dalloc<int64_t>(PREP_N_INT * ld); d_fp = dalloc<double>(PREP_N_FP * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (any_mask) {
+            d_valid = dalloc<uint8_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+        }
+        if (dated) {
+            d_dates = dalloc<int64_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_dates, db.data(), T * ld * sizeof(int64_t), hipMemcpyHostToDevice));
+        }
+        // count, size the output block, run
+        if (!anofox_hip_prepare_device(d_y, d_valid, d_dates, ld, d_len, n_series, T, options, struct_size, 0, nullptr, nullptr, nullptr, d_lo,
+                                       d_int, d_fp, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(lo.data(), d_lo, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < n_series; s++) t_out = std::max(t_out, (size_t)lo[s]);
+        d_yo = dalloc<double>(t_out * ld); d_vo = dalloc<uint8_t>(t_out * ld);
+        if (dated) d_do = dalloc<int64_t>(t_out * ld);
+        if (!anofox_hip_prepare_device(d_y, d_valid, d_dates, ld, d_len, n_series, T, options, struct_size, t_out, d_yo, d_vo, d_do, d_lo, d_int,
+                                       d_fp, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        yo.resize(t_out * ld); vo.resize(t_out * ld);
+        HIPCHECK(hipMemcpy(lo.data(), d_lo, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(yo.data(), d_yo, yo.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(vo.data(), d_vo, vo.size(), hipMemcpyDeviceToHost));
+        if (dated) {
+            dto.resize(t_out * ld);
+            HIPCHECK(hipMemcpy(dto.data(), d_do, dto.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        }
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++) {
+        AnofoxHipPrepared &r = out_results[s];
+        for (int i = 0; i < PREP_N_INT; i++) r.figures[i] = oi[i * ld + s];
+        r.min = of[s]; r.max = of[ld + s];
+        const size_t n = (size_t)lo[s];
+        r.length = n;
+        if (n == 0) continue;
+        r.values = (double *)std::malloc(n * sizeof(double));
+        r.validity = (uint64_t *)std::calloc((n + 63) / 64, sizeof(uint64_t));
+        if (dated) r.dates = (int64_t *)std::malloc(n * sizeof(int64_t));
+        if (!r.values || !r.validity || (dated && !r.dates)) {
+            anofox_hip_free_prepared(out_results, n_series);
+            set_error(out_batch_error, ALLOCATION_ERROR, "Failed to allocate prepared series");
+            return false;
+        }
+        for (size_t t = 0; t < n; t++) {
+            r.values[t] = yo[t * ld + s];
+            if (vo[t * ld + s]) r.validity[t >> 6] |= 1ull << (t & 63);
+            if (dated) r.dates[t] = dto[t * ld + s];
+        }
+    }
+    return true;
+}
+
+// one series through anofox_hip_prepare_batch with one stage on
+static bool prep_single(const double *values, const uint64_t *validity, const int64_t *dates, size_t length, const AnofoxHipPrepOptions &o,
+                        AnofoxHipPrepared *r, AnofoxError *out_error)
+{
+    const double *v[1] = {values};
+    const uint64_t *m[1] = {validity};
+    const int64_t *d[1] = {dates};
+    const size_t len[1] = {length};
+    if (!anofox_hip_prepare_batch(v, m, dates ? d : nullptr, len, 1, &o, sizeof o, r, out_error)) return false;
+    if (r->figures[7] != PREP_OK) {
+        anofox_hip_free_prepared(r, 1);
+        set_error(out_error, COMPUTATION_ERROR, "Computation error: the gap-filled series exceeds 16777216 rows");
+        return false;
+    }
+    return true;
+}
+
+static bool prep_fill_values(const double *values, const uint64_t *validity, size_t length, int fill, double fill_value, double **out_values,
+                             AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_values) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxHipPrepOptions o{};
+    o.fill = fill; o.fill_value = fill_value;
+    AnofoxHipPrepared r;
+    if (!prep_single(values, validity, nullptr, length, o, &r, out_error)) return false;
+    *out_values = r.values;
+    std::free(r.validity);
+    return true;
+}
+
+bool anofox_ts_fill_nulls_const(const double *values, const uint64_t *validity, size_t length, double fill_value, double **out_values,
+                                AnofoxError *out_error)
+{
+    return prep_fill_values(values, validity, length, PREP_FILL_CONST, fill_value, out_values, out_error);
+}
+
+bool anofox_ts_fill_nulls_mean(const double *values, const uint64_t *validity, size_t length, double **out_values, AnofoxError *out_error)
+{
+    return prep_fill_values(values, validity, length, PREP_FILL_MEAN, 0.0, out_values, out_error);
+}
+
+bool anofox_ts_fill_nulls_interpolate(const double *values, const uint64_t *validity, size_t length, double **out_values, AnofoxError *out_error)
+{
+    return prep_fill_values(values, validity, length, PREP_FILL_INTERPOLATE, 0.0, out_values, out_error);
+}
+
+static bool prep_fill_masked(const double *values, const uint64_t *validity, size_t length, int fill, FilledValuesResult *out_result,
+                             AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxHipPrepOptions o{};
+    o.fill = fill;
+    AnofoxHipPrepared r;
+    if (!prep_single(values, validity, nullptr, length, o, &r, out_error)) return false;
+    out_result->values = r.values; out_result->validity = r.validity; out_result->length = r.length;
+    return true;
+}
+
+bool anofox_ts_fill_nulls_forward(const double *values, const uint64_t *validity, size_t length, FilledValuesResult *out_result,
+                                  AnofoxError *out_error)
+{
+    return prep_fill_masked(values, validity, length, PREP_FILL_FORWARD, out_result, out_error);
+}
+
+bool anofox_ts_fill_nulls_backward(const double *values, const uint64_t *validity, size_t length, FilledValuesResult *out_result,
+                                   AnofoxError *out_error)
+{
+    return prep_fill_masked(values, validity, length, PREP_FILL_BACKWARD, out_result, out_error);
+}
+
+bool anofox_ts_fill_gaps(const int64_t *dates, const double *values, const uint64_t *validity, size_t length, int64_t frequency_micros,
+                         FrequencyType frequency_type, GapFillResult *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!dates || !values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (frequency_type == FIXED && frequency_micros <= 0) {
+        set_error(out_error, INVALID_FREQUENCY, "Frequency must be positive for fixed intervals");
+        return false;
+    }
+    AnofoxHipPrepOptions o{};
+    o.gaps = 1; o.frequency_type = (int32_t)frequency_type; o.frequency_micros = frequency_micros;
+    AnofoxHipPrepared r;
+    if (!prep_single(values, validity, dates, length, o, &r, out_error)) return false;
+    out_result->dates = r.dates; out_result->values = r.values; out_result->validity = r.validity; out_result->length = r.length;
+    return true;
+}
+
+void anofox_free_gap_fill_result(GapFillResult *result)
+{
+    if (!result) return;
+    std::free(result->dates); std::free(result->values); std::free(result->validity);
+    result->dates = nullptr; result->values = nullptr; result->validity = nullptr; result->length = 0;
+}
+
+void anofox_free_filled_values_result(FilledValuesResult *result)
+{
+    if (!result) return;
+    std::free(result->values); std::free(result->validity);
+    result->values = nullptr; result->validity = nullptr; result->length = 0;
+}
+
+void anofox_free_double_array(double *ptr) { std::free(ptr); }
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Period detection (periods.rs lomb_scargle, aic_comparison, sazed_period, detect_periods_with_validation; periods.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(LombScargleResultFFI) == 64 && offsetof(LombScargleResultFFI, false_alarm_prob) == 24 &&

@@ -237,6 +237,28 @@ size_t stats_work_stride(size_t t_rows);  // words per workspace slice (0: no wo
 int stats_work_waves(int n_series);
 void launch_stats(const StatsArgs &, hipStream_t);
 
+// Series preparation (gaps.rs fill_gaps, the ts_drop_*_zeros_by macros, imputation.rs; dataprep.hip)
+constexpr int PREP_TRIM_NONE = 0, PREP_TRIM_LEADING = 1, PREP_TRIM_TRAILING = 2, PREP_TRIM_EDGE = 3;
+constexpr int PREP_FILL_NONE = 0, PREP_FILL_CONST = 1, PREP_FILL_FORWARD = 2, PREP_FILL_BACKWARD = 3, PREP_FILL_MEAN = 4,
+              PREP_FILL_INTERPOLATE = 5;
+constexpr int PREP_N_INT = 8, PREP_N_FP = 2;
+constexpr int64_t PREP_MAX_ROWS = (int64_t)1 << 24;      // rows of one series after the gaps stage; more: PREP_OVER_LIMIT
+constexpr int64_t PREP_OK = 0, PREP_NO_ROOM = 1, PREP_OVER_LIMIT = 2;
+struct DataprepArgs {
+    const double *y; const uint8_t *valid; const int64_t *dates;      // [t_rows x ld]; valid and dates may be null
+    size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    int gaps, freq_type; int64_t freq_us;
+    int trim, fill; double fill_value;
+    size_t t_out;                // rows of the output blocks
+    double *y_out; uint8_t *valid_out; int64_t *dates_out;            // [t_out x ld]; y_out null: count only; the others may be null
+    int32_t *len_out;            // [n_series]
+    int64_t *out_int;            // [PREP_N_INT x ld] input rows, input NULLs, inserted, trimmed front, trimmed back, output NULLs,
+                                 //                   output rows valid and != 0, status
+    double *out_fp;              // [PREP_N_FP x ld] min, max of the valid output values (NaN ranks above every number)
+};
+void launch_dataprep(const DataprepArgs &, hipStream_t);
+
 // Period detection (periods.rs lomb_scargle, aic_comparison, sazed_period; periods.hip)
 constexpr int PERIODS_LOMB_SCARGLE = 0, PERIODS_AIC = 1, PERIODS_SAZED = 2;
 constexpr int PERIODS_TILE = 2048;       // rows of a series staged in LDS at a time; a longer series is walked tile by tile

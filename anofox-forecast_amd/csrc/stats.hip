@@ -30,6 +30,7 @@
 // built without the switch.
 #include "kernels.hpp"
 #include "det_math.hpp"
+#include "civil_date.hpp"
 
 #ifndef ANOFOX_STATS_SKIP
 #define ANOFOX_STATS_SKIP 0
@@ -97,30 +98,12 @@ __device__ __forceinline__ void st_sort(B buf, int p2, int lane)
     }
 }
 
-__device__ __forceinline__ int64_t st_floor_div(int64_t a, int64_t b)    // b > 0
-{
-    const int64_t q = a / b;
-    return (a % b < 0) ? q - 1 : q;
-}
-
-// year * 12 + month, year * 4 + quarter or year of micros_to_datetime(us) (stats.rs:365-371): seconds by truncating division; a
-// negative remainder makes the nanosecond argument invalid, and the source then falls back to 1970-01-01, as for a date outside
-// chrono's range
+// year * 12 + month, year * 4 + quarter or year of micros_to_datetime(us) (stats.rs:365-371; civil_date.hpp, shared with the gaps
+// stage of dataprep.hip)
 __device__ __forceinline__ int64_t st_period(int64_t us, int type)
 {
-    int64_t y = 1970, m = 1;
-    const int64_t secs = us / 1000000, rem = us % 1000000;
-    if (rem >= 0) {
-        const int64_t z = st_floor_div(secs, 86400) + 719468;
-        const int64_t era = st_floor_div(z, 146097);
-        const int64_t doe = z - era * 146097;
-        const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
-        const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
-        const int64_t mp = (5 * doy + 2) / 153;
-        const int64_t mm = mp < 10 ? mp + 3 : mp - 9;
-        const int64_t yy = yoe + era * 400 + (mm <= 2 ? 1 : 0);
-        if (yy >= -262143 && yy <= 262142) { y = yy; m = mm; }
-    }
+    int64_t y, m;
+    cd_year_month(us, y, m);
     return type == STATS_FREQ_MONTHLY ? y * 12 + m : type == STATS_FREQ_QUARTERLY ? y * 4 + (m - 1) / 3 : y;
 }
 

@@ -23,6 +23,75 @@ def pack_time_major(series_major: np.ndarray, ld: int | None = None) -> np.ndarr
     return out
 
 
+def prepare_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | None = None, dates: torch.Tensor | None = None, *,
+                  n_series: int | None = None, gaps: bool = False, frequency_micros: int = 0, frequency_type: str = "FIXED",
+                  trim: str = "none", fill: str = "none", fill_value: float = 0.0, t_out: int | None = None,
+                  count_only: bool = False, out: dict | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_prepare_device on torch tensors: raw block in, clean block out, no host round trip.
+
+    y [t_rows, ld] fp64, valid [t_rows, ld] uint8 or bool (0 = NULL; None: all valid), dates [t_rows, ld] int64 microseconds (needed
+    for gaps=True), lengths int32 [>= n_series] -- all on one HIP device, contiguous.  The stages run in the fixed order gaps, trim
+    ("none" / "leading" / "trailing" / "edge"), fill ("none" / "const" / "forward" / "backward" / "mean" / "interpolate").  Without
+    t_out a count call sizes the output block first (one device-to-host read of the largest length).  `out` may bring the output
+    tensors "y", "valid", "dates" ([t_out, ld]) and "lengths" (int32 [ld]); else they are allocated, zero-filled.
+
+    Returns {"y", "valid", "dates" (None without input dates), "lengths", "figures" (int64 [8, ld], rows lib.PREP_FIGURES),
+    "minmax" (fp64 [2, ld]), "t_out"}; with count_only the blocks are None.  DeviceBatch(n_series, t_out, opts).set_block(r["y"],
+    r["lengths"]) takes the result as it is (after a fill that leaves no NULL)."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and tuple(valid.shape) == (t_rows, ld)
+    if dates is not None:
+        assert dates.dtype == torch.int64 and dates.is_cuda and dates.is_contiguous() and tuple(dates.shape) == (t_rows, ld)
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    opts = _lib.make_prep_options(gaps, frequency_micros, frequency_type, trim, fill, fill_value)
+    out = dict(out or {})
+    len_out = out.get("lengths")
+    if len_out is None:
+        len_out = torch.zeros(ld, dtype=torch.int32, device=dev)
+    figures = torch.zeros((8, ld), dtype=torch.int64, device=dev)
+    minmax = torch.zeros((2, ld), dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+
+    def call(rows, yo, vo, do):
+        err = _lib.AnofoxError()
+        ok = L.anofox_hip_prepare_device(y.data_ptr(), ptr(valid), ptr(dates), ld, lengths.data_ptr(), n, t_rows, C.byref(opts),
+                                         C.sizeof(opts), rows, ptr(yo), ptr(vo), ptr(do), len_out.data_ptr(), figures.data_ptr(),
+                                         minmax.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+        if not ok:
+            raise RuntimeError(f"anofox_hip_prepare_device failed: [{err.code}] {err.message.decode()}")
+
+    yo, vo, do = out.get("y"), out.get("valid"), out.get("dates")
+    if t_out is None and yo is not None:
+        t_out = int(yo.shape[0])
+    if t_out is None or count_only:
+        call(0, None, None, None)
+        if count_only:
+            return {"y": None, "valid": None, "dates": None, "lengths": len_out, "figures": figures, "minmax": minmax, "t_out": None}
+        t_out = max(1, int(len_out[:n].max().item())) if n else 1
+    t_out = int(t_out)
+    if yo is None:
+        yo = torch.zeros((t_out, ld), dtype=torch.float64, device=dev)
+    if vo is None:
+        vo = torch.zeros((t_out, ld), dtype=torch.uint8, device=dev)
+    if do is None and dates is not None:
+        do = torch.zeros((t_out, ld), dtype=torch.int64, device=dev)
+    for t, dt in ((yo, torch.float64), (vo, torch.uint8), (do, torch.int64)):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (t_out, ld))
+    call(t_out, yo, vo, do)
+    return {"y": yo, "valid": vo, "dates": do if dates is not None else None, "lengths": len_out, "figures": figures, "minmax": minmax,
+            "t_out": t_out}
+
+
 class DeviceBatch:
     """anofox_hip_batch_* over torch-owned HBM."""
 

@@ -168,6 +168,34 @@ METRIC_FIGURES = ("mae", "mse", "rmse", "mape", "smape", "r2", "bias", "rmae", "
 METRICS_MAX_LEVELS = 16
 
 
+class FilledValuesResult(C.Structure):
+    _fields_ = [("values", C.POINTER(C.c_double)), ("validity", C.POINTER(C.c_uint64)), ("length", C.c_size_t)]
+
+
+class GapFillResult(C.Structure):
+    _fields_ = [("dates", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_double)), ("validity", C.POINTER(C.c_uint64)),
+                ("length", C.c_size_t)]
+
+
+class AnofoxHipPrepOptions(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipPrepOptions: the stages of anofox_hip_prepare_device / _batch (32 bytes)."""
+    _fields_ = [("gaps", C.c_int32), ("frequency_type", C.c_int32), ("frequency_micros", C.c_int64), ("trim", C.c_int32),
+                ("fill", C.c_int32), ("fill_value", C.c_double)]
+
+
+class AnofoxHipPrepared(C.Structure):
+    _fields_ = [("dates", C.POINTER(C.c_int64)), ("values", C.POINTER(C.c_double)), ("validity", C.POINTER(C.c_uint64)),
+                ("length", C.c_size_t), ("figures", C.c_int64 * 8), ("min", C.c_double), ("max", C.c_double)]
+
+
+assert (C.sizeof(FilledValuesResult), C.sizeof(GapFillResult), C.sizeof(AnofoxHipPrepOptions), C.sizeof(AnofoxHipPrepared)) == (24, 32, 32, 112)
+PREP_TRIMS = {"none": 0, "leading": 1, "trailing": 2, "edge": 3}
+PREP_FILLS = {"none": 0, "const": 1, "forward": 2, "backward": 3, "mean": 4, "interpolate": 5}
+# rows of out_int of anofox_hip_prepare_device, in order; out_fp holds min, max
+PREP_FIGURES = ("n_input", "n_null_input", "n_inserted", "n_trim_front", "n_trim_back", "n_null_output", "n_nonzero_output", "status")
+PREP_OK, PREP_NO_ROOM, PREP_OVER_LIMIT = 0, 1, 2
+
+
 FREQUENCY_TYPES = {"FIXED": 0, "MONTHLY": 1, "QUARTERLY": 2, "YEARLY": 3}      # include/anofox_fcst_hip.h FrequencyType
 STATS_INT_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[:12])
 STATS_FP_FIELDS = tuple(n for n, _ in TsStatsResult._fields_[12:34])
@@ -235,6 +263,9 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_mae", "anofox_ts_mse", "anofox_ts_rmse", "anofox_ts_mape", "anofox_ts_smape", "anofox_ts_r2", "anofox_ts_bias",
     "anofox_ts_rmae", "anofox_ts_mase", "anofox_ts_quantile_loss", "anofox_ts_mqloss", "anofox_ts_coverage",
     "anofox_hip_metrics_batch", "anofox_hip_metrics_device",
+    "anofox_ts_fill_nulls_const", "anofox_ts_fill_nulls_mean", "anofox_ts_fill_nulls_interpolate", "anofox_ts_fill_nulls_forward",
+    "anofox_ts_fill_nulls_backward", "anofox_ts_fill_gaps", "anofox_free_gap_fill_result", "anofox_free_filled_values_result",
+    "anofox_free_double_array", "anofox_hip_prepare_device", "anofox_hip_prepare_batch", "anofox_hip_free_prepared",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -391,6 +422,29 @@ def load():
     L.anofox_hip_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_double,
                                             C.c_bool, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_fill_nulls_const.restype = C.c_bool
+    L.anofox_ts_fill_nulls_const.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, P(P(C.c_double)), P(AnofoxError)]
+    for name in ("mean", "interpolate"):
+        f = getattr(L, "anofox_ts_fill_nulls_" + name)
+        f.restype = C.c_bool
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(P(C.c_double)), P(AnofoxError)]
+    for name in ("forward", "backward"):
+        f = getattr(L, "anofox_ts_fill_nulls_" + name)
+        f.restype = C.c_bool
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(FilledValuesResult), P(AnofoxError)]
+    L.anofox_ts_fill_gaps.restype = C.c_bool
+    L.anofox_ts_fill_gaps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int, P(GapFillResult), P(AnofoxError)]
+    L.anofox_free_gap_fill_result.argtypes = [P(GapFillResult)]
+    L.anofox_free_filled_values_result.argtypes = [P(FilledValuesResult)]
+    L.anofox_free_double_array.argtypes = [C.c_void_p]
+    L.anofox_hip_prepare_device.restype = C.c_bool
+    L.anofox_hip_prepare_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                            P(AnofoxHipPrepOptions), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_prepare_batch.restype = C.c_bool
+    L.anofox_hip_prepare_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(AnofoxHipPrepOptions), C.c_size_t,
+                                           P(AnofoxHipPrepared), P(AnofoxError)]
+    L.anofox_hip_free_prepared.argtypes = [P(AnofoxHipPrepared), C.c_size_t]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -429,6 +483,18 @@ def make_options(model, horizon, *, ets_model="", seasonal_period=0, confidence_
     o.window = int(window)
     o.seasonal_periods_str = seasonal_periods_str.encode()[:63]
     o.model_pool = model_pool.encode()[:31]
+    return o
+
+
+def make_prep_options(gaps=False, frequency_micros=0, frequency_type="FIXED", trim="none", fill="none", fill_value=0.0):
+    """AnofoxHipPrepOptions from names: trim in PREP_TRIMS, fill in PREP_FILLS, frequency_type in FREQUENCY_TYPES."""
+    o = AnofoxHipPrepOptions()
+    o.gaps = 1 if gaps else 0
+    o.frequency_type = FREQUENCY_TYPES[frequency_type]
+    o.frequency_micros = int(frequency_micros)
+    o.trim = PREP_TRIMS[trim]
+    o.fill = PREP_FILLS[fill]
+    o.fill_value = float(fill_value)
     return o
 
 

@@ -325,6 +325,83 @@ bool anofox_ts_stats_with_dates_and_type(const double *values,
 
 void anofox_free_ts_stats_result(struct TsStatsResult *result);
 
+/* Values with a validity bitmask (bit i of word i / 64), the reference's FilledValuesResult: sizeof == 24. */
+typedef struct FilledValuesResult {
+    double *values;
+    uint64_t *validity;
+    size_t length;
+} FilledValuesResult;
+
+/* Dates, values and validity after the gaps stage, the reference's GapFillResult: sizeof == 32. */
+typedef struct GapFillResult {
+    int64_t *dates;
+    double *values;
+    uint64_t *validity;
+    size_t length;
+} GapFillResult;
+
+/*
+ * The NULL fills of ONE series, the reference's imputation.rs behind its FFI wrappers.  `validity` (bit i of word i / 64; NULL =
+ * all valid) marks NULLs.  const, mean and interpolate return *out_values, `length` doubles (malloc; anofox_free_double_array;
+ * NULL for length 0): mean is the sum of the valid values in row order from 0.0 over their count, and NaN everywhere when there is
+ * none; interpolate extends the edges with the first / last valid value, fills interior runs with prev + slope * j, slope =
+ * (v - prev) / gap, and gives NaN everywhere when there is no valid value.  forward and backward keep leading / trailing NULLs:
+ * they return values (NaN where NULL) with a validity bitmask (anofox_free_filled_values_result; both NULL for length 0).  NULL
+ * `values` or output: NULL_POINTER "Null pointer argument".  Each runs on the GPU as a batch of one, through the kernels of
+ * anofox_hip_prepare_device: the same bits.
+ */
+bool anofox_ts_fill_nulls_const(const double *values,
+                                const uint64_t *validity,
+                                size_t length,
+                                double fill_value,
+                                double **out_values,
+                                struct AnofoxError *out_error);
+
+bool anofox_ts_fill_nulls_mean(const double *values,
+                               const uint64_t *validity,
+                               size_t length,
+                               double **out_values,
+                               struct AnofoxError *out_error);
+
+bool anofox_ts_fill_nulls_interpolate(const double *values,
+                                      const uint64_t *validity,
+                                      size_t length,
+                                      double **out_values,
+                                      struct AnofoxError *out_error);
+
+bool anofox_ts_fill_nulls_forward(const double *values,
+                                  const uint64_t *validity,
+                                  size_t length,
+                                  struct FilledValuesResult *out_result,
+                                  struct AnofoxError *out_error);
+
+bool anofox_ts_fill_nulls_backward(const double *values,
+                                   const uint64_t *validity,
+                                   size_t length,
+                                   struct FilledValuesResult *out_result,
+                                   struct AnofoxError *out_error);
+
+/*
+ * The gaps stage of ONE series (gaps.rs fill_gaps): the rows are stable-sorted by date, then for every pair of consecutive rows
+ * FIXED inserts (d_i - d_prev) / frequency_micros - 1 NULL rows (truncating division) dated d_prev + step * frequency_micros,
+ * and the calendar types insert one row per missing month, quarter or year, dated at the start of the previous row's period plus
+ * `step` periods, 00:00:00 UTC.  Original rows keep their dates.  Inserted values are NaN with a clear validity bit.  FIXED with
+ * frequency_micros <= 0: INVALID_FREQUENCY "Frequency must be positive for fixed intervals".  NULL dates, values or out_result:
+ * NULL_POINTER.  length 0: all three arrays NULL.  A result above 16,777,216 rows: COMPUTATION_ERROR.
+ */
+bool anofox_ts_fill_gaps(const int64_t *dates,
+                         const double *values,
+                         const uint64_t *validity,
+                         size_t length,
+                         int64_t frequency_micros,
+                         enum FrequencyType frequency_type,
+                         struct GapFillResult *out_result,
+                         struct AnofoxError *out_error);
+
+void anofox_free_gap_fill_result(struct GapFillResult *result);
+void anofox_free_filled_values_result(struct FilledValuesResult *result);
+void anofox_free_double_array(double *ptr);
+
 /* One exogenous regressor: `values[n_values]` aligned with the series, `future_values[n_future]` with the horizon. */
 typedef struct ExogenousRegressor {
     const double *values;
@@ -553,6 +630,87 @@ bool anofox_hip_stats_device(const double *y,
                              double *out_fp,
                              void *stream,
                              struct AnofoxError *out_error);
+
+/* What anofox_hip_prepare_device / _batch run, in this fixed order: gaps, trim, fill.  Zero everywhere is "copy the rows". */
+typedef struct AnofoxHipPrepOptions {
+    int32_t gaps;             /* 1: the gaps stage of anofox_ts_fill_gaps runs (needs dates) */
+    int32_t frequency_type;   /* FrequencyType of the gaps stage */
+    int64_t frequency_micros; /* FIXED: > 0 */
+    int32_t trim;             /* 0 none, 1 leading, 2 trailing, 3 edge: the ts_drop_*_zeros_by macros.  A row is non-zero when it
+                                 is valid and y != 0 (-0.0 is a zero, NaN is non-zero, a NULL is not non-zero) */
+    int32_t fill;             /* 0 none, 1 const, 2 forward, 3 backward, 4 mean, 5 interpolate: anofox_ts_fill_nulls_* */
+    double fill_value;        /* const */
+} AnofoxHipPrepOptions;
+
+/*
+ * Prepares every series of a device-resident time-major block for anofox_hip_batch_set_device_block without a host round trip.
+ * Layout as anofox_hip_stats_device: y[t * ld + s] (fp64, t < t_rows), `valid` (uint8 [t_rows x ld], 0 = NULL; NULL pointer: all
+ * valid), `dates` (int64 [t_rows x ld], microseconds; may be NULL unless options->gaps, then INVALID_INPUT), lengths[n_series]
+ * (int32; cut to t_rows).  struct_size is sizeof(AnofoxHipPrepOptions) (anything else: INVALID_INPUT).  The entry does NOT sort: the
+ * gaps stage walks the rows as they lie (descending or duplicate dates insert nothing).  Outputs: y_out, valid_out (may be NULL),
+ * dates_out (may be NULL; written only when `dates` is given) are [t_out x ld] blocks, len_out is int32 [n_series]; a NULL output
+ * row holds NaN and valid 0; output rows start at row 0 (dates move with their rows).  Outputs must not overlap inputs
+ * (INVALID_INPUT).  Columns s >= n_series and rows >= len_out[s] are left untouched.
+ *
+ * out_int is int64 [8 x ld]: input rows, input NULLs, rows inserted by the gaps stage, rows trimmed at the front, rows trimmed
+ * at the back, output NULLs, output rows that are valid and != 0, status.  out_fp is fp64 [2 x ld]: min and max of the valid
+ * output values, NaN ranking above every number (both NaN without a valid value).  A series with no non-zero row is trimmed to
+ * length 0 (counted at the front, for trailing-only at the back).  status 1: the result needs more than t_out rows; len_out[s] = 0,
+ * nothing written, the counts hold (input rows + inserted - trimmed is the need), the output figures are 0 / NaN, and the
+ * neighbours are unaffected.  status 2: more than 16,777,216 rows after the gaps stage; as status 1, in count mode too (the
+ * inserted count saturates at 2^40).  y_out == NULL is count mode: len_out and all figures, no blocks; it sizes t_out.
+ *
+ * One lane per series, two sweeps (dataprep.hip); the same bits on every run and through every entry.  Runs on `stream` (NULL:
+ * the null stream) on the calling thread's current device and returns after it has finished.
+ */
+bool anofox_hip_prepare_device(const double *y,
+                               const uint8_t *valid,
+                               const int64_t *dates,
+                               size_t ld,
+                               const int32_t *lengths,
+                               size_t n_series,
+                               size_t t_rows,
+                               const AnofoxHipPrepOptions *options,
+                               size_t struct_size,
+                               size_t t_out,
+                               double *y_out,
+                               uint8_t *valid_out,
+                               int64_t *dates_out,
+                               int32_t *len_out,
+                               int64_t *out_int,
+                               double *out_fp,
+                               void *stream,
+                               struct AnofoxError *out_error);
+
+/* One prepared series of anofox_hip_prepare_batch: malloc'd arrays (NULL for length 0; dates NULL when none were given). */
+typedef struct AnofoxHipPrepared {
+    int64_t *dates;
+    double *values;
+    uint64_t *validity;
+    size_t length;
+    int64_t figures[8];       /* out_int of anofox_hip_prepare_device */
+    double min, max;
+} AnofoxHipPrepared;
+
+/*
+ * The same for host series, in one pass (a count call sizes the output block).  `validity` and `dates` may be NULL, and so may
+ * validity[i]; dates[i] must be given for every series or for none (INVALID_INPUT), and must be given when options->gaps.  With
+ * dates, every series is stable-sorted by date first, as fill_gaps does.  out_results is AnofoxHipPrepared[n_series], released by
+ * anofox_hip_free_prepared.  A series above the row limit gets status 2 and length 0.  Replaces the per-group loop of the
+ * reference's _ts_fill_gaps_native finalize.  The return value is false only for batch-level failures, also reported through
+ * `out_batch_error`.
+ */
+bool anofox_hip_prepare_batch(const double *const *values,
+                              const uint64_t *const *validity,
+                              const int64_t *const *dates,
+                              const size_t *lengths,
+                              size_t n_series,
+                              const AnofoxHipPrepOptions *options,
+                              size_t struct_size,
+                              AnofoxHipPrepared *out_results,
+                              struct AnofoxError *out_batch_error);
+
+void anofox_hip_free_prepared(AnofoxHipPrepared *results, size_t n_series);
 
 /*
  * Period detection of `n_series` series with ONE method and one parameter set, in one GPU pass.  Replaces the per-group calls of
