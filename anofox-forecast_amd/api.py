@@ -1728,6 +1728,400 @@ def ts_detect_periods(date, value, params=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# Conformal prediction intervals: learn -> apply for every group in ONE call
+# ------------------------------------------------------------------------------------------------------------------------------
+def conformal_batch(residuals, forecasts=None, alphas=(0.1,), method="symmetric", strategy="split", difficulty=None, valids=None,
+                    want_sorted=False):
+    """anofox_hip_conformal_batch: the reference's conformalize (conformal_learn, then conformal_apply) for every group from one GPU
+    pass each.  residuals and forecasts are lists with one 1-D array per group; `valids[i]` (booleans, False = NULL, dropped) may be
+    None per group; difficulty (adaptive method) has one array per group of its forecasts' length.  forecasts=None learns only.
+    method: "symmetric" / "asymmetric" / "adaptive"; strategy: "split" / "crossval" / "jackknife+" (the scores are the same, as in the
+    source; want_sorted returns the sorted |residual| that Jackknife+ stores).
+
+    Returns a dict of per-group lists: "scores_lower", "scores_upper" (arrays [n_alphas]), "n_residuals", "lower", "upper" (arrays
+    [n_alphas, n_forecasts], None without forecasts), "sorted" (array or None), "coverage" (1 - alpha per level), and "code" (int array,
+    0 = SUCCESS) and "message" per group; a failed group holds None in every list."""
+    m = str(method).lower()
+    sg = str(strategy).lower()
+    if m not in _lib.CONFORMAL_METHODS:
+        raise InvalidInputException(f"Invalid input: Unknown conformal method: '{method}'. Valid: symmetric, asymmetric, adaptive")
+    if sg not in _lib.CONFORMAL_STRATEGIES:
+        raise InvalidInputException(f"Invalid input: Unknown conformal strategy: '{strategy}'. Valid: split, crossval, jackknife+")
+    L = _lib.load()
+    n = len(residuals)
+    keep = []
+
+    def column(cols):
+        if cols is None:
+            return None, None, None
+        arrs, p = _metric_columns(cols, n)
+        keep.append(arrs)
+        return arrs, p, np.array([len(a) for a in arrs], dtype=np.uint64)
+
+    r_arrs, r_ptr, r_len = column(residuals)
+    f_arrs, f_ptr, f_len = column(forecasts)
+    d_arrs, d_ptr, _ = column(difficulty if m == "adaptive" else None)
+    if d_arrs is not None and (f_arrs is None or any(len(a) != len(b) for a, b in zip(d_arrs, f_arrs))):
+        raise InvalidInputException("Invalid input: Difficulty length must match forecasts length")
+    v_ptr = None
+    if valids is not None:
+        if len(valids) != n:
+            raise InvalidInputException("Invalid input: every supplied block needs one array per group")
+        words = []
+        for v, a in zip(valids, r_arrs):
+            if v is None:
+                words.append(None)
+                continue
+            b = np.asarray(v, dtype=bool)
+            if len(b) != len(a):
+                raise InvalidInputException("Invalid input: the arrays of a group must have the same length")
+            w = np.zeros((len(b) + 63) // 64 + 1, dtype=np.uint64)
+            for t in np.nonzero(b)[0]:
+                w[t // 64] |= np.uint64(1) << np.uint64(t % 64)
+            words.append(w)
+        keep.append(words)
+        v_ptr = (C.c_void_p * max(n, 1))(*[None if w is None else w.ctypes.data for w in words])
+    al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+    res = (_lib.AnofoxHipConformal * max(n, 1))()
+    errs = (_lib.AnofoxError * max(n, 1))()
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_conformal_batch(r_ptr, v_ptr, r_len.ctypes.data, f_ptr, d_ptr, None if f_len is None else f_len.ctypes.data, n,
+                                      al.ctypes.data, len(al), _lib.CONFORMAL_METHODS[m], _lib.CONFORMAL_STRATEGIES[sg], bool(want_sorted),
+                                      res, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = {k: [None] * n for k in ("scores_lower", "scores_upper", "n_residuals", "lower", "upper", "sorted")}
+    try:
+        for i in range(n):
+            if errs[i].code != _lib.SUCCESS:
+                continue
+            r = res[i]
+            k, h, nr = int(r.n_levels), int(r.n_forecasts), int(r.n_residuals)
+            out["scores_lower"][i] = np.ctypeslib.as_array(r.scores_lower, (k,)).copy()
+            out["scores_upper"][i] = np.ctypeslib.as_array(r.scores_upper, (k,)).copy()
+            out["n_residuals"][i] = nr
+            if forecasts is not None:
+                out["lower"][i] = np.ctypeslib.as_array(r.lower, (max(k * h, 1),))[:k * h].reshape(k, h).copy()
+                out["upper"][i] = np.ctypeslib.as_array(r.upper, (max(k * h, 1),))[:k * h].reshape(k, h).copy()
+            if want_sorted:
+                out["sorted"][i] = np.ctypeslib.as_array(r.sorted, (max(nr, 1),))[:nr].copy()
+    finally:
+        L.anofox_hip_free_conformal(res, n)
+    out["coverage"] = [1.0 - float(a) for a in al]
+    out["code"] = np.array([errs[i].code for i in range(n)], dtype=np.int32)
+    out["message"] = [errs[i].message.decode(errors="replace") for i in range(n)]
+    return out
+
+
+def _conformal_list(values):
+    """ExtractListAsDouble (conformal.cpp:14-32) of a list argument: None for a NULL list, else its non-NULL elements.  An empty
+    vector hands the FFI a null pointer, which fails the call: callers return None then."""
+    return None if values is None else _list_values(values)
+
+
+def _conformal_result(r):
+    n = int(r.n_forecasts)
+    take = lambda p: [float(p[i]) for i in range(n)]
+    return {"point": take(r.point), "lower": take(r.lower), "upper": take(r.upper), "coverage": float(r.coverage),
+            "conformity_score": float(r.conformity_score), "method": r.method.decode()}
+
+
+def ts_conformal_quantile(residuals, alpha):
+    """The scalar ts_conformal_quantile(residuals[], alpha) (conformal.cpp:38-75) over anofox_ts_conformal_quantile: the conformity
+    score, or None for a NULL argument and for every failure of the call (an empty list, an alpha outside [0, 1))."""
+    r = _conformal_list(residuals)
+    if r is None or alpha is None or len(r) == 0:
+        return None
+    L = _lib.load()
+    out, err = C.c_double(), _lib.AnofoxError()
+    if not L.anofox_ts_conformal_quantile(r.ctypes.data, None, len(r), float(alpha), C.byref(out), C.byref(err)):
+        return None
+    return float(out.value)
+
+
+def ts_conformal_intervals(forecasts, conformity_score):
+    """ts_conformal_intervals(forecasts[], score) -> {"lower", "upper"} (conformal.cpp:126-200)."""
+    f = _conformal_list(forecasts)
+    if f is None or conformity_score is None or len(f) == 0:
+        return None
+    L = _lib.load()
+    lo, up, err = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), _lib.AnofoxError()
+    if not L.anofox_ts_conformal_intervals(f.ctypes.data, len(f), float(conformity_score), C.byref(lo), C.byref(up), C.byref(err)):
+        return None
+    out = {"lower": [float(lo[i]) for i in range(len(f))], "upper": [float(up[i]) for i in range(len(f))]}
+    L.anofox_free_double_array(lo)
+    L.anofox_free_double_array(up)
+    return out
+
+
+def _conformal_predict(entry, residuals, forecasts, alpha):
+    r, f = _conformal_list(residuals), _conformal_list(forecasts)
+    if r is None or f is None or alpha is None or len(r) == 0 or len(f) == 0:
+        return None
+    L = _lib.load()
+    res, err = _lib.ConformalResultFFI(), _lib.AnofoxError()
+    if not getattr(L, entry)(r.ctypes.data, None, len(r), f.ctypes.data, len(f), float(alpha), C.byref(res), C.byref(err)):
+        return None
+    out = _conformal_result(res)
+    L.anofox_free_conformal_result(C.byref(res))
+    return out
+
+
+def ts_conformal_predict(residuals, forecasts, alpha):
+    """ts_conformal_predict(residuals[], forecasts[], alpha) -> {"point", "lower", "upper", "coverage", "conformity_score", "method"}
+    (conformal.cpp:250-350); None where the source answers NULL."""
+    return _conformal_predict("anofox_ts_conformal_predict", residuals, forecasts, alpha)
+
+
+def ts_conformal_predict_asymmetric(residuals, forecasts, alpha):
+    """ts_conformal_predict_asymmetric: separate margins from the positive and the negative residuals (conformal.cpp:405-505)."""
+    return _conformal_predict("anofox_ts_conformal_predict_asymmetric", residuals, forecasts, alpha)
+
+
+def _conformal_method_code(text):
+    """ParseConformalMethod (conformal.cpp:560-569): anything unknown is symmetric."""
+    return {"symmetric": 0, "Symmetric": 0, "asymmetric": 1, "Asymmetric": 1, "adaptive": 2, "Adaptive": 2}.get(str(text), 0)
+
+
+def _conformal_strategy_code(text):
+    """ParseConformalStrategy (conformal.cpp:571-580): anything unknown is split."""
+    return {"split": 0, "Split": 0, "crossval": 1, "CrossVal": 1, "cross_val": 1, "jackknife_plus": 2, "JackknifePlus": 2,
+            "jackknife+": 2}.get(str(text), 0)
+
+
+_CONFORMAL_METHOD_TEXT = ("symmetric", "asymmetric", "adaptive")
+_CONFORMAL_STRATEGY_TEXT = ("split", "crossval", "jackknife_plus")
+
+
+def ts_conformal_learn(residuals, alphas, method="symmetric", strategy="split"):
+    """ts_conformal_learn(residuals[], alphas[], method, strategy) -> the profile {"method", "strategy", "alphas", "state_vector",
+    "scores_lower", "scores_upper", "n_residuals"} (conformal.cpp:600-735).  The scalar passes no difficulty scores, so the adaptive
+    method answers None, as every failure does."""
+    r, a = _conformal_list(residuals), _conformal_list(alphas)
+    if r is None or a is None or method is None or strategy is None or len(r) == 0 or len(a) == 0:
+        return None
+    L = _lib.load()
+    prof, err = _lib.CalibrationProfileFFI(), _lib.AnofoxError()
+    if not L.anofox_ts_conformal_learn(r.ctypes.data, None, len(r), a.ctypes.data, len(a), _conformal_method_code(method),
+                                       _conformal_strategy_code(strategy), None, C.byref(prof), C.byref(err)):
+        return None
+    k = int(prof.n_levels)
+    out = {"method": _CONFORMAL_METHOD_TEXT[prof.method], "strategy": _CONFORMAL_STRATEGY_TEXT[prof.strategy],
+           "alphas": [float(prof.alphas[i]) for i in range(k)],
+           "state_vector": [float(prof.state_vector[i]) for i in range(int(prof.state_vector_len))],
+           "scores_lower": [float(prof.scores_lower[i]) for i in range(k)],
+           "scores_upper": [float(prof.scores_upper[i]) for i in range(k)], "n_residuals": int(prof.n_residuals)}
+    L.anofox_free_calibration_profile(C.byref(prof))
+    return out
+
+
+def ts_conformal_apply(forecasts, profile):
+    """ts_conformal_apply(forecasts[], profile) -> {"point", "coverage", "lower", "upper", "method"} with lower / upper one list per
+    level (conformal.cpp:788-935); `profile` is what ts_conformal_learn returned."""
+    f = _conformal_list(forecasts)
+    if f is None or profile is None or len(f) == 0:
+        return None
+    al, sv = _list_values(profile["alphas"]), _list_values(profile["state_vector"])
+    sl, su = _list_values(profile["scores_lower"]), _list_values(profile["scores_upper"])
+    if len(al) == 0 or len(sl) < len(al) or len(su) < len(al):
+        return None
+    L = _lib.load()
+    prof = _lib.CalibrationProfileFFI()
+    prof.method, prof.strategy = _conformal_method_code(profile["method"]), _conformal_strategy_code(profile["strategy"])
+    as_ptr = lambda a: C.cast(a.ctypes.data, C.POINTER(C.c_double)) if len(a) else C.POINTER(C.c_double)()
+    prof.alphas, prof.state_vector, prof.scores_lower, prof.scores_upper = as_ptr(al), as_ptr(sv), as_ptr(sl), as_ptr(su)
+    prof.state_vector_len, prof.n_levels, prof.n_residuals = len(sv), len(al), int(profile["n_residuals"])
+    iv, err = _lib.PredictionIntervalsFFI(), _lib.AnofoxError()
+    if not L.anofox_ts_conformal_apply(f.ctypes.data, len(f), C.byref(prof), None, C.byref(iv), C.byref(err)):
+        return None
+    k, h = int(iv.n_levels), int(iv.n_forecasts)
+    out = {"point": [float(iv.point[t]) for t in range(h)], "coverage": [float(iv.coverage[i]) for i in range(k)],
+           "lower": [[float(iv.lower[i * h + t]) for t in range(h)] for i in range(k)],
+           "upper": [[float(iv.upper[i * h + t]) for t in range(h)] for i in range(k)], "method": _CONFORMAL_METHOD_TEXT[iv.method]}
+    L.anofox_free_prediction_intervals(C.byref(iv))
+    return out
+
+
+def _conformal_three(actuals, lower, upper):
+    a, l, u = _conformal_list(actuals), _conformal_list(lower), _conformal_list(upper)
+    if a is None or l is None or u is None or len(a) != len(l) or len(a) != len(u) or len(a) == 0:
+        return None
+    return a, l, u
+
+
+def ts_conformal_coverage(actuals, lower, upper):
+    """ts_conformal_coverage(actuals[], lower[], upper[]) (conformal.cpp:989-1030): NULL cells are dropped from each list on its
+    own; lists of different lengths then, or empty ones, give None."""
+    cols = _conformal_three(actuals, lower, upper)
+    if cols is None:
+        return None
+    a, l, u = cols
+    L = _lib.load()
+    out, err = C.c_double(), _lib.AnofoxError()
+    if not L.anofox_ts_conformal_coverage(a.ctypes.data, l.ctypes.data, u.ctypes.data, len(a), C.byref(out), C.byref(err)):
+        return None
+    return float(out.value)
+
+
+def ts_conformal_evaluate(actuals, lower, upper, alpha):
+    """ts_conformal_evaluate(actuals[], lower[], upper[], alpha) -> {"coverage", "violation_rate", "mean_width", "winkler_score",
+    "n_observations"} (conformal.cpp:1084-1150)."""
+    cols = _conformal_three(actuals, lower, upper)
+    if cols is None or alpha is None:
+        return None
+    a, l, u = cols
+    L = _lib.load()
+    ev, err = _lib.ConformalEvaluationFFI(), _lib.AnofoxError()
+    if not L.anofox_ts_conformal_evaluate(a.ctypes.data, l.ctypes.data, u.ctypes.data, len(a), float(alpha), C.byref(ev), C.byref(err)):
+        return None
+    return {"coverage": float(ev.coverage), "violation_rate": float(ev.violation_rate), "mean_width": float(ev.mean_width),
+            "winkler_score": float(ev.winkler_score), "n_observations": int(ev.n_observations)}
+
+
+def ts_mean_interval_width(lower, upper):
+    """ts_mean_interval_width(lower[], upper[]) (conformal.cpp:1206-1245)."""
+    l, u = _conformal_list(lower), _conformal_list(upper)
+    if l is None or u is None or len(l) != len(u) or len(l) == 0:
+        return None
+    L = _lib.load()
+    out, err = C.c_double(), _lib.AnofoxError()
+    if not L.anofox_ts_mean_interval_width(l.ctypes.data, u.ctypes.data, len(l), C.byref(out), C.byref(err)):
+        return None
+    return float(out.value)
+
+
+for _name in ("conformal_quantile", "conformal_intervals", "conformal_predict", "conformal_predict_asymmetric", "conformal_learn",
+              "conformal_apply", "conformal_coverage", "conformal_evaluate", "mean_interval_width"):
+    globals()["anofox_fcst_ts_" + _name] = globals()["ts_" + _name]            # the aliases conformal.cpp registers
+
+
+def _conformal_params(params):
+    """alpha and method of the macros' params MAP: TRY_CAST(alpha AS DOUBLE) with 0.1 for a missing or unreadable one; the method
+    text as it stands, 'symmetric' when missing."""
+    alpha, method = 0.1, "symmetric"
+    a = _param(params, "alpha")
+    if a is not None:
+        try:
+            alpha = float(a)
+        except (TypeError, ValueError):
+            alpha = 0.1
+    m = _param(params, "method")
+    if m is not None:
+        method = str(m)
+    return alpha, method
+
+
+def _conformal_groups(names_cols, n_rows, keep):
+    """Group keys in order of first appearance and their member rows, over the rows of `keep`."""
+    names, gcols = names_cols
+    order, members = [], {}
+    for i in range(n_rows):
+        if not keep[i]:
+            continue
+        g = tuple(c[i] for c in gcols)
+        if g not in members:
+            members[g] = []
+            order.append(g)
+        members[g].append(i)
+    return order, members
+
+
+def ts_conformal_by(group_columns, actual, forecast, point_forecast, params=None):
+    """ts_conformal_by(backtest_results, group_col, actual_col, forecast_col, point_forecast_col, params) (ts_macros.cpp:1446-1506):
+    the residuals (actual - forecast)::DOUBLE of the rows where both are not NULL calibrate, per group, intervals around the group's
+    point forecasts -- which the macro orders ASCENDING BY VALUE (its LIST(... ORDER BY point_forecast_col)).  params: alpha (default
+    0.1), method ('asymmetric', anything else is symmetric).  Groups that have both residuals and point forecasts, in order of first
+    appearance; ALL groups go to the GPU in one anofox_hip_conformal_batch call.  Returns a dict of columns: the group columns, point,
+    lower, upper (lists), coverage, conformity_score, method; a group whose call fails (an alpha outside [0, 1)) holds None."""
+    alpha, method = _conformal_params(params)
+    a, a_null = _changepoint_values(actual)
+    f, f_null = _changepoint_values(forecast)
+    p, p_null = _changepoint_values(point_forecast)
+    n_rows = len(a)
+    if len(f) != n_rows or len(p) != n_rows:
+        raise InvalidInputException("Invalid input: every column needs one value per row")
+    nc = _metric_group_columns(group_columns, n_rows)
+    r_order, r_members = _conformal_groups(nc, n_rows, ~(a_null | f_null))
+    _, p_members = _conformal_groups(nc, n_rows, ~p_null)
+    order = [g for g in r_order if g in p_members]
+    out = {name: [g[j] for g in order] for j, name in enumerate(nc[0])}
+    cols = ("point", "lower", "upper", "coverage", "conformity_score", "method")
+    out.update({c: [None] * len(order) for c in cols})
+    if not order:
+        return out
+    asym = method == "asymmetric"
+    res = [a[np.array(r_members[g])] - f[np.array(r_members[g])] for g in order]
+    pts = [np.sort(p[np.array(p_members[g])]) for g in order]
+    if not (0.0 <= alpha < 1.0):
+        return out                                                 # every group's call fails: NULL structs
+    r = conformal_batch(res, pts, [alpha], method="asymmetric" if asym else "symmetric")
+    for i in range(len(order)):
+        if r["code"][i] != _lib.SUCCESS:
+            continue
+        lo, up = float(r["scores_lower"][i][0]), float(r["scores_upper"][i][0])
+        out["point"][i] = [float(v) for v in pts[i]]
+        out["lower"][i] = [float(v) for v in r["lower"][i][0]]
+        out["upper"][i] = [float(v) for v in r["upper"][i][0]]
+        out["coverage"][i] = 1.0 - alpha
+        out["conformity_score"][i] = (up + lo) / 2.0 if asym else lo
+        out["method"][i] = "asymmetric_conformal" if asym else "split_conformal"
+    return out
+
+
+def ts_conformal_calibrate(actual, forecast, params=None):
+    """ts_conformal_calibrate(backtest_results, actual_col, forecast_col, params) (ts_macros.cpp:1515-1535): ONE group over all rows
+    where both columns are not NULL.  Returns one row: {"conformity_score" (None when the call fails or no row is left), "coverage"
+    (1.0 - alpha), "n_residuals"}."""
+    alpha, _ = _conformal_params(params)
+    a, a_null = _changepoint_values(actual)
+    f, f_null = _changepoint_values(forecast)
+    if len(a) != len(f):
+        raise InvalidInputException("Invalid input: every column needs one value per row")
+    keep = ~(a_null | f_null)
+    res = a[keep] - f[keep]
+    return {"conformity_score": ts_conformal_quantile(res.tolist(), alpha) if len(res) else None, "coverage": 1.0 - alpha,
+            "n_residuals": int(len(res))}
+
+
+def ts_conformal_apply_by(group_columns, forecast, conformity_score):
+    """ts_conformal_apply_by(forecast_results, group_col, forecast_col, conformity_score) (ts_macros.cpp:1543-1562): the bounds
+    forecast -/+ score of every group's forecasts, which the macro orders ascending by value; rows with a NULL forecast are dropped.
+    Returns the group columns, lower and upper (lists; None for a NULL score).  One call per group."""
+    f, f_null = _changepoint_values(forecast)
+    n_rows = len(f)
+    nc = _metric_group_columns(group_columns, n_rows)
+    order, members = _conformal_groups(nc, n_rows, ~f_null)
+    out = {name: [g[j] for g in order] for j, name in enumerate(nc[0])}
+    out["lower"], out["upper"] = [], []
+    for g in order:
+        r = ts_conformal_intervals(np.sort(f[np.array(members[g])]).tolist(), conformity_score)
+        out["lower"].append(None if r is None else r["lower"])
+        out["upper"].append(None if r is None else r["upper"])
+    return out
+
+
+def ts_interval_width_by(group_columns, lower, upper):
+    """ts_interval_width_by(results, group_col, lower_col, upper_col) (ts_macros.cpp:1568-1580): over the rows where both bounds are
+    not NULL, the macro sorts `lower` and `upper` INDEPENDENTLY (two ordered LISTs) before the widths are taken, so the figure is the
+    mean of upper_(i) - lower_(i) over the order statistics.  Returns the group columns, mean_width and n_intervals.  One call per
+    group."""
+    l, l_null = _changepoint_values(lower)
+    u, u_null = _changepoint_values(upper)
+    n_rows = len(l)
+    if len(u) != n_rows:
+        raise InvalidInputException("Invalid input: every column needs one value per row")
+    nc = _metric_group_columns(group_columns, n_rows)
+    order, members = _conformal_groups(nc, n_rows, ~(l_null | u_null))
+    out = {name: [g[j] for g in order] for j, name in enumerate(nc[0])}
+    out["mean_width"], out["n_intervals"] = [], []
+    for g in order:
+        idx = np.array(members[g])
+        out["mean_width"].append(ts_mean_interval_width(np.sort(l[idx]).tolist(), np.sort(u[idx]).tolist()))
+        out["n_intervals"].append(int(len(idx)))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # Forecast accuracy metrics: the twelve scalars, the eleven table macros, and every requested figure of every group in ONE call
 # ------------------------------------------------------------------------------------------------------------------------------
 def _metric_columns(cols, n):

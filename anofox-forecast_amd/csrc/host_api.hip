@@ -4897,6 +4897,804 @@ bool anofox_ts_coverage(const double *actual, size_t actual_len, const double *l
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Conformal prediction intervals (conformal.rs conformal_learn / conformal_apply / conformal_evaluate; conformal.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+const char *const CONFORMAL_EMPTY_TEXT = "Insufficient data: need at least 1 observations, got 0";     // ForecastError::InsufficientData
+const char *const CONFORMAL_NO_ALPHA_TEXT = "Invalid input: At least one alpha value is required";     // conformal.rs:706-710
+const char *const CONFORMAL_NO_FORECAST_TEXT = "Invalid input: At least one forecast is required";     // conformal.rs:897-901
+const char *const CONFORMAL_DIFFICULTY_TEXT = "Invalid input: Difficulty scores must be positive";     // conformal.rs:736-740, 918-922
+const char *const CONFORMAL_NEED_DIFFICULTY_TEXT = "Invalid input: Difficulty scores required for adaptive method";
+const char *const CONFORMAL_NAN_TEXT = "Invalid input: a residual is NaN";                             // the backend's limit
+
+bool conformal_alpha_ok(double a) { return a >= 0.0 && a < 1.0; }            // (0.0..1.0).contains: 0 is in, a NaN is not
+
+// Rust's `{}` of an f64: the shortest decimal that reads back the same, never with an exponent ("1", "1.5", "0.0000001", "NaN", "inf")
+std::string conformal_show(double v)
+{
+    if (v != v) return "NaN";
+    if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
+    char buf[1200];
+    for (int decimals = 0; decimals <= 780; decimals++) {
+        std::snprintf(buf, sizeof buf, "%.*f", decimals, v);
+        if (std::strtod(buf, nullptr) == v) break;
+    }
+    return buf;
+}
+
+bool conformal_check_levels(const double *alphas, size_t n_alphas, bool need, AnofoxError *err)
+{
+    if (n_alphas > (size_t)CONFORMAL_MAX_LEVELS) {
+        set_error(err, INVALID_INPUT, "Invalid input: at most " + std::to_string(CONFORMAL_MAX_LEVELS) + " coverage levels per call, got " +
+                                          std::to_string(n_alphas));
+        return false;
+    }
+    if (n_alphas == 0) { set_error(err, INVALID_INPUT, CONFORMAL_NO_ALPHA_TEXT); return false; }
+    if (!need) return true;
+    if (!alphas) { set_error(err, NULL_POINTER, "Null pointer argument"); return false; }
+    for (size_t k = 0; k < n_alphas; k++)
+        if (!conformal_alpha_ok(alphas[k])) {
+            set_error(err, INVALID_INPUT, "Invalid input: Alpha must be in (0, 1), got " + conformal_show(alphas[k]));     // conformal.rs:712-719
+            return false;
+        }
+    return true;
+}
+
+bool conformal_check_method(int method, AnofoxError *err)
+{
+    if (method == CONFORMAL_SYMMETRIC || method == CONFORMAL_ASYMMETRIC || method == CONFORMAL_ADAPTIVE) return true;
+    set_error(err, INVALID_INPUT, "Invalid input: unknown conformal method (0 symmetric, 1 asymmetric, 2 adaptive)");
+    return false;
+}
+
+bool conformal_check_block(size_t n_groups, size_t t_rows, size_t ld, AnofoxError *err)
+{
+    if (ld < n_groups) { set_error(err, INVALID_INPUT, "Invalid input: ld is smaller than n_groups"); return false; }
+    if (n_groups > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
+        set_error(err, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    return true;
+}
+
+} // namespace
+} // extern "C++"
+
+bool anofox_hip_conformal_learn_device(const double *residual, const double *actual, const double *forecast, const uint8_t *valid,
+                                       size_t stride_s, size_t stride_t, const int32_t *lengths, size_t n_groups, size_t t_rows,
+                                       const double *alphas, size_t n_alphas, int method, double *scores_lower, double *scores_upper,
+                                       size_t ld, double *sorted, int32_t *n_kept, int32_t *status, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if ((!residual && !(actual && forecast)) || !lengths || !scores_lower || !scores_upper || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!conformal_check_levels(alphas, n_alphas, true, out_error) || !conformal_check_method(method, out_error)) return false;
+    if (!conformal_check_block(n_groups, t_rows, ld, out_error)) return false;
+    if (n_groups == 0) return true;
+    if (!device_ready(out_error)) return false;
+    ConformalLearnArgs a{};
+    a.residual = residual; a.actual = actual; a.forecast = forecast; a.valid = valid;
+    a.stride_s = stride_s; a.stride_t = stride_t; a.len = lengths; a.n_groups = (int)n_groups; a.t_rows = t_rows;
+    a.method = method; a.n_alphas = (int)n_alphas;
+    for (size_t k = 0; k < n_alphas; k++) a.alphas[k] = alphas[k];
+    a.scores_lower = scores_lower; a.scores_upper = scores_upper; a.ld = ld;
+    a.sorted = sorted; a.n_kept = n_kept; a.status = status;
+    a.tile = conformal_tile(t_rows);
+    a.work_stride = conformal_work_stride(t_rows);
+    a.work_waves = a.work_stride ? conformal_work_waves((int)n_groups) : 0;
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *work = nullptr;
+    try {
+        (void)hipGetLastError();
+        if (a.work_stride && a.work_waves > 0) work = dalloc<uint64_t>(a.work_stride * (size_t)a.work_waves);
+        a.work = work;
+        launch_conformal_learn(a, st);
+        LAUNCHCHECK("conformal_learn");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(work, true);
+    } catch (const HipFail &f) {
+        dev_free(work, false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_conformal_apply_device(const double *forecast, const double *difficulty, size_t stride_s, size_t stride_t,
+                                       const int32_t *lengths, size_t n_groups, size_t h_rows, const double *scores_lower,
+                                       const double *scores_upper, size_t ld, size_t n_alphas, int method, double *lower, double *upper,
+                                       size_t stride_q, int32_t *status, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!forecast || !scores_lower || !scores_upper || !lower || !upper || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!conformal_check_levels(nullptr, n_alphas, false, out_error) || !conformal_check_method(method, out_error)) return false;
+    if (method == CONFORMAL_ADAPTIVE && !difficulty) { set_error(out_error, INVALID_INPUT, CONFORMAL_NEED_DIFFICULTY_TEXT); return false; }
+    if (!conformal_check_block(n_groups, h_rows, ld, out_error)) return false;
+    if (h_rows == 0) { set_error(out_error, INVALID_INPUT, CONFORMAL_NO_FORECAST_TEXT); return false; }
+    if (n_groups == 0) return true;
+    if (!device_ready(out_error)) return false;
+    ConformalApplyArgs a{};
+    a.forecast = forecast; a.difficulty = difficulty; a.stride_s = stride_s; a.stride_t = stride_t;
+    a.len = lengths; a.n_groups = (int)n_groups; a.h_rows = (int)h_rows;
+    a.scores_lower = scores_lower; a.scores_upper = scores_upper; a.ld = ld;
+    a.method = method; a.n_alphas = (int)n_alphas;
+    a.lower = lower; a.upper = upper; a.stride_q = stride_q; a.status = status;
+    hipStream_t st = (hipStream_t)stream;
+    try {
+        (void)hipGetLastError();
+        launch_conformal_apply(a, st);
+        LAUNCHCHECK("conformal_apply");
+        HIPCHECK(hipStreamSynchronize(st));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_conformal_evaluate_device(const double *actual, const double *lower, const double *upper, size_t stride_s, size_t stride_t,
+                                          const int32_t *lengths, size_t n_groups, size_t t_rows, double alpha, double *figures, size_t ld,
+                                          int32_t *status, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!actual || !lower || !upper || !lengths || !figures || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!conformal_check_levels(&alpha, 1, true, out_error)) return false;
+    if (!conformal_check_block(n_groups, t_rows, ld, out_error)) return false;
+    if (n_groups == 0) return true;
+    if (!device_ready(out_error)) return false;
+    ConformalEvalArgs a{};
+    a.actual = actual; a.lower = lower; a.upper = upper; a.stride_s = stride_s; a.stride_t = stride_t;
+    a.len = lengths; a.n_groups = (int)n_groups; a.t_rows = t_rows; a.alpha = alpha;
+    a.figures = figures; a.ld = ld; a.status = status;
+    hipStream_t st = (hipStream_t)stream;
+    try {
+        (void)hipGetLastError();
+        launch_conformal_evaluate(a, st);
+        LAUNCHCHECK("conformal_evaluate");
+        HIPCHECK(hipStreamSynchronize(st));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+void anofox_hip_free_conformal(AnofoxHipConformal *results, size_t n_groups)
+{
+    if (!results) return;
+    for (size_t s = 0; s < n_groups; s++) {
+        AnofoxHipConformal &r = results[s];
+        std::free(r.scores_lower); std::free(r.scores_upper); std::free(r.sorted); std::free(r.lower); std::free(r.upper);
+        std::memset(&r, 0, sizeof r);
+    }
+}
+
+bool anofox_hip_conformal_batch(const double *const *residuals, const uint64_t *const *residual_validity, const size_t *residual_lengths,
+                                const double *const *forecasts, const double *const *difficulty, const size_t *forecast_lengths,
+                                size_t n_groups, const double *alphas, size_t n_alphas, int method, int strategy, bool want_sorted,
+                                AnofoxHipConformal *out_results, AnofoxError *out_errors, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_groups > 0 && (!residuals || !residual_lengths || !out_results || (forecasts && !forecast_lengths))) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!conformal_check_levels(alphas, n_alphas, true, out_batch_error) || !conformal_check_method(method, out_batch_error)) return false;
+    if (strategy < 0 || strategy > 2) {
+        set_error(out_batch_error, INVALID_INPUT, "Invalid input: unknown conformal strategy (0 split, 1 crossval, 2 jackknife+)");
+        return false;
+    }
+    if (strategy == 2 && method == CONFORMAL_ASYMMETRIC) {          // conformal.rs:746-750
+        set_error(out_batch_error, INVALID_INPUT, "Invalid input: JackknifePlus strategy does not support asymmetric method");
+        return false;
+    }
+    if (forecasts && method == CONFORMAL_ADAPTIVE && !difficulty) {
+        set_error(out_batch_error, INVALID_INPUT, CONFORMAL_NEED_DIFFICULTY_TEXT);
+        return false;
+    }
+    size_t t_max = 0, h_max = 0;
+    for (size_t s = 0; s < n_groups; s++) {
+        const size_t h = forecasts ? forecast_lengths[s] : 0;
+        if ((residual_lengths[s] > 0 && !residuals[s]) || (h > 0 && (!forecasts[s] || (method == CONFORMAL_ADAPTIVE && !difficulty[s])))) {
+            set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+            return false;
+        }
+        if (residual_lengths[s] > (size_t)(1u << 30) || h > (size_t)(1u << 30)) {
+            set_error(out_batch_error, INVALID_INPUT, "Invalid input: a group is too long");
+            return false;
+        }
+        t_max = std::max(t_max, residual_lengths[s]);
+        h_max = std::max(h_max, h);
+    }
+    if (n_groups == 0) return true;
+    for (size_t s = 0; s < n_groups; s++) std::memset(&out_results[s], 0, sizeof out_results[s]);
+    const size_t ld = (n_groups + 63) / 64 * 64, T = std::max<size_t>(t_max, 1), H = h_max, K = n_alphas;
+    const bool adaptive = method == CONFORMAL_ADAPTIVE;
+    std::vector<double> sl(K * ld), su(K * ld), sorted, lower, upper;
+    std::vector<int32_t> len(ld, 0), hlen(ld, 0), kept(n_groups, 0), st_learn(n_groups, CONFORMAL_OK), st_apply(n_groups, CONFORMAL_OK);
+    double *d_r = nullptr, *d_sorted = nullptr, *d_sl = nullptr, *d_su = nullptr, *d_f = nullptr, *d_d = nullptr, *d_lo = nullptr, *d_up = nullptr;
+    uint8_t *d_valid = nullptr;
+    int32_t *d_len = nullptr, *d_hlen = nullptr, *d_kept = nullptr, *d_st = nullptr;
+    auto release = [&](bool quiesced) {
+        dev_free(d_r, quiesced);
+        dev_free(d_sorted, true); dev_free(d_sl, true); dev_free(d_su, true); dev_free(d_f, true); dev_free(d_d, true); dev_free(d_lo, true);
+        dev_free(d_up, true); dev_free(d_valid, true); dev_free(d_len, true); dev_free(d_hlen, true); dev_free(d_kept, true); dev_free(d_st, true);
+    };
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        // time-major blocks [T x ld] and [H x ld]
+        std::vector<double> blk(T * ld, 0.0);
+        std::vector<uint8_t> vb;
+        bool any_mask = false;
+        for (size_t s = 0; s < n_groups; s++) any_mask = any_mask || (residual_validity && residual_validity[s] && residual_lengths[s] > 0);
+        if (any_mask) vb.assign(T * ld, 1);
+        for (size_t s = 0; s < n_groups; s++) {
+            len[s] = (int32_t)residual_lengths[s];
+            for (size_t t = 0; t < residual_lengths[s]; t++) blk[t * ld + s] = residuals[s][t];
+            if (any_mask && residual_validity[s])
+                for (size_t t = 0; t < residual_lengths[s]; t++) vb[t * ld + s] = (uint8_t)((residual_validity[s][t / 64] >> (t % 64)) & 1ull);
+        }
+        d_r = dalloc<double>(T * ld); d_sl = dalloc<double>(K * ld); d_su = dalloc<double>(K * ld);
+        d_len = dalloc<int32_t>(ld); d_kept = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+        HIPCHECK(hipMemcpy(d_r, blk.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (any_mask) {
+            d_valid = dalloc<uint8_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+        }
+        if (want_sorted) d_sorted = dalloc<double>(T * ld);
+        if (!anofox_hip_conformal_learn_device(d_r, nullptr, nullptr, d_valid, 1, ld, d_len, n_groups, T, alphas, K, method, d_sl, d_su, ld,
+                                               d_sorted, d_kept, d_st, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(sl.data(), d_sl, K * ld * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(su.data(), d_su, K * ld * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(kept.data(), d_kept, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(st_learn.data(), d_st, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (want_sorted) {
+            sorted.resize(T * ld);
+            HIPCHECK(hipMemcpy(sorted.data(), d_sorted, T * ld * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (forecasts && H > 0) {
+            std::vector<double> fb(H * ld, 0.0), db;
+            if (adaptive) db.assign(H * ld, 1.0);
+            for (size_t s = 0; s < n_groups; s++) {
+                hlen[s] = (int32_t)forecast_lengths[s];
+                for (size_t t = 0; t < forecast_lengths[s]; t++) {
+                    fb[t * ld + s] = forecasts[s][t];
+                    if (adaptive) db[t * ld + s] = difficulty[s][t];
+                }
+            }
+            d_f = dalloc<double>(H * ld); d_lo = dalloc<double>(K * H * ld); d_up = dalloc<double>(K * H * ld); d_hlen = dalloc<int32_t>(ld);
+            HIPCHECK(hipMemcpy(d_f, fb.data(), H * ld * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_hlen, hlen.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (adaptive) {
+                d_d = dalloc<double>(H * ld);
+                HIPCHECK(hipMemcpy(d_d, db.data(), H * ld * sizeof(double), hipMemcpyHostToDevice));
+            }
+            if (!anofox_hip_conformal_apply_device(d_f, d_d, 1, ld, d_hlen, n_groups, H, d_sl, d_su, ld, K, method, d_lo, d_up, H * ld, d_st,
+                                                   nullptr, out_batch_error)) {
+                release(false);
+                return false;
+            }
+            lower.resize(K * H * ld); upper.resize(K * H * ld);
+            HIPCHECK(hipMemcpy(lower.data(), d_lo, lower.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHECK(hipMemcpy(upper.data(), d_up, upper.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHECK(hipMemcpy(st_apply.data(), d_st, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    auto copy_out = [](size_t n) { return (double *)std::malloc(std::max<size_t>(n, 1) * sizeof(double)); };
+    for (size_t s = 0; s < n_groups; s++) {
+        AnofoxError *e = out_errors ? &out_errors[s] : nullptr;
+        if (e) { e->code = SUCCESS; std::memset(e->message, 0, sizeof e->message); }
+        const size_t h = forecasts ? forecast_lengths[s] : 0;
+        // the order of the source's checks: conformal_learn first (no residual; the difficulty of the calibration set is not part of
+        // this entry), then conformal_apply (no forecast, then the difficulty)
+        if (st_learn[s] == CONFORMAL_EMPTY) { set_error(e, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); continue; }
+        if (st_learn[s] == CONFORMAL_NAN) { set_error(e, COMPUTATION_ERROR, CONFORMAL_NAN_TEXT); continue; }
+        if (forecasts && h == 0) { set_error(e, COMPUTATION_ERROR, CONFORMAL_NO_FORECAST_TEXT); continue; }
+        if (forecasts && st_apply[s] == CONFORMAL_DIFFICULTY) { set_error(e, COMPUTATION_ERROR, CONFORMAL_DIFFICULTY_TEXT); continue; }
+        AnofoxHipConformal r{};
+        r.n_levels = K; r.n_residuals = (size_t)kept[s]; r.n_forecasts = h;
+        r.scores_lower = copy_out(K); r.scores_upper = copy_out(K);
+        if (want_sorted) r.sorted = copy_out(r.n_residuals);
+        if (forecasts) { r.lower = copy_out(K * h); r.upper = copy_out(K * h); }
+        if (!r.scores_lower || !r.scores_upper || (want_sorted && !r.sorted) || (forecasts && (!r.lower || !r.upper))) {
+            anofox_hip_free_conformal(&r, 1);
+            set_error(e, ALLOCATION_ERROR, "Failed to allocate the conformal result");
+            continue;
+        }
+        for (size_t k = 0; k < K; k++) {
+            r.scores_lower[k] = sl[k * ld + s]; r.scores_upper[k] = su[k * ld + s];
+            for (size_t t = 0; t < h; t++) {
+                r.lower[k * h + t] = lower[k * H * ld + t * ld + s];
+                r.upper[k * h + t] = upper[k * H * ld + t * ld + s];
+            }
+        }
+        for (size_t t = 0; want_sorted && t < r.n_residuals; t++) r.sorted[t] = sorted[t * ld + s];
+        out_results[s] = r;
+    }
+    return true;
+}
+
+// ---- the reference's entries (lib.rs:4747-5400): each a batch of one through the same kernels ----
+extern "C++" {
+namespace {
+
+const char *const CONFORMAL_ALPHA_V1_TEXT = "Invalid input: Alpha must be between 0 and 1 (exclusive)";      // conformal.rs:123-127
+
+void conformal_init(AnofoxError *e) { if (e) { e->code = SUCCESS; std::memset(e->message, 0, sizeof e->message); } }
+
+size_t conformal_count_valid(const uint64_t *validity, size_t n)
+{
+    if (!validity) return n;
+    size_t c = 0;
+    for (size_t t = 0; t < n; t++) c += (size_t)((validity[t / 64] >> (t % 64)) & 1ull);
+    return c;
+}
+
+// a malloc'ed copy, NULL for an empty array (vec_to_c_double_array)
+double *conformal_copy(const double *p, size_t n)
+{
+    if (n == 0) return nullptr;
+    double *q = (double *)std::malloc(n * sizeof(double));
+    if (q) std::memcpy(q, p, n * sizeof(double));
+    return q;
+}
+
+// learn (and apply, when forecasts != NULL) for ONE group through anofox_hip_conformal_batch; a failure of either kind -> out_error
+bool conformal_one(const double *residuals, const uint64_t *validity, size_t n, const double *forecasts, const double *difficulty, size_t h,
+                   const double *alphas, size_t n_alphas, int method, int strategy, bool want_sorted, AnofoxHipConformal *out,
+                   AnofoxError *out_error)
+{
+    AnofoxError gerr, berr;
+    const double *r[1] = {residuals}, *f[1] = {forecasts}, *d[1] = {difficulty};
+    const uint64_t *v[1] = {validity};
+    const size_t rl[1] = {n}, fl[1] = {h};
+    if (!anofox_hip_conformal_batch(r, validity ? v : nullptr, rl, forecasts ? f : nullptr, difficulty ? d : nullptr, fl, 1, alphas, n_alphas, method,
+                                    strategy, want_sorted, out, &gerr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (gerr.code != SUCCESS) { if (out_error) *out_error = gerr; return false; }
+    return true;
+}
+
+// apply alone for ONE group: bounds of every level around `forecasts` from host scores, through anofox_hip_conformal_apply_device
+bool conformal_apply_one(const double *forecasts, const double *difficulty, size_t h, const double *scores_lower, const double *scores_upper,
+                         size_t K, int method, std::vector<double> &lower, std::vector<double> &upper, int32_t &status, AnofoxError *out_error)
+{
+    lower.assign(K * h, 0.0); upper.assign(K * h, 0.0);
+    status = CONFORMAL_OK;
+    if (h == 0 || K == 0) return true;
+    const size_t ld = 64;
+    std::vector<double> sl(K * ld, 0.0), su(K * ld, 0.0);
+    for (size_t k = 0; k < K; k++) { sl[k * ld] = scores_lower[k]; su[k * ld] = scores_upper[k]; }
+    double *d_f = nullptr, *d_d = nullptr, *d_sl = nullptr, *d_su = nullptr, *d_lo = nullptr, *d_up = nullptr;
+    int32_t *d_st = nullptr;
+    auto release = [&](bool quiesced) {
+        dev_free(d_f, quiesced);
+        dev_free(d_d, true); dev_free(d_sl, true); dev_free(d_su, true); dev_free(d_lo, true); dev_free(d_up, true); dev_free(d_st, true);
+    };
+    try {
+        if (!device_ready(out_error)) return false;
+        d_f = dalloc<double>(h); d_sl = dalloc<double>(K * ld); d_su = dalloc<double>(K * ld);
+        d_lo = dalloc<double>(K * h); d_up = dalloc<double>(K * h); d_st = dalloc<int32_t>(ld);
+        HIPCHECK(hipMemcpy(d_f, forecasts, h * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_sl, sl.data(), K * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_su, su.data(), K * ld * sizeof(double), hipMemcpyHostToDevice));
+        if (method == CONFORMAL_ADAPTIVE) {
+            d_d = dalloc<double>(h);
+            HIPCHECK(hipMemcpy(d_d, difficulty, h * sizeof(double), hipMemcpyHostToDevice));
+        }
+        // one group, series-major: its steps are neighbours
+        if (!anofox_hip_conformal_apply_device(d_f, d_d, h, 1, nullptr, 1, h, d_sl, d_su, ld, K, method, d_lo, d_up, h, d_st, nullptr, out_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(lower.data(), d_lo, K * h * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(upper.data(), d_up, K * h * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(&status, d_st, sizeof(int32_t), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+// the five evaluation figures of ONE group through anofox_hip_conformal_evaluate_device (n > 0)
+bool conformal_evaluate_one(const double *actuals, const double *lower, const double *upper, size_t n, double alpha, double *fig,
+                            AnofoxError *out_error)
+{
+    const size_t ld = 64;
+    double *d_a = nullptr, *d_l = nullptr, *d_u = nullptr, *d_fig = nullptr;
+    int32_t *d_len = nullptr, *d_st = nullptr;
+    auto release = [&](bool quiesced) {
+        dev_free(d_a, quiesced);
+        dev_free(d_l, true); dev_free(d_u, true); dev_free(d_fig, true); dev_free(d_len, true); dev_free(d_st, true);
+    };
+    try {
+        if (!device_ready(out_error)) return false;
+        const int32_t len = (int32_t)n;
+        d_a = dalloc<double>(n); d_l = dalloc<double>(n); d_u = dalloc<double>(n);
+        d_fig = dalloc<double>(CONFORMAL_N_EVAL * ld); d_len = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+        HIPCHECK(hipMemcpy(d_a, actuals, n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_l, lower, n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_u, upper, n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, &len, sizeof len, hipMemcpyHostToDevice));
+        if (!anofox_hip_conformal_evaluate_device(d_a, d_l, d_u, n, 1, d_len, 1, n, alpha, d_fig, ld, d_st, nullptr, out_error)) {
+            release(false);
+            return false;
+        }
+        for (int k = 0; k < CONFORMAL_N_EVAL; k++) HIPCHECK(hipMemcpy(&fig[k], d_fig + (size_t)k * ld, sizeof(double), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool conformal_too_many(size_t n_alphas, AnofoxError *err)
+{
+    if (n_alphas <= (size_t)CONFORMAL_MAX_LEVELS) return false;
+    set_error(err, INVALID_INPUT, "Invalid input: at most " + std::to_string(CONFORMAL_MAX_LEVELS) + " coverage levels per call, got " +
+                                      std::to_string(n_alphas));
+    return true;
+}
+
+void conformal_method_name(ConformalResultFFI *out, const char *name)
+{
+    std::memset(out->method, 0, sizeof out->method);
+    std::strncpy(out->method, name, sizeof out->method - 1);
+}
+
+// conformal_predict / _adaptive / _asymmetric behind their checks: one alpha, one group
+bool conformal_predict_one(const double *residuals, const uint64_t *validity, size_t n, const double *forecasts, const double *difficulty,
+                           size_t h, double alpha, int method, const char *name, ConformalResultFFI *out, AnofoxError *out_error)
+{
+    if (conformal_count_valid(validity, n) == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
+    if (!conformal_alpha_ok(alpha)) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_ALPHA_V1_TEXT); return false; }
+    AnofoxHipConformal r{};
+    // a forecast list may be empty here (the source answers with empty bounds): learn alone then
+    if (!conformal_one(residuals, validity, n, h ? forecasts : nullptr, h ? difficulty : nullptr, h, &alpha, 1, method, 0, false, &r, out_error))
+        return false;
+    std::memset(out, 0, sizeof *out);
+    out->point = conformal_copy(forecasts, h);
+    out->lower = conformal_copy(r.lower, h);
+    out->upper = conformal_copy(r.upper, h);
+    out->n_forecasts = h;
+    out->coverage = 1.0 - alpha;
+    out->conformity_score = method == CONFORMAL_ASYMMETRIC ? (r.scores_upper[0] + r.scores_lower[0]) / 2.0 : r.scores_lower[0];
+    conformal_method_name(out, name);
+    anofox_hip_free_conformal(&r, 1);
+    if (h > 0 && (!out->point || !out->lower || !out->upper)) {
+        anofox_free_conformal_result(out);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate the conformal result");
+        return false;
+    }
+    return true;
+}
+
+} // namespace
+} // extern "C++"
+
+void anofox_free_conformal_result(ConformalResultFFI *r)
+{
+    if (!r) return;
+    std::free(r->point); r->point = nullptr;
+    std::free(r->lower); r->lower = nullptr;
+    std::free(r->upper); r->upper = nullptr;
+}
+
+void anofox_free_conformal_multi_result(ConformalMultiResultFFI *r)
+{
+    if (!r) return;
+    std::free(r->point); r->point = nullptr;
+    std::free(r->coverage_levels); r->coverage_levels = nullptr;
+    std::free(r->conformity_scores); r->conformity_scores = nullptr;
+    std::free(r->lower); r->lower = nullptr;
+    std::free(r->upper); r->upper = nullptr;
+}
+
+void anofox_free_calibration_profile(CalibrationProfileFFI *r)
+{
+    if (!r) return;
+    std::free(r->alphas); r->alphas = nullptr;
+    std::free(r->state_vector); r->state_vector = nullptr;
+    std::free(r->scores_lower); r->scores_lower = nullptr;
+    std::free(r->scores_upper); r->scores_upper = nullptr;
+}
+
+void anofox_free_prediction_intervals(PredictionIntervalsFFI *r)
+{
+    if (!r) return;
+    std::free(r->point); r->point = nullptr;
+    std::free(r->coverage); r->coverage = nullptr;
+    std::free(r->lower); r->lower = nullptr;
+    std::free(r->upper); r->upper = nullptr;
+}
+
+bool anofox_ts_conformal_quantile(const double *residuals, const uint64_t *validity, size_t length, double alpha, double *out_result,
+                                  AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!residuals) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!out_result) { set_error(out_error, NULL_POINTER, "Null output pointer"); return false; }
+    if (conformal_count_valid(validity, length) == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
+    if (!conformal_alpha_ok(alpha)) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_ALPHA_V1_TEXT); return false; }
+    AnofoxHipConformal r{};
+    if (!conformal_one(residuals, validity, length, nullptr, nullptr, 0, &alpha, 1, CONFORMAL_SYMMETRIC, 0, false, &r, out_error)) return false;
+    *out_result = r.scores_lower[0];
+    anofox_hip_free_conformal(&r, 1);
+    return true;
+}
+
+bool anofox_ts_conformal_intervals(const double *forecasts, size_t length, double conformity_score, double **out_lower, double **out_upper,
+                                   AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!forecasts || !out_lower || !out_upper) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    std::vector<double> lo, up;
+    int32_t status;
+    if (!conformal_apply_one(forecasts, nullptr, length, &conformity_score, &conformity_score, 1, CONFORMAL_SYMMETRIC, lo, up, status, out_error))
+        return false;
+    double *l = conformal_copy(lo.data(), length), *u = conformal_copy(up.data(), length);
+    if (length > 0 && (!l || !u)) {
+        std::free(l); std::free(u);
+        set_error(out_error, ALLOCATION_ERROR, l ? "Failed to allocate upper bounds" : "Failed to allocate lower bounds");
+        return false;
+    }
+    *out_lower = l; *out_upper = u;
+    return true;
+}
+
+bool anofox_ts_conformal_predict(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length, const double *forecasts,
+                                 size_t forecasts_length, double alpha, ConformalResultFFI *out_result, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!residuals || !forecasts || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    return conformal_predict_one(residuals, residuals_validity, residuals_length, forecasts, nullptr, forecasts_length, alpha, CONFORMAL_SYMMETRIC,
+                                 "split_conformal", out_result, out_error);
+}
+
+bool anofox_ts_conformal_predict_adaptive(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                          const double *forecasts, const double *difficulty, size_t forecasts_length, double alpha,
+                                          ConformalResultFFI *out_result, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!residuals || !forecasts || !difficulty || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    for (size_t t = 0; t < forecasts_length; t++)                  // before the quantile's own checks (conformal.rs:315-323)
+        if (difficulty[t] <= 0.0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_DIFFICULTY_TEXT); return false; }
+    return conformal_predict_one(residuals, residuals_validity, residuals_length, forecasts, difficulty, forecasts_length, alpha, CONFORMAL_ADAPTIVE,
+                                 "adaptive_conformal", out_result, out_error);
+}
+
+bool anofox_ts_conformal_predict_asymmetric(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                            const double *forecasts, size_t forecasts_length, double alpha, ConformalResultFFI *out_result,
+                                            AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!residuals || !forecasts || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    return conformal_predict_one(residuals, residuals_validity, residuals_length, forecasts, nullptr, forecasts_length, alpha, CONFORMAL_ASYMMETRIC,
+                                 "asymmetric_conformal", out_result, out_error);
+}
+
+bool anofox_ts_conformal_predict_multi(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                       const double *forecasts, size_t forecasts_length, const double *alphas, size_t n_alphas,
+                                       ConformalMultiResultFFI *out_result, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!residuals || !forecasts || !alphas || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (conformal_too_many(n_alphas, out_error)) return false;
+    if (n_alphas == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_NO_ALPHA_TEXT); return false; }
+    if (conformal_count_valid(residuals_validity, residuals_length) == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
+    for (size_t k = 0; k < n_alphas; k++)
+        if (!conformal_alpha_ok(alphas[k])) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_ALPHA_V1_TEXT); return false; }
+    const size_t h = forecasts_length;
+    AnofoxHipConformal r{};
+    if (!conformal_one(residuals, residuals_validity, residuals_length, h ? forecasts : nullptr, nullptr, h, alphas, n_alphas, CONFORMAL_SYMMETRIC, 0,
+                       false, &r, out_error))
+        return false;
+    std::memset(out_result, 0, sizeof *out_result);
+    out_result->point = conformal_copy(forecasts, h);
+    out_result->n_forecasts = h;
+    out_result->n_levels = n_alphas;
+    out_result->coverage_levels = (double *)std::malloc(n_alphas * sizeof(double));
+    out_result->conformity_scores = conformal_copy(r.scores_lower, n_alphas);
+    out_result->lower = conformal_copy(r.lower, n_alphas * h);
+    out_result->upper = conformal_copy(r.upper, n_alphas * h);
+    anofox_hip_free_conformal(&r, 1);
+    if (!out_result->coverage_levels || !out_result->conformity_scores || (h > 0 && (!out_result->point || !out_result->lower || !out_result->upper))) {
+        anofox_free_conformal_multi_result(out_result);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate the conformal result");
+        return false;
+    }
+    for (size_t k = 0; k < n_alphas; k++) out_result->coverage_levels[k] = 1.0 - alphas[k];
+    return true;
+}
+
+bool anofox_ts_mean_interval_width(const double *lower, const double *upper, size_t length, double *out_result, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!lower || !upper || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (length == 0) { *out_result = std::numeric_limits<double>::quiet_NaN(); return true; }          // conformal.rs:461-463
+    double fig[CONFORMAL_N_EVAL];
+    if (!conformal_evaluate_one(lower, lower, upper, length, 0.5, fig, out_error)) return false;
+    *out_result = fig[2];
+    return true;
+}
+
+bool anofox_ts_conformal_learn(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length, const double *alphas,
+                               size_t n_alphas, ConformalMethodFFI method, ConformalStrategyFFI strategy, const double *difficulty,
+                               CalibrationProfileFFI *out_profile, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!residuals || !alphas || !out_profile) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (conformal_too_many(n_alphas, out_error) || !conformal_check_method((int)method, out_error)) return false;
+    if ((int)strategy < 0 || (int)strategy > 2) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: unknown conformal strategy (0 split, 1 crossval, 2 jackknife+)");
+        return false;
+    }
+    // conformal_learn's checks in its order (conformal.rs:702-750)
+    const size_t kept = conformal_count_valid(residuals_validity, residuals_length);
+    if (kept == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
+    if (n_alphas == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_NO_ALPHA_TEXT); return false; }
+    for (size_t k = 0; k < n_alphas; k++)
+        if (!conformal_alpha_ok(alphas[k])) {
+            set_error(out_error, COMPUTATION_ERROR, "Invalid input: Alpha must be in (0, 1), got " + conformal_show(alphas[k]));
+            return false;
+        }
+    if ((int)method == CONFORMAL_ADAPTIVE) {
+        if (!difficulty) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_NEED_DIFFICULTY_TEXT); return false; }
+        if (residuals_length != kept) {                            // the difficulty keeps the list's length, the residuals lost their NULLs
+            set_error(out_error, COMPUTATION_ERROR, "Invalid input: Difficulty length (" + std::to_string(residuals_length) +
+                                                        ") must match residuals length (" + std::to_string(kept) + ")");
+            return false;
+        }
+        for (size_t t = 0; t < residuals_length; t++)
+            if (difficulty[t] <= 0.0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_DIFFICULTY_TEXT); return false; }
+    }
+    if ((int)strategy == 2 && (int)method == CONFORMAL_ASYMMETRIC) {
+        set_error(out_error, COMPUTATION_ERROR, "Invalid input: JackknifePlus strategy does not support asymmetric method");
+        return false;
+    }
+    const bool jk = (int)strategy == 2;
+    AnofoxHipConformal r{};
+    if (!conformal_one(residuals, residuals_validity, residuals_length, nullptr, nullptr, 0, alphas, n_alphas, (int)method, (int)strategy, jk, &r,
+                       out_error))
+        return false;
+    std::memset(out_profile, 0, sizeof *out_profile);
+    out_profile->method = method; out_profile->strategy = strategy;
+    out_profile->alphas = conformal_copy(alphas, n_alphas);
+    out_profile->scores_lower = conformal_copy(r.scores_lower, n_alphas);
+    out_profile->scores_upper = conformal_copy(r.scores_upper, n_alphas);
+    out_profile->n_levels = n_alphas;
+    out_profile->n_residuals = r.n_residuals;
+    if (jk) {
+        out_profile->state_vector_len = r.n_residuals;
+        out_profile->state_vector = conformal_copy(r.sorted, r.n_residuals);
+    } else {
+        out_profile->state_vector_len = 2 * n_alphas;
+        out_profile->state_vector = (double *)std::malloc(2 * n_alphas * sizeof(double));
+        if (out_profile->state_vector) {
+            std::memcpy(out_profile->state_vector, r.scores_lower, n_alphas * sizeof(double));
+            std::memcpy(out_profile->state_vector + n_alphas, r.scores_upper, n_alphas * sizeof(double));
+        }
+    }
+    anofox_hip_free_conformal(&r, 1);
+    if (!out_profile->alphas || !out_profile->scores_lower || !out_profile->scores_upper || !out_profile->state_vector) {
+        anofox_free_calibration_profile(out_profile);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate the calibration profile");
+        return false;
+    }
+    return true;
+}
+
+bool anofox_ts_conformal_apply(const double *forecasts, size_t n_forecasts, const CalibrationProfileFFI *profile, const double *difficulty,
+                               PredictionIntervalsFFI *out_intervals, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!forecasts || !profile || !out_intervals) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const size_t K = profile->n_levels, h = n_forecasts;
+    const int method = (int)profile->method;
+    if (conformal_too_many(K, out_error) || !conformal_check_method(method, out_error)) return false;
+    if (K > 0 && (!profile->alphas || !profile->scores_lower || !profile->scores_upper)) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    // conformal_apply's checks in its order (conformal.rs:897-925)
+    if (h == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_NO_FORECAST_TEXT); return false; }
+    if (method == CONFORMAL_ADAPTIVE) {
+        if (!difficulty) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_NEED_DIFFICULTY_TEXT); return false; }
+        for (size_t t = 0; t < h; t++)
+            if (difficulty[t] <= 0.0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_DIFFICULTY_TEXT); return false; }
+    }
+    std::vector<double> sl(profile->scores_lower, profile->scores_lower + K), su(profile->scores_upper, profile->scores_upper + K), lo, up;
+    if ((int)profile->strategy == 2 && K > 0) {
+        // Jackknife+: the scores come from the stored residual distribution at apply time (conformal.rs:941-954); it is sorted and not
+        // negative, so learning from it sorts it into itself
+        if (profile->state_vector && profile->state_vector_len > 0) {
+            AnofoxHipConformal r{};
+            if (!conformal_one(profile->state_vector, nullptr, profile->state_vector_len, nullptr, nullptr, 0, profile->alphas, K, CONFORMAL_SYMMETRIC,
+                               0, false, &r, out_error))
+                return false;
+            for (size_t k = 0; k < K; k++) sl[k] = su[k] = r.scores_lower[k];
+            anofox_hip_free_conformal(&r, 1);
+        } else {
+            for (size_t k = 0; k < K; k++) sl[k] = su[k] = std::numeric_limits<double>::quiet_NaN();   // compute_quantile of nothing
+        }
+    }
+    int32_t status;
+    if (!conformal_apply_one(forecasts, difficulty, h, sl.data(), su.data(), K, method, lo, up, status, out_error)) return false;
+    std::memset(out_intervals, 0, sizeof *out_intervals);
+    out_intervals->point = conformal_copy(forecasts, h);
+    out_intervals->n_forecasts = h;
+    out_intervals->n_levels = K;
+    out_intervals->coverage = (double *)std::malloc(std::max<size_t>(K, 1) * sizeof(double));
+    out_intervals->lower = (double *)std::malloc(std::max<size_t>(K * h, 1) * sizeof(double));
+    out_intervals->upper = (double *)std::malloc(std::max<size_t>(K * h, 1) * sizeof(double));
+    out_intervals->method = profile->method;
+    if (!out_intervals->point || !out_intervals->coverage || !out_intervals->lower || !out_intervals->upper) {
+        anofox_free_prediction_intervals(out_intervals);
+        set_error(out_error, ALLOCATION_ERROR, "Failed to allocate the prediction intervals");
+        return false;
+    }
+    for (size_t k = 0; k < K; k++) out_intervals->coverage[k] = 1.0 - profile->alphas[k];
+    std::memcpy(out_intervals->lower, lo.data(), K * h * sizeof(double));
+    std::memcpy(out_intervals->upper, up.data(), K * h * sizeof(double));
+    return true;
+}
+
+bool anofox_ts_conformal_coverage(const double *actuals, const double *lower, const double *upper, size_t length, double *out_coverage,
+                                  AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!actuals || !lower || !upper || !out_coverage) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (length == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
+    double fig[CONFORMAL_N_EVAL];
+    if (!conformal_evaluate_one(actuals, lower, upper, length, 0.5, fig, out_error)) return false;
+    *out_coverage = fig[0];
+    return true;
+}
+
+bool anofox_ts_conformal_evaluate(const double *actuals, const double *lower, const double *upper, size_t length, double alpha,
+                                  ConformalEvaluationFFI *out_eval, AnofoxError *out_error)
+{
+    conformal_init(out_error);
+    if (!actuals || !lower || !upper || !out_eval) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (length == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
+    if (!conformal_alpha_ok(alpha)) {                              // winkler_score's check, after coverage has succeeded (conformal.rs:1123-1128)
+        set_error(out_error, COMPUTATION_ERROR, "Invalid input: Alpha must be in (0, 1), got " + conformal_show(alpha));
+        return false;
+    }
+    double fig[CONFORMAL_N_EVAL];
+    if (!conformal_evaluate_one(actuals, lower, upper, length, alpha, fig, out_error)) return false;
+    out_eval->coverage = fig[0]; out_eval->violation_rate = fig[1]; out_eval->mean_width = fig[2]; out_eval->winkler_score = fig[3];
+    out_eval->n_observations = length;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Exogenous regressors: ARIMAX (forecast.rs forecast_with_exog; fit_exog.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 } // extern "C"

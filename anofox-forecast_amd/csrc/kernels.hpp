@@ -307,6 +307,54 @@ struct MetricsArgs {
 };
 void launch_metrics(const MetricsArgs &, hipStream_t);
 
+// Conformal prediction intervals per group (conformal.rs learn / apply / evaluate; conformal.hip)
+constexpr int CONFORMAL_MAX_LEVELS = 16;     // alphas per call; more fail loudly
+constexpr int CONFORMAL_RESIDENT = 2048;     // keys of the longest group that is sorted in LDS; longer ones use the global workspace
+constexpr int CONFORMAL_WORK_WAVES = 1024;   // waves (and workspace slices) that walk the longer groups
+constexpr int CONFORMAL_N_EVAL = 5;          // rows of the evaluate figures: coverage, violation_rate, mean_width, winkler_score, n_observations
+enum { CONFORMAL_SYMMETRIC = 0, CONFORMAL_ASYMMETRIC = 1, CONFORMAL_ADAPTIVE = 2 };
+constexpr int32_t CONFORMAL_OK = 0, CONFORMAL_EMPTY = 1, CONFORMAL_NAN = 2, CONFORMAL_DIFFICULTY = 3;
+// element (group s, row t) of every block of a call at s * stride_s + t * stride_t
+struct ConformalLearnArgs {
+    const double *residual;      // the residuals, or null: actual - forecast
+    const double *actual, *forecast;
+    const uint8_t *valid;        // null, or one byte per element: a row whose byte is 0 is dropped
+    size_t stride_s, stride_t;
+    const int32_t *len; int n_groups;
+    size_t t_rows;               // a longer group is cut to it
+    int method; int n_alphas; double alphas[CONFORMAL_MAX_LEVELS];
+    double *scores_lower, *scores_upper; size_t ld;   // [n_alphas x ld]; only the columns s < n_groups are written
+    double *sorted;              // null, or a block with the inputs' strides: rows 0 .. n_kept - 1 receive the sorted |residual|
+    int32_t *n_kept;             // null, or [n_groups] rows kept
+    int32_t *status;             // [n_groups]
+    int tile;                    // keys per wave of the LDS kernel: a power of two, 64 .. CONFORMAL_RESIDENT
+    uint64_t *work;              // [work_waves x work_stride] or null when t_rows <= CONFORMAL_RESIDENT
+    size_t work_stride; int work_waves;
+};
+struct ConformalApplyArgs {
+    const double *forecast, *difficulty;         // difficulty: read by the adaptive method only
+    size_t stride_s, stride_t;
+    const int32_t *len; int n_groups; int h_rows;            // len null: every group has h_rows steps
+    const double *scores_lower, *scores_upper; size_t ld;    // [n_alphas x ld]
+    int method; int n_alphas;
+    double *lower, *upper; size_t stride_q;      // level k's block at + k * stride_q, the forecast's strides within it
+    int32_t *status;             // [n_groups]
+};
+struct ConformalEvalArgs {
+    const double *actual, *lower, *upper;
+    size_t stride_s, stride_t;
+    const int32_t *len; int n_groups; size_t t_rows;
+    double alpha;
+    double *figures; size_t ld;  // [CONFORMAL_N_EVAL x ld]
+    int32_t *status;             // [n_groups]
+};
+int conformal_tile(size_t t_rows);               // the LDS tile of a batch whose longest group has t_rows rows
+size_t conformal_work_stride(size_t t_rows);     // words per workspace slice (0: no workspace needed)
+int conformal_work_waves(int n_groups);
+void launch_conformal_learn(const ConformalLearnArgs &, hipStream_t);
+void launch_conformal_apply(const ConformalApplyArgs &, hipStream_t);
+void launch_conformal_evaluate(const ConformalEvalArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

@@ -25,12 +25,15 @@
 // restatement tests/stats_ref.py within the measured tolerance of DESIGN.md section 3; counts, min, max, range and the percentiles
 // are exact.  A float -> index cast is clamped by hand where Rust's `as usize` saturates.
 //
+// The key functions and the network (st_key, st_unkey, st_sync, st_sort) live in wave_sort.hpp, shared with conformal.hip.
+//
 // ANOFOX_STATS_SKIP (an experiment build only, tools/time_stats.py --ab): bit 0 leaves out step 4, bit 1 the sorting network of step
 // 5, so that the time of each can be read from the difference.  The figures of such a build are wrong by design; the product is
 // built without the switch.
 #include "kernels.hpp"
 #include "det_math.hpp"
 #include "civil_date.hpp"
+#include "wave_sort.hpp"
 
 #ifndef ANOFOX_STATS_SKIP
 #define ANOFOX_STATS_SKIP 0
@@ -43,7 +46,6 @@ namespace {
 constexpr int ST_WAVES = 4;
 constexpr int ST_BLOCK = 64 * ST_WAVES;
 constexpr double ST_EPS = 2.220446049250313e-16;             // f64::EPSILON
-constexpr uint64_t ST_SIGN = 0x8000000000000000ull;
 
 __device__ __forceinline__ double st_wave_sum(double v)
 {
@@ -65,37 +67,10 @@ __device__ __forceinline__ double st_wave_fmax(double v)
     for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o); v = w > v ? w : v; }
     return v;
 }
-// what one lane wrote to the buffer becomes visible to the other lanes of its wave
-__device__ __forceinline__ void st_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ uint64_t st_key(uint64_t bits) { return (bits >> 63) ? ~bits : (bits | ST_SIGN); }
-__device__ __forceinline__ double st_unkey(uint64_t k) { return dm_from_bits((k >> 63) ? (k ^ ST_SIGN) : ~k); }
 __device__ __forceinline__ int st_prev_bit(uint64_t mask, int lane)      // highest set bit below `lane`, -1 if none
 {
     const uint64_t below = mask & ((1ull << lane) - 1ull);
     return below ? 63 - __clzll((long long)below) : -1;
-}
-
-// ascending bitonic network over buf[0 .. p2), p2 a power of two, one wave
-template <class B>
-__device__ __forceinline__ void st_sort(B buf, int p2, int lane)
-{
-    for (int k = 2; k <= p2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int p = lane; p < (p2 >> 1); p += 64) {
-                const int lo = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                const int hi = lo | j;
-                const bool up = (lo & k) == 0;
-                const uint64_t x = buf[lo], y = buf[hi];
-                if ((x > y) == up) { buf[lo] = y; buf[hi] = x; }
-            }
-            st_sync();
-        }
-    }
 }
 
 // year * 12 + month, year * 4 + quarter or year of micros_to_datetime(us) (stats.rs:365-371; civil_date.hpp, shared with the gaps

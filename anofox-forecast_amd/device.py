@@ -92,6 +92,86 @@ def prepare_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | 
             "t_out": t_out}
 
 
+def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | None = None, actual: torch.Tensor | None = None,
+                    calibration_forecast: torch.Tensor | None = None, valid: torch.Tensor | None = None,
+                    lengths: torch.Tensor | None = None, n_groups: int | None = None, method: str = "symmetric",
+                    difficulty: torch.Tensor | None = None, series_major: bool = False, calibration_series_major: bool | None = None,
+                    want_sorted: bool = False, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_conformal_learn_device then anofox_hip_conformal_apply_device on torch tensors: calibration residuals in, lower and
+    upper blocks out, no host copy.
+
+    The calibration set is `residual`, or `actual` and `calibration_forecast` (the residual is formed on the device as actual -
+    forecast); valid (uint8 or bool, 0 = dropped) has the same shape.  A time-major block is [t_rows, ld] with group s in column s; a
+    series-major one (calibration_series_major, default: as series_major) is [n_groups, t_rows].  lengths (int32, on the device) gives
+    the rows of every group; None: all rows.  `forecast` is the point block the intervals go around: time-major [h, ld], or with
+    series_major=True the [n_series, h] layout of DeviceBatch.results()["yhat"]; difficulty (adaptive method) has its shape.
+
+    Returns {"lower", "upper": [n_alphas, *forecast.shape], "scores_lower", "scores_upper": fp64 [n_alphas, ld], "n_kept", "status",
+    "apply_status": int32 [n_groups], "sorted": a block shaped like the calibration set (rows 0 .. n_kept - 1 of a group hold its
+    ascending |residual|) or None}.  status per group: lib.CONFORMAL_OK / _EMPTY / _NAN, apply_status: _OK / _DIFFICULTY."""
+    L = _lib.load()
+    cal = residual if residual is not None else actual
+    assert cal is not None and (residual is not None or calibration_forecast is not None)
+    cal_sm = series_major if calibration_series_major is None else calibration_series_major
+    blocks = [t for t in (residual, actual, calibration_forecast) if t is not None]
+    for t in blocks + [forecast] + ([difficulty] if difficulty is not None else []):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 2
+    assert all(tuple(t.shape) == tuple(cal.shape) for t in blocks)
+    dev = forecast.device
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and tuple(valid.shape) == tuple(cal.shape)
+    if cal_sm:
+        n_cal, t_rows = int(cal.shape[0]), int(cal.shape[1])
+        cs, ct = t_rows, 1
+    else:
+        t_rows, n_cal = int(cal.shape[0]), int(cal.shape[1])
+        cs, ct = 1, n_cal
+    if series_major:
+        n_f, h = int(forecast.shape[0]), int(forecast.shape[1])
+        fs, ft = h, 1
+    else:
+        h, n_f = int(forecast.shape[0]), int(forecast.shape[1])
+        fs, ft = 1, n_f
+    n = min(n_cal, n_f) if n_groups is None else int(n_groups)
+    assert 0 < n <= n_cal and n <= n_f
+    if difficulty is not None:
+        assert tuple(difficulty.shape) == tuple(forecast.shape)
+    if lengths is None:
+        lengths = torch.full((n,), t_rows, dtype=torch.int32, device=dev)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+    k = len(al)
+    ld = (n + 63) // 64 * 64
+    code = _lib.CONFORMAL_METHODS[str(method).lower()]
+    sl = torch.full((max(k, 1), ld), float("nan"), dtype=torch.float64, device=dev)
+    su = torch.full((max(k, 1), ld), float("nan"), dtype=torch.float64, device=dev)
+    kept = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    apply_status = torch.zeros(n, dtype=torch.int32, device=dev)
+    srt = torch.zeros_like(cal) if want_sorted else None
+    lower = torch.full((max(k, 1),) + tuple(forecast.shape), float("nan"), dtype=torch.float64, device=dev)
+    upper = torch.full((max(k, 1),) + tuple(forecast.shape), float("nan"), dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_conformal_learn_device(ptr(residual), ptr(actual), ptr(calibration_forecast), ptr(valid), cs, ct, lengths.data_ptr(), n,
+                                             t_rows, al.ctypes.data, k, code, sl.data_ptr(), su.data_ptr(), ld, ptr(srt), kept.data_ptr(),
+                                             status.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_conformal_learn_device failed: [{err.code}] {err.message.decode()}")
+    ok = L.anofox_hip_conformal_apply_device(forecast.data_ptr(), ptr(difficulty), fs, ft, None, n, h, sl.data_ptr(), su.data_ptr(), ld, k, code,
+                                             lower.data_ptr(), upper.data_ptr(), forecast.numel(), apply_status.data_ptr(),
+                                             C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_conformal_apply_device failed: [{err.code}] {err.message.decode()}")
+    return {"lower": lower, "upper": upper, "scores_lower": sl, "scores_upper": su, "n_kept": kept, "status": status,
+            "apply_status": apply_status, "sorted": srt}
+
+
 class DeviceBatch:
     """anofox_hip_batch_* over torch-owned HBM."""
 

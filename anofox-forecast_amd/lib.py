@@ -168,6 +168,60 @@ METRIC_FIGURES = ("mae", "mse", "rmse", "mape", "smape", "r2", "bias", "rmae", "
 METRICS_MAX_LEVELS = 16
 
 
+# include/anofox_fcst_hip.h: the conformal entries (anofox_hip_conformal_learn_device / _apply_device / _evaluate_device / _batch)
+CONFORMAL_METHODS = {"symmetric": 0, "asymmetric": 1, "adaptive": 2}
+CONFORMAL_STRATEGIES = {"split": 0, "crossval": 1, "jackknife+": 2}
+CONFORMAL_MAX_LEVELS = 16
+CONFORMAL_OK, CONFORMAL_EMPTY, CONFORMAL_NAN, CONFORMAL_DIFFICULTY = 0, 1, 2, 3
+CONFORMAL_EVAL_FIGURES = ("coverage", "violation_rate", "mean_width", "winkler_score", "n_observations")
+
+
+class AnofoxHipConformal(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipConformal: one group's answer of anofox_hip_conformal_batch (64 bytes)."""
+    _fields_ = [("scores_lower", C.POINTER(C.c_double)), ("scores_upper", C.POINTER(C.c_double)), ("sorted", C.POINTER(C.c_double)),
+                ("n_residuals", C.c_size_t), ("lower", C.POINTER(C.c_double)), ("upper", C.POINTER(C.c_double)),
+                ("n_forecasts", C.c_size_t), ("n_levels", C.c_size_t)]
+
+
+assert C.sizeof(AnofoxHipConformal) == 64
+
+
+class ConformalResultFFI(C.Structure):
+    """anofox_fcst_ffi.h ConformalResultFFI (types.rs:1427-1444): 80 bytes."""
+    _fields_ = [("point", C.POINTER(C.c_double)), ("lower", C.POINTER(C.c_double)), ("upper", C.POINTER(C.c_double)),
+                ("n_forecasts", C.c_size_t), ("coverage", C.c_double), ("conformity_score", C.c_double), ("method", C.c_char * 32)]
+
+
+class ConformalMultiResultFFI(C.Structure):
+    """types.rs:1478-1493: lower / upper are [n_levels x n_forecasts], level-major (56 bytes)."""
+    _fields_ = [("point", C.POINTER(C.c_double)), ("n_forecasts", C.c_size_t), ("coverage_levels", C.POINTER(C.c_double)),
+                ("conformity_scores", C.POINTER(C.c_double)), ("n_levels", C.c_size_t), ("lower", C.POINTER(C.c_double)),
+                ("upper", C.POINTER(C.c_double))]
+
+
+class CalibrationProfileFFI(C.Structure):
+    """types.rs:1585-1606: method and strategy are the C enums ConformalMethodFFI / ConformalStrategyFFI (64 bytes)."""
+    _fields_ = [("method", C.c_int), ("strategy", C.c_int), ("alphas", C.POINTER(C.c_double)), ("state_vector", C.POINTER(C.c_double)),
+                ("state_vector_len", C.c_size_t), ("scores_lower", C.POINTER(C.c_double)), ("scores_upper", C.POINTER(C.c_double)),
+                ("n_levels", C.c_size_t), ("n_residuals", C.c_size_t)]
+
+
+class PredictionIntervalsFFI(C.Structure):
+    """types.rs:1628-1643 (56 bytes)."""
+    _fields_ = [("point", C.POINTER(C.c_double)), ("n_forecasts", C.c_size_t), ("coverage", C.POINTER(C.c_double)), ("n_levels", C.c_size_t),
+                ("lower", C.POINTER(C.c_double)), ("upper", C.POINTER(C.c_double)), ("method", C.c_int)]
+
+
+class ConformalEvaluationFFI(C.Structure):
+    """types.rs:1661-1672 (40 bytes)."""
+    _fields_ = [("coverage", C.c_double), ("violation_rate", C.c_double), ("mean_width", C.c_double), ("winkler_score", C.c_double),
+                ("n_observations", C.c_size_t)]
+
+
+assert (C.sizeof(ConformalResultFFI), C.sizeof(ConformalMultiResultFFI), C.sizeof(CalibrationProfileFFI), C.sizeof(PredictionIntervalsFFI),
+        C.sizeof(ConformalEvaluationFFI)) == (80, 56, 64, 56, 40)
+
+
 class FilledValuesResult(C.Structure):
     _fields_ = [("values", C.POINTER(C.c_double)), ("validity", C.POINTER(C.c_uint64)), ("length", C.c_size_t)]
 
@@ -266,6 +320,12 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_fill_nulls_const", "anofox_ts_fill_nulls_mean", "anofox_ts_fill_nulls_interpolate", "anofox_ts_fill_nulls_forward",
     "anofox_ts_fill_nulls_backward", "anofox_ts_fill_gaps", "anofox_free_gap_fill_result", "anofox_free_filled_values_result",
     "anofox_free_double_array", "anofox_hip_prepare_device", "anofox_hip_prepare_batch", "anofox_hip_free_prepared",
+    "anofox_hip_conformal_learn_device", "anofox_hip_conformal_apply_device", "anofox_hip_conformal_evaluate_device",
+    "anofox_hip_conformal_batch", "anofox_hip_free_conformal",
+    "anofox_ts_conformal_quantile", "anofox_ts_conformal_intervals", "anofox_ts_conformal_predict", "anofox_ts_conformal_predict_multi",
+    "anofox_ts_conformal_predict_adaptive", "anofox_ts_conformal_predict_asymmetric", "anofox_ts_mean_interval_width",
+    "anofox_ts_conformal_learn", "anofox_ts_conformal_apply", "anofox_ts_conformal_coverage", "anofox_ts_conformal_evaluate",
+    "anofox_free_conformal_result", "anofox_free_conformal_multi_result", "anofox_free_calibration_profile", "anofox_free_prediction_intervals",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -445,6 +505,50 @@ def load():
     L.anofox_hip_prepare_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(AnofoxHipPrepOptions), C.c_size_t,
                                            P(AnofoxHipPrepared), P(AnofoxError)]
     L.anofox_hip_free_prepared.argtypes = [P(AnofoxHipPrepared), C.c_size_t]
+    L.anofox_hip_conformal_learn_device.restype = C.c_bool
+    L.anofox_hip_conformal_learn_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_conformal_apply_device.restype = C.c_bool
+    L.anofox_hip_conformal_apply_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                    C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_conformal_evaluate_device.restype = C.c_bool
+    L.anofox_hip_conformal_evaluate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                       C.c_size_t, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_conformal_batch.restype = C.c_bool
+    L.anofox_hip_conformal_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_size_t, C.c_int, C.c_int, C.c_bool, P(AnofoxHipConformal), C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_free_conformal.argtypes = [P(AnofoxHipConformal), C.c_size_t]
+    L.anofox_ts_conformal_quantile.restype = C.c_bool
+    L.anofox_ts_conformal_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, P(C.c_double), P(AnofoxError)]
+    L.anofox_ts_conformal_intervals.restype = C.c_bool
+    L.anofox_ts_conformal_intervals.argtypes = [C.c_void_p, C.c_size_t, C.c_double, P(P(C.c_double)), P(P(C.c_double)), P(AnofoxError)]
+    for name in ("predict", "predict_asymmetric"):
+        f = getattr(L, "anofox_ts_conformal_" + name)
+        f.restype = C.c_bool
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, P(ConformalResultFFI), P(AnofoxError)]
+    L.anofox_ts_conformal_predict_multi.restype = C.c_bool
+    L.anofox_ts_conformal_predict_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    P(ConformalMultiResultFFI), P(AnofoxError)]
+    L.anofox_ts_conformal_predict_adaptive.restype = C.c_bool
+    L.anofox_ts_conformal_predict_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double,
+                                                       P(ConformalResultFFI), P(AnofoxError)]
+    L.anofox_ts_mean_interval_width.restype = C.c_bool
+    L.anofox_ts_mean_interval_width.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_double), P(AnofoxError)]
+    L.anofox_ts_conformal_learn.restype = C.c_bool
+    L.anofox_ts_conformal_learn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                            P(CalibrationProfileFFI), P(AnofoxError)]
+    L.anofox_ts_conformal_apply.restype = C.c_bool
+    L.anofox_ts_conformal_apply.argtypes = [C.c_void_p, C.c_size_t, P(CalibrationProfileFFI), C.c_void_p, P(PredictionIntervalsFFI), P(AnofoxError)]
+    L.anofox_ts_conformal_coverage.restype = C.c_bool
+    L.anofox_ts_conformal_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_double), P(AnofoxError)]
+    L.anofox_ts_conformal_evaluate.restype = C.c_bool
+    L.anofox_ts_conformal_evaluate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, P(ConformalEvaluationFFI), P(AnofoxError)]
+    L.anofox_free_conformal_result.argtypes = [P(ConformalResultFFI)]
+    L.anofox_free_conformal_multi_result.argtypes = [P(ConformalMultiResultFFI)]
+    L.anofox_free_calibration_profile.argtypes = [P(CalibrationProfileFFI)]
+    L.anofox_free_prediction_intervals.argtypes = [P(PredictionIntervalsFFI)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

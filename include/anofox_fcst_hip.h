@@ -938,6 +938,244 @@ bool anofox_hip_metrics_device(const double *actual,
                                struct AnofoxError *out_error);
 
 /*
+ * Conformal prediction intervals per group on device-resident fp64 blocks (the reference's conformal.rs: conformal_learn,
+ * conformal_apply, conformal_coverage / winkler_score / conformal_evaluate).  The contract is equality of bits with the source.
+ * Element (group s, row t) of every block of a call is at s * stride_s + t * stride_t, as for anofox_hip_metrics_device: both the
+ * time-major block and the series-major [n_series x horizon] layout of anofox_hip_batch_device_results work, with the same bits.
+ * `alphas` is a HOST array of 1 .. 16 miscoverage rates, each in [0, 1) (0 is valid, as in the source); an alpha outside, no
+ * alpha or more than 16 fail the call with INVALID_INPUT (the last one naming the limit).  Every call runs on `stream` (NULL: the
+ * null stream) and returns after it has finished.  Runs on the calling thread's current device (anofox_hip_set_devices does not
+ * shard it).  Outputs shaped [rows x ld] have only their columns s < n_groups written.
+ *
+ * method: 0 symmetric, 1 asymmetric, 2 adaptive.  status, int32 [n_groups]: 0 done; 1 no row (left), figures NaN; 2 a residual
+ * is NaN, scores NaN (the source leaves the order of such a vector to its sort's internals); 3 a difficulty <= 0, bounds NaN.
+ *
+ * learn: the residual of row t is residual[..] or, when `residual` is NULL, actual[..] - forecast[..] (one fp64 subtraction).
+ * valid (may be NULL) has one byte per element at the same offsets; a row whose byte is 0 is dropped.  lengths is int32
+ * [n_groups] on the device (a length above t_rows is cut to it; pass the longest group's length as t_rows, the kernel's LDS tile is
+ * sized from it).  Symmetric and adaptive: the conformity score of level k, compute_quantile(sorted |r|, clamp(ceil((n + 1)
+ * (1 - alpha_k)) / n, 0, 1)), goes to scores_lower[k * ld + s] and scores_upper[k * ld + s].  Asymmetric: alpha_k / 2, the
+ * positives (r > 0) give scores_upper, the magnitudes of the negatives (r < 0) scores_lower, an empty set gives 0.0.  sorted (may
+ * be NULL) is a block with the inputs' strides whose rows 0 .. n_kept - 1 receive the ascending |r| of the group (Jackknife+'s
+ * state vector; not written for status 2); n_kept (may be NULL) is int32 [n_groups].  One wavefront per group sorts in LDS; groups
+ * above 2,048 rows sort in a global workspace.
+ */
+bool anofox_hip_conformal_learn_device(const double *residual,
+                                       const double *actual,
+                                       const double *forecast,
+                                       const uint8_t *valid,
+                                       size_t stride_s,
+                                       size_t stride_t,
+                                       const int32_t *lengths,
+                                       size_t n_groups,
+                                       size_t t_rows,
+                                       const double *alphas,
+                                       size_t n_alphas,
+                                       int method,
+                                       double *scores_lower,
+                                       double *scores_upper,
+                                       size_t ld,
+                                       double *sorted,
+                                       int32_t *n_kept,
+                                       int32_t *status,
+                                       void *stream,
+                                       struct AnofoxError *out_error);
+
+/*
+ * apply: for level k and step t < lengths[s] (lengths NULL: every group has h_rows steps), lower = f - scores_lower[k * ld + s] * d
+ * and upper = f + scores_upper[k * ld + s] * d, written to lower + k * stride_q and upper + k * stride_q at the forecast's offsets.
+ * d = 1 (no multiplication) unless the method is adaptive; then d = difficulty / mean, the mean being the group's sequential sum
+ * in row order divided by its count.  A difficulty <= 0 anywhere in the group: status 3 and NaN bounds.  A group with no step:
+ * status 1.  The scores of a group that learn could not answer are NaN, and so are its bounds.
+ */
+bool anofox_hip_conformal_apply_device(const double *forecast,
+                                       const double *difficulty,
+                                       size_t stride_s,
+                                       size_t stride_t,
+                                       const int32_t *lengths,
+                                       size_t n_groups,
+                                       size_t h_rows,
+                                       const double *scores_lower,
+                                       const double *scores_upper,
+                                       size_t ld,
+                                       size_t n_alphas,
+                                       int method,
+                                       double *lower,
+                                       double *upper,
+                                       size_t stride_q,
+                                       int32_t *status,
+                                       void *stream,
+                                       struct AnofoxError *out_error);
+
+/*
+ * evaluate: figures is fp64 [5 x ld]: 0 coverage (rows with lower <= actual <= upper over n), 1 violation_rate (1 - coverage),
+ * 2 mean_width (sequential sum of upper - lower over n), 3 winkler_score (penalty 2 / alpha), 4 n_observations.  A group with no
+ * row: status 1, figures NaN (n_observations 0).
+ */
+bool anofox_hip_conformal_evaluate_device(const double *actual,
+                                          const double *lower,
+                                          const double *upper,
+                                          size_t stride_s,
+                                          size_t stride_t,
+                                          const int32_t *lengths,
+                                          size_t n_groups,
+                                          size_t t_rows,
+                                          double alpha,
+                                          double *figures,
+                                          size_t ld,
+                                          int32_t *status,
+                                          void *stream,
+                                          struct AnofoxError *out_error);
+
+/* One group's answer of anofox_hip_conformal_batch; every array is owned by the result (anofox_hip_free_conformal). */
+typedef struct AnofoxHipConformal {
+    double *scores_lower;  /* [n_levels] conformity score of every level (asymmetric: from the negatives) */
+    double *scores_upper;  /* [n_levels] the same value, or (asymmetric) the score from the positives     */
+    double *sorted;        /* [n_residuals] ascending |residual| (Jackknife+'s state vector), NULL unless requested */
+    size_t n_residuals;    /* residuals kept (not NULL)                                                    */
+    double *lower;         /* [n_levels x n_forecasts] level k's lower bounds at k * n_forecasts           */
+    double *upper;         /* [n_levels x n_forecasts]                                                      */
+    size_t n_forecasts;
+    size_t n_levels;
+} AnofoxHipConformal;
+
+/*
+ * learn -> apply for many groups from host pointers in ONE call (the reference's conformalize, one FFI call per group there).
+ * residuals[i] points to the residual_lengths[i] calibration residuals of group i; residual_validity (may be NULL, and so may
+ * residual_validity[i]) is its validity bitmask, bit t of word t / 64 clear = NULL, dropped as the table macros' IS NOT NULL filter
+ * does.  forecasts[i] points to the forecast_lengths[i] point forecasts (forecasts may be NULL as a whole: learn only, no bounds).
+ * difficulty[i] (adaptive method only) has forecast_lengths[i] values.  strategy: 0 split, 1 cross-validation, 2 Jackknife+ --
+ * the scores are the same for all three (as in the source); Jackknife+ with the asymmetric method is INVALID_INPUT.  want_sorted:
+ * also return the sorted |residual| of every group.  Batch-level failures (a NULL argument, no alpha, more than 16, an alpha outside
+ * [0, 1), an unknown method or strategy, a device failure) return false and are reported through out_batch_error.  Per-group
+ * errors (out_errors[i], may be NULL; the result's arrays are NULL then) carry the source's texts: no residual (left)
+ * "Insufficient data: need at least 1 observations, got 0"; no forecast "Invalid input: At least one forecast is required"; a
+ * difficulty <= 0 "Invalid input: Difficulty scores must be positive"; a NaN residual "Invalid input: a residual is NaN" (this
+ * backend's limit).  Release with anofox_hip_free_conformal(results, n_groups).
+ */
+bool anofox_hip_conformal_batch(const double *const *residuals,
+                                const uint64_t *const *residual_validity,
+                                const size_t *residual_lengths,
+                                const double *const *forecasts,
+                                const double *const *difficulty,
+                                const size_t *forecast_lengths,
+                                size_t n_groups,
+                                const double *alphas,
+                                size_t n_alphas,
+                                int method,
+                                int strategy,
+                                bool want_sorted,
+                                struct AnofoxHipConformal *out_results,
+                                struct AnofoxError *out_errors,
+                                struct AnofoxError *out_batch_error);
+void anofox_hip_free_conformal(struct AnofoxHipConformal *results, size_t n_groups);
+
+/*
+ * The reference's conformal entries (anofox_fcst_ffi.h, lib.rs:4747-5400) with its signatures, struct layouts and error texts, each
+ * a batch of one through the same kernels; the argument checks come first and need no device.  A NULL pointer: NULL_POINTER "Null
+ * pointer argument" (anofox_ts_conformal_quantile's out_result: "Null output pointer").  `validity` / `residuals_validity` (may be
+ * NULL) is the bitmask of the residuals, bit t of word t / 64 clear = NULL, dropped before anything else.  What the source's
+ * functions refuse is COMPUTATION_ERROR with their text, in their order: "Insufficient data: need at least 1 observations, got 0",
+ * "Invalid input: Alpha must be between 0 and 1 (exclusive)" (quantile, predict, predict_multi, predict_adaptive,
+ * predict_asymmetric), "Invalid input: Alpha must be in (0, 1), got 1.5" (learn, evaluate), "Invalid input: At least one alpha value
+ * is required", "Invalid input: At least one forecast is required" (apply), "Invalid input: Difficulty scores required for adaptive
+ * method", "Invalid input: Difficulty length (4) must match residuals length (3)", "Invalid input: Difficulty scores must be
+ * positive", "Invalid input: JackknifePlus strategy does not support asymmetric method".  This backend's own limits: more than 16
+ * levels is INVALID_INPUT naming the limit, a NaN residual is COMPUTATION_ERROR "Invalid input: a residual is NaN" (DESIGN.md
+ * section 7).  Arrays of a result are malloc'ed, NULL when empty, and released by the result's free function (anofox_ts_conformal_
+ * intervals' two arrays by anofox_free_double_array).  anofox_ts_conformal_predict_per_step and the bootstrap entries are not
+ * provided.
+ */
+#ifndef ANOFOX_FCST_FFI_H
+typedef struct ConformalResultFFI {
+    double *point;
+    double *lower;
+    double *upper;
+    size_t n_forecasts;
+    double coverage;          /* 1 - alpha */
+    double conformity_score;
+    char method[32];          /* "split_conformal", "adaptive_conformal", "asymmetric_conformal" */
+} ConformalResultFFI;
+
+typedef struct ConformalMultiResultFFI {
+    double *point;
+    size_t n_forecasts;
+    double *coverage_levels;  /* [n_levels] */
+    double *conformity_scores;/* [n_levels] */
+    size_t n_levels;
+    double *lower;            /* [n_levels x n_forecasts], level-major */
+    double *upper;
+} ConformalMultiResultFFI;
+
+typedef enum ConformalMethodFFI { CONFORMAL_METHOD_SYMMETRIC = 0, CONFORMAL_METHOD_ASYMMETRIC = 1, CONFORMAL_METHOD_ADAPTIVE = 2 } ConformalMethodFFI;
+typedef enum ConformalStrategyFFI { CONFORMAL_STRATEGY_SPLIT = 0, CONFORMAL_STRATEGY_CROSS_VAL = 1, CONFORMAL_STRATEGY_JACKKNIFE_PLUS = 2 } ConformalStrategyFFI;
+
+typedef struct CalibrationProfileFFI {
+    ConformalMethodFFI method;
+    ConformalStrategyFFI strategy;
+    double *alphas;           /* [n_levels] */
+    double *state_vector;     /* split / crossval: scores_lower then scores_upper; jackknife+: the sorted |residual| */
+    size_t state_vector_len;
+    double *scores_lower;     /* [n_levels] */
+    double *scores_upper;     /* [n_levels] */
+    size_t n_levels;
+    size_t n_residuals;
+} CalibrationProfileFFI;
+
+typedef struct PredictionIntervalsFFI {
+    double *point;
+    size_t n_forecasts;
+    double *coverage;         /* [n_levels] 1 - alpha */
+    size_t n_levels;
+    double *lower;            /* [n_levels x n_forecasts], level-major */
+    double *upper;
+    ConformalMethodFFI method;
+} PredictionIntervalsFFI;
+
+typedef struct ConformalEvaluationFFI {
+    double coverage;
+    double violation_rate;
+    double mean_width;
+    double winkler_score;
+    size_t n_observations;
+} ConformalEvaluationFFI;
+#endif /* ANOFOX_FCST_FFI_H */
+
+bool anofox_ts_conformal_quantile(const double *residuals, const uint64_t *validity, size_t length, double alpha, double *out_result,
+                                  struct AnofoxError *out_error);
+bool anofox_ts_conformal_intervals(const double *forecasts, size_t length, double conformity_score, double **out_lower, double **out_upper,
+                                   struct AnofoxError *out_error);
+bool anofox_ts_conformal_predict(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                 const double *forecasts, size_t forecasts_length, double alpha, struct ConformalResultFFI *out_result,
+                                 struct AnofoxError *out_error);
+bool anofox_ts_conformal_predict_multi(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                       const double *forecasts, size_t forecasts_length, const double *alphas, size_t n_alphas,
+                                       struct ConformalMultiResultFFI *out_result, struct AnofoxError *out_error);
+bool anofox_ts_conformal_predict_adaptive(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                          const double *forecasts, const double *difficulty, size_t forecasts_length, double alpha,
+                                          struct ConformalResultFFI *out_result, struct AnofoxError *out_error);
+bool anofox_ts_conformal_predict_asymmetric(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length,
+                                            const double *forecasts, size_t forecasts_length, double alpha,
+                                            struct ConformalResultFFI *out_result, struct AnofoxError *out_error);
+bool anofox_ts_mean_interval_width(const double *lower, const double *upper, size_t length, double *out_result,
+                                   struct AnofoxError *out_error);
+/* difficulty (may be NULL unless the method is adaptive) has residuals_length values */
+bool anofox_ts_conformal_learn(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length, const double *alphas,
+                               size_t n_alphas, ConformalMethodFFI method, ConformalStrategyFFI strategy, const double *difficulty,
+                               struct CalibrationProfileFFI *out_profile, struct AnofoxError *out_error);
+/* difficulty (may be NULL unless the profile's method is adaptive) has n_forecasts values */
+bool anofox_ts_conformal_apply(const double *forecasts, size_t n_forecasts, const struct CalibrationProfileFFI *profile,
+                               const double *difficulty, struct PredictionIntervalsFFI *out_intervals, struct AnofoxError *out_error);
+bool anofox_ts_conformal_coverage(const double *actuals, const double *lower, const double *upper, size_t length, double *out_coverage,
+                                  struct AnofoxError *out_error);
+bool anofox_ts_conformal_evaluate(const double *actuals, const double *lower, const double *upper, size_t length, double alpha,
+                                  struct ConformalEvaluationFFI *out_eval, struct AnofoxError *out_error);
+void anofox_free_conformal_result(struct ConformalResultFFI *result);
+void anofox_free_conformal_multi_result(struct ConformalMultiResultFFI *result);
+void anofox_free_calibration_profile(struct CalibrationProfileFFI *result);
+void anofox_free_prediction_intervals(struct PredictionIntervalsFFI *result);
+
+/*
  * Multi-device execution of the batch entry.  The reference's finalize loop is ONE process walking all groups
  * (src/table_functions/ts_forecast_native.cpp:559-800); series are independent, so anofox_ts_forecast_batch shards
  * contiguous series-id ranges [g * ceil(N / G), (g + 1) * ceil(N / G)) over the G devices named here: one host thread,
