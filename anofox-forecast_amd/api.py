@@ -1181,6 +1181,114 @@ anofox_fcst_ts_stats_agg = ts_stats_agg
 
 
 # --------------------------------------------------------------------------------------------
+# data quality: anofox_hip_quality_batch and the mirrors of _ts_data_quality, ts_data_quality, ts_data_quality_by,
+# ts_data_quality_summary and ts_data_quality_agg
+# --------------------------------------------------------------------------------------------
+QUALITY_FIELDS = _lib.QUALITY_FIELDS
+
+
+def quality_batch(series, valids=None):
+    """anofox_hip_quality_batch over a list of 1-D arrays: one GPU pass for all series.  `valids[i]` (booleans, False = NULL) may be
+    None per series, as may the list.  Per series a dict keyed by QUALITY_FIELDS plus "status": 0, or 2 for a series with a NaN
+    among its valid values -- its five scores are NaN (the single entry and the SQL mirrors fail / give NULL there)."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks = None
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+    res = (_lib.DataQualityResult * max(n, 1))()
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_quality_batch(vals, masks, lens.ctypes.data, n, res, status.ctypes.data, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    for i in range(n):
+        r = res[i]
+        d = {f: float(getattr(r, f)) for f in _lib.QUALITY_FP_FIELDS}
+        d.update(n_gaps=int(r.n_gaps), n_missing=int(r.n_missing), is_constant=bool(r.is_constant), status=int(status[i]))
+        out.append(d)
+    return out
+
+
+def _quality_struct(d):
+    """The STRUCT of the SQL functions: None where the wrapper fails (a NaN among the values), else the eight fields."""
+    return None if d["status"] != _lib.QUALITY_OK else {f: d[f] for f in QUALITY_FIELDS}
+
+
+def _ts_data_quality(values):
+    """The scalar _ts_data_quality(values) (ts_data_quality.cpp TsDataQualityFunction): None for a NULL list; a NULL element is an
+    invalid slot and counts as missing.  An EMPTY list also gives None: the C++ hands the wrapper the data() of an empty vector, a
+    null pointer with libstdc++, and turns every failure of the wrapper into SQL NULL (ts_data_quality.cpp:89-92) -- as it does
+    for a list that holds a NaN, which this library refuses (the C entry anofox_ts_data_quality itself keeps the `length == 0`
+    rule: every figure 0).  Else the STRUCT as a dict."""
+    if values is None or len(values) == 0:
+        return None
+    v, ok = _stats_cells(list(values))
+    return _quality_struct(quality_batch([v], [ok])[0])
+
+
+def ts_data_quality(group, date, value, n_short=None, frequency=None):
+    """The macro ts_data_quality(source, unique_id_col, date_col, value_col, n_short, frequency) (ts_macros.cpp:124-146): per group
+    _ts_data_quality of the values ordered by date (NULL dates last).  `n_short` and `frequency` are accepted and IGNORED, as the
+    macro's text never mentions them.  All groups go to the GPU in one quality_batch call.  Returns a dict of the macro's nine
+    columns: unique_id (groups in first-arrival order) and the eight figures (lists; None = NULL: a group with a NaN value)."""
+    order, series, valids, _ = _stats_groups(group, date, value, True)
+    res = [_quality_struct(d) for d in quality_batch(series, valids)] if order else []
+    out = {"unique_id": list(order)}
+    for f in QUALITY_FIELDS:
+        out[f] = [None if r is None else r[f] for r in res]
+    return out
+
+
+def ts_data_quality_by(group, date, value, n_short=None, frequency=None):
+    """ts_data_quality_by (ts_macros.cpp:1616-): the same text as ts_data_quality under the _by name; n_short and frequency ignored."""
+    return ts_data_quality(group, date, value, n_short, frequency)
+
+
+def ts_data_quality_summary(group, date, value, n_short=None):
+    """The macro ts_data_quality_summary(source, unique_id_col, date_col, value_col, n_short) (ts_macros.cpp:151-170): n_total, n_good
+    (overall_score >= 0.8), n_fair (in [0.5, 0.8)), n_poor (< 0.5) and avg_score over the groups, on the host from the per-series
+    results.  n_short is accepted and ignored.  A group whose STRUCT is NULL counts in n_total only; no group: n_total 0 and the
+    SUMs / AVG NULL (None)."""
+    overall = ts_data_quality(group, date, value)["overall_score"]
+    n = len(overall)
+    if n == 0:
+        return {"n_total": 0, "n_good": None, "n_fair": None, "n_poor": None, "avg_score": None}
+    known = [x for x in overall if x is not None]
+    total = 0.0
+    for x in known:                                        # a plain running sum (the built-in sum() compensates its float sums)
+        total += x
+    return {"n_total": n, "n_good": sum(1 for x in known if x >= 0.8), "n_fair": sum(1 for x in known if 0.5 <= x < 0.8),
+            "n_poor": sum(1 for x in known if x < 0.5), "avg_score": total / len(known) if known else None}
+
+
+def ts_data_quality_agg(ts, value):
+    """The aggregate ts_data_quality_agg(ts, value) over ONE group (ts_data_quality_agg.cpp:94-170): rows with a NULL timestamp or
+    value are dropped, the rest ordered by (timestamp, value) as std::sort orders the pairs, all valid.  None when no row is left
+    (or a value is NaN)."""
+    dates = np.asarray(ts)
+    vals, vnull = _changepoint_values(value)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), dtype=bool)
+    keep = np.nonzero(~(null_date | vnull))[0]
+    if len(keep) == 0:
+        return None
+    us = _to_micros(dates[keep], _date_kind(dates))
+    v = vals[keep]
+    return _quality_struct(quality_batch([v[np.lexsort((v, us))]])[0])
+
+
+anofox_fcst_ts_data_quality = ts_data_quality
+anofox_fcst_ts_data_quality_by = ts_data_quality_by
+anofox_fcst_ts_data_quality_summary = ts_data_quality_summary
+anofox_fcst_ts_data_quality_agg = ts_data_quality_agg      # ts_data_quality_agg.cpp:253-262
+
+
+# --------------------------------------------------------------------------------------------
 # series preparation: anofox_hip_prepare_batch, the single entries of gaps.rs / imputation.rs, and the mirrors of ts_fill_gaps_by,
 # ts_fill_nulls_*_by, ts_drop_*_zeros_by and the four drop filters (ts_macros.cpp:172-413)
 # --------------------------------------------------------------------------------------------

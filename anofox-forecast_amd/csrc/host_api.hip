@@ -3932,6 +3932,143 @@ bool anofox_ts_stats(const double *values, const uint64_t *validity, size_t leng
 void anofox_free_ts_stats_result(TsStatsResult *result) { (void)result; }      // the struct owns no memory (as the reference's)
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Data quality per series (quality.rs compute_data_quality without dates; quality.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(DataQualityResult) == 64 && offsetof(DataQualityResult, overall_score) == 32 && offsetof(DataQualityResult, n_gaps) == 40 &&
+              offsetof(DataQualityResult, n_missing) == 48 && offsetof(DataQualityResult, is_constant) == 56, "DataQualityResult layout");
+static const char *const QUALITY_NAN_TEXT = "Invalid input: a value is NaN";
+
+bool anofox_hip_quality_device(const double *y, const uint8_t *valid, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
+                               double *out_fp, int64_t *out_int, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !out_fp || !out_int) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    QualityArgs a{};
+    a.y = y; a.valid = valid; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.out_fp = out_fp; a.out_int = out_int;
+    a.tile = quality_tile(t_rows);
+    a.work_stride = quality_work_stride(t_rows);
+    a.work_waves = a.work_stride ? quality_work_waves((int)n_series) : 0;
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *work = nullptr;
+    try {
+        (void)hipGetLastError();
+        if (a.work_stride && a.work_waves > 0) work = dalloc<uint64_t>(a.work_stride * (size_t)a.work_waves);
+        a.work = work;
+        launch_quality(a, st);
+        LAUNCHCHECK("quality");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(work, true);
+    } catch (const HipFail &f) {
+        dev_free(work, false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_quality_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
+                              DataQualityResult *out_results, int32_t *out_status, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_series > 0 && (!values || !lengths || !out_results)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    size_t t_max = 0;
+    bool any_mask = false;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        t_max = std::max(t_max, lengths[s]);
+        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
+    }
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    double *d_y = nullptr, *d_fp = nullptr;
+    uint8_t *d_valid = nullptr;
+    int64_t *d_int = nullptr;
+    int32_t *d_len = nullptr;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_valid, (void *)d_int, (void *)d_len}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<int64_t> oi(QUALITY_N_INT * ld);
+    std::vector<double> of(QUALITY_N_FP * ld);
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
+        std::vector<int32_t> len(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            const uint64_t *m = validity ? validity[s] : nullptr;
+            for (size_t t = 0; t < lengths[s]; t++) {
+                yb[t * ld + s] = values[s][t];
+                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
+            }
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
+        d_int = dalloc<int64_t>(QUALITY_N_INT * ld); d_fp = dalloc<double>(QUALITY_N_FP * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (any_mask) {
+            d_valid = dalloc<uint8_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+        }
+        if (!anofox_hip_quality_device(d_y, d_valid, ld, d_len, n_series, T, d_fp, d_int, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++) {
+        DataQualityResult &r = out_results[s];
+        std::memset(&r, 0, sizeof r);
+        double *fp = &r.structural_score;                         // five consecutive doubles, structural .. overall
+        for (int i = 0; i < QUALITY_N_FP; i++) fp[i] = of[i * ld + s];
+        r.n_gaps = (size_t)oi[0 * ld + s];
+        r.n_missing = (size_t)oi[1 * ld + s];
+        r.is_constant = oi[2 * ld + s] != 0;
+        if (out_status) out_status[s] = (int32_t)oi[3 * ld + s];
+    }
+    return true;
+}
+
+bool anofox_ts_data_quality(const double *values, const uint64_t *validity, size_t length, DataQualityResult *out_result, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const double *v[1] = {values};
+    const uint64_t *m[1] = {validity};
+    const size_t len[1] = {length};
+    DataQualityResult r;
+    int32_t status = 0;
+    if (!anofox_hip_quality_batch(v, m, len, 1, &r, &status, out_error)) return false;
+    if (status == (int32_t)QUALITY_NAN) { set_error(out_error, COMPUTATION_ERROR, QUALITY_NAN_TEXT); return false; }
+    *out_result = r;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Series preparation: gaps, zero trimming, NULL fills (gaps.rs, ts_macros.cpp:208-256, imputation.rs; dataprep.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(GapFillResult) == 32 && offsetof(GapFillResult, values) == 8 && offsetof(GapFillResult, validity) == 16 &&

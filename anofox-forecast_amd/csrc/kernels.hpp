@@ -355,6 +355,26 @@ void launch_conformal_learn(const ConformalLearnArgs &, hipStream_t);
 void launch_conformal_apply(const ConformalApplyArgs &, hipStream_t);
 void launch_conformal_evaluate(const ConformalEvalArgs &, hipStream_t);
 
+// Data quality scores per series (quality.rs compute_data_quality without dates; quality.hip)
+constexpr int QUALITY_RESIDENT = 2048;       // rows of the longest series that is sorted in LDS; longer ones use the global workspace
+constexpr int QUALITY_WORK_WAVES = 1024;     // waves (and workspace slices) that walk the longer series
+constexpr int QUALITY_N_FP = 5, QUALITY_N_INT = 4;
+constexpr int64_t QUALITY_OK = 0, QUALITY_NAN = 2;
+struct QualityArgs {
+    const double *y; const uint8_t *valid;       // [t_rows x ld]; valid may be null
+    size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    double *out_fp;              // [QUALITY_N_FP x ld] structural, temporal, magnitude, behavioral, overall
+    int64_t *out_int;            // [QUALITY_N_INT x ld] n_gaps, n_missing, is_constant (0 / 1), status (QUALITY_OK / QUALITY_NAN)
+    int tile;                    // words per wave of the LDS kernel: a power of two, 64 .. QUALITY_RESIDENT
+    uint64_t *work;              // [work_waves x work_stride] or null when t_rows <= QUALITY_RESIDENT
+    size_t work_stride; int work_waves;
+};
+int quality_tile(size_t t_rows);                 // the LDS tile of a batch whose longest series has t_rows rows
+size_t quality_work_stride(size_t t_rows);       // words per workspace slice (0: no workspace needed)
+int quality_work_waves(int n_series);
+void launch_quality(const QualityArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

@@ -1,5 +1,5 @@
-// wave_sort.hpp -- the one-wavefront sorting network on total-order keys, shared by the selections of stats.hip and the residual
-// quantiles of conformal.hip.  An fp64 value becomes a 64-bit key whose unsigned order is the order of the values (negatives: all
+// wave_sort.hpp -- the one-wavefront sorting network on total-order keys, shared by the selections of stats.hip, the residual
+// quantiles of conformal.hip and the quartiles of quality.hip.  An fp64 value becomes a 64-bit key whose unsigned order is the order of the values (negatives: all
 // bits flipped, others: sign bit flipped; -0.0 sorts below +0.0, a NaN beyond the infinity of its sign); the buffer -- LDS or a
 // slice of a global workspace -- is sorted in place by a bitonic network, every stage closed by st_sync.  The largest key ~0 pads
 // the buffer to a power of two.

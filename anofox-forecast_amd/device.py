@@ -92,6 +92,40 @@ def prepare_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | 
             "t_out": t_out}
 
 
+def quality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | None = None, *, n_series: int | None = None,
+                  stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_quality_device on torch tensors: the eight ts_data_quality figures of every series of a block, no host copy.
+
+    y [t_rows, ld] fp64, valid [t_rows, ld] uint8 or bool (0 = NULL; None: all valid), lengths int32 [>= n_series], on one HIP device,
+    contiguous -- what prepare_block returns: r = prepare_block(...); q = quality_block(r["y"], r["lengths"], r["valid"]); then filter
+    on q["scores"] / q["status"] and hand the kept columns to DeviceBatch.set_block.
+
+    Returns {"scores": fp64 [5, ld], rows lib.QUALITY_FP_FIELDS; "figures": int64 [4, ld], rows lib.QUALITY_INT_FIELDS (n_gaps,
+    n_missing, is_constant as 0 / 1, status: lib.QUALITY_OK, or lib.QUALITY_NAN with five NaN scores)}.  Columns s >= n_series hold
+    NaN and -1."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and tuple(valid.shape) == (t_rows, ld)
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    scores = torch.full((5, ld), float("nan"), dtype=torch.float64, device=dev)
+    figures = torch.full((4, ld), -1, dtype=torch.int64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_quality_device(y.data_ptr(), valid.data_ptr() if valid is not None else None, ld, lengths.data_ptr(), n, t_rows,
+                                     scores.data_ptr(), figures.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_quality_device failed: [{err.code}] {err.message.decode()}")
+    return {"scores": scores, "figures": figures}
+
+
 def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | None = None, actual: torch.Tensor | None = None,
                     calibration_forecast: torch.Tensor | None = None, valid: torch.Tensor | None = None,
                     lengths: torch.Tensor | None = None, n_groups: int | None = None, method: str = "symmetric",

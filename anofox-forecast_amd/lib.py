@@ -124,6 +124,19 @@ class TsStatsResult(C.Structure):
                 + [("expected_length", C.c_size_t), ("n_gaps", C.c_size_t), ("has_date_metrics", C.c_bool)])
 
 
+class DataQualityResult(C.Structure):
+    """include/anofox_fcst_hip.h DataQualityResult: five scores, n_gaps, n_missing, is_constant (64 bytes)."""
+    _fields_ = ([(n, C.c_double) for n in ("structural_score", "temporal_score", "magnitude_score", "behavioral_score", "overall_score")]
+                + [("n_gaps", C.c_size_t), ("n_missing", C.c_size_t), ("is_constant", C.c_bool)])
+
+
+assert C.sizeof(DataQualityResult) == 64
+QUALITY_FP_FIELDS = tuple(n for n, _ in DataQualityResult._fields_[:5])    # rows of out_fp of anofox_hip_quality_device
+QUALITY_INT_FIELDS = ("n_gaps", "n_missing", "is_constant", "status")      # rows of its out_int
+QUALITY_FIELDS = tuple(n for n, _ in DataQualityResult._fields_)
+QUALITY_OK, QUALITY_NAN = 0, 2
+
+
 class LombScargleResultFFI(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("period", "frequency", "power", "false_alarm_prob")] + [("method", C.c_char * 32)]
 
@@ -312,6 +325,7 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_detect_changepoints_bocpd", "anofox_free_bocpd_result", "anofox_hip_changepoints_batch", "anofox_hip_changepoints_device",
     "anofox_ts_stats", "anofox_ts_stats_with_dates", "anofox_ts_stats_with_dates_and_type", "anofox_free_ts_stats_result",
     "anofox_hip_stats_batch", "anofox_hip_stats_device",
+    "anofox_ts_data_quality", "anofox_hip_quality_batch", "anofox_hip_quality_device",
     "anofox_ts_lomb_scargle", "anofox_ts_aic_period", "anofox_ts_sazed_period", "anofox_ts_detect_periods_flat",
     "anofox_free_flat_multi_period_result", "anofox_hip_periods_batch", "anofox_hip_periods_device",
     "anofox_ts_mae", "anofox_ts_mse", "anofox_ts_rmse", "anofox_ts_mape", "anofox_ts_smape", "anofox_ts_r2", "anofox_ts_bias",
@@ -445,6 +459,13 @@ def load():
     L.anofox_hip_stats_device.restype = C.c_bool
     L.anofox_hip_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_data_quality.restype = C.c_bool
+    L.anofox_ts_data_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(DataQualityResult), P(AnofoxError)]
+    L.anofox_hip_quality_batch.restype = C.c_bool
+    L.anofox_hip_quality_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_quality_device.restype = C.c_bool
+    L.anofox_hip_quality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, P(AnofoxError)]
     L.anofox_ts_lomb_scargle.restype = C.c_bool
     L.anofox_ts_lomb_scargle.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_size_t, P(LombScargleResultFFI), P(AnofoxError)]
     L.anofox_ts_aic_period.restype = C.c_bool

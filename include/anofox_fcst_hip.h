@@ -325,6 +325,36 @@ bool anofox_ts_stats_with_dates_and_type(const double *values,
 
 void anofox_free_ts_stats_result(struct TsStatsResult *result);
 
+/*
+ * The eight data quality figures of one series (layout of the reference's anofox_fcst_ffi.h: five doubles, two size_t and a bool,
+ * sizeof == 64, n_gaps at 40, is_constant at 56).  Holds no pointer.
+ */
+typedef struct DataQualityResult {
+    double structural_score, temporal_score, magnitude_score, behavioral_score, overall_score;
+    size_t n_gaps;    /* always 0: the entry passes no dates, as the reference's */
+    size_t n_missing; /* NULLs */
+    bool is_constant;
+} DataQualityResult;
+
+/*
+ * Data quality of ONE series, the reference's compute_data_quality(series, None) (quality.rs) behind its FFI wrapper.  `validity`
+ * (bit i of word i / 64; NULL = all valid) marks NULLs.  With x the non-NULL values in row order and k their count: n_missing =
+ * length - k, n_gaps = 0; is_constant: k < 2, or every |x_i - x_0| < DBL_EPSILON; structural = clamp(k / length * 0.7 +
+ * min(k / 30, 1) * 0.3) (0 when k == 0); temporal = 1; magnitude = clamp(1 - 2 * outliers / k - 3 * extreme / k) with the outliers
+ * beyond 1.5 interquartile ranges of sorted[(size_t)(k * 0.25)] and sorted[(size_t)(k * 0.75)] and the extremes beyond 4 population
+ * deviations of the mean (0 when k == 0); behavioral = 0.5 when k < 3, 0 when the population variance is below DBL_EPSILON, 0.8
+ * when the lag-1 autocorrelation exceeds 0.95 in magnitude, else 1; overall = the mean of the four.  length == 0: every figure 0,
+ * is_constant false, and true.  Every sum runs left to right from 0.0 as the source's, so the figures equal the reference's bit
+ * for bit.  +-inf are ordinary values.  A NaN among the valid values: false, COMPUTATION_ERROR "Invalid
+ * input: a value is NaN" (the source leaves that answer to its sort's internals).  NULL `values` or `out_result`: NULL_POINTER.
+ * Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_data_quality(const double *values,
+                            const uint64_t *validity,
+                            size_t length,
+                            struct DataQualityResult *out_result,
+                            struct AnofoxError *out_error);
+
 /* Values with a validity bitmask (bit i of word i / 64), the reference's FilledValuesResult: sizeof == 24. */
 typedef struct FilledValuesResult {
     double *values;
@@ -630,6 +660,41 @@ bool anofox_hip_stats_device(const double *y,
                              double *out_fp,
                              void *stream,
                              struct AnofoxError *out_error);
+
+/*
+ * Data quality of `n_series` series in one GPU pass (per series the semantics of anofox_ts_data_quality).  Replaces the reference's
+ * one FFI call per group.  `validity` may be NULL, and so may validity[i] (all valid).  out_results is DataQualityResult[n_series],
+ * out_status int32[n_series] (may be NULL): 0, or 2 for a series with a NaN among its valid values -- its five scores are NaN, its
+ * n_missing, n_gaps and is_constant are set.  No other per-series failure exists; the return value is false only for batch-level
+ * failures (NULL pointers, no GPU), also reported through `out_batch_error`.  Runs on the calling thread's current device
+ * (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_quality_batch(const double *const *values,
+                              const uint64_t *const *validity,
+                              const size_t *lengths,
+                              size_t n_series,
+                              struct DataQualityResult *out_results,
+                              int32_t *out_status,
+                              struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block, e.g. the output of anofox_hip_prepare_device: y[t * ld + s] (fp64, t < t_rows),
+ * `valid` (uint8 [t_rows x ld], 0 = NULL; may be NULL), lengths[n_series] (int32; a length above t_rows is cut to it); the outputs
+ * are device pointers.  out_fp is fp64 [5 x ld], the scores in struct order; out_int is int64 [4 x ld]: n_gaps, n_missing,
+ * is_constant as 0 / 1, status (0 or 2).  Columns s >= n_series are left untouched.  One wavefront per series: a series of at most
+ * 2,048 rows is sorted in LDS, a longer one in a workspace in global memory that the call allocates (slower, the same figures).
+ * The same bits on every run and through every entry.  Runs on `stream` (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_quality_device(const double *y,
+                               const uint8_t *valid,
+                               size_t ld,
+                               const int32_t *lengths,
+                               size_t n_series,
+                               size_t t_rows,
+                               double *out_fp,
+                               int64_t *out_int,
+                               void *stream,
+                               struct AnofoxError *out_error);
 
 /* What anofox_hip_prepare_device / _batch run, in this fixed order: gaps, trim, fill.  Zero everywhere is "copy the rows". */
 typedef struct AnofoxHipPrepOptions {
