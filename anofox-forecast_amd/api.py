@@ -3129,3 +3129,100 @@ def ts_backtest_native(group, date, value, horizon=7, folds=5, params=None, metr
 
 _ts_backtest_native = ts_backtest_native
 _anofox_fcst_ts_backtest_native = ts_backtest_native
+
+
+# --------------------------------------------------------------------------------------------
+# The same operator with the fold loop on the device (anofox_hip_backtest_batch)
+# --------------------------------------------------------------------------------------------
+def backtest_batch(series, opts, folds, metric="rmse"):
+    """anofox_hip_backtest_batch: the whole walk-forward backtest of `series` (sorted, without NULLs) in one call -- pack, expand on
+    the device, ONE batch run of the len(series) * len(folds) pairs, collect, copy back.  `folds` is the table of
+    backtest_fold_bounds.  Pair p = s * F + f is series s in fold index f.
+
+    Returns ({"n_rows", "status": int32 [n_pairs]; "model_name": list [n_pairs] ("" unless status is 0); "yhat", "lower", "upper",
+    "actual": fp64 [n_pairs, h]; "scores": fp64 [F]}, batch_error).  A refused option block (INVALID_MODEL for "ETS:AAA") is the
+    batch error and every pair has 0 rows."""
+    L = _lib.load()
+    n, F, h = len(series), len(folds), max(int(opts.horizon), 0)
+    arrs = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+    tab = _lib.make_folds(folds)
+    n_pairs = n * F
+    out = {"n_rows": np.zeros(n_pairs, dtype=np.int32), "status": np.full(n_pairs, _lib.INTERNAL_ERROR, dtype=np.int32),
+           "yhat": np.full((n_pairs, h), np.nan), "lower": np.full((n_pairs, h), np.nan), "upper": np.full((n_pairs, h), np.nan),
+           "actual": np.full((n_pairs, h), np.nan), "scores": np.full(F, np.nan)}
+    names = ((C.c_char * 64) * max(n_pairs, 1))()
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_backtest_batch(ptrs, lens, n, C.byref(opts), tab, F, str(metric).encode(), out["n_rows"].ctypes.data,
+                                     out["status"].ctypes.data, names, out["yhat"].ctypes.data, out["lower"].ctypes.data,
+                                     out["upper"].ctypes.data, out["actual"].ctypes.data, out["scores"].ctypes.data, C.byref(err))
+    out["model_name"] = [names[p].value.decode() for p in range(n_pairs)]
+    return out, {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+
+
+def ts_backtest_native_gpu(group, date, value, horizon=7, folds=5, params=None, metric="rmse", group_name="id", date_name="date"):
+    """ts_backtest_native with the fold loop on the device: the same signature, columns and row order, the same bits.  Rows are
+    grouped and sorted on the host ONCE per group; every group's sorted values go to backtest_batch, which cuts the folds out of the
+    resident block, fits all (group, fold) pairs in one batch run, matches the forecasts to the test rows and scores the folds
+    there."""
+    p = params or {}
+
+    def as_int(key, default):
+        try:
+            return int(str(p[key])) if p.get(key) is not None else default
+        except ValueError:
+            return default
+    method = str(p["method"]) if p.get("method") is not None else "AutoETS"
+    spec = str(p["model"]) if p.get("model") is not None else ""
+    window_type = str(p["window_type"]) if p.get("window_type") is not None else "expanding"
+    clip = str(p.get("clip_horizon", "false")).lower() in ("true", "1", "yes")
+    dates = np.asarray(date)
+    kind = _date_kind(dates)
+    us = _to_micros(dates, kind)
+    if kind == "TIMESTAMP":
+        us = (us // 1_000_000) * 1_000_000
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), bool)
+    grp = np.asarray(group, dtype=object)
+    val = np.ma.filled(np.ma.asarray(value, dtype=object), None) if np.ma.isMaskedArray(value) else np.asarray(value, dtype=object)
+    order, rows = [], {}
+    for i in range(len(grp)):
+        if null_date[i] or val[i] is None:
+            continue
+        k = "__NULL__" if grp[i] is None else grp[i]
+        if k not in rows:
+            rows[k] = []
+            order.append(k)
+        rows[k].append(i)
+    kept = np.array([i for k in order for i in rows[k]], dtype=np.int64)
+    bounds = _lib.backtest_folds(len(np.unique(us[kept])) if len(kept) else 0, horizon, folds, window_type, as_int("min_train_size", 1),
+                                 as_int("gap", 0), as_int("embargo", 0), as_int("initial_train_size", -1), as_int("skip_length", -1), clip)
+    sorted_rows, series = [], []
+    for k in order:
+        idx = np.array(rows[k])
+        idx = idx[np.argsort(us[idx], kind="stable")]
+        sorted_rows.append(idx)
+        series.append(np.array([float(val[i]) for i in idx], dtype=np.float64))
+    cols = {c: [] for c in ("fold_id", group_name, date_name, "yhat", "actual", "error", "abs_error", "yhat_lower", "yhat_upper",
+                            "model_name", "fold_metric_score")}
+    F = len(bounds)
+    if F and series:
+        opts = _lib.make_options(method + (":" + spec if spec else ""), int(horizon), confidence_level=0.0, auto_detect=False)
+        res, berr = backtest_batch(series, opts, bounds, metric)
+        if berr["ok"]:
+            for f, (fid, _tr0, _tr1, te0, _te1) in enumerate(bounds):
+                for s, k in enumerate(order):
+                    q = s * F + f
+                    for hh in range(int(res["n_rows"][q])):
+                        yhat, actual = res["yhat"][q, hh], res["actual"][q, hh]
+                        cols["fold_id"].append(fid); cols[group_name].append(None if k == "__NULL__" else k)
+                        cols[date_name].append(int(us[sorted_rows[s][te0 + hh]])); cols["yhat"].append(yhat); cols["actual"].append(actual)
+                        cols["error"].append(yhat - actual); cols["abs_error"].append(abs(yhat - actual))
+                        cols["yhat_lower"].append(res["lower"][q, hh]); cols["yhat_upper"].append(res["upper"][q, hh])
+                        cols["model_name"].append(res["model_name"][q] if res["model_name"][q] else method)
+                        cols["fold_metric_score"].append(res["scores"][f])
+    cols["fold_id"] = np.array(cols["fold_id"], dtype=np.int64)
+    cols[date_name] = _from_micros(np.array(cols[date_name], dtype=np.int64), kind, dates.dtype)
+    for c in ("yhat", "actual", "error", "abs_error", "yhat_lower", "yhat_upper", "fold_metric_score"):
+        cols[c] = np.array(cols[c], dtype=np.float64)
+    return cols

@@ -6129,3 +6129,264 @@ bool anofox_ts_forecast_exog(const double *values, const uint64_t *validity, siz
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Walk-forward backtest on a resident block (_ts_backtest_native: ts_backtest_native.cpp:623-711, 768-880, 280-373; backtest.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t BT_POS_MAX = (int64_t)INT32_MAX - 1;       // a position at or above it lies behind every block (t_rows <= 2^30)
+
+// the host fold table -> the kernels' int32 table; *t_train = the longest training window (at least 1)
+bool backtest_fold_table(const AnofoxHipFold *folds, size_t n_folds, std::vector<BacktestFoldPos> *out, size_t *t_train, AnofoxError *err)
+{
+    if (n_folds > 0 && !folds) { set_error(err, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_folds > (size_t)INT32_MAX) { set_error(err, INVALID_INPUT, "Invalid input: too many folds"); return false; }
+    size_t longest = 1;
+    if (out) out->resize(n_folds);
+    for (size_t f = 0; f < n_folds; f++) {
+        const AnofoxHipFold &q = folds[f];
+        if (q.train_start < 0 || q.train_end < 0 || q.test_start < 0 || q.test_end < 0) {
+            set_error(err, INVALID_INPUT, "Invalid input: a fold position is negative");
+            return false;
+        }
+        if (q.train_start <= q.train_end) {
+            const int64_t w = q.train_end - q.train_start + 1;
+            if (w > (int64_t)(1u << 30)) { set_error(err, INVALID_INPUT, "Invalid input: a training window is too long"); return false; }
+            longest = std::max(longest, (size_t)w);
+        }
+        if (out)
+            (*out)[f] = BacktestFoldPos{(int32_t)std::min(q.train_start, BT_POS_MAX), (int32_t)std::min(q.train_end, BT_POS_MAX),
+                                        (int32_t)std::min(q.test_start, BT_POS_MAX), (int32_t)std::min(q.test_end, BT_POS_MAX)};
+    }
+    if (t_train) *t_train = longest;
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+static_assert(sizeof(AnofoxHipFold) == 40 && offsetof(AnofoxHipFold, test_end) == 32, "AnofoxHipFold layout");
+
+size_t anofox_hip_backtest_folds(int64_t n_dates, int64_t horizon, int64_t folds, int window_type, int64_t min_train_size, int64_t gap,
+                                 int64_t embargo, int64_t initial_train_size, int64_t skip_length, bool clip_horizon, AnofoxHipFold *out_folds,
+                                 size_t capacity)
+{
+    return backtest_folds(n_dates, horizon, folds, window_type, min_train_size, gap, embargo, initial_train_size, skip_length, clip_horizon,
+                          out_folds, capacity);
+}
+
+bool anofox_hip_backtest_sizes(const AnofoxHipFold *folds, size_t n_folds, size_t n_series, size_t *t_train, size_t *n_pairs, size_t *ld_pairs,
+                               AnofoxError *out_error)
+{
+    clear_error(out_error);
+    size_t longest = 1;
+    if (!backtest_fold_table(folds, n_folds, nullptr, &longest, out_error)) return false;
+    if (n_series > (size_t)INT32_MAX || (n_folds > 0 && n_series > (size_t)INT32_MAX / n_folds)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: more than 2^31 - 1 (series, fold) pairs");
+        return false;
+    }
+    const size_t np = n_series * n_folds;
+    if (t_train) *t_train = longest;
+    if (n_pairs) *n_pairs = np;
+    if (ld_pairs) *ld_pairs = std::max<size_t>((np + 63) / 64 * 64, 64);
+    return true;
+}
+
+bool anofox_hip_backtest_expand_device(const double *y, size_t ld_src, const int32_t *lengths, size_t n_series, size_t t_rows,
+                                       const AnofoxHipFold *folds, size_t n_folds, size_t t_train, double *y_out, size_t ld_pairs,
+                                       int32_t *len_pairs, int32_t *n_test, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!y_out || !len_pairs || !n_test || (n_series > 0 && (!y || !lengths))) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (ld_src < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld_src is smaller than n_series"); return false; }
+    if (t_rows > (size_t)(1u << 30)) { set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large"); return false; }
+    std::vector<BacktestFoldPos> tab;
+    size_t need_t = 1, np = 0, need_ld = 64;
+    if (!backtest_fold_table(folds, n_folds, &tab, nullptr, out_error)) return false;
+    if (!anofox_hip_backtest_sizes(folds, n_folds, n_series, &need_t, &np, &need_ld, out_error)) return false;
+    if (ld_pairs != need_ld || t_train < need_t) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: t_train or ld_pairs is not what anofox_hip_backtest_sizes returns");
+        return false;
+    }
+    if (!device_ready(out_error)) return false;
+    hipStream_t st = (hipStream_t)stream;
+    BacktestFoldPos *d_tab = nullptr;
+    try {
+        (void)hipGetLastError();
+        d_tab = dalloc<BacktestFoldPos>(n_folds);
+        if (n_folds) HIPCHECK(hipMemcpyAsync(d_tab, tab.data(), n_folds * sizeof(BacktestFoldPos), hipMemcpyHostToDevice, st));
+        BacktestArgs a{};
+        a.y = y; a.ld_src = ld_src; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+        a.folds = d_tab; a.n_folds = (int)std::max<size_t>(n_folds, 1); a.n_pairs = (int)np; a.ld_pairs = ld_pairs;
+        a.t_train = t_train; a.y_out = y_out; a.len_pairs = len_pairs; a.n_test = n_test;
+        launch_backtest_expand(a, st);
+        LAUNCHCHECK("backtest expand");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(d_tab, true);
+    } catch (const HipFail &f) {
+        dev_free(d_tab, false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_backtest_collect_device(const double *y, size_t ld_src, size_t n_series, size_t t_rows, const AnofoxHipFold *folds,
+                                        size_t n_folds, const int32_t *n_test, const int32_t *status, const double *yhat, const double *lower,
+                                        const double *upper, size_t horizon, const char *metric, double *actual, double *error,
+                                        double *abs_error, uint8_t *valid, int32_t *n_rows, double *scores, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::vector<BacktestFoldPos> tab;
+    size_t np = 0;
+    if (!backtest_fold_table(folds, n_folds, &tab, nullptr, out_error)) return false;
+    if (!anofox_hip_backtest_sizes(folds, n_folds, n_series, nullptr, &np, nullptr, out_error)) return false;
+    if (np > 0 && (!y || !n_test || !status || !yhat || !actual || !error || !abs_error || !n_rows)) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (ld_src < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld_src is smaller than n_series"); return false; }
+    if (t_rows > (size_t)(1u << 30)) { set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large"); return false; }
+    if (horizon < 1 || horizon > (size_t)(1u << 30) || (double)np * (double)horizon >= 256.0 * 2147483647.0) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: horizon must be at least 1 (and n_pairs x horizon below 2^39)");
+        return false;
+    }
+    if (n_folds == 0) return true;
+    if (!device_ready(out_error)) return false;
+    hipStream_t st = (hipStream_t)stream;
+    BacktestFoldPos *d_tab = nullptr;
+    try {
+        (void)hipGetLastError();
+        d_tab = dalloc<BacktestFoldPos>(n_folds);
+        HIPCHECK(hipMemcpyAsync(d_tab, tab.data(), n_folds * sizeof(BacktestFoldPos), hipMemcpyHostToDevice, st));
+        BacktestArgs a{};
+        a.y = y; a.ld_src = ld_src; a.n_series = (int)n_series; a.t_rows = t_rows;
+        a.folds = d_tab; a.n_folds = (int)n_folds; a.n_pairs = (int)np;
+        a.h = (int)horizon; a.n_test = (int32_t *)n_test; a.status = status; a.yhat = yhat; a.lower = lower; a.upper = upper;
+        a.actual = actual; a.error = error; a.abs_error = abs_error; a.valid = valid; a.n_rows = n_rows;
+        a.metric = backtest_metric_code(metric); a.scores = scores;
+        launch_backtest_collect(a, st);
+        LAUNCHCHECK("backtest collect");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(d_tab, true);
+    } catch (const HipFail &f) {
+        dev_free(d_tab, false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_backtest_batch(const double *const *values, const size_t *lengths, size_t n_series, const ForecastOptions *options,
+                               const AnofoxHipFold *folds, size_t n_folds, const char *metric, int32_t *out_n_rows, int32_t *out_status,
+                               char (*out_model_names)[64], double *out_yhat, double *out_lower, double *out_upper, double *out_actual,
+                               double *out_scores, AnofoxError *out_batch_error)
+{
+    clear_error(out_batch_error);
+    if (!options || (n_series > 0 && (!values || !lengths))) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+    size_t t_train = 1, np = 0, ld_pairs = 64, T = 1;
+    if (!anofox_hip_backtest_sizes(folds, n_folds, n_series, &t_train, &np, &ld_pairs, out_batch_error)) return false;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        T = std::max(T, lengths[s]);
+    }
+    if (options->horizon < 1) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: horizon must be at least 1"); return false; }
+    if (np == 0) return true;
+    const size_t h = (size_t)options->horizon, nh = np * h, ld_src = (n_series + 63) / 64 * 64;
+    AnofoxHipBatch *b = nullptr;
+    if (!anofox_hip_batch_create(np, t_train, options, &b, out_batch_error)) return false;      // e.g. "ETS:AAA": INVALID_MODEL, no rows
+    double *d_src = nullptr, *d_exp = nullptr, *d_fp = nullptr, *d_work = nullptr;
+    int32_t *d_len = nullptr, *d_int = nullptr;
+    bool ok = true;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_src, (void *)d_exp, (void *)d_fp, (void *)d_work, (void *)d_len, (void *)d_int}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    // ONE arena of results, so that one copy brings them back: yhat, lower, upper, actual, the scores, then error and abs_error
+    // (fp64), then n_rows, status, model_code [np] and, not copied, len_pairs and n_test [ld_pairs] (int32)
+    const size_t n_fp_back = 4 * nh + n_folds;
+    std::vector<double> back(n_fp_back + (3 * np + 1) / 2);      // the doubles that go back, then the three int32 arrays
+    try {
+        DeviceGuard guard(b->dev);
+        hipStream_t st = b->own_stream;
+        {
+            std::vector<double> yb(T * ld_src, 0.0);
+            std::vector<int32_t> len(ld_src, 0);
+            for (size_t s = 0; s < n_series; s++) {
+                len[s] = (int32_t)lengths[s];
+                for (size_t t = 0; t < lengths[s]; t++) yb[t * ld_src + s] = values[s][t];
+            }
+            d_src = dalloc<double>(T * ld_src); d_len = dalloc<int32_t>(ld_src);
+            HIPCHECK(hipMemcpy(d_src, yb.data(), T * ld_src * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld_src * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        try { d_exp = dalloc<double>(t_train * ld_pairs); }
+        catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_batch_error, COMPUTATION_ERROR, "Computation error: the expanded backtest block of " + std::to_string(t_train) + " x " +
+                      std::to_string(ld_pairs) + " values needs " + std::to_string(t_train * ld_pairs * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            d_fp = dalloc<double>(n_fp_back + (3 * np + 1) / 2);
+            d_int = dalloc<int32_t>(2 * ld_pairs);
+            d_work = dalloc<double>(2 * nh);
+            int32_t *d_rows = (int32_t *)(d_fp + n_fp_back), *d_stat = d_rows + np, *d_code = d_rows + 2 * np, *d_lenp = d_int, *d_ntest = d_int + ld_pairs;
+            double *d_yh = d_fp, *d_lo = d_fp + nh, *d_hi = d_fp + 2 * nh, *d_act = d_fp + 3 * nh, *d_sc = d_fp + 4 * nh, *d_err = d_work,
+                   *d_abs = d_work + nh;
+            ok = anofox_hip_backtest_expand_device(d_src, ld_src, d_len, n_series, T, folds, n_folds, t_train, d_exp, ld_pairs, d_lenp, d_ntest, st,
+                                                   out_batch_error) &&
+                 anofox_hip_batch_set_device_block(b, d_exp, ld_pairs, d_lenp, out_batch_error) && anofox_hip_batch_run(b, nullptr, out_batch_error);
+            if (ok) {
+                HIPCHECK(hipStreamSynchronize(b->last_stream));
+                b->quiesced = true;
+                ok = anofox_hip_backtest_collect_device(d_src, ld_src, n_series, T, folds, n_folds, d_ntest, b->d_status, b->d_yhat, b->d_lo, b->d_hi, h,
+                                                        metric, d_act, d_err, d_abs, nullptr, d_rows, d_sc, st, out_batch_error);
+            }
+            if (ok) {
+                HIPCHECK(hipMemcpyAsync(d_yh, b->d_yhat, nh * sizeof(double), hipMemcpyDeviceToDevice, st));
+                HIPCHECK(hipMemcpyAsync(d_lo, b->d_lo, nh * sizeof(double), hipMemcpyDeviceToDevice, st));
+                HIPCHECK(hipMemcpyAsync(d_hi, b->d_hi, nh * sizeof(double), hipMemcpyDeviceToDevice, st));
+                HIPCHECK(hipMemcpyAsync(d_stat, b->d_status, np * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+                HIPCHECK(hipMemcpyAsync(d_code, b->d_model_code, np * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+                HIPCHECK(hipStreamSynchronize(st));
+                HIPCHECK(hipMemcpy(back.data(), d_fp, back.size() * sizeof(double), hipMemcpyDeviceToHost));
+            }
+        }
+        release(ok);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        anofox_hip_batch_destroy(b);
+        return false;
+    }
+    if (ok) {
+        const double *fp = back.data();
+        const int32_t *rows = (const int32_t *)(fp + n_fp_back), *stat = rows + np, *code = rows + 2 * np;
+        for (size_t p = 0; p < np; p++) {
+            const int32_t st_p = stat[p] == STATUS_NOT_COMPUTED ? (int32_t)INTERNAL_ERROR : stat[p];
+            if (out_n_rows) out_n_rows[p] = rows[p];
+            if (out_status) out_status[p] = st_p;
+            if (out_model_names) {
+                out_model_names[p][0] = 0;
+                if (st_p == 0) anofox_hip_batch_model_name(b, p, code[p], out_model_names[p]);
+            }
+        }
+        if (out_yhat) std::memcpy(out_yhat, fp, nh * sizeof(double));
+        if (out_lower) std::memcpy(out_lower, fp + nh, nh * sizeof(double));
+        if (out_upper) std::memcpy(out_upper, fp + 2 * nh, nh * sizeof(double));
+        if (out_actual) std::memcpy(out_actual, fp + 3 * nh, nh * sizeof(double));
+        if (out_scores) std::memcpy(out_scores, fp + 4 * nh, n_folds * sizeof(double));
+    } else if (out_batch_error && out_batch_error->code == SUCCESS) {
+        set_error(out_batch_error, INTERNAL_ERROR, "Internal error: device batch failed");
+    }
+    anofox_hip_batch_destroy(b);
+    return ok;
+}
+
+} // extern "C"

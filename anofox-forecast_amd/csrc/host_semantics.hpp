@@ -184,6 +184,50 @@ inline void set_error(AnofoxError *e, int code, const std::string &msg)
     e->message[n] = 0;
 }
 
+// ComputeFoldBoundaries (ts_backtest_native.cpp:623-711): position-based fold boundaries over the number of distinct dates of the
+// whole input, all inclusive.  Writes the first `capacity` folds to `out` (may be null) and returns how many there are.  The
+// reference's unsigned arithmetic is kept where it matters: no training window starts before position 0, and a fold whose test
+// window does not fit ends the list.  window_type 0 is the expanding window; every other value cuts the window to min_train_size.
+inline size_t backtest_folds(int64_t n_dates, int64_t horizon, int64_t folds, int window_type, int64_t min_train_size, int64_t gap,
+                             int64_t embargo, int64_t initial_train_size, int64_t skip_length, bool clip_horizon, AnofoxHipFold *out,
+                             size_t capacity)
+{
+    size_t n = 0;
+    if (n_dates < 2) return 0;
+    int64_t init;
+    if (initial_train_size > 0) init = initial_train_size;
+    else {
+        const int64_t needed = horizon * folds;
+        init = n_dates > needed ? n_dates - needed : 1;
+    }
+    const int64_t skip = skip_length > 0 ? skip_length : horizon;
+    int64_t prev_test_end = 0;
+    for (int64_t fold = 0; fold < folds; fold++) {
+        const int64_t train_end = init - 1 + fold * skip;
+        const int64_t test_start = train_end + 1 + gap;
+        int64_t test_end = test_start + horizon - 1;
+        if (clip_horizon && test_end >= n_dates) test_end = n_dates - 1;
+        if (!(clip_horizon ? test_start < n_dates : test_end < n_dates)) break;
+        int64_t train_start = 0;
+        if (window_type != 0) train_start = train_end + 1 >= min_train_size ? train_end + 1 - min_train_size : 0;
+        if (fold > 0 && embargo > 0 && n > 0) train_start = std::max(train_start, prev_test_end + 1 + embargo);
+        if (out && n < capacity) out[n] = AnofoxHipFold{fold + 1, train_start, train_end, test_start, test_end};
+        prev_test_end = test_end;
+        n++;
+    }
+    return n;
+}
+
+// the fold metric's name -> its code in kernels.hpp (BT_MAE .. BT_RMSE); "rmse" and every unknown name are 7 (:280-373)
+inline int backtest_metric_code(const char *metric)
+{
+    static const char *const names[7] = {"mae", "mse", "mape", "smape", "bias", "r2", "coverage"};
+    if (metric)
+        for (int i = 0; i < 7; i++)
+            if (std::strcmp(metric, names[i]) == 0) return i;
+    return 7;
+}
+
 inline std::string cstr_field(const char *p, size_t cap)
 {
     size_t n = 0;

@@ -375,6 +375,31 @@ size_t quality_work_stride(size_t t_rows);       // words per workspace slice (0
 int quality_work_waves(int n_series);
 void launch_quality(const QualityArgs &, hipStream_t);
 
+// Walk-forward backtest on a resident block (_ts_backtest_native's folds, cut by position; backtest.hip).  Pair p = s * n_folds + f
+// is series s in fold f; ld_pairs is n_pairs rounded up to 64.
+enum { BT_MAE = 0, BT_MSE = 1, BT_MAPE = 2, BT_SMAPE = 3, BT_BIAS = 4, BT_R2 = 5, BT_COVERAGE = 6, BT_RMSE = 7 };
+struct BacktestFoldPos { int32_t train_start, train_end, test_start, test_end; };      // inclusive positions, all >= 0
+struct BacktestArgs {
+    const double *y; size_t ld_src;              // the source block [t_rows x ld_src]
+    const int32_t *len; int n_series;            // [n_series]; a length above t_rows is cut to it
+    size_t t_rows;
+    const BacktestFoldPos *folds; int n_folds;   // [n_folds], in device memory
+    int n_pairs; size_t ld_pairs;
+    // expand
+    size_t t_train; double *y_out;               // [t_train x ld_pairs]
+    int32_t *len_pairs, *n_test;                 // [ld_pairs]
+    // collect and score
+    int h;
+    const int32_t *status;                       // [n_pairs] of the batch run
+    const double *yhat, *lower, *upper;          // [n_pairs x h] series-major; lower / upper may be null (coverage is then NaN)
+    double *actual, *error, *abs_error;          // [n_pairs x h]
+    uint8_t *valid;                              // null, or [n_pairs x h]: 1 where the row exists
+    int32_t *n_rows;                             // [n_pairs]
+    int metric; double *scores;                  // BT_*; null, or [n_folds]
+};
+void launch_backtest_expand(const BacktestArgs &, hipStream_t);
+void launch_backtest_collect(const BacktestArgs &, hipStream_t);     // collect, then (scores != null) the fold scores
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

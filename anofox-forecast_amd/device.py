@@ -206,6 +206,70 @@ def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | 
             "apply_status": apply_status, "sorted": srt}
 
 
+def backtest_block(y: torch.Tensor, lengths: torch.Tensor, opts: _lib.ForecastOptions, folds, *, n_series: int | None = None,
+                   metric: str = "rmse", stream: torch.cuda.Stream | None = None) -> dict:
+    """The walk-forward backtest of a resident block, no host copy: anofox_hip_backtest_expand_device -> DeviceBatch(n_pairs, t_train,
+    opts).set_block -> run -> anofox_hip_backtest_collect_device.
+
+    y [t_rows, ld] fp64 time-major without NULLs, lengths int32 [>= n_series], on one HIP device, contiguous; folds is the table of
+    api.backtest_fold_bounds / lib.backtest_folds ([(fold_id, train_start, train_end, test_start, test_end)], positions inclusive, the
+    same for every series).  Any ForecastOptions block is allowed.  Pair p = s * F + f is series s in fold index f, so every
+    [n_pairs, h] result viewed as [n_series, F * h] is the series-major block of one group per series that conformal_block(...,
+    series_major=True) and anofox_hip_metrics_device(stride_s = F * h, stride_t = 1) take as it lies.
+
+    Returns {"yhat", "lower", "upper" (views of the batch's results), "actual", "error", "abs_error": fp64 [n_pairs, h], NaN in the
+    last three where the row does not exist; "valid": uint8 [n_pairs, h]; "n_rows", "status", "model_code": int32 [n_pairs];
+    "scores": fp64 [F], the fold metric (backtest_metrics.backtest_metric's bits); "len_pairs", "n_test": int32 [ld_pairs]; "train":
+    the expanded block [t_train, ld_pairs]; "batch": the DeviceBatch (model names: batch.model_name(code, p)); "n_pairs",
+    "n_folds", "t_train"}."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    F = len(folds)
+    tab = _lib.make_folds(folds)
+    t_train, n_pairs, ld_pairs = _lib.backtest_sizes(tab, F, n)
+    h = int(opts.horizon)
+    try:
+        train = torch.empty((t_train, ld_pairs), dtype=torch.float64, device=dev)
+    except torch.cuda.OutOfMemoryError as e:
+        raise RuntimeError(f"the expanded backtest block of {t_train} x {ld_pairs} values needs {t_train * ld_pairs * 8} bytes of device "
+                           "memory") from e
+    len_pairs = torch.empty(ld_pairs, dtype=torch.int32, device=dev)
+    n_test = torch.empty(ld_pairs, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_backtest_expand_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, tab, F, t_train, train.data_ptr(), ld_pairs,
+                                             len_pairs.data_ptr(), n_test.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_backtest_expand_device failed: [{err.code}] {err.message.decode()}")
+    batch = DeviceBatch(n_pairs, t_train, opts, dev)
+    batch.set_block(train, len_pairs)
+    batch.run(st)
+    res = batch.results()
+    actual = torch.empty((n_pairs, h), dtype=torch.float64, device=dev)
+    error = torch.empty_like(actual)
+    abs_error = torch.empty_like(actual)
+    valid = torch.empty((n_pairs, h), dtype=torch.uint8, device=dev)
+    n_rows = torch.zeros(n_pairs, dtype=torch.int32, device=dev)
+    scores = torch.full((F,), float("nan"), dtype=torch.float64, device=dev)
+    ok = L.anofox_hip_backtest_collect_device(y.data_ptr(), ld, n, t_rows, tab, F, n_test.data_ptr(), res["status"].data_ptr(),
+                                              res["yhat"].data_ptr(), res["lower"].data_ptr(), res["upper"].data_ptr(), h,
+                                              str(metric).encode(), actual.data_ptr(), error.data_ptr(), abs_error.data_ptr(),
+                                              valid.data_ptr(), n_rows.data_ptr(), scores.data_ptr(), C.c_void_p(st.cuda_stream),
+                                              C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_backtest_collect_device failed: [{err.code}] {err.message.decode()}")
+    return {"yhat": res["yhat"], "lower": res["lower"], "upper": res["upper"], "actual": actual, "error": error, "abs_error": abs_error,
+            "valid": valid, "n_rows": n_rows, "status": res["status"], "model_code": res["model_code"], "scores": scores,
+            "len_pairs": len_pairs, "n_test": n_test, "train": train, "batch": batch, "n_pairs": n_pairs, "n_folds": F,
+            "t_train": t_train}
+
+
 class DeviceBatch:
     """anofox_hip_batch_* over torch-owned HBM."""
 

@@ -296,6 +296,15 @@ class ForecastOptionsExog(C.Structure):
     ]
 
 
+class AnofoxHipFold(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipFold: one fold of the backtest, inclusive row positions (40 bytes)."""
+    _fields_ = [(n, C.c_int64) for n in ("fold_id", "train_start", "train_end", "test_start", "test_end")]
+
+
+assert C.sizeof(AnofoxHipFold) == 40
+BACKTEST_WINDOWS = {"expanding": 0, "fixed": 1, "sliding": 2}      # window_type of anofox_hip_backtest_folds
+
+
 assert C.sizeof(ExogenousRegressor) == 32 and C.sizeof(ExogenousData) == 16 and C.sizeof(ForecastOptionsExog) == 192
 MODEL_CODE_ARIMAX = 50             # include/anofox_fcst_hip.h: model_code of a series the ARIMAX path forecast
 
@@ -340,6 +349,8 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_conformal_predict_adaptive", "anofox_ts_conformal_predict_asymmetric", "anofox_ts_mean_interval_width",
     "anofox_ts_conformal_learn", "anofox_ts_conformal_apply", "anofox_ts_conformal_coverage", "anofox_ts_conformal_evaluate",
     "anofox_free_conformal_result", "anofox_free_conformal_multi_result", "anofox_free_calibration_profile", "anofox_free_prediction_intervals",
+    "anofox_hip_backtest_folds", "anofox_hip_backtest_sizes", "anofox_hip_backtest_expand_device", "anofox_hip_backtest_collect_device",
+    "anofox_hip_backtest_batch",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -570,6 +581,23 @@ def load():
     L.anofox_free_conformal_multi_result.argtypes = [P(ConformalMultiResultFFI)]
     L.anofox_free_calibration_profile.argtypes = [P(CalibrationProfileFFI)]
     L.anofox_free_prediction_intervals.argtypes = [P(PredictionIntervalsFFI)]
+    # block 5: the walk-forward backtest
+    L.anofox_hip_backtest_folds.restype = C.c_size_t
+    L.anofox_hip_backtest_folds.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_bool, C.c_void_p, C.c_size_t]
+    L.anofox_hip_backtest_sizes.restype = C.c_bool
+    L.anofox_hip_backtest_sizes.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
+    L.anofox_hip_backtest_expand_device.restype = C.c_bool
+    L.anofox_hip_backtest_expand_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_backtest_collect_device.restype = C.c_bool
+    L.anofox_hip_backtest_collect_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_char_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_backtest_batch.restype = C.c_bool
+    L.anofox_hip_backtest_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(ForecastOptions), C.c_void_p, C.c_size_t, C.c_char_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -609,6 +637,38 @@ def make_options(model, horizon, *, ets_model="", seasonal_period=0, confidence_
     o.seasonal_periods_str = seasonal_periods_str.encode()[:63]
     o.model_pool = model_pool.encode()[:31]
     return o
+
+
+def make_folds(folds):
+    """AnofoxHipFold array from [(fold_id, train_start, train_end, test_start, test_end)] (api.backtest_fold_bounds) or from such an array."""
+    if isinstance(folds, C.Array) and folds._type_ is AnofoxHipFold:
+        return folds
+    arr = (AnofoxHipFold * max(len(folds), 1))()
+    for k, f in enumerate(folds):
+        arr[k] = AnofoxHipFold(*[int(v) for v in f])
+    return arr
+
+
+def backtest_folds(n_dates, horizon, folds, window_type="expanding", min_train_size=1, gap=0, embargo=0, initial_train_size=-1,
+                   skip_length=-1, clip_horizon=False):
+    """anofox_hip_backtest_folds: the fold table as [(fold_id, train_start, train_end, test_start, test_end)] (host only, no device)."""
+    L = load()
+    code = BACKTEST_WINDOWS.get(window_type, 1) if isinstance(window_type, str) else int(window_type)
+    args = (int(n_dates), int(horizon), int(folds), code, int(min_train_size), int(gap), int(embargo), int(initial_train_size),
+            int(skip_length), bool(clip_horizon))
+    n = L.anofox_hip_backtest_folds(*args, None, 0)
+    arr = (AnofoxHipFold * max(n, 1))()
+    L.anofox_hip_backtest_folds(*args, arr, n)
+    return [(f.fold_id, f.train_start, f.train_end, f.test_start, f.test_end) for f in arr[:n]]
+
+
+def backtest_sizes(folds, n_folds, n_series):
+    """anofox_hip_backtest_sizes -> (t_train, n_pairs, ld_pairs)."""
+    t, n, ld = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    err = AnofoxError()
+    if not load().anofox_hip_backtest_sizes(folds, n_folds, n_series, C.byref(t), C.byref(n), C.byref(ld), C.byref(err)):
+        raise ValueError(f"anofox_hip_backtest_sizes failed: [{err.code}] {err.message.decode()}")
+    return t.value, n.value, ld.value
 
 
 def make_prep_options(gaps=False, frequency_micros=0, frequency_type="FIXED", trim="none", fill="none", fill_value=0.0):

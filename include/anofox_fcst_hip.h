@@ -1517,6 +1517,142 @@ const uint64_t *const *anofox_hip_ingest_validity(const AnofoxHipIngest *ingest)
 bool anofox_hip_batch_pack_ingest(AnofoxHipBatch *batch, const AnofoxHipIngest *ingest,
                                   struct AnofoxError *out_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 5: the walk-forward backtest of _ts_backtest_native on the device    */
+/* ------------------------------------------------------------------------- */
+/* One fold of ComputeFoldBoundaries (ts_backtest_native.cpp:623-711): inclusive row positions, the same for every series. */
+typedef struct AnofoxHipFold {
+    int64_t fold_id;          /* 1-based, as the operator's fold_id column */
+    int64_t train_start, train_end;
+    int64_t test_start, test_end;
+} AnofoxHipFold;
+
+/*
+ * ComputeFoldBoundaries restated: the folds of `n_dates` distinct dates.  window_type: 0 expanding, 1 fixed, 2 sliding (both cut
+ * the training window to min_train_size rows); initial_train_size <= 0: n_dates - horizon * folds (at least 1); skip_length <= 0:
+ * horizon; embargo > 0 moves a later fold's train_start past the previous test window; clip_horizon cuts the last test windows
+ * to the data instead of dropping their folds.  Writes the first `capacity` folds to out_folds (may be NULL: count call) and
+ * returns their number.  Host only: no device is touched.
+ */
+size_t anofox_hip_backtest_folds(int64_t n_dates,
+                                 int64_t horizon,
+                                 int64_t folds,
+                                 int window_type,
+                                 int64_t min_train_size,
+                                 int64_t gap,
+                                 int64_t embargo,
+                                 int64_t initial_train_size,
+                                 int64_t skip_length,
+                                 bool clip_horizon,
+                                 AnofoxHipFold *out_folds,
+                                 size_t capacity);
+
+/*
+ * Sizes of the expanded block of `n_series` series under a fold table: pair p = s * n_folds + f is series s in fold index f,
+ * *n_pairs = n_series * n_folds, *ld_pairs = n_pairs rounded up to 64 (at least 64), *t_train = the longest training window,
+ * max_f(train_end_f - train_start_f + 1) (at least 1).  With this pair order the batch's series-major result [n_pairs x h] is, as
+ * it lies, the series-major block [n_series x n_folds * h] that anofox_hip_conformal_learn_device and anofox_hip_metrics_device
+ * (stride_s = n_folds * h, stride_t = 1) take with one group per series.  Fails with INVALID_INPUT when a position is negative or
+ * n_pairs exceeds 2^31 - 1.  The expanded block costs t_train * ld_pairs * 8 bytes.  Host only.
+ */
+bool anofox_hip_backtest_sizes(const AnofoxHipFold *folds,
+                               size_t n_folds,
+                               size_t n_series,
+                               size_t *t_train,
+                               size_t *n_pairs,
+                               size_t *ld_pairs,
+                               struct AnofoxError *out_error);
+
+/*
+ * Cuts every fold's training window out of a device-resident time-major block y[t * ld_src + s] (fp64, t < t_rows; the block holds
+ * no NULLs, as for anofox_hip_batch_set_device_block; lengths int32 [n_series], cut to t_rows): `folds` is a HOST array, t_train and
+ * ld_pairs are what anofox_hip_backtest_sizes returns (t_train may be larger).  A pair is live exactly when the operator keeps it
+ * (:785-790): train_end < len, test_start < len and train_start <= train_end (and test_start <= test_end).  For a live pair rows t < L = train_end - train_start
+ * + 1 of column p of y_out [t_train x ld_pairs] are y[(train_start + t) * ld_src + s], len_pairs[p] = L and n_test[p] =
+ * min(test_end, len - 1) - test_start + 1.  EVERYTHING else in y_out is 0.0 and both counts are 0: rows past L, dead pairs, the
+ * padding columns p >= n_pairs (len_pairs and n_test are int32 [ld_pairs]).  y_out and len_pairs are what
+ * anofox_hip_batch_create(n_pairs, t_train, ...) + anofox_hip_batch_set_device_block take: a dead pair is a series of length 0
+ * there (INSUFFICIENT_DATA).  No exogenous regressors; not sharded over devices.  Runs on `stream` (NULL: the null stream) on the
+ * calling thread's current device and returns after it has finished.
+ */
+bool anofox_hip_backtest_expand_device(const double *y,
+                                       size_t ld_src,
+                                       const int32_t *lengths,
+                                       size_t n_series,
+                                       size_t t_rows,
+                                       const AnofoxHipFold *folds,
+                                       size_t n_folds,
+                                       size_t t_train,
+                                       double *y_out,
+                                       size_t ld_pairs,
+                                       int32_t *len_pairs,
+                                       int32_t *n_test,
+                                       void *stream,
+                                       struct AnofoxError *out_error);
+
+/*
+ * After the batch has run: matches forecasts to test rows and scores the folds.  n_test is the expand entry's; status, yhat, lower,
+ * upper are the batch's device results (anofox_hip_batch_device_results: int32 [n_pairs], fp64 [n_pairs x horizon] series-major;
+ * lower and upper may be NULL, the coverage score is then NaN).  Row i of pair p exists when the pair is live, status[p] == 0 and
+ * i < n_test[p].  For an existing row actual = y[(test_start + i) * ld_src + s], error = yhat - actual, abs_error = |error|; every
+ * row that does not exist is NaN in all three blocks ([n_pairs x horizon]; the row filter of anofox_hip_metrics_device is
+ * drop_nan) and 0 in `valid` (uint8 [n_pairs x horizon], may be NULL: the mask anofox_hip_conformal_learn_device takes);
+ * n_rows[p] (int32 [n_pairs]) counts the existing rows.  scores (fp64 [n_folds], may be NULL) receives ComputeMetric (:280-373)
+ * of `metric` -- "mae", "mse", "mape", "smape", "bias", "r2", "coverage", "rmse"; every other name is rmse -- per fold over its
+ * existing rows in the operator's row order (series, then steps), every sum sequential in that order: the bits of the host
+ * route.  A fold without a row scores NaN.  horizon >= 1.  Runs on `stream` and returns after it has finished.
+ */
+bool anofox_hip_backtest_collect_device(const double *y,
+                                        size_t ld_src,
+                                        size_t n_series,
+                                        size_t t_rows,
+                                        const AnofoxHipFold *folds,
+                                        size_t n_folds,
+                                        const int32_t *n_test,
+                                        const int32_t *status,
+                                        const double *yhat,
+                                        const double *lower,
+                                        const double *upper,
+                                        size_t horizon,
+                                        const char *metric,
+                                        double *actual,
+                                        double *error,
+                                        double *abs_error,
+                                        uint8_t *valid,
+                                        int32_t *n_rows,
+                                        double *scores,
+                                        void *stream,
+                                        struct AnofoxError *out_error);
+
+/*
+ * The whole backtest of `n_series` series held on the host (values[i] points to lengths[i] values, sorted by date, no NULLs: the
+ * operator drops NULL rows at :534) -- what _ts_backtest_native's finalize would call instead of its serial loop over (fold, group)
+ * (:873-880): pack the block, expand, ONE batch run of the n_series * n_folds pairs, collect, one copy back.  Outputs, pair p =
+ * s * n_folds + f: out_n_rows and out_status int32 [n_pairs] (status: the ErrorCode of the pair's fit; a dead pair is
+ * INSUFFICIENT_DATA with 0 rows), out_model_names char [n_pairs][64] (anofox_hip_batch_model_name; empty unless status is 0),
+ * out_yhat, out_lower, out_upper, out_actual fp64 [n_pairs x horizon] (rows i >= out_n_rows[p]: actual is NaN), out_scores fp64
+ * [n_folds].  Any output may be NULL.  An option block that anofox_hip_batch_create refuses (e.g. a "Method:model" string:
+ * INVALID_MODEL) fails the call with that error and produces no row, as the host route does.  Limits: n_pairs <= 2^31 - 1; the
+ * expanded block costs t_train * ld_pairs * 8 bytes of device memory (a failed allocation is a COMPUTATION_ERROR that names the
+ * size); no exogenous regressors; runs on the calling thread's current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_backtest_batch(const double *const *values,
+                               const size_t *lengths,
+                               size_t n_series,
+                               const struct ForecastOptions *options,
+                               const AnofoxHipFold *folds,
+                               size_t n_folds,
+                               const char *metric,
+                               int32_t *out_n_rows,
+                               int32_t *out_status,
+                               char (*out_model_names)[64],
+                               double *out_yhat,
+                               double *out_lower,
+                               double *out_upper,
+                               double *out_actual,
+                               double *out_scores,
+                               struct AnofoxError *out_batch_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
