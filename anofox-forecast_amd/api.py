@@ -1289,6 +1289,90 @@ anofox_fcst_ts_data_quality_agg = ts_data_quality_agg      # ts_data_quality_agg
 
 
 # --------------------------------------------------------------------------------------------
+# seasonality analysis: anofox_hip_seasonality_batch and the mirrors of ts_detect_seasonality and ts_analyze_seasonality
+# --------------------------------------------------------------------------------------------
+def seasonality_batch(series, valids=None, max_period=0):
+    """anofox_hip_seasonality_batch over a list of 1-D arrays: one GPU pass for all series.  `valids[i]` (booleans, False = NULL,
+    dropped) may be None per series, as may the list; one `max_period` for all (<= 0: half of each series' length).  Per series a
+    dict: detected_periods (list, strongest first, at most 5), strengths and acf (lists of the same length), primary_period,
+    seasonal_strength, trend_strength, is_seasonal (seasonal_strength > 0.1) and status: 0, or 1 for fewer than 4 values (every
+    figure 0; the single entries and the SQL mirrors fail / give NULL there)."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks = None
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+    res = (_lib.AnofoxHipSeasonality * max(n, 1))()
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_seasonality_batch(vals, masks, lens.ctypes.data, n, int(max_period), res, status.ctypes.data, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    for i in range(n):
+        r = res[i]
+        k = int(r.n_periods)
+        out.append({"detected_periods": [int(p) for p in r.periods[:k]], "strengths": [float(v) for v in r.strengths[:k]],
+                    "acf": [float(v) for v in r.acf[:k]], "primary_period": int(r.primary_period),
+                    "seasonal_strength": float(r.seasonal_strength), "trend_strength": float(r.trend_strength),
+                    "is_seasonal": bool(r.seasonal_strength > 0.1), "status": int(status[i])})
+    return out
+
+
+def _seasonality_values(values):
+    """The non-NULL elements of a SQL list (ts_seasonality.cpp:27-32 drops the NULL ones), as a contiguous fp64 array."""
+    return np.array([float(v) for v in values if v is not None and v is not np.ma.masked], dtype=np.float64)
+
+
+def ts_detect_seasonality(values):
+    """The scalar ts_detect_seasonality(values) (ts_seasonality.cpp TsDetectSeasonalityFunction) through anofox_ts_detect_seasonality:
+    None for a NULL list; NULL elements are dropped; the list of periods (possibly empty), strongest first.  Every failure of the
+    entry gives None, as the C++ turns it into SQL NULL (ts_seasonality.cpp:63-66): fewer than 4 values, and the empty list, whose
+    data() is a null pointer."""
+    if values is None:
+        return None
+    v = _seasonality_values(values)
+    L = _lib.load()
+    periods = C.POINTER(C.c_int)()
+    n = C.c_size_t(0)
+    err = _lib.AnofoxError()
+    if not L.anofox_ts_detect_seasonality(v.ctypes.data if len(v) else None, len(v), 0, C.byref(periods), C.byref(n), C.byref(err)):
+        return None
+    out = [int(periods[i]) for i in range(n.value)]
+    L.anofox_free_int_array(periods)
+    return out
+
+
+def ts_analyze_seasonality(*args):
+    """The scalar ts_analyze_seasonality(values) / (timestamps, values) (ts_seasonality.cpp:145-300) through
+    anofox_ts_analyze_seasonality; the timestamps are ignored.  None for a NULL values list and for every failure of the entry
+    (ts_seasonality.cpp:175-178); else the STRUCT as a dict: detected_periods, primary_period, seasonal_strength, trend_strength."""
+    if len(args) not in (1, 2):
+        raise InvalidInputException("ts_analyze_seasonality takes (values) or (timestamps, values)")
+    values = args[-1]
+    if values is None:
+        return None
+    v = _seasonality_values(values)
+    L = _lib.load()
+    res = _lib.SeasonalityResult()
+    err = _lib.AnofoxError()
+    if not L.anofox_ts_analyze_seasonality(None, 0, v.ctypes.data if len(v) else None, len(v), 0, C.byref(res), C.byref(err)):
+        return None
+    out = {"detected_periods": [int(res.detected_periods[i]) for i in range(res.n_periods)], "primary_period": int(res.primary_period),
+           "seasonal_strength": float(res.seasonal_strength), "trend_strength": float(res.trend_strength)}
+    L.anofox_free_seasonality_result(C.byref(res))
+    return out
+
+
+anofox_fcst_ts_detect_seasonality = ts_detect_seasonality      # ts_seasonality.cpp:109-126
+anofox_fcst_ts_analyze_seasonality = ts_analyze_seasonality
+
+
+# --------------------------------------------------------------------------------------------
 # series preparation: anofox_hip_prepare_batch, the single entries of gaps.rs / imputation.rs, and the mirrors of ts_fill_gaps_by,
 # ts_fill_nulls_*_by, ts_drop_*_zeros_by and the four drop filters (ts_macros.cpp:172-413)
 # --------------------------------------------------------------------------------------------

@@ -4069,6 +4069,199 @@ bool anofox_ts_data_quality(const double *values, const uint64_t *validity, size
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Seasonality analysis per series (seasonality.rs detect_seasonality / analyze_seasonality / compute_trend_strength; seasonality.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(SeasonalityResult) == 40 && offsetof(SeasonalityResult, n_periods) == 8 && offsetof(SeasonalityResult, primary_period) == 16 &&
+              offsetof(SeasonalityResult, seasonal_strength) == 24 && offsetof(SeasonalityResult, trend_strength) == 32, "SeasonalityResult layout");
+static_assert(sizeof(AnofoxHipSeasonality) == 128 && offsetof(AnofoxHipSeasonality, n_periods) == 20 && offsetof(AnofoxHipSeasonality, primary_period) == 24 &&
+              offsetof(AnofoxHipSeasonality, strengths) == 32 && offsetof(AnofoxHipSeasonality, acf) == 72 &&
+              offsetof(AnofoxHipSeasonality, seasonal_strength) == 112 && offsetof(AnofoxHipSeasonality, trend_strength) == 120, "AnofoxHipSeasonality layout");
+
+bool anofox_hip_seasonality_device(const double *y, const uint8_t *valid, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
+                                   int max_period, int32_t *out_int, double *out_fp, void *stream, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!y || !lengths || !out_fp || !out_int) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
+        return false;
+    }
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    SeasonalityArgs a{};
+    a.y = y; a.valid = valid; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = (int)t_rows;
+    a.max_period = max_period; a.out_int = out_int; a.out_fp = out_fp;
+    hipStream_t st = (hipStream_t)stream;
+    double *work = nullptr;
+    try {
+        (void)hipGetLastError();
+        const size_t need = seasonality_work_doubles(a.n_series, a.t_rows);
+        if (need) work = dalloc<double>(need);
+        a.work = work;
+        launch_seasonality(a, st);
+        LAUNCHCHECK("seasonality");
+        HIPCHECK(hipStreamSynchronize(st));
+        dev_free(work, true);
+    } catch (const HipFail &f) {
+        dev_free(work, false);
+        report_hip_failure(out_error, f);
+        return false;
+    } catch (const std::runtime_error &e) {
+        dev_free(work, false);
+        set_error(out_error, COMPUTATION_ERROR, e.what());
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_seasonality_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
+                                  int max_period, AnofoxHipSeasonality *out_results, int32_t *out_status, AnofoxError *out_batch_error)
+{
+    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    if (n_series > 0 && (!values || !lengths || !out_results)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    size_t t_max = 0;
+    bool any_mask = false;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
+        t_max = std::max(t_max, lengths[s]);
+        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
+    }
+    if (n_series == 0) return true;
+    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
+    double *d_y = nullptr, *d_fp = nullptr;
+    uint8_t *d_valid = nullptr;
+    int32_t *d_int = nullptr, *d_len = nullptr;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_valid, (void *)d_int, (void *)d_len}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<int32_t> oi(SEASONALITY_N_INT * ld);
+    std::vector<double> of(SEASONALITY_N_FP * ld);
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
+        std::vector<int32_t> len(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            const uint64_t *m = validity ? validity[s] : nullptr;
+            for (size_t t = 0; t < lengths[s]; t++) {
+                yb[t * ld + s] = values[s][t];
+                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
+            }
+        }
+        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
+        d_int = dalloc<int32_t>(SEASONALITY_N_INT * ld); d_fp = dalloc<double>(SEASONALITY_N_FP * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (any_mask) {
+            d_valid = dalloc<uint8_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+        }
+        if (!anofox_hip_seasonality_device(d_y, d_valid, ld, d_len, n_series, T, max_period, d_int, d_fp, nullptr, out_batch_error)) {
+            release(false);
+            return false;
+        }
+        HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++) {
+        AnofoxHipSeasonality &r = out_results[s];
+        std::memset(&r, 0, sizeof r);
+        for (int k = 0; k < SEASONALITY_TOP; k++) {
+            r.periods[k] = oi[k * ld + s];
+            r.strengths[k] = of[k * ld + s];
+            r.acf[k] = of[(SEASONALITY_TOP + k) * ld + s];
+        }
+        r.n_periods = oi[5 * ld + s];
+        r.primary_period = oi[6 * ld + s];
+        r.seasonal_strength = of[10 * ld + s];
+        r.trend_strength = of[11 * ld + s];
+        if (out_status) out_status[s] = oi[7 * ld + s];
+    }
+    return true;
+}
+
+// one series through the kernel; false with the source's error when it is too short
+static bool seasonality_single(const double *values, size_t length, int max_period, AnofoxHipSeasonality *r, AnofoxError *out_error)
+{
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    int32_t status = 0;
+    if (!anofox_hip_seasonality_batch(v, nullptr, len, 1, max_period, r, &status, out_error)) return false;
+    if (status == SEASONALITY_SHORT) {
+        set_error(out_error, COMPUTATION_ERROR, "Insufficient data: need at least 4 observations, got " + std::to_string(length));
+        return false;
+    }
+    return true;
+}
+
+static bool seasonality_periods(const AnofoxHipSeasonality &r, int **out, AnofoxError *out_error)
+{
+    *out = nullptr;
+    if (r.n_periods <= 0) return true;
+    int *p = (int *)std::malloc((size_t)r.n_periods * sizeof(int));
+    if (!p) { set_error(out_error, ALLOCATION_ERROR, "Memory allocation failed"); return false; }
+    for (int k = 0; k < r.n_periods; k++) p[k] = r.periods[k];
+    *out = p;
+    return true;
+}
+
+bool anofox_ts_detect_seasonality(const double *values, size_t length, int max_period, int **out_periods, size_t *out_n_periods, AnofoxError *out_error)
+{
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_periods || !out_n_periods) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxHipSeasonality r;
+    if (!seasonality_single(values, length, max_period, &r, out_error)) return false;
+    if (!seasonality_periods(r, out_periods, out_error)) return false;
+    *out_n_periods = (size_t)r.n_periods;
+    return true;
+}
+
+bool anofox_ts_analyze_seasonality(const int64_t *timestamps, size_t timestamps_len, const double *values, size_t length, int max_period,
+                                   SeasonalityResult *out_result, AnofoxError *out_error)
+{
+    (void)timestamps; (void)timestamps_len;                  // ignored, as the reference ignores them
+    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxHipSeasonality r;
+    if (!seasonality_single(values, length, max_period, &r, out_error)) return false;
+    int *p = nullptr;
+    if (!seasonality_periods(r, &p, out_error)) return false;
+    out_result->detected_periods = p;
+    out_result->n_periods = (size_t)r.n_periods;
+    out_result->primary_period = r.primary_period;
+    out_result->seasonal_strength = r.seasonal_strength;
+    out_result->trend_strength = r.trend_strength;
+    return true;
+}
+
+void anofox_free_seasonality_result(SeasonalityResult *result)
+{
+    if (!result) return;
+    std::free(result->detected_periods);
+    result->detected_periods = nullptr;
+    result->n_periods = 0;
+}
+
+void anofox_free_int_array(int *ptr) { std::free(ptr); }
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Series preparation: gaps, zero trimming, NULL fills (gaps.rs, ts_macros.cpp:208-256, imputation.rs; dataprep.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(GapFillResult) == 32 && offsetof(GapFillResult, values) == 8 && offsetof(GapFillResult, validity) == 16 &&

@@ -375,6 +375,26 @@ size_t quality_work_stride(size_t t_rows);       // words per workspace slice (0
 int quality_work_waves(int n_series);
 void launch_quality(const QualityArgs &, hipStream_t);
 
+// Seasonality analysis per series (seasonality.rs detect_seasonality, analyze_seasonality, compute_trend_strength; seasonality.hip):
+// the up to five strongest autocorrelation peaks, their strengths and the trend strength of every column of a time-major block
+constexpr int SEASONALITY_LDS_ROWS = 5120;   // rows of the longest block whose working buffers live in LDS (63,504 bytes of it)
+constexpr int SEASONALITY_LONG_GRID = 1024;  // workgroups (and workspace slices) of the global-memory variant
+constexpr int SEASONALITY_TOP = 5;           // periods kept
+constexpr int SEASONALITY_N_INT = 8, SEASONALITY_N_FP = 12;
+constexpr int32_t SEASONALITY_OK = 0, SEASONALITY_SHORT = 1;
+struct SeasonalityArgs {
+    const double *y; const uint8_t *valid;       // [t_rows x ld]; valid may be null
+    size_t ld; const int32_t *len; int n_series;
+    int t_rows;                  // a longer series is cut to it
+    int max_period;              // <= 0: n / 2 of each series
+    int32_t *out_int;            // [SEASONALITY_N_INT x ld] periods[0..4], n_periods, primary_period, status
+    double *out_fp;              // [SEASONALITY_N_FP x ld] strengths[0..4], acf[0..4], seasonal_strength, trend_strength
+    double *work;                // [grid x seasonality_work_stride] or null when t_rows <= SEASONALITY_LDS_ROWS
+};
+size_t seasonality_work_stride(int t_rows);      // doubles per workgroup: the centred series, its zero tail and the lag sums
+size_t seasonality_work_doubles(int n_series, int t_rows);     // 0: the block fits the LDS variant
+void launch_seasonality(const SeasonalityArgs &, hipStream_t);
+
 // Walk-forward backtest on a resident block (_ts_backtest_native's folds, cut by position; backtest.hip).  Pair p = s * n_folds + f
 // is series s in fold f; ld_pairs is n_pairs rounded up to 64.
 enum { BT_MAE = 0, BT_MSE = 1, BT_MAPE = 2, BT_SMAPE = 3, BT_BIAS = 4, BT_R2 = 5, BT_COVERAGE = 6, BT_RMSE = 7 };

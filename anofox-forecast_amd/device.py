@@ -126,6 +126,43 @@ def quality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | 
     return {"scores": scores, "figures": figures}
 
 
+def seasonality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | None = None, max_period: int = 0, *,
+                      n_series: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_seasonality_device on torch tensors: the ts_analyze_seasonality figures of every series of a block, no host copy.
+
+    y [t_rows, ld] fp64, valid [t_rows, ld] uint8 or bool (0 = NULL, dropped; None: all valid), lengths int32 [>= n_series], on one HIP
+    device, contiguous -- what prepare_block returns.  max_period <= 0: half of each series' length.
+
+    Returns device tensors: {"periods": int32 [5, ld] (strongest first, 0 beyond n_periods), "n_periods", "primary_period", "status"
+    (int32 [ld] views; lib.SEASONALITY_OK, or lib.SEASONALITY_SHORT for fewer than 4 values), "strengths", "acf" (fp64 [5, ld]),
+    "seasonal_strength", "trend_strength" (fp64 [ld] views), "is_seasonal" (bool [ld]: seasonal_strength > 0.1), and the two blocks
+    "figures" (int32 [8, ld], rows lib.SEASONALITY_INT_FIELDS) and "values" (fp64 [12, ld], rows lib.SEASONALITY_FP_FIELDS)}.
+    Columns s >= n_series hold -1 and NaN."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and tuple(valid.shape) == (t_rows, ld)
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    figures = torch.full((8, ld), -1, dtype=torch.int32, device=dev)
+    values = torch.full((12, ld), float("nan"), dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_seasonality_device(y.data_ptr(), valid.data_ptr() if valid is not None else None, ld, lengths.data_ptr(), n, t_rows,
+                                         int(max_period), figures.data_ptr(), values.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_seasonality_device failed: [{err.code}] {err.message.decode()}")
+    return {"periods": figures[:5], "n_periods": figures[5], "primary_period": figures[6], "status": figures[7],
+            "strengths": values[:5], "acf": values[5:10], "seasonal_strength": values[10], "trend_strength": values[11],
+            "is_seasonal": values[10] > 0.1, "figures": figures, "values": values}
+
+
 def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | None = None, actual: torch.Tensor | None = None,
                     calibration_forecast: torch.Tensor | None = None, valid: torch.Tensor | None = None,
                     lengths: torch.Tensor | None = None, n_groups: int | None = None, method: str = "symmetric",

@@ -137,6 +137,27 @@ QUALITY_FIELDS = tuple(n for n, _ in DataQualityResult._fields_)
 QUALITY_OK, QUALITY_NAN = 0, 2
 
 
+class SeasonalityResult(C.Structure):
+    """include/anofox_fcst_hip.h SeasonalityResult (the reference's layout, 40 bytes): detected_periods is malloc'ed by the entry."""
+    _fields_ = [("detected_periods", C.POINTER(C.c_int)), ("n_periods", C.c_size_t), ("primary_period", C.c_int),
+                ("seasonal_strength", C.c_double), ("trend_strength", C.c_double)]
+
+
+class AnofoxHipSeasonality(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipSeasonality: one record of anofox_hip_seasonality_batch (128 bytes, no pointer)."""
+    _fields_ = [("periods", C.c_int32 * 5), ("n_periods", C.c_int32), ("primary_period", C.c_int32), ("reserved", C.c_int32),
+                ("strengths", C.c_double * 5), ("acf", C.c_double * 5), ("seasonal_strength", C.c_double), ("trend_strength", C.c_double)]
+
+
+assert C.sizeof(SeasonalityResult) == 40 and C.sizeof(AnofoxHipSeasonality) == 128
+# rows of out_int / out_fp of anofox_hip_seasonality_device
+SEASONALITY_INT_FIELDS = ("period_0", "period_1", "period_2", "period_3", "period_4", "n_periods", "primary_period", "status")
+SEASONALITY_FP_FIELDS = ("strength_0", "strength_1", "strength_2", "strength_3", "strength_4", "acf_0", "acf_1", "acf_2", "acf_3", "acf_4",
+                         "seasonal_strength", "trend_strength")
+SEASONALITY_OK, SEASONALITY_SHORT = 0, 1
+SEASONALITY_LDS_ROWS = 5120     # csrc/kernels.hpp: a block above it is worked on in global memory
+
+
 class LombScargleResultFFI(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("period", "frequency", "power", "false_alarm_prob")] + [("method", C.c_char * 32)]
 
@@ -335,6 +356,8 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_stats", "anofox_ts_stats_with_dates", "anofox_ts_stats_with_dates_and_type", "anofox_free_ts_stats_result",
     "anofox_hip_stats_batch", "anofox_hip_stats_device",
     "anofox_ts_data_quality", "anofox_hip_quality_batch", "anofox_hip_quality_device",
+    "anofox_ts_detect_seasonality", "anofox_ts_analyze_seasonality", "anofox_free_seasonality_result", "anofox_free_int_array",
+    "anofox_hip_seasonality_batch", "anofox_hip_seasonality_device",
     "anofox_ts_lomb_scargle", "anofox_ts_aic_period", "anofox_ts_sazed_period", "anofox_ts_detect_periods_flat",
     "anofox_free_flat_multi_period_result", "anofox_hip_periods_batch", "anofox_hip_periods_device",
     "anofox_ts_mae", "anofox_ts_mse", "anofox_ts_rmse", "anofox_ts_mape", "anofox_ts_smape", "anofox_ts_r2", "anofox_ts_bias",
@@ -477,6 +500,19 @@ def load():
     L.anofox_hip_quality_device.restype = C.c_bool
     L.anofox_hip_quality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                             C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_detect_seasonality.restype = C.c_bool
+    L.anofox_ts_detect_seasonality.argtypes = [C.c_void_p, C.c_size_t, C.c_int, P(P(C.c_int)), P(C.c_size_t), P(AnofoxError)]
+    L.anofox_ts_analyze_seasonality.restype = C.c_bool
+    L.anofox_ts_analyze_seasonality.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, P(SeasonalityResult), P(AnofoxError)]
+    L.anofox_free_seasonality_result.restype = None
+    L.anofox_free_seasonality_result.argtypes = [P(SeasonalityResult)]
+    L.anofox_free_int_array.restype = None
+    L.anofox_free_int_array.argtypes = [P(C.c_int)]
+    L.anofox_hip_seasonality_batch.restype = C.c_bool
+    L.anofox_hip_seasonality_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_seasonality_device.restype = C.c_bool
+    L.anofox_hip_seasonality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, P(AnofoxError)]
     L.anofox_ts_lomb_scargle.restype = C.c_bool
     L.anofox_ts_lomb_scargle.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_size_t, P(LombScargleResultFFI), P(AnofoxError)]
     L.anofox_ts_aic_period.restype = C.c_bool

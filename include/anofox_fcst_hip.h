@@ -355,6 +355,58 @@ bool anofox_ts_data_quality(const double *values,
                             struct DataQualityResult *out_result,
                             struct AnofoxError *out_error);
 
+/*
+ * Seasonality analysis of one series (layout of the reference's anofox_fcst_ffi.h: a pointer, a size_t, an int, two doubles; sizeof ==
+ * 40, primary_period at 16, seasonal_strength at 24).  detected_periods is malloc'ed by the entry (NULL when n_periods == 0) and
+ * released by anofox_free_seasonality_result.
+ */
+typedef struct SeasonalityResult {
+    int *detected_periods;    /* strongest first, at most 5 */
+    size_t n_periods;
+    int primary_period;       /* detected_periods[0], or 0 */
+    double seasonal_strength; /* the strength of the primary period, or 0 */
+    double trend_strength;
+} SeasonalityResult;
+
+/*
+ * Seasonal periods of ONE series, the reference's detect_seasonality (seasonality.rs).  With n = length, max_lag = min(max_period > 0
+ * ? max_period : n / 2, n / 2), mean the sum of the values from 0.0 in order divided by n, d_i = x_i - mean, variance = sum d_i * d_i
+ * and acf[lag] = (sum over i < n - lag of d_i * d_(i + lag)) / variance for lag = 1 .. max_lag, every sum sequential with multiply and
+ * add separate: the periods are the lags 2 .. max_lag - 1 whose acf exceeds both neighbours and 0.1, ordered by acf descending (equal
+ * values by ascending lag, as the source's stable sort leaves them), the first five.  max_lag < 2 or |variance| < DBL_EPSILON: none.
+ * The periods are the reference's bit for bit.  *out_periods is malloc'ed (release with anofox_free_int_array),
+ * NULL with *out_n_periods == 0 when there is none.  NULL `values`, `out_periods` or `out_n_periods`: NULL_POINTER.  length < 4:
+ * COMPUTATION_ERROR "Insufficient data: need at least 4 observations, got N".  Non-finite values follow the arithmetic (no periods).
+ * Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_detect_seasonality(const double *values,
+                                  size_t length,
+                                  int max_period,
+                                  int **out_periods,
+                                  size_t *out_n_periods,
+                                  struct AnofoxError *out_error);
+
+/*
+ * The reference's analyze_seasonality: the periods of anofox_ts_detect_seasonality; seasonal_strength = clamp(acf[primary], 0, 1) (0
+ * without a period, and 0 when |variance| equals DBL_EPSILON exactly, as the source's second test is `>`); trend_strength =
+ * clamp(sqrt(ss_xy^2 / (ss_xx * ss_yy)), 0, 1) of the regression on the row number, 0 when |ss_xx| or |ss_yy| < DBL_EPSILON, NaN
+ * when the arithmetic gives NaN (non-finite values).  `timestamps` and `timestamps_len` are ignored, as the reference ignores them.
+ * NULL `values` or `out_result`: NULL_POINTER.  length < 4: COMPUTATION_ERROR as above.  Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_analyze_seasonality(const int64_t *timestamps,
+                                   size_t timestamps_len,
+                                   const double *values,
+                                   size_t length,
+                                   int max_period,
+                                   struct SeasonalityResult *out_result,
+                                   struct AnofoxError *out_error);
+
+/* Frees detected_periods and clears it; NULL and zeroed structs are accepted. */
+void anofox_free_seasonality_result(struct SeasonalityResult *result);
+
+/* Frees an array returned by anofox_ts_detect_seasonality; NULL is accepted. */
+void anofox_free_int_array(int *ptr);
+
 /* Values with a validity bitmask (bit i of word i / 64), the reference's FilledValuesResult: sizeof == 24. */
 typedef struct FilledValuesResult {
     double *values;
@@ -695,6 +747,59 @@ bool anofox_hip_quality_device(const double *y,
                                int64_t *out_int,
                                void *stream,
                                struct AnofoxError *out_error);
+
+/*
+ * The seasonality analysis of one series of a batch: sizeof == 128, no pointer.  Entries k >= n_periods of the arrays are 0.
+ */
+typedef struct AnofoxHipSeasonality {
+    int32_t periods[5];       /* strongest first */
+    int32_t n_periods;
+    int32_t primary_period;   /* periods[0], or 0 */
+    int32_t reserved;
+    double strengths[5];      /* clamp(acf, 0, 1) of each period */
+    double acf[5];            /* the autocorrelation at each period as computed */
+    double seasonal_strength; /* strengths[0], or 0 */
+    double trend_strength;
+} AnofoxHipSeasonality;
+
+/*
+ * Seasonality analysis of `n_series` series in one GPU pass (per series the semantics of anofox_ts_analyze_seasonality, with all five
+ * strengths).  Replaces the reference's one FFI call per series.  `validity` may be NULL, and so may validity[i] (all valid); a NULL
+ * value is dropped, as the SQL scalars drop NULL list elements, so n is the count of valid values.  One `max_period` for the batch (<=
+ * 0: n / 2 of each series).  out_results is AnofoxHipSeasonality[n_series], out_status int32[n_series] (may be NULL): 0, or 1 for a
+ * series of fewer than 4 valid values, whose record is all zero.  No other per-series failure exists; the return value is false only
+ * for batch-level failures (NULL pointers, no GPU), also reported through `out_batch_error`.  Runs on the calling thread's current
+ * device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_seasonality_batch(const double *const *values,
+                                  const uint64_t *const *validity,
+                                  const size_t *lengths,
+                                  size_t n_series,
+                                  int max_period,
+                                  struct AnofoxHipSeasonality *out_results,
+                                  int32_t *out_status,
+                                  struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows), `valid` (uint8 [t_rows x ld], 0 = NULL; may be
+ * NULL), lengths[n_series] (int32; a length above t_rows is cut to it); the outputs are device pointers.  out_int is int32 [8 x ld]:
+ * periods[0..4] (0 beyond n_periods), n_periods, primary_period, status (0 or 1).  out_fp is fp64 [12 x ld]: strengths[0..4] (0.0
+ * beyond n_periods), the five autocorrelation values as computed, seasonal_strength, trend_strength.  Columns s >= n_series are left
+ * untouched.  One workgroup per series; a block of at most 5,120 rows is worked on in LDS, a higher one in a workspace in global
+ * memory that the call allocates (slower, the same figures).  The same bits on every run and through every entry.  Runs on `stream`
+ * (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_seasonality_device(const double *y,
+                                   const uint8_t *valid,
+                                   size_t ld,
+                                   const int32_t *lengths,
+                                   size_t n_series,
+                                   size_t t_rows,
+                                   int max_period,
+                                   int32_t *out_int,
+                                   double *out_fp,
+                                   void *stream,
+                                   struct AnofoxError *out_error);
 
 /* What anofox_hip_prepare_device / _batch run, in this fixed order: gaps, trim, fill.  Zero everywhere is "copy the rows". */
 typedef struct AnofoxHipPrepOptions {
