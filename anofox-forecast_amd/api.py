@@ -3310,3 +3310,254 @@ def ts_backtest_native_gpu(group, date, value, horizon=7, folds=5, params=None, 
     for c in ("yhat", "actual", "error", "abs_error", "yhat_lower", "yhat_upper", "fold_metric_score"):
         cols[c] = np.array(cols[c], dtype=np.float64)
     return cols
+
+
+# --------------------------------------------------------------------------------------------
+# ts_aggregate_hierarchy and its string companions (docs/api/02-hierarchical.md; ts_aggregate_hierarchy.cpp, ts_combine_keys.cpp,
+# ts_split_keys.cpp, ts_validate_separator.cpp): validate the separator, aggregate up the key hierarchy, forecast, split the keys
+# --------------------------------------------------------------------------------------------
+def hierarchy_batch(series, column_of, first=None, valids=None, presents=None, route="auto", tile_min_members=0):
+    """anofox_hip_hierarchy_batch: series s holds positions first[s] .. first[s] + len - 1 of a common date grid; column_of int32
+    [n_groupings, n_series] is its output column under every grouping (-1: none).  valids / presents: per-series boolean arrays or None
+    (valid False = NULL: counts as 0.0, the row exists; present False = no row at that position).  Output column c is the serial sum,
+    from +0.0, of its members ordered by (series, grouping): the bits of the operator.
+
+    Returns ({"y": fp64 [t_out, ld_out] time-major; "present": uint8 [t_out, ld_out]; "lengths": int32 [n_out]; "first": int64 [n_out];
+    "n_out", "t_out"}, error)."""
+    L = _lib.load()
+    n = len(series)
+    arrs = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    co = np.ascontiguousarray(column_of, dtype=np.int32).reshape(-1, n) if n else np.zeros((0, 0), dtype=np.int32)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+
+    def masks(ms):
+        if ms is None:
+            return None, None
+        words = [None if m is None else validity_mask(m) for m in ms]
+        return words, (C.c_void_p * max(n, 1))(*[None if w is None else w.ctypes.data for w in words])
+    _vw, vptr = masks(valids)
+    _pw, pptr = masks(presents)
+    fst = None if first is None else np.ascontiguousarray(first, dtype=np.int64)
+    opts = _lib.make_hierarchy_options(route, tile_min_members)
+    n_out, t_out, ld_out = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    err = _lib.AnofoxError()
+    out = {"y": np.zeros((0, 0)), "present": np.zeros((0, 0), dtype=np.uint8), "lengths": np.zeros(0, dtype=np.int32),
+           "first": np.zeros(0, dtype=np.int64), "n_out": 0, "t_out": 0}
+
+    def call(rows, ld, y, pr, ln, fo):
+        return L.anofox_hip_hierarchy_batch(ptrs, vptr, pptr, lens, None if fst is None else fst.ctypes.data, n, co.ctypes.data, co.shape[0],
+                                            C.byref(opts), C.sizeof(opts), rows, ld, y, pr, ln, fo, C.byref(n_out), C.byref(t_out),
+                                            C.byref(ld_out), C.byref(err))
+    ok = call(0, 0, None, None, None, None)
+    if ok:
+        out = {"y": np.zeros((t_out.value, ld_out.value)), "present": np.zeros((t_out.value, ld_out.value), dtype=np.uint8),
+               "lengths": np.zeros(n_out.value, dtype=np.int32), "first": np.zeros(n_out.value, dtype=np.int64),
+               "n_out": n_out.value, "t_out": t_out.value}
+        ok = call(t_out.value, ld_out.value, out["y"].ctypes.data, out["present"].ctypes.data, out["lengths"].ctypes.data,
+                  out["first"].ctypes.data)
+    return out, {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+
+
+def _hierarchy_strings(col, n_rows):
+    a = np.ma.filled(np.ma.asarray(col, dtype=object), None) if np.ma.isMaskedArray(col) else np.asarray(col, dtype=object)
+    if len(a) != n_rows:
+        raise InvalidInputException("every column of the input table must have the same number of rows")
+    return ["NULL" if v is None else str(v) for v in a]
+
+
+def _hierarchy_params(params):
+    p = params or {}
+    sep = str(p["separator"]) if p.get("separator") is not None else "|"
+    keyword = str(p["aggregate_keyword"]) if p.get("aggregate_keyword") is not None else "AGGREGATED"
+    return sep, keyword
+
+
+def _hierarchy_unique_id(parts, level, sep, keyword):
+    """BuildUniqueId (ts_aggregate_hierarchy.cpp:108-130): the first `level` ids, the keyword for the rest."""
+    return sep.join(parts[i] if i < level else keyword for i in range(len(parts)))
+
+
+def _hierarchy_host(us, vals, id_rows, sep, keyword):
+    """The operator's finalize as it stands (:346-381): one map of maps, += in row order, sorted by (unique_id bytes, date)."""
+    cells = {}
+    for d, v, parts in zip(us, vals, id_rows):
+        for level in range(len(parts) + 1):
+            by_date = cells.setdefault(_hierarchy_unique_id(parts, level, sep, keyword), {})
+            by_date[d] = by_date.get(d, 0.0) + v
+    rows = []
+    for uid in sorted(cells, key=lambda u: u.encode("utf-8")):
+        for d in sorted(cells[uid]):
+            rows.append((uid, d, cells[uid][d]))
+    return rows
+
+
+def _hierarchy_leaf_order(leaf_of_row, rank_of_row, leaf_keys):
+    """A leaf numbering under which the rows of every date arrive in strictly ascending leaf number -- first appearance, else the
+    sorted id tuples -- or None: then no single series order reproduces the operator's row order, or a (leaf, date) occurs twice."""
+    n_leaf = len(leaf_keys)
+    by_key = np.empty(n_leaf, dtype=np.int64)
+    by_key[np.array(sorted(range(n_leaf), key=lambda i: leaf_keys[i]), dtype=np.int64)] = np.arange(n_leaf)
+    at = np.argsort(rank_of_row, kind="stable")
+    same_date = np.diff(rank_of_row[at]) == 0
+    for numbering in (np.arange(n_leaf, dtype=np.int64), by_key):
+        if np.all(np.diff(numbering[leaf_of_row][at])[same_date] > 0):
+            return numbering
+    return None
+
+
+def ts_aggregate_hierarchy(date, value, ids, params=None, date_name="date", value_name="value", route="auto", info=None):
+    """ts_aggregate_hierarchy(TABLE(date, value, id_1 .. id_N), MAP{separator, aggregate_keyword}) (ts_aggregate_hierarchy.cpp).
+
+    `ids` is the list of id columns.  Rows with a NULL date (NaT, or masked) are dropped; a NULL value counts as 0.0 and the row
+    exists; a NULL id is the string "NULL".  Every row is added to one cell (unique_id, date) per level 0 .. N, where unique_id keeps
+    the first L ids and writes the keyword for the rest; a cell is ((0.0 + v_a) + v_b) + ... in row order.  Returns the columns
+    unique_id, <date_name> (the input's date type) and <value_name> (fp64), sorted by unique_id (byte order), then date.
+
+    The sums run on the GPU (anofox_hip_hierarchy_batch: leaf series = distinct id tuples, the distinct dates ranked onto a grid,
+    column_of from the byte-sorted unique_ids, cells without a row dropped) ONLY when one series order reproduces the operator's row
+    order: the rows of every date arrive in one consistent leaf order and no (leaf, date) occurs twice -- a table sorted by (ids,
+    date) or by (date, ids) meets this.  Any other table runs the host restatement of the operator's map of maps: the mirror never
+    returns a sum in an order the reference would not have used.  (The reference's own row order under several DuckDB threads is not
+    determined; this is its single-thread order.)  `info`, a dict, receives {"route": "gpu" | "host"}."""
+    ids = list(ids)
+    if len(ids) < 1:
+        raise InvalidInputException("ts_aggregate_hierarchy requires at least 3 columns: date_col, value_col, and at least one id_col. "
+                                    f"Got {2 + len(ids)} columns.")
+    sep, keyword = _hierarchy_params(params)
+    masked_date = np.ma.getmaskarray(date) if np.ma.isMaskedArray(date) else None
+    dates = np.ma.getdata(date) if masked_date is not None else np.asarray(date)
+    kind = _date_kind(dates)
+    us_all = _to_micros(dates, kind)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), bool)
+    if masked_date is not None:
+        null_date = null_date | masked_date
+    val = np.ma.filled(np.ma.asarray(value, dtype=object), None) if np.ma.isMaskedArray(value) else np.asarray(value, dtype=object)
+    if len(val) != len(dates):
+        raise InvalidInputException("every column of the input table must have the same number of rows")
+    id_cols = [_hierarchy_strings(c, len(dates)) for c in ids]
+    keep = np.nonzero(~null_date)[0]
+    us = [int(us_all[i]) for i in keep]
+    is_null = [val[i] is None for i in keep]
+    vals = [0.0 if val[i] is None else float(val[i]) for i in keep]
+    id_rows = [tuple(c[i] for c in id_cols) for i in keep]
+    if info is not None:
+        info["route"] = "host"
+    rows = None
+    if len(keep):
+        grid, rank_of_row = np.unique(np.array(us, dtype=np.int64), return_inverse=True)
+        leaf_index, leaf_keys = {}, []
+        leaf_of_row = np.empty(len(keep), dtype=np.int64)
+        for r, parts in enumerate(id_rows):
+            k = leaf_index.get(parts)
+            if k is None:
+                k = leaf_index[parts] = len(leaf_keys)
+                leaf_keys.append(parts)
+            leaf_of_row[r] = k
+        numbering = _hierarchy_leaf_order(leaf_of_row, rank_of_row, leaf_keys)
+        if numbering is not None:
+            n_leaf, N = len(leaf_keys), len(ids)
+            series_of_row = numbering[leaf_of_row]
+            key_of_series = [None] * n_leaf
+            for k, parts in enumerate(leaf_keys):
+                key_of_series[int(numbering[k])] = parts
+            lo = np.full(n_leaf, np.iinfo(np.int64).max, dtype=np.int64)
+            hi = np.full(n_leaf, -1, dtype=np.int64)
+            np.minimum.at(lo, series_of_row, rank_of_row)
+            np.maximum.at(hi, series_of_row, rank_of_row)
+            series = [np.zeros(int(hi[s] - lo[s] + 1)) for s in range(n_leaf)]
+            valids = [np.ones(len(a), dtype=bool) for a in series]
+            presents = [np.zeros(len(a), dtype=bool) for a in series]
+            for r in range(len(keep)):
+                s = int(series_of_row[r])
+                t = int(rank_of_row[r] - lo[s])
+                presents[s][t] = True
+                if is_null[r]:
+                    valids[s][t] = False
+                else:
+                    series[s][t] = vals[r]
+            uid = [[_hierarchy_unique_id(key_of_series[s], level, sep, keyword) for s in range(n_leaf)] for level in range(N + 1)]
+            names = sorted({u for level in uid for u in level}, key=lambda u: u.encode("utf-8"))
+            column = {u: c for c, u in enumerate(names)}
+            column_of = np.array([[column[u] for u in level] for level in uid], dtype=np.int32)
+            res, err = hierarchy_batch(series, column_of, first=lo, valids=valids, presents=presents, route=route)
+            if not err["ok"]:
+                raise RuntimeError(f"anofox_hip_hierarchy_batch failed: [{err['code']}] {err['message']}")
+            rows = []
+            for c, u in enumerate(names):
+                f0 = int(res["first"][c])
+                for t in range(int(res["lengths"][c])):
+                    if res["present"][t, c]:
+                        rows.append((u, int(grid[f0 + t]), float(res["y"][t, c])))
+            if info is not None:
+                info["route"] = "gpu"
+    if rows is None:
+        rows = _hierarchy_host(us, vals, id_rows, sep, keyword)
+    return {"unique_id": np.array([r[0] for r in rows], dtype=object),
+            date_name: _from_micros(np.array([r[1] for r in rows], dtype=np.int64), kind, dates.dtype),
+            value_name: np.array([r[2] for r in rows], dtype=np.float64)}
+
+
+def ts_combine_keys(date, value, ids, params=None, date_name="date", value_name="value"):
+    """ts_combine_keys(TABLE(date, value, id_1 .. id_N), MAP{separator}) (ts_combine_keys.cpp:169-205): every row passes through with
+    its ids joined by the separator (default '|'; a NULL id is "NULL").  Returns unique_id, <date_name>, <value_name>."""
+    ids = list(ids)
+    if len(ids) < 1:
+        raise InvalidInputException("ts_combine_keys requires at least 3 columns: date_col, value_col, and at least one id_col. "
+                                    f"Got {2 + len(ids)} columns.")
+    sep, _ = _hierarchy_params(params)
+    n = len(date)
+    id_cols = [_hierarchy_strings(c, n) for c in ids]
+    return {"unique_id": np.array([sep.join(c[i] for c in id_cols) for i in range(n)], dtype=object), date_name: date, value_name: value}
+
+
+def _split_key(text, sep):
+    """SplitString (ts_split_keys.cpp:127-143): an empty separator does not split."""
+    return [text] if sep == "" else text.split(sep)
+
+
+def ts_split_keys(unique_id, date, value, separator="|", columns=None, date_name="date", value_name="value"):
+    """ts_split_keys(TABLE(unique_id, date, value), separator := '|', columns := [...]) (ts_split_keys.cpp:157-395): the parts of
+    every unique_id in the columns `columns` (NULL names dropped) or, without them, id_part_1 .. id_part_3; missing parts are '',
+    surplus parts are cut; rows with a NULL unique_id are dropped.  The date and value columns pass through."""
+    names = [str(c) for c in (columns or []) if c is not None]
+    if not names:
+        names = [f"id_part_{i + 1}" for i in range(3)]
+    uid = np.ma.filled(np.ma.asarray(unique_id, dtype=object), None) if np.ma.isMaskedArray(unique_id) else np.asarray(unique_id, dtype=object)
+    keep = np.array([i for i in range(len(uid)) if uid[i] is not None], dtype=np.int64)
+    out = {c: [] for c in names}
+    for i in keep:
+        parts = _split_key(str(uid[i]), str(separator))
+        parts = (parts + [""] * len(names))[:len(names)]
+        for c, part in zip(names, parts):
+            out[c].append(part)
+    out = {c: np.array(v, dtype=object) for c, v in out.items()}
+    out[date_name] = np.asarray(date)[keep] if len(keep) else np.asarray(date)[:0]
+    out[value_name] = np.asarray(value)[keep] if len(keep) else np.asarray(value)[:0]
+    return out
+
+
+def ts_validate_separator(ids, separator="|"):
+    """ts_validate_separator(TABLE(id_1 .. id_N), separator := '|') (ts_validate_separator.cpp:134-259): one row -- separator,
+    is_valid, n_conflicts, conflicting_values (the distinct non-NULL id values that contain the separator, in byte order), message."""
+    ids = list(ids)
+    if len(ids) < 1:
+        raise InvalidInputException("ts_validate_separator requires at least 1 ID column.")
+    sep = str(separator)
+    distinct = set()
+    for col in ids:
+        a = np.ma.filled(np.ma.asarray(col, dtype=object), None) if np.ma.isMaskedArray(col) else np.asarray(col, dtype=object)
+        distinct.update(str(v) for v in a if v is not None)
+    conflicts = [v for v in sorted(distinct, key=lambda u: u.encode("utf-8")) if sep in v]
+    if not conflicts:
+        message = "Separator is safe to use"
+    else:
+        tries = [f"'{alt}'" for alt in ("-", ".", "::", "__", "#") if sep != alt and alt not in sep]
+        message = f"Separator '{sep}' found in {len(conflicts)} value(s). Try: " + ", ".join(tries)
+    return {"separator": sep, "is_valid": not conflicts, "n_conflicts": len(conflicts), "conflicting_values": conflicts, "message": message}
+
+
+anofox_fcst_ts_aggregate_hierarchy = ts_aggregate_hierarchy
+anofox_fcst_ts_combine_keys = ts_combine_keys
+anofox_fcst_ts_split_keys = ts_split_keys
+anofox_fcst_ts_validate_separator = ts_validate_separator

@@ -6583,3 +6583,275 @@ bool anofox_hip_backtest_batch(const double *const *values, const size_t *length
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Aggregation up a key hierarchy on a resident block (ts_aggregate_hierarchy.cpp:246-386; hierarchy.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+bool hierarchy_options_ok(const AnofoxHipHierarchyOptions *o, size_t struct_size, AnofoxError *err)
+{
+    if (!o) { set_error(err, NULL_POINTER, "Null pointer argument"); return false; }
+    if (struct_size != sizeof(AnofoxHipHierarchyOptions)) {
+        set_error(err, INVALID_INPUT, "Invalid input: struct_size is not sizeof(AnofoxHipHierarchyOptions)");
+        return false;
+    }
+    if (o->route < HIER_ROUTE_AUTO || o->route > HIER_ROUTE_TILE || o->tile_min_members < 0) {
+        set_error(err, INVALID_INPUT, "Invalid input: route must be 0 (automatic), 1 (lane per column) or 2 (tile), tile_min_members >= 0");
+        return false;
+    }
+    return true;
+}
+
+// first and last set bit of a DuckDB mask among rows [0, n); false when there is none.  A NULL mask is all ones.
+bool hierarchy_mask_range(const uint64_t *m, size_t n, size_t *t0, size_t *t1)
+{
+    if (n == 0) return false;
+    if (!m) { *t0 = 0; *t1 = n - 1; return true; }
+    size_t a = 0, b = n;
+    while (a < n && !((m[a >> 6] >> (a & 63)) & 1)) a++;
+    if (a == n) return false;
+    while (!((m[(b - 1) >> 6] >> ((b - 1) & 63)) & 1)) b--;
+    *t0 = a; *t1 = b - 1;
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+static_assert(sizeof(AnofoxHipHierarchyOptions) == 16 && offsetof(AnofoxHipHierarchyOptions, tile_min_members) == 4, "AnofoxHipHierarchyOptions layout");
+
+bool anofox_hip_hierarchy_plan(const int32_t *column_of, size_t n_groupings, size_t n_series, size_t *n_out, size_t *nnz, int32_t *col_offsets,
+                               int32_t *members, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (n_series > (size_t)INT32_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: more than 2^31 - 1 series"); return false; }
+    const bool cells = n_groupings > 0 && n_series > 0;
+    if (cells && !column_of) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if ((col_offsets == nullptr) != (members == nullptr)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    int64_t largest = -1;
+    size_t count = 0;
+    if (cells)
+        for (size_t g = 0; g < n_groupings; g++)
+            for (size_t s = 0; s < n_series; s++) {
+                const int32_t c = column_of[g * n_series + s];
+                if (c < -1) { set_error(out_error, INVALID_INPUT, "Invalid input: a column_of entry is below -1"); return false; }
+                if (c >= 0) { count++; largest = std::max<int64_t>(largest, c); }
+            }
+    if (largest + 1 > (int64_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: n_out exceeds the limit of 2^31 - 1 output columns");
+        return false;
+    }
+    if (count > (size_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: nnz exceeds the limit of 2^31 - 1 plan entries");
+        return false;
+    }
+    const size_t no = (size_t)(largest + 1);
+    if (n_out) *n_out = no;
+    if (nnz) *nnz = count;
+    if (!col_offsets) return true;
+    // stable counting sort by column: entries are visited by (series, grouping), so that is their order within a column
+    std::vector<int32_t> at(no + 1, 0);
+    if (cells)
+        for (size_t i = 0; i < n_groupings * n_series; i++)
+            if (column_of[i] >= 0) at[(size_t)column_of[i] + 1]++;
+    for (size_t c = 0; c < no; c++) at[c + 1] += at[c];
+    std::memcpy(col_offsets, at.data(), (no + 1) * sizeof(int32_t));
+    if (cells)
+        for (size_t s = 0; s < n_series; s++)
+            for (size_t g = 0; g < n_groupings; g++) {
+                const int32_t c = column_of[g * n_series + s];
+                if (c >= 0) members[at[(size_t)c]++] = (int32_t)s;
+            }
+    return true;
+}
+
+bool anofox_hip_hierarchy_device(const double *y, const uint8_t *valid, const uint8_t *present, size_t ld, const int32_t *lengths,
+                                 const int64_t *first, size_t n_series, size_t t_rows, const int32_t *col_offsets, const int32_t *members,
+                                 size_t n_out, size_t nnz, const AnofoxHipHierarchyOptions *options, size_t struct_size, size_t t_out,
+                                 double *y_out, uint8_t *present_out, size_t ld_out, int32_t *lengths_out, int64_t *first_out, void *stream,
+                                 AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!hierarchy_options_ok(options, struct_size, out_error)) return false;
+    if ((n_out > 0 && (!col_offsets || !lengths_out || !first_out)) || (nnz > 0 && (!members || !y || !lengths))) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (n_out > (size_t)INT32_MAX || nnz > (size_t)INT32_MAX || n_series > (size_t)INT32_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: n_out, nnz and n_series are limited to 2^31 - 1");
+        return false;
+    }
+    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
+    if (t_rows > (size_t)HIER_SPAN_MAX || t_out > (size_t)HIER_SPAN_MAX) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: t_rows and t_out are limited to 2^30 rows");
+        return false;
+    }
+    const bool full = y_out != nullptr && t_out > 0;
+    if (full && ld_out < n_out) { set_error(out_error, INVALID_INPUT, "Invalid input: ld_out is smaller than n_out"); return false; }
+    if (n_out == 0) return true;
+    if (!device_ready(out_error)) return false;
+    HierarchyArgs a{};
+    a.y = y; a.ld = ld; a.valid = valid; a.present = present; a.len = lengths; a.first = first; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.col_offsets = col_offsets; a.members = members; a.n_out = (int)n_out; a.nnz = (int)nnz;
+    a.route = options->route; a.tile_min = options->tile_min_members > 0 ? options->tile_min_members : HIER_TILE_MIN_MEMBERS;
+    a.t_out = full ? t_out : 0; a.ld_out = ld_out; a.y_out = full ? y_out : nullptr; a.present_out = full ? present_out : nullptr;
+    a.len_out = lengths_out; a.first_out = first_out;
+    try {
+        (void)hipGetLastError();
+        launch_hierarchy(a, (hipStream_t)stream);
+        LAUNCHCHECK("hierarchy");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_hierarchy_batch(const double *const *values, const uint64_t *const *validity, const uint64_t *const *present,
+                                const size_t *lengths, const int64_t *first, size_t n_series, const int32_t *column_of, size_t n_groupings,
+                                const AnofoxHipHierarchyOptions *options, size_t struct_size, size_t t_out, size_t ld_out, double *out_y,
+                                uint8_t *out_present, int32_t *out_lengths, int64_t *out_first, size_t *out_n_out, size_t *out_t_out,
+                                size_t *out_ld, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!hierarchy_options_ok(options, struct_size, out_error)) return false;
+    if (n_series > 0 && (!values || !lengths)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    size_t n_out = 0, nnz = 0, T = 1;
+    if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, nullptr, nullptr, out_error)) return false;
+    std::vector<int32_t> offs(n_out + 1), memb(std::max<size_t>(nnz, 1));
+    if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, offs.data(), memb.data(), out_error)) return false;
+    // the span of every series, then of every column: the sizes come from the host's copy, the device only confirms them
+    std::vector<int64_t> s_lo(n_series, 0), s_hi(n_series, -1);
+    bool any_valid = false, any_present = false;
+    for (size_t s = 0; s < n_series; s++) {
+        const size_t n = lengths[s];
+        if (n > 0 && !values[s]) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (n > (size_t)HIER_SPAN_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: a series is longer than the limit of 2^30 rows"); return false; }
+        const int64_t f = first ? first[s] : 0;
+        if (f > HIER_FIRST_MAX || f < -HIER_FIRST_MAX) {
+            set_error(out_error, INVALID_INPUT, "Invalid input: a first position is outside the limit of +-2^61");
+            return false;
+        }
+        T = std::max(T, n);
+        any_valid = any_valid || (validity && validity[s] && n > 0);
+        any_present = any_present || (present && present[s] && n > 0);
+        size_t t0 = 0, t1 = 0;
+        if (hierarchy_mask_range(present ? present[s] : nullptr, n, &t0, &t1)) { s_lo[s] = f + (int64_t)t0; s_hi[s] = f + (int64_t)t1; }
+        else { s_lo[s] = 0; s_hi[s] = -1; }
+    }
+    std::vector<int32_t> c_len(n_out, 0);
+    std::vector<int64_t> c_first(n_out, 0);
+    size_t longest = 1;
+    for (size_t c = 0; c < n_out; c++) {
+        int64_t lo = INT64_MAX, hi = INT64_MIN;
+        for (int32_t i = offs[c]; i < offs[c + 1]; i++) {
+            const size_t s = (size_t)memb[(size_t)i];
+            if (s_lo[s] > s_hi[s]) continue;
+            lo = std::min(lo, s_lo[s]); hi = std::max(hi, s_hi[s]);
+        }
+        if (lo > hi) continue;
+        if (hi - lo + 1 > HIER_SPAN_MAX) {
+            set_error(out_error, INVALID_INPUT, "Invalid input: output column " + std::to_string(c) + " spans " + std::to_string(hi - lo + 1) +
+                      " rows, above the limit of 2^30");
+            return false;
+        }
+        c_len[c] = (int32_t)(hi - lo + 1); c_first[c] = lo;
+        longest = std::max(longest, (size_t)c_len[c]);
+    }
+    const size_t need_ld = std::max<size_t>((n_out + 63) / 64 * 64, 64);
+    if (out_n_out) *out_n_out = n_out;
+    if (out_t_out) *out_t_out = longest;
+    if (out_ld) *out_ld = need_ld;
+    if (!out_y) return true;
+    if (t_out != longest || ld_out != need_ld) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: t_out or ld_out is not what the sizing call returns");
+        return false;
+    }
+    if (!out_lengths || !out_first) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_out == 0) return true;
+    if (!device_ready(out_error)) return false;
+    const size_t ld = (std::max<size_t>(n_series, 1) + 63) / 64 * 64;
+    // ONE arena of results, so that one copy brings them back: y, first (8-byte items), lengths, then the present bytes
+    const size_t cells = t_out * ld_out, back_bytes = cells * 8 + ld_out * 8 + ld_out * 4 + cells;
+    double *d_y = nullptr;
+    uint8_t *d_valid = nullptr, *d_present = nullptr, *d_back = nullptr;
+    int32_t *d_len = nullptr, *d_plan = nullptr;
+    int64_t *d_first = nullptr;
+    auto release = [&](bool quiesced) {
+        for (void *q : {(void *)d_y, (void *)d_valid, (void *)d_present, (void *)d_back, (void *)d_len, (void *)d_plan, (void *)d_first}) {
+            dev_free(q, quiesced);
+            quiesced = true;
+        }
+    };
+    std::vector<uint8_t> back(back_bytes);
+    bool ok = true;
+    try {
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<uint8_t> vb(any_valid ? T * ld : 0, 1), pb(any_present ? T * ld : 0, 1);
+        std::vector<int32_t> len(ld, 0);
+        std::vector<int64_t> fst(ld, 0);
+        for (size_t s = 0; s < n_series; s++) {
+            len[s] = (int32_t)lengths[s];
+            fst[s] = first ? first[s] : 0;
+            const uint64_t *m = validity ? validity[s] : nullptr, *p = present ? present[s] : nullptr;
+            for (size_t t = 0; t < lengths[s]; t++) {
+                yb[t * ld + s] = values[s][t];
+                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
+                if (p) pb[t * ld + s] = (uint8_t)((p[t >> 6] >> (t & 63)) & 1);
+            }
+        }
+        try {
+            d_y = dalloc<double>(T * ld);
+            if (any_valid) d_valid = dalloc<uint8_t>(T * ld);
+            if (any_present) d_present = dalloc<uint8_t>(T * ld);
+            d_back = dalloc<uint8_t>(back_bytes);
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the source block of " + std::to_string(T) + " x " + std::to_string(ld) +
+                      " values and the aggregated block of " + std::to_string(t_out) + " x " + std::to_string(ld_out) + " values need " +
+                      std::to_string(T * ld * (8 + (any_valid ? 1 : 0) + (any_present ? 1 : 0)) + back_bytes) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            d_len = dalloc<int32_t>(ld); d_first = dalloc<int64_t>(ld); d_plan = dalloc<int32_t>(n_out + 1 + nnz);
+            HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+            if (any_valid) HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+            if (any_present) HIPCHECK(hipMemcpy(d_present, pb.data(), T * ld, hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_first, fst.data(), ld * sizeof(int64_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_plan, offs.data(), (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (nnz) HIPCHECK(hipMemcpy(d_plan + n_out + 1, memb.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+            double *d_yo = (double *)d_back;
+            int64_t *d_fo = (int64_t *)(d_back + cells * 8);
+            int32_t *d_lo = (int32_t *)(d_back + cells * 8 + ld_out * 8);
+            uint8_t *d_po = d_back + cells * 8 + ld_out * 8 + ld_out * 4;
+            HIPCHECK(hipMemset(d_back, 0, back_bytes));                    // the padding columns of the arena
+            ok = anofox_hip_hierarchy_device(d_y, d_valid, d_present, ld, d_len, d_first, n_series, T, d_plan, d_plan + n_out + 1, n_out, nnz,
+                                             options, struct_size, t_out, d_yo, d_po, ld_out, d_lo, d_fo, nullptr, out_error);
+            if (ok) HIPCHECK(hipMemcpy(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost));      // waits for the null stream
+            else HIPCHECK(hipDeviceSynchronize());
+        }
+        release(true);
+    } catch (const HipFail &f) {
+        release(false);
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    if (!ok) return false;
+    const int64_t *fo = (const int64_t *)(back.data() + cells * 8);
+    const int32_t *lo = (const int32_t *)(back.data() + cells * 8 + ld_out * 8);
+    for (size_t c = 0; c < n_out; c++)
+        if (lo[c] != c_len[c] || fo[c] != c_first[c]) {
+            set_error(out_error, INTERNAL_ERROR, "Internal error: the device sized output column " + std::to_string(c) + " differently from the host");
+            return false;
+        }
+    std::memcpy(out_y, back.data(), cells * 8);
+    std::memcpy(out_first, fo, n_out * sizeof(int64_t));
+    std::memcpy(out_lengths, lo, n_out * sizeof(int32_t));
+    if (out_present) std::memcpy(out_present, back.data() + cells * 8 + ld_out * 8 + ld_out * 4, cells);
+    return true;
+}
+
+} // extern "C"

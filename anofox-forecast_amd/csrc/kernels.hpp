@@ -420,6 +420,31 @@ struct BacktestArgs {
 void launch_backtest_expand(const BacktestArgs &, hipStream_t);
 void launch_backtest_collect(const BacktestArgs &, hipStream_t);     // collect, then (scores != null) the fold scores
 
+// Aggregation up a key hierarchy (ts_aggregate_hierarchy.cpp:246-386; hierarchy.hip).  Output column c is the sum over the series
+// members[col_offsets[c] .. col_offsets[c + 1]) IN THAT ORDER, per position of a common date grid; first[s] is the grid position of
+// series s' row 0.
+enum { HIER_ROUTE_AUTO = 0, HIER_ROUTE_LANE = 1, HIER_ROUTE_TILE = 2 };
+constexpr int64_t HIER_FIRST_MAX = (int64_t)1 << 61;    // |first[s]| above it marks the column invalid (position arithmetic stays in int64)
+constexpr int64_t HIER_SPAN_MAX = (int64_t)1 << 30;      // rows of an output column
+// columns with at least this many members take the tile route under HIER_ROUTE_AUTO.  Measured (profiles/hierarchy_m5.txt): on plans
+// of equal-width columns the tile route is the faster one from 16 members on while there are enough columns to fill the chip with
+// lanes, and the M5 plans give the same time for every threshold from 2 to 1,024 (their wide columns have 3,049 members or more,
+// their narrow ones 10 or fewer); 64, one full tile, lies inside both ranges.
+constexpr int HIER_TILE_MIN_MEMBERS = 64;
+struct HierarchyArgs {
+    const double *y; size_t ld;                  // the source block [t_rows x ld]
+    const uint8_t *valid, *present;              // null, or [t_rows x ld]: valid 0 = NULL (adds 0.0), present 0 = no row there
+    const int32_t *len; const int64_t *first;    // [n_series]; first may be null (all 0); a length above t_rows is cut to it
+    int n_series; size_t t_rows;
+    const int32_t *col_offsets, *members;        // CSR plan: [n_out + 1], [nnz]
+    int n_out, nnz;
+    int route, tile_min;                         // HIER_ROUTE_*; member count from which HIER_ROUTE_AUTO takes the tile route
+    size_t t_out, ld_out;
+    double *y_out; uint8_t *present_out;         // [t_out x ld_out]; null for the sizing call (present_out may be null alone)
+    int32_t *len_out; int64_t *first_out;        // [n_out]
+};
+void launch_hierarchy(const HierarchyArgs &, hipStream_t);     // spans, then (y_out != null) the two routes
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

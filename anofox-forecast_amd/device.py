@@ -307,6 +307,118 @@ def backtest_block(y: torch.Tensor, lengths: torch.Tensor, opts: _lib.ForecastOp
             "t_train": t_train}
 
 
+def hierarchy_plan_device(column_of: torch.Tensor) -> dict:
+    """The CSR plan of anofox_hip_hierarchy_plan made on the device with torch: column_of int32 / int64 [n_groupings, n_series]
+    (-1: none) -> {"col_offsets": int32 [n_out + 1], "members": int32 [nnz], "n_out", "nnz"}.  The entries are laid out by (series,
+    grouping) and sorted by column with a STABLE sort, so that is their order within a column.  One device-to-host read (n_out)."""
+    assert column_of.is_cuda and column_of.dim() == 2
+    G, n = int(column_of.shape[0]), int(column_of.shape[1])
+    dev = column_of.device
+    flat = column_of.t().contiguous().reshape(-1).to(torch.int64)                     # entry e = s * G + g
+    assert G * n == 0 or int(flat.min().item()) >= -1, "a column_of entry is below -1"
+    keep = flat >= 0
+    cols = flat[keep]
+    series = torch.div(torch.arange(G * n, device=dev), max(G, 1), rounding_mode="floor")[keep]
+    nnz = int(cols.numel())
+    n_out = int(cols.max().item()) + 1 if nnz else 0
+    assert n_out <= 2**31 - 1 and nnz <= 2**31 - 1, "n_out and nnz are limited to 2^31 - 1"
+    order = torch.sort(cols, stable=True).indices
+    offsets = torch.zeros(n_out + 1, dtype=torch.int64, device=dev)
+    if nnz:
+        offsets[1:] = torch.cumsum(torch.bincount(cols, minlength=n_out), 0)
+    return {"col_offsets": offsets.to(torch.int32), "members": series[order].to(torch.int32).contiguous(), "n_out": n_out, "nnz": nnz}
+
+
+def aggregate_block(y: torch.Tensor, lengths: torch.Tensor, column_of, *, first: torch.Tensor | None = None,
+                    valid: torch.Tensor | None = None, present: torch.Tensor | None = None, n_series: int | None = None,
+                    t_out: int | None = None, route: str | int = "auto", tile_min_members: int = 0, out: dict | None = None,
+                    stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_hierarchy_device on torch tensors: ts_aggregate_hierarchy's sums of a resident block, no host round trip.
+
+    y [t_rows, ld] fp64 time-major, left-aligned with lengths int32 [>= n_series]; first int64 [>= n_series]: the position of each
+    series' row 0 on a common date grid (None: all 0); valid / present [t_rows, ld] uint8 or bool (valid 0 = NULL: counts as 0.0, the
+    row exists; present 0 = no row there) -- all on one HIP device, contiguous.  column_of: an int tensor [n_groupings, n_series] with
+    the output column of every series under every grouping (-1: none; the plan is then made on the device, hierarchy_plan_device), or
+    a ready-made plan {"col_offsets", "members", "n_out"} of device tensors.  Output column c is the sum of its members in ascending
+    series order, every cell one serial chain from +0.0: the bits of the operator on a table that arrives in series order per date.
+    route "auto" / "lane" / "tile" (lib.HIERARCHY_ROUTES) gives the same bits.
+
+    Without t_out a sizing call runs first (one device-to-host read of the lengths); it raises when a column is marked -1 (a member
+    outside the block, a span above 2^30 rows).  `out` may bring "y", "present" ([t_out, ld_out]), "lengths" (int32 [ld_out]) and
+    "first" (int64 [ld_out]); else they are allocated zero-filled with ld_out = n_out rounded up to 64.
+
+    Returns {"y", "present", "lengths", "first", "t_out", "n_out"}.  DeviceBatch(n_out, t_out, opts).set_block(r["y"], r["lengths"])
+    takes the result as it is when no column has a hole (r["present"] is 1 in every row below the column's length)."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    dev = y.device
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    if first is not None:
+        assert first.dtype == torch.int64 and first.is_cuda and first.is_contiguous() and first.numel() >= n
+    masks = []
+    for m in (valid, present):
+        if m is not None:
+            if m.dtype == torch.bool:
+                m = m.to(torch.uint8)
+            assert m.dtype == torch.uint8 and m.is_cuda and m.is_contiguous() and tuple(m.shape) == (t_rows, ld)
+        masks.append(m)
+    valid, present = masks
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    if isinstance(column_of, dict):
+        plan = column_of
+    else:
+        assert int(column_of.shape[-1]) == n, "column_of has one entry per series and grouping"
+        plan = hierarchy_plan_device(column_of.reshape(-1, n))
+    offsets, members, n_out = plan["col_offsets"], plan["members"], int(plan["n_out"])
+    nnz = int(plan.get("nnz", members.numel()))
+    assert offsets.dtype == torch.int32 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= n_out + 1
+    assert members.dtype == torch.int32 and members.is_cuda and members.is_contiguous() and members.numel() >= nnz
+    opts = _lib.make_hierarchy_options(route, tile_min_members)
+    out = dict(out or {})
+    yo, po, len_out, first_out = out.get("y"), out.get("present"), out.get("lengths"), out.get("first")
+    ld_out = int(yo.shape[1]) if yo is not None else max((n_out + 63) // 64 * 64, 64)
+    if len_out is None:
+        len_out = torch.zeros(ld_out, dtype=torch.int32, device=dev)
+    if first_out is None:
+        first_out = torch.zeros(ld_out, dtype=torch.int64, device=dev)
+    assert len_out.dtype == torch.int32 and len_out.is_cuda and len_out.numel() >= n_out
+    assert first_out.dtype == torch.int64 and first_out.is_cuda and first_out.numel() >= n_out
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+
+    def call(rows, y_o, p_o):
+        err = _lib.AnofoxError()
+        ok = L.anofox_hip_hierarchy_device(y.data_ptr(), ptr(valid), ptr(present), ld, lengths.data_ptr(), ptr(first), n, t_rows,
+                                           offsets.data_ptr(), members.data_ptr(), n_out, nnz, C.byref(opts), C.sizeof(opts), rows,
+                                           ptr(y_o), ptr(p_o), ld_out, len_out.data_ptr(), first_out.data_ptr(),
+                                           C.c_void_p(st.cuda_stream), C.byref(err))
+        if not ok:
+            raise RuntimeError(f"anofox_hip_hierarchy_device failed: [{err.code}] {err.message.decode()}")
+
+    if t_out is None and yo is not None:
+        t_out = int(yo.shape[0])
+    if t_out is None:
+        call(0, None, None)
+        st.synchronize()
+        sized = len_out[:n_out]
+        if n_out and int(sized.min().item()) < 0:
+            raise ValueError("aggregate_block: a column has a member outside the block, a first position above 2^61 or a span above "
+                             "the limit of 2^30 rows (lengths -1)")
+        t_out = max(1, int(sized.max().item())) if n_out else 1
+    t_out = int(t_out)
+    if yo is None:
+        yo = torch.zeros((t_out, ld_out), dtype=torch.float64, device=dev)
+    if po is None:
+        po = torch.zeros((t_out, ld_out), dtype=torch.uint8, device=dev)
+    for t, dt in ((yo, torch.float64), (po, torch.uint8)):
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (t_out, ld_out) and ld_out >= n_out
+    call(t_out, yo, po)
+    return {"y": yo, "present": po, "lengths": len_out, "first": first_out, "t_out": t_out, "n_out": n_out}
+
+
 class DeviceBatch:
     """anofox_hip_batch_* over torch-owned HBM."""
 

@@ -326,6 +326,15 @@ assert C.sizeof(AnofoxHipFold) == 40
 BACKTEST_WINDOWS = {"expanding": 0, "fixed": 1, "sliding": 2}      # window_type of anofox_hip_backtest_folds
 
 
+class AnofoxHipHierarchyOptions(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipHierarchyOptions: route and the member count of the automatic choice (16 bytes)."""
+    _fields_ = [("route", C.c_int32), ("tile_min_members", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+assert C.sizeof(AnofoxHipHierarchyOptions) == 16
+HIERARCHY_ROUTES = {"auto": 0, "lane": 1, "tile": 2}      # include/anofox_fcst_hip.h ANOFOX_HIERARCHY_ROUTE_*
+
+
 assert C.sizeof(ExogenousRegressor) == 32 and C.sizeof(ExogenousData) == 16 and C.sizeof(ForecastOptionsExog) == 192
 MODEL_CODE_ARIMAX = 50             # include/anofox_fcst_hip.h: model_code of a series the ARIMAX path forecast
 
@@ -374,6 +383,7 @@ EXPORTED_SYMBOLS = [
     "anofox_free_conformal_result", "anofox_free_conformal_multi_result", "anofox_free_calibration_profile", "anofox_free_prediction_intervals",
     "anofox_hip_backtest_folds", "anofox_hip_backtest_sizes", "anofox_hip_backtest_expand_device", "anofox_hip_backtest_collect_device",
     "anofox_hip_backtest_batch",
+    "anofox_hip_hierarchy_plan", "anofox_hip_hierarchy_device", "anofox_hip_hierarchy_batch",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -634,6 +644,19 @@ def load():
     L.anofox_hip_backtest_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(ForecastOptions), C.c_void_p, C.c_size_t, C.c_char_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             P(AnofoxError)]
+    # block 6: aggregation up a key hierarchy
+    L.anofox_hip_hierarchy_plan.restype = C.c_bool
+    L.anofox_hip_hierarchy_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, P(C.c_size_t), P(C.c_size_t), C.c_void_p, C.c_void_p,
+                                            P(AnofoxError)]
+    L.anofox_hip_hierarchy_device.restype = C.c_bool
+    L.anofox_hip_hierarchy_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, P(AnofoxHipHierarchyOptions), C.c_size_t,
+                                              C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              P(AnofoxError)]
+    L.anofox_hip_hierarchy_batch.restype = C.c_bool
+    L.anofox_hip_hierarchy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             P(AnofoxHipHierarchyOptions), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -705,6 +728,34 @@ def backtest_sizes(folds, n_folds, n_series):
     if not load().anofox_hip_backtest_sizes(folds, n_folds, n_series, C.byref(t), C.byref(n), C.byref(ld), C.byref(err)):
         raise ValueError(f"anofox_hip_backtest_sizes failed: [{err.code}] {err.message.decode()}")
     return t.value, n.value, ld.value
+
+
+def make_hierarchy_options(route="auto", tile_min_members=0):
+    """AnofoxHipHierarchyOptions: route in HIERARCHY_ROUTES (or its code), tile_min_members 0 = the library's default."""
+    o = AnofoxHipHierarchyOptions()
+    o.route = HIERARCHY_ROUTES[route] if isinstance(route, str) else int(route)
+    o.tile_min_members = int(tile_min_members)
+    return o
+
+
+def hierarchy_plan(column_of, n_series=None):
+    """anofox_hip_hierarchy_plan: column_of int32 [n_groupings, n_series] (-1: none) -> (n_out, col_offsets int32 [n_out + 1], members
+    int32 [nnz]), the members of a column ordered by (series, grouping).  Host only, no device."""
+    import numpy as np
+    co = np.ascontiguousarray(column_of, dtype=np.int32)
+    if co.ndim == 1:
+        co = co.reshape(1, -1) if n_series is None else co.reshape(-1, int(n_series))
+    G, n = co.shape
+    L = load()
+    n_out, nnz = C.c_size_t(), C.c_size_t()
+    err = AnofoxError()
+    if not L.anofox_hip_hierarchy_plan(co.ctypes.data, G, n, C.byref(n_out), C.byref(nnz), None, None, C.byref(err)):
+        raise ValueError(f"anofox_hip_hierarchy_plan failed: [{err.code}] {err.message.decode()}")
+    offs = np.zeros(n_out.value + 1, dtype=np.int32)
+    memb = np.zeros(max(nnz.value, 1), dtype=np.int32)
+    if not L.anofox_hip_hierarchy_plan(co.ctypes.data, G, n, C.byref(n_out), C.byref(nnz), offs.ctypes.data, memb.ctypes.data, C.byref(err)):
+        raise ValueError(f"anofox_hip_hierarchy_plan failed: [{err.code}] {err.message.decode()}")
+    return n_out.value, offs, memb[:nnz.value]
 
 
 def make_prep_options(gaps=False, frequency_micros=0, frequency_type="FIXED", trim="none", fill="none", fill_value=0.0):

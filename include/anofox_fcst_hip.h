@@ -1758,6 +1758,119 @@ bool anofox_hip_backtest_batch(const double *const *values,
                                double *out_scores,
                                struct AnofoxError *out_batch_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 6: ts_aggregate_hierarchy on the device                               */
+/* ------------------------------------------------------------------------- */
+/*
+ * The operator (ts_aggregate_hierarchy.cpp:246-386) adds every row's value to one cell (unique_id, date) per level in the order the
+ * rows arrive: a cell is ((0.0 + v_a) + v_b) + ... over its rows in table order, and exists only if a row reached it.  These entries
+ * restate that on a time-major block: series s holds consecutive positions first[s] .. first[s] + lengths[s] - 1 of a common date
+ * grid, and output column c is the sum over members[col_offsets[c] .. col_offsets[c + 1]) IN THAT ORDER (a series listed twice is
+ * added twice, one after the other).  The contract is equality of bits with that chain: additions only, from +0.0 (so -0.0 never
+ * comes out), no level built from another level's sums.  The groupings are arbitrary, not only key prefixes.
+ */
+enum { ANOFOX_HIERARCHY_ROUTE_AUTO = 0, ANOFOX_HIERARCHY_ROUTE_LANE = 1, ANOFOX_HIERARCHY_ROUTE_TILE = 2 };
+typedef struct AnofoxHipHierarchyOptions {
+    int32_t route;               /* 0: by member count; 1: lane per output column; 2: LDS tiles, one wavefront per (column, 64 rows).  Same bits. */
+    int32_t tile_min_members;    /* route 0: columns with at least this many members take the tile route; 0: the built-in default (64) */
+    int32_t reserved[2];         /* 0 */
+} AnofoxHipHierarchyOptions;
+
+/*
+ * The CSR plan of a table of groupings.  column_of int32 [n_groupings x n_series]: column_of[g * n_series + s] is the output column
+ * of series s under grouping g, -1 for none.  *n_out = the largest column + 1; *nnz = the entries that are not -1; col_offsets int32
+ * [n_out + 1]; members int32 [nnz], within a column ordered by (series, grouping) -- the order in which the operator's rows (a row,
+ * then its levels) reach the cell; a stable counting sort.  A column nobody maps to is empty.  col_offsets and members may both be
+ * NULL: the sizing call.  INVALID_INPUT: an entry below -1, n_out or nnz above 2^31 - 1, n_series above 2^31 - 1.  Host only.
+ */
+bool anofox_hip_hierarchy_plan(const int32_t *column_of,
+                               size_t n_groupings,
+                               size_t n_series,
+                               size_t *n_out,
+                               size_t *nnz,
+                               int32_t *col_offsets,
+                               int32_t *members,
+                               struct AnofoxError *out_error);
+
+/*
+ * Aggregates a device-resident block y[t * ld + s] (fp64, t < t_rows, left-aligned with lengths int32 [n_series], cut to t_rows).
+ * first int64 [n_series]: the grid position of each series' row 0 (NULL: all 0; |first| <= 2^61).  valid / present uint8
+ * [t_rows x ld], each may be NULL: valid 0 is a NULL value -- it counts as 0.0 and the row exists (:291); present 0 means there is
+ * no row at that position -- it adds nothing and does not make the cell exist.  col_offsets, members: the plan, in device memory.
+ *
+ * Outputs, all in device memory: lengths_out int32 [n_out] and first_out int64 [n_out] -- a column spans the smallest to the largest
+ * grid position at which a member has a row (length 0, first 0 when there is none); y_out [t_out x ld_out] time-major, left-aligned,
+ * and present_out uint8 [t_out x ld_out] (may be NULL): 0 and 0.0 where no member has a row inside the span, and in rows
+ * lengths_out[c] .. t_out - 1.  ld_out >= n_out (n_out rounded up to 64 is what the batch layer takes); columns >= n_out are not
+ * touched; rows >= t_out of a longer column are not written (lengths_out says so).  t_out = 0 (or y_out NULL) writes only
+ * lengths_out and first_out: the sizing call, as in anofox_hip_prepare_device.  y_out and lengths_out are what
+ * anofox_hip_batch_set_device_block takes when no column has a hole.
+ *
+ * The call only enqueues on `stream` (NULL: the null stream) and does NOT wait on the host.  What only the device can see is
+ * therefore reported in lengths_out: a column whose offsets leave the plan, that has a member outside [0, n_series) or a |first|
+ * above 2^61, or whose span exceeds 2^30 rows has length -1 and is written as an empty column -- never a cut sum.
+ * INVALID_INPUT on the host: struct_size, an unknown route, ld < n_series, ld_out < n_out, n_out / nnz / n_series above 2^31 - 1,
+ * t_rows or t_out above 2^30.
+ */
+bool anofox_hip_hierarchy_device(const double *y,
+                                 const uint8_t *valid,
+                                 const uint8_t *present,
+                                 size_t ld,
+                                 const int32_t *lengths,
+                                 const int64_t *first,
+                                 size_t n_series,
+                                 size_t t_rows,
+                                 const int32_t *col_offsets,
+                                 const int32_t *members,
+                                 size_t n_out,
+                                 size_t nnz,
+                                 const AnofoxHipHierarchyOptions *options,
+                                 size_t struct_size,
+                                 size_t t_out,
+                                 double *y_out,
+                                 uint8_t *present_out,
+                                 size_t ld_out,
+                                 int32_t *lengths_out,
+                                 int64_t *first_out,
+                                 void *stream,
+                                 struct AnofoxError *out_error);
+
+/*
+ * The same for series held on the host -- what the operator's finalize would call instead of its map of maps: values[s] points to
+ * lengths[s] values at grid positions first[s] + t (first may be NULL); validity[s] / present[s] are bit masks in DuckDB's layout
+ * (bit t % 64 of word t / 64; 1 = valid / there is a row), each array and each entry may be NULL (= all ones).  column_of as for
+ * anofox_hip_hierarchy_plan.  The call plans, sizes on the host, uploads, runs and reads back once.
+ *
+ * *out_n_out, *out_t_out (the longest column, at least 1) and *out_ld (n_out rounded up to 64, at least 64) are always written.
+ * With out_y NULL that is all: the sizing call, which needs no device.  Otherwise t_out and ld_out must be what the sizing call
+ * returned and the caller's arrays receive out_y fp64 [t_out x ld_out] and out_present uint8 [t_out x ld_out] (time-major, as on the
+ * device; may be NULL), out_lengths int32 [n_out], out_first int64 [n_out].
+ *
+ * INVALID_INPUT, each naming its limit: n_out or nnz above 2^31 - 1, a column_of entry below -1, a series longer than 2^30 rows, a
+ * |first| above 2^61, a column whose span exceeds 2^30 rows.  A failed device allocation is a COMPUTATION_ERROR that names the
+ * size.  One device (the calling thread's current one); fp64 only.
+ */
+bool anofox_hip_hierarchy_batch(const double *const *values,
+                                const uint64_t *const *validity,
+                                const uint64_t *const *present,
+                                const size_t *lengths,
+                                const int64_t *first,
+                                size_t n_series,
+                                const int32_t *column_of,
+                                size_t n_groupings,
+                                const AnofoxHipHierarchyOptions *options,
+                                size_t struct_size,
+                                size_t t_out,
+                                size_t ld_out,
+                                double *out_y,
+                                uint8_t *out_present,
+                                int32_t *out_lengths,
+                                int64_t *out_first,
+                                size_t *out_n_out,
+                                size_t *out_t_out,
+                                size_t *out_ld,
+                                struct AnofoxError *out_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
