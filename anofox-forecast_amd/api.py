@@ -633,6 +633,56 @@ def inspect_batch(series, opts, valids=None):
         L.anofox_hip_batch_destroy(hb)
 
 
+ARIMA_FIT_INTS = ("status", "model_code", "seasonal_period", "p", "d", "q", "P", "D", "Q", "has_constant", "n_diff", "models_tried", "evals")
+
+
+def arima_fit_record(x):
+    """An AnofoxHipArimaFit as a dict (coefficient groups as float64 arrays)."""
+    d = {k: int(getattr(x, k)) for k in ARIMA_FIT_INTS}
+    d.update({k: np.array(getattr(x, k)[:], dtype=np.float64) for k in ("phi", "theta", "Phi", "Theta")})
+    d.update(constant=float(x.constant), aicc=float(x.aicc))
+    return d
+
+
+def arima_fit_batch(series, opts, method=None, valids=None):
+    """Fit an AutoARIMA batch and read the selected fits back (anofox_hip_batch_arima_fit): per series a dict with the forecast
+    result, the orders, the coefficients as the recursion reads them, the AICc and the search counters.  `method`: lib.ARIMA_CSS
+    or lib.ARIMA_CSS_ML for this batch (default: the one in force)."""
+    L = _lib.load()
+    n = len(series)
+    arrs = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    t_max = max((len(a) for a in arrs), default=0)
+    hb, err = C.c_void_p(), _lib.AnofoxError()
+    if not L.anofox_hip_batch_create(n, t_max, C.byref(opts), C.byref(hb), C.byref(err)):
+        raise InvalidInputException(err.message.decode(errors="replace"))
+    try:
+        if method is not None and not L.anofox_hip_batch_set_arima_method(hb, int(method), C.byref(err)):
+            raise InvalidInputException(err.message.decode(errors="replace"))
+        masks = [validity_mask(v) for v in valids] if valids is not None else None
+        vptr = (C.c_void_p * n)(*[a.ctypes.data if len(a) else _EMPTY_SERIES_ADDR for a in arrs])
+        mptr = (C.c_void_p * n)(*[m.ctypes.data if len(m) else None for m in masks]) if masks is not None else None
+        lens = (C.c_size_t * n)(*[len(a) for a in arrs])
+        if not L.anofox_hip_batch_pack_host(hb, vptr, mptr, lens, C.byref(err)) or not L.anofox_hip_batch_run(hb, None, C.byref(err)):
+            raise InvalidInputException(err.message.decode(errors="replace"))
+        results = (_lib.ForecastResult * n)()
+        errors = (_lib.AnofoxError * n)()
+        L.anofox_hip_batch_fetch(hb, results, errors)
+        fits = (_lib.AnofoxHipArimaFit * n)()
+        if not L.anofox_hip_batch_arima_fit(hb, fits, C.byref(err)):
+            raise InvalidInputException(err.message.decode(errors="replace"))
+        out = []
+        for i in range(n):
+            d = {"ok": errors[i].code == 0, "code": int(errors[i].code), "message": errors[i].message.decode(errors="replace")}
+            if d["ok"]:
+                d.update(_result_dict(results[i], len(arrs[i])))
+                L.anofox_free_forecast_result(C.byref(results[i]))
+            d.update(arima_fit_record(fits[i]))
+            out.append(d)
+        return out
+    finally:
+        L.anofox_hip_batch_destroy(hb)
+
+
 def _collect_groups(group, date, target):
     """Groups in first-appearance order, rows by date, NULL targets as invalid slots (the LIST(... ORDER BY date) of the macros)."""
     dates = np.asarray(date)

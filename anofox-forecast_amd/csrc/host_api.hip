@@ -2588,6 +2588,65 @@ bool anofox_hip_batch_inspect(AnofoxHipBatch *b, AnofoxHipInspection *out, doubl
     return true;
 }
 
+// The selected AutoARIMA fit of every series of the last run: orders, the coefficients as the recursion reads them (ar_pacf's box clip
+// of the optimiser's coordinates, applied here), criterion and search counters.  Copies only; no kernel runs.
+bool anofox_hip_batch_arima_fit(AnofoxHipBatch *b, AnofoxHipArimaFit *out, AnofoxError *out_error)
+{
+    if (!b || !out) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!b->ran) { set_error(out_error, INVALID_INPUT, "Invalid input: the batch has not been run"); return false; }
+    if (b->plan.model != M_AutoARIMA) { set_error(out_error, INVALID_INPUT, "Invalid input: the ARIMA fit readback needs an AutoARIMA batch"); return false; }
+    DeviceGuard guard(b->dev);
+    const size_t n = b->n, ld = b->ld;
+    try {
+        if (b->h_period.size() < n) throw HipFail{"the batch has no series block"};
+        for (size_t s = 1; s < n; s++)
+            if (b->h_period[s] != b->h_period[0]) throw HipFail{"the ARIMA fit readback needs one seasonal period for the whole batch"};
+        HIPCHECK(hipStreamSynchronize(b->last_stream));
+        std::vector<int32_t> code(n), status(n), ord(5 * ld), dd(n), DD(n), wlen(n), models(n), evals(n);
+        std::vector<double> x(6 * ld), aicc(n);
+        HIPCHECK(hipMemcpy(code.data(), b->d_model_code, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(status.data(), b->d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(ord.data(), b->ar_order, 5 * ld * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(dd.data(), b->ar_d, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(DD.data(), b->ar_D, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(wlen.data(), b->ar_wlen, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(models.data(), b->ar_models, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(evals.data(), b->d_evals_total, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(x.data(), b->ar_x, 6 * ld * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(aicc.data(), b->ar_aicc, n * sizeof(double), hipMemcpyDeviceToHost));
+        const double nan = std::nan("");
+        for (size_t s = 0; s < n; s++) {
+            AnofoxHipArimaFit &o = out[s];
+            std::memset(&o, 0, sizeof o);
+            o.status = status[s]; o.model_code = code[s]; o.seasonal_period = b->h_period[s];
+            if (!(status[s] == 0 && code[s] >= 1000000)) {      // nothing was fitted (or the fallback chain forecast it): no stale values
+                for (double &v : o.phi) v = nan;
+                for (double &v : o.theta) v = nan;
+                o.Phi[0] = o.Phi[1] = o.Theta[0] = o.Theta[1] = o.constant = o.aicc = nan;
+                continue;
+            }
+            o.p = ord[0 * ld + s]; o.q = ord[1 * ld + s]; o.P = ord[2 * ld + s]; o.Q = ord[3 * ld + s]; o.has_constant = ord[4 * ld + s];
+            o.d = dd[s]; o.D = DD[s];
+            o.n_diff = wlen[s]; o.models_tried = models[s]; o.evals = evals[s];
+            auto box = [](double a) { return a < -0.99 ? -0.99 : (a > 0.99 ? 0.99 : a); };      // arima.hip AR_COEF_BOX
+            size_t k = 0;
+            for (int i = 0; i < o.p && i < 5; i++) o.phi[i] = box(x[(k++) * ld + s]);
+            for (int i = 0; i < o.q && i < 5; i++) o.theta[i] = box(x[(k++) * ld + s]);
+            for (int i = 0; i < o.P && i < 2; i++) o.Phi[i] = box(x[(k++) * ld + s]);
+            for (int i = 0; i < o.Q && i < 2; i++) o.Theta[i] = box(x[(k++) * ld + s]);
+            o.constant = (o.has_constant && k < 6) ? x[k * ld + s] : 0.0;
+            o.aicc = aicc[s];
+        }
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    } catch (const std::exception &e) {
+        set_error(out_error, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
+        return false;
+    }
+    return true;
+}
+
 // one plan, one device batch: create, pack, run, fetch (the whole of the batch entry unless periods are auto-detected)
 static bool forecast_batch_uniform(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
                                    const ForecastOptions *options, const int *horizons, ForecastResult *out_results,

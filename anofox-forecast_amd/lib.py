@@ -347,6 +347,17 @@ class AnofoxHipInspection(C.Structure):
                 ("level", C.c_double), ("trend", C.c_double)]
 
 
+class AnofoxHipArimaFit(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipArimaFit: the selected AutoARIMA fit of one series (184 bytes)."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "model_code", "seasonal_period", "p", "d", "q", "P", "D", "Q", "has_constant",
+                                         "n_diff", "models_tried", "evals", "reserved")] + \
+               [("phi", C.c_double * 5), ("theta", C.c_double * 5), ("Phi", C.c_double * 2), ("Theta", C.c_double * 2),
+                ("constant", C.c_double), ("aicc", C.c_double)]
+
+
+assert C.sizeof(AnofoxHipArimaFit) == 184
+
+
 EXPORTED_SYMBOLS = [
     "anofox_ts_forecast", "anofox_free_forecast_result", "anofox_fcst_version", "anofox_ts_forecast_batch",
     "anofox_hip_device_count", "anofox_hip_set_device", "anofox_hip_batch_create", "anofox_hip_batch_destroy",
@@ -354,7 +365,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_batch_stats", "anofox_hip_batch_device_results", "anofox_hip_batch_fetch", "anofox_hip_model_name", "anofox_hip_batch_model_name",
     "anofox_hip_ingest_create", "anofox_hip_ingest_destroy", "anofox_hip_ingest_append", "anofox_hip_ingest_finish",
     "anofox_hip_ingest_group_keys", "anofox_hip_ingest_last_dates", "anofox_hip_ingest_lengths", "anofox_hip_ingest_values",
-    "anofox_hip_ingest_validity", "anofox_hip_batch_pack_ingest", "anofox_hip_batch_inspect",
+    "anofox_hip_ingest_validity", "anofox_hip_batch_pack_ingest", "anofox_hip_batch_inspect", "anofox_hip_batch_arima_fit",
     "anofox_hip_batch_n_series", "anofox_hip_batch_periods", "anofox_hip_batch_set_fixed_params",
     "anofox_hip_set_devices", "anofox_hip_get_devices", "anofox_hip_set_min_series_per_device", "anofox_hip_shard_range",
     "anofox_hip_set_default_arima_method", "anofox_hip_batch_set_arima_method", "anofox_hip_release_caches",
@@ -449,6 +460,8 @@ def load():
     L.anofox_hip_batch_model_name.restype = None
     L.anofox_hip_batch_inspect.restype = C.c_bool
     L.anofox_hip_batch_inspect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(AnofoxError)]
+    L.anofox_hip_batch_arima_fit.restype = C.c_bool
+    L.anofox_hip_batch_arima_fit.argtypes = [C.c_void_p, C.c_void_p, P(AnofoxError)]
     L.anofox_hip_set_devices.restype = C.c_bool
     L.anofox_hip_set_devices.argtypes = [C.c_void_p, C.c_size_t]
     L.anofox_hip_get_devices.restype = C.c_size_t

@@ -1576,6 +1576,34 @@ bool anofox_hip_batch_inspect(AnofoxHipBatch *batch, AnofoxHipInspection *out,
                               double *fitted, double *seasonal, size_t seasonal_stride,
                               struct AnofoxError *out_error);
 
+/*
+ * The selected AutoARIMA fit of every series of a batch that has been run: what a caller needs to evaluate the model itself.
+ * Waits for the run; copies only, no kernel runs.  The coefficients are the ones the recursion reads -- the optimiser's
+ * coordinates clipped to the box [-0.99, 0.99] -- in the convention (1 - phi(B))(1 - Phi(B^m)) w'_t = (1 - theta(B))(1 - Theta(B^m)) e_t
+ * with w' = w - constant on the differenced series w (seasonal difference first, then the d ordinary ones); slots beyond the
+ * orders are 0.0.  `aicc` is the criterion of the conditional sum of squares the model was selected and polished with,
+ * n_diff log(css / (n_diff - p - m P)) + 2 k + 2 k (k + 1) / (n_diff - k - 1), k = p + q + P + Q + has_constant + 1; after an
+ * ANOFOX_ARIMA_CSS_ML run the coefficients are the exact-likelihood refit's and `aicc` is still the CSS run's.  It reports what
+ * the LAST run left.  A series nothing was fitted to (status != 0, or a model_code below 1000000) has zero orders and counters
+ * and NaN in every double.  False with an error when the batch's model is not AutoARIMA, has not been run, or does not have one
+ * seasonal period.
+ */
+typedef struct AnofoxHipArimaFit {
+    int32_t status;          /* ErrorCode of the series */
+    int32_t model_code;      /* as in anofox_hip_batch_device_results */
+    int32_t seasonal_period; /* the period the series was fitted with */
+    int32_t p, d, q, P, D, Q;
+    int32_t has_constant;
+    int32_t n_diff;          /* length of the differenced series: n - d - D m */
+    int32_t models_tried;    /* candidates of the stepwise search */
+    int32_t evals;           /* objective evaluations of the search, the polish and the refit */
+    int32_t reserved;
+    double phi[5], theta[5], Phi[2], Theta[2];
+    double constant;         /* mean of the differenced series (0.0 without a constant) */
+    double aicc;
+} AnofoxHipArimaFit;
+bool anofox_hip_batch_arima_fit(AnofoxHipBatch *batch, AnofoxHipArimaFit *out, struct AnofoxError *out_error);
+
 /* Render a device model_code to the reference's model_name text (<= 63 chars). */
 void anofox_hip_model_name(const struct ForecastOptions *options, int32_t model_code,
                            char out_name[64]);

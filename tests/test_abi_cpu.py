@@ -53,7 +53,7 @@ int main(void) {
 
 def test_additive_structs_match_their_ctypes_mirrors(hiplib):
     """The backend's own structs (AnofoxHipStats -- round 6: `reserved` became `y_storage`, same place --, AnofoxHipLaneStats,
-    AnofoxHipInspection): size and the offsets that matter, as gcc lays out include/anofox_fcst_hip.h against lib.py's ctypes mirrors."""
+    AnofoxHipInspection, AnofoxHipArimaFit): size and the offsets that matter, as gcc lays out include/anofox_fcst_hip.h against lib.py's ctypes mirrors."""
     src = r"""
 #include <stdio.h>
 #include <stddef.h>
@@ -62,6 +62,9 @@ int main(void) {
   printf("%zu %zu %zu %zu %zu\n", sizeof(AnofoxHipStats), offsetof(AnofoxHipStats, fit_kernel_launches), offsetof(AnofoxHipStats, y_storage),
          offsetof(AnofoxHipStats, total_iters), offsetof(AnofoxHipStats, min_pass_bytes));
   printf("%zu %zu\n", sizeof(AnofoxHipLaneStats), sizeof(AnofoxHipInspection));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(AnofoxHipArimaFit), offsetof(AnofoxHipArimaFit, seasonal_period), offsetof(AnofoxHipArimaFit, p),
+         offsetof(AnofoxHipArimaFit, Q), offsetof(AnofoxHipArimaFit, has_constant), offsetof(AnofoxHipArimaFit, n_diff), offsetof(AnofoxHipArimaFit, evals),
+         offsetof(AnofoxHipArimaFit, phi), offsetof(AnofoxHipArimaFit, Phi), offsetof(AnofoxHipArimaFit, constant), offsetof(AnofoxHipArimaFit, aicc));
   return 0; }"""
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "t.c"), "w").write(src)
@@ -70,6 +73,12 @@ int main(void) {
     S = hiplib.AnofoxHipStats
     assert out[0] == f"{C.sizeof(S)} {S.fit_kernel_launches.offset} {S.y_storage.offset} {S.total_iters.offset} {S.min_pass_bytes.offset}"
     assert out[1] == f"{C.sizeof(hiplib.AnofoxHipLaneStats)} {C.sizeof(hiplib.AnofoxHipInspection)}"
+    A = hiplib.AnofoxHipArimaFit
+    assert out[2] == " ".join(str(v) for v in [C.sizeof(A)] + [getattr(A, f).offset for f in (
+        "seasonal_period", "p", "Q", "has_constant", "n_diff", "evals", "phi", "Phi", "constant", "aicc")])
+    assert out[2] == "184 8 12 32 36 40 48 56 136 168 176"
+    assert [f for f, _ in A._fields_] == ["status", "model_code", "seasonal_period", "p", "d", "q", "P", "D", "Q", "has_constant", "n_diff",
+                                          "models_tried", "evals", "reserved", "phi", "theta", "Phi", "Theta", "constant", "aicc"]
 
 
 def test_no_gpu_fails_loudly(hiplib):
@@ -118,6 +127,8 @@ def test_device_list_api_without_a_gpu(hiplib):
     assert L.anofox_hip_set_default_arima_method(1) and L.anofox_hip_set_default_arima_method(0) and not L.anofox_hip_set_default_arima_method(2)
     err = hiplib.AnofoxError()
     assert not L.anofox_hip_batch_set_arima_method(None, 0, C.byref(err)) and err.code == hiplib.NULL_POINTER
+    err = hiplib.AnofoxError()
+    assert not L.anofox_hip_batch_arima_fit(None, None, C.byref(err)) and err.code == hiplib.NULL_POINTER
     assert not L.anofox_hip_batch_run_many(None, 1, None)
 
 
