@@ -38,6 +38,7 @@ namespace {
 constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which every problem runs on a wave of its own in one launch
 
 #include "host_resources.hpp"     // HipFail / HIPCHECK, the tunables, DeviceGuard, the device / pinned / stream caches, the device list
+#include "host_scratch.hpp"       // Scratch (a call's device blocks), the shape and packing of a batch of series, the _device entry's checks and launch
 
 struct Plan {
     ModelType model;
@@ -1988,7 +1989,7 @@ bool anofox_hip_set_default_arima_method(int method)
 
 bool anofox_hip_batch_set_arima_method(AnofoxHipBatch *b, int method, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!b) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (method != ANOFOX_ARIMA_CSS && method != ANOFOX_ARIMA_CSS_ML) {
         set_error(out_error, INVALID_INPUT, "Invalid input: unknown ARIMA estimation method (0 = CSS, 1 = CSS-ML)");
@@ -2001,7 +2002,7 @@ bool anofox_hip_batch_set_arima_method(AnofoxHipBatch *b, int method, AnofoxErro
 bool anofox_hip_batch_create(size_t n_series, size_t t_max, const ForecastOptions *options, AnofoxHipBatch **out_batch,
                              AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!options || !out_batch) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     Plan plan;
     if (!make_plan(options, plan, out_error)) return false;
@@ -2090,7 +2091,7 @@ bool anofox_hip_batch_periods(const AnofoxHipBatch *b, int32_t *out_periods)
 
 bool anofox_hip_batch_set_fixed_params(AnofoxHipBatch *b, double alpha, double beta, double gamma, double phi, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!b) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!(b->plan.model == M_ETS && b->plan.ets_spec_id >= 0)) {
         set_error(out_error, INVALID_INPUT, "Invalid input: fixed smoothing parameters need model 'ETS' with an explicit ets_model");
@@ -2446,7 +2447,7 @@ bool anofox_hip_batch_fetch(AnofoxHipBatch *b, ForecastResult *out_results, Anof
     for (size_t s = s_lo; s < s_hi; s++) {
         ForecastResult &r = out_results[s];
         std::memset(&r, 0, sizeof r);
-        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        if (out_errors) clear_error(&out_errors[s]);
         if (status[s] == STATUS_NOT_COMPUTED) status[s] = INTERNAL_ERROR;
         if (status[s] != 0) {
             if (out_errors) set_error(&out_errors[s], status[s], series_error_message(b, s, status[s], detail[s]));
@@ -3132,7 +3133,7 @@ bool anofox_ts_forecast_batch(const double *const *values, const uint64_t *const
                               const ForecastOptions *options, const int *horizons, ForecastResult *out_results,
                               AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (!values || !lengths || !options || !out_results) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
     for (size_t s = 0; s < n_series; s++) {
         std::memset(&out_results[s], 0, sizeof(ForecastResult));
@@ -3285,7 +3286,7 @@ constexpr size_t COALESCE_MAX = 256;
 bool anofox_ts_forecast(const double *values, const uint64_t *validity, size_t length, const ForecastOptions *options,
                         ForecastResult *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !options || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     // argument errors come first, exactly like the reference (lib.rs:3368-3380, forecast.rs:514-565)
     {
@@ -3432,7 +3433,7 @@ bool anofox_hip_mstl_decompose_device(const double *y, size_t ld, const int32_t 
                                       const int *periods, size_t n_periods, int insufficient_data_mode, double *trend,
                                       double *seasonal, double *remainder, int32_t *info, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !trend || !remainder || !info || (n_periods > 0 && (!periods || !seasonal))) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
@@ -3465,21 +3466,15 @@ bool anofox_hip_mstl_decompose_device(const double *y, size_t ld, const int32_t 
     }
     a.trend = trend; a.remainder = remainder; a.seasonal = seasonal; a.info = info;
     hipStream_t st = (hipStream_t)stream;
-    try {
-        a.tab = rows ? dalloc<double>(rows * ld) : nullptr;
-        a.mean = dalloc<double>((size_t)MSTL_MAX_PERIODS * ld);
-        a.used = dalloc<int32_t>(ld);
-        (void)hipGetLastError();
+    Scratch scratch;
+    const bool ok = launch_and_wait("mstl", st, out_error, [&] {
+        a.tab = rows ? scratch.get<double>(rows * ld) : nullptr;
+        a.mean = scratch.get<double>((size_t)MSTL_MAX_PERIODS * ld);
+        a.used = scratch.get<int32_t>(ld);
         launch_mstl(a, st);
-        LAUNCHCHECK("mstl");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(a.tab, true); dev_free(a.mean, true); dev_free(a.used, true);
-    } catch (const HipFail &f) {
-        dev_free(a.tab); dev_free(a.mean); dev_free(a.used);        // (not quiesced: waits for the device first)
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_mstl_decompose_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
@@ -3487,17 +3482,14 @@ bool anofox_hip_mstl_decompose_batch(const double *const *values, const uint64_t
                                      double *out_seasonal, double *out_remainder, int32_t *out_periods, int32_t *out_applied,
                                      AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if ((n_series > 0 && (!values || !lengths || !out_applied)) || (n_periods > 0 && !periods)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    size_t total = 0, t_max = 0;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        total += lengths[s];
-        t_max = std::max(t_max, lengths[s]);
-    }
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, SIZE_MAX, &shape, out_batch_error)) return false;
+    const size_t total = shape.total;
     if (total > 0 && (!out_trend || !out_remainder || (n_periods > 0 && !out_seasonal))) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
@@ -3508,50 +3500,40 @@ bool anofox_hip_mstl_decompose_batch(const double *const *values, const uint64_t
         return false;
     }
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1), K = n_periods;
+    const size_t ld = shape.ld, T = shape.T, K = n_periods;
     std::vector<int> ps(periods, periods + n_periods);
     std::sort(ps.begin(), ps.end(), std::greater<int>());
     int min_period = 0;
     for (int p : ps) if (p > 0 && (min_period == 0 || p < min_period)) min_period = p;
-    double *d_y = nullptr, *d_trend = nullptr, *d_seas = nullptr, *d_rem = nullptr;
-    int32_t *d_len = nullptr, *d_info = nullptr;
-    // quiesced: on the success path the device entry has waited for its stream and the copies are synchronous; after a failure
-    // the first free waits for the device
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_trend, (void *)d_seas, (void *)d_rem, (void *)d_len, (void *)d_info}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    // settled once the device entry has waited for its stream and the synchronous copies are back
+    Scratch scratch;
     std::vector<int32_t> info(n_series);
     std::vector<double> trend, seas, rem;
     try {
         if (!device_ready(out_batch_error)) return false;
         // time-major block; a NULL counts as 0.0, as the reference's table function passes it (ts_mstl_decomposition_native.cpp:215)
         std::vector<double> yb(T * ld, 0.0);
-        std::vector<int32_t> len(ld, 0);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
         for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
             const uint64_t *m = validity ? validity[s] : nullptr;
-            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = (m && !((m[t >> 6] >> (t & 63)) & 1)) ? 0.0 : values[s][t];
+            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = (m && !valid_bit(m, t)) ? 0.0 : values[s][t];
         }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld); d_info = dalloc<int32_t>(ld);
-        d_trend = dalloc<double>(T * ld); d_rem = dalloc<double>(T * ld); d_seas = dalloc<double>(std::max<size_t>(K, 1) * T * ld);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld), *d_info = scratch.get<int32_t>(ld);
+        double *d_trend = scratch.get<double>(T * ld), *d_rem = scratch.get<double>(T * ld);
+        double *d_seas = scratch.get<double>(std::max<size_t>(K, 1) * T * ld);
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (!anofox_hip_mstl_decompose_device(d_y, ld, d_len, n_series, T, ps.data(), K, insufficient_data_mode, d_trend, d_seas, d_rem,
-                                              d_info, nullptr, out_batch_error)) {
-            release(false);
+                                              d_info, nullptr, out_batch_error))
             return false;
-        }
         trend.resize(T * ld); rem.resize(T * ld); seas.resize(K * T * ld);
         HIPCHECK(hipMemcpy(info.data(), d_info, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(trend.data(), d_trend, T * ld * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(rem.data(), d_rem, T * ld * sizeof(double), hipMemcpyDeviceToHost));
         if (K) HIPCHECK(hipMemcpy(seas.data(), d_seas, K * T * ld * sizeof(double), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -3561,7 +3543,7 @@ bool anofox_hip_mstl_decompose_batch(const double *const *values, const uint64_t
     for (size_t s = 0; s < n_series; s++) {
         const size_t n = lengths[s];
         const int state = info[s] >> 8, used = info[s] & 0xff;
-        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        if (out_errors) clear_error(&out_errors[s]);
         const bool applied = state == MSTL_APPLIED || state == MSTL_TREND_ONLY;
         out_applied[s] = applied ? 1 : 0;
         if (state == MSTL_FAILED && out_errors)
@@ -3590,7 +3572,7 @@ bool anofox_hip_mstl_decompose_batch(const double *const *values, const uint64_t
 bool anofox_ts_mstl_decomposition(const double *values, size_t length, const int *periods, size_t n_periods, int insufficient_data_mode,
                                   MstlResult *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     const size_t K = (periods && n_periods) ? n_periods : 0;        // (lib.rs: a NULL list is no periods)
     std::vector<double> tr(std::max<size_t>(length, 1)), rm(std::max<size_t>(length, 1)), se(std::max<size_t>(K * length, 1));
@@ -3656,16 +3638,12 @@ void anofox_free_mstl_result(MstlResult *result)
 bool anofox_hip_changepoints_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, double hazard_lambda,
                                     double *probability, uint8_t *flags, int32_t *counts, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !probability || !flags || !counts) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
-    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)INT32_MAX) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, (size_t)INT32_MAX, out_error)) return false;
     if (!device_ready(out_error)) return false;
     const double lambda = hazard_lambda > 0.0 ? hazard_lambda : 250.0;       // the FFI wrapper (lib.rs:3077-3081)
     ChangepointArgs a{};
@@ -3673,51 +3651,27 @@ bool anofox_hip_changepoints_device(const double *y, size_t ld, const int32_t *l
     a.hazard = 1.0 / std::fmax(lambda, 1.0);                                 // changepoint.rs:210
     a.prob = probability; a.flag = flags; a.count = counts;
     hipStream_t st = (hipStream_t)stream;
-    try {
-        (void)hipGetLastError();
-        launch_bocpd(a, st);
-        LAUNCHCHECK("bocpd");
-        HIPCHECK(hipStreamSynchronize(st));
-    } catch (const HipFail &f) {
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    return launch_and_wait("bocpd", st, out_error, [&] { launch_bocpd(a, st); });
 }
 
 bool anofox_hip_changepoints_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
                                    double hazard_lambda, double *out_probability, uint8_t *out_is_changepoint, int32_t *out_n_changepoints,
                                    AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_series > 0 && (!values || !lengths || !out_n_changepoints)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    size_t total = 0, t_max = 0;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)INT32_MAX) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        total += lengths[s];
-        t_max = std::max(t_max, lengths[s]);
-    }
-    if (total > 0 && (!out_probability || !out_is_changepoint)) {
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, (size_t)INT32_MAX, &shape, out_batch_error)) return false;
+    if (shape.total > 0 && (!out_probability || !out_is_changepoint)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
-    double *d_y = nullptr, *d_prob = nullptr;
-    uint8_t *d_flag = nullptr;
-    int32_t *d_len = nullptr, *d_cnt = nullptr;
-    // quiesced: on the success path the device entry has waited for its stream and the copies are synchronous; after a failure
-    // the first free waits for the device
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_prob, (void *)d_flag, (void *)d_len, (void *)d_cnt}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    const size_t ld = shape.ld, T = shape.T;
+    Scratch scratch;
     std::vector<int32_t> cnt(n_series);
     std::vector<double> prob;
     std::vector<uint8_t> flag;
@@ -3725,27 +3679,25 @@ bool anofox_hip_changepoints_batch(const double *const *values, const uint64_t *
         if (!device_ready(out_batch_error)) return false;
         // time-major block; a NULL counts as 0.0, as the reference's table function passes it (ts_changepoints.cpp:599)
         std::vector<double> yb(T * ld, 0.0);
-        std::vector<int32_t> len(ld, 0);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
         for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
             const uint64_t *m = validity ? validity[s] : nullptr;
-            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = (m && !((m[t >> 6] >> (t & 63)) & 1)) ? 0.0 : values[s][t];
+            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = (m && !valid_bit(m, t)) ? 0.0 : values[s][t];
         }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld); d_cnt = dalloc<int32_t>(ld);
-        d_prob = dalloc<double>(T * ld); d_flag = dalloc<uint8_t>(T * ld);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld), *d_cnt = scratch.get<int32_t>(ld);
+        double *d_prob = scratch.get<double>(T * ld);
+        uint8_t *d_flag = scratch.get<uint8_t>(T * ld);
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (!anofox_hip_changepoints_device(d_y, ld, d_len, n_series, T, hazard_lambda, d_prob, d_flag, d_cnt, nullptr, out_batch_error)) {
-            release(false);
+        if (!anofox_hip_changepoints_device(d_y, ld, d_len, n_series, T, hazard_lambda, d_prob, d_flag, d_cnt, nullptr, out_batch_error))
             return false;
-        }
         prob.resize(T * ld); flag.resize(T * ld);
         HIPCHECK(hipMemcpy(cnt.data(), d_cnt, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(prob.data(), d_prob, T * ld * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(flag.data(), d_flag, T * ld * sizeof(uint8_t), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -3754,7 +3706,7 @@ bool anofox_hip_changepoints_batch(const double *const *values, const uint64_t *
     for (size_t s = 0; s < n_series; s++) {
         const size_t n = lengths[s];
         const bool ok = cnt[s] >= 0;
-        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        if (out_errors) clear_error(&out_errors[s]);
         if (!ok && out_errors)      // ForecastError::InsufficientData { needed: 3, got: n } (changepoint.rs:205-207)
             set_error(&out_errors[s], COMPUTATION_ERROR, "Insufficient data: need at least 3 observations, got " + std::to_string(n));
         out_n_changepoints[s] = ok ? cnt[s] : -1;
@@ -3770,7 +3722,7 @@ bool anofox_hip_changepoints_batch(const double *const *values, const uint64_t *
 bool anofox_ts_detect_changepoints_bocpd(const double *values, size_t length, double hazard_lambda, bool include_probabilities,
                                          BocpdResult *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     std::vector<double> pr(std::max<size_t>(length, 1));
     std::vector<uint8_t> fl(std::max<size_t>(length, 1));
@@ -3826,16 +3778,12 @@ bool anofox_hip_stats_device(const double *y, const uint8_t *valid, const int64_
                              size_t t_rows, int64_t frequency_micros, FrequencyType frequency_type, int64_t *out_int, double *out_fp,
                              void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !out_int || !out_fp) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
-    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, (size_t)1 << 30, out_error)) return false;
     if ((int)frequency_type < STATS_FREQ_FIXED || (int)frequency_type > STATS_FREQ_YEARLY) {
         set_error(out_error, INVALID_INPUT, "Invalid input: unknown frequency type");
         return false;
@@ -3848,53 +3796,32 @@ bool anofox_hip_stats_device(const double *y, const uint8_t *valid, const int64_
     a.work_stride = stats_work_stride(t_rows);
     a.work_waves = a.work_stride ? stats_work_waves((int)n_series) : 0;
     hipStream_t st = (hipStream_t)stream;
-    uint64_t *work = nullptr;
-    try {
-        (void)hipGetLastError();
-        if (a.work_stride && a.work_waves > 0) work = dalloc<uint64_t>(a.work_stride * (size_t)a.work_waves);
-        a.work = work;
+    Scratch scratch;
+    const bool ok = launch_and_wait("stats", st, out_error, [&] {
+        if (a.work_stride && a.work_waves > 0) a.work = scratch.get<uint64_t>(a.work_stride * (size_t)a.work_waves);
         launch_stats(a, st);
-        LAUNCHCHECK("stats");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(work, true);
-    } catch (const HipFail &f) {
-        dev_free(work, false);
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_stats_batch(const double *const *values, const uint64_t *const *validity, const int64_t *const *dates, const size_t *lengths,
                             size_t n_series, int64_t frequency_micros, FrequencyType frequency_type, TsStatsResult *out_results,
                             AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_series > 0 && (!values || !lengths || !out_results)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    size_t t_max = 0;
-    bool any_mask = false, any_dates = false;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        t_max = std::max(t_max, lengths[s]);
-        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
-        any_dates = any_dates || (dates && dates[s] && lengths[s] > 0);
-    }
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, (size_t)1 << 30, &shape, out_batch_error)) return false;
+    bool any_dates = false;
+    for (size_t s = 0; s < n_series; s++) any_dates = any_dates || (dates && dates[s] && lengths[s] > 0);
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
-    double *d_y = nullptr, *d_fp = nullptr;
-    uint8_t *d_valid = nullptr;
-    int64_t *d_dates = nullptr, *d_int = nullptr;
-    int32_t *d_len = nullptr;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_valid, (void *)d_dates, (void *)d_int, (void *)d_len}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    const size_t ld = shape.ld, T = shape.T;
+    const bool any_mask = shape.any_mask;
+    Scratch scratch;
     std::vector<int64_t> oi(STATS_N_INT * ld);
     std::vector<double> of(STATS_N_FP * ld);
     try {
@@ -3902,39 +3829,32 @@ bool anofox_hip_stats_batch(const double *const *values, const uint64_t *const *
         std::vector<double> yb(T * ld, 0.0);
         std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
         std::vector<int64_t> db(any_dates ? T * ld : 0, 0);
-        std::vector<int32_t> len(ld, 0);
-        for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
-            const uint64_t *m = validity ? validity[s] : nullptr;
-            const int64_t *d = dates ? dates[s] : nullptr;
-            for (size_t t = 0; t < lengths[s]; t++) {
-                yb[t * ld + s] = values[s][t];
-                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
-                if (d) db[t * ld + s] = d[t];
-            }
-        }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
-        d_int = dalloc<int64_t>(STATS_N_INT * ld); d_fp = dalloc<double>(STATS_N_FP * ld);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
+        pack_time_major(yb.data(), ld, values, lengths, n_series);
+        if (any_mask) pack_validity(vb.data(), ld, validity, lengths, n_series);
+        if (any_dates) pack_time_major(db.data(), ld, dates, lengths, n_series);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld);
+        int64_t *d_int = scratch.get<int64_t>(STATS_N_INT * ld), *d_dates = nullptr;
+        double *d_fp = scratch.get<double>(STATS_N_FP * ld);
+        uint8_t *d_valid = nullptr;
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (any_mask) {
-            d_valid = dalloc<uint8_t>(T * ld);
+            d_valid = scratch.get<uint8_t>(T * ld);
             HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
         }
         if (any_dates) {
-            d_dates = dalloc<int64_t>(T * ld);
+            d_dates = scratch.get<int64_t>(T * ld);
             HIPCHECK(hipMemcpy(d_dates, db.data(), T * ld * sizeof(int64_t), hipMemcpyHostToDevice));
         }
         if (!anofox_hip_stats_device(d_y, d_valid, d_dates, ld, d_len, n_series, T, frequency_micros, frequency_type, d_int, d_fp, nullptr,
-                                     out_batch_error)) {
-            release(false);
+                                     out_batch_error))
             return false;
-        }
         HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -3963,7 +3883,7 @@ bool anofox_ts_stats_with_dates_and_type(const double *values, const uint64_t *v
                                          int64_t frequency_micros, FrequencyType frequency_type, TsStatsResult *out_result,
                                          AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !dates || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     const double *v[1] = {values};
     const uint64_t *m[1] = {validity};
@@ -3980,7 +3900,7 @@ bool anofox_ts_stats_with_dates(const double *values, const uint64_t *validity, 
 
 bool anofox_ts_stats(const double *values, const uint64_t *validity, size_t length, TsStatsResult *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     const double *v[1] = {values};
     const uint64_t *m[1] = {validity};
@@ -4000,16 +3920,12 @@ static const char *const QUALITY_NAN_TEXT = "Invalid input: a value is NaN";
 bool anofox_hip_quality_device(const double *y, const uint8_t *valid, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
                                double *out_fp, int64_t *out_int, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !out_fp || !out_int) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
-    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, (size_t)1 << 30, out_error)) return false;
     if (n_series == 0) return true;
     if (!device_ready(out_error)) return false;
     QualityArgs a{};
@@ -4019,83 +3935,54 @@ bool anofox_hip_quality_device(const double *y, const uint8_t *valid, size_t ld,
     a.work_stride = quality_work_stride(t_rows);
     a.work_waves = a.work_stride ? quality_work_waves((int)n_series) : 0;
     hipStream_t st = (hipStream_t)stream;
-    uint64_t *work = nullptr;
-    try {
-        (void)hipGetLastError();
-        if (a.work_stride && a.work_waves > 0) work = dalloc<uint64_t>(a.work_stride * (size_t)a.work_waves);
-        a.work = work;
+    Scratch scratch;
+    const bool ok = launch_and_wait("quality", st, out_error, [&] {
+        if (a.work_stride && a.work_waves > 0) a.work = scratch.get<uint64_t>(a.work_stride * (size_t)a.work_waves);
         launch_quality(a, st);
-        LAUNCHCHECK("quality");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(work, true);
-    } catch (const HipFail &f) {
-        dev_free(work, false);
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_quality_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
                               DataQualityResult *out_results, int32_t *out_status, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_series > 0 && (!values || !lengths || !out_results)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    size_t t_max = 0;
-    bool any_mask = false;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        t_max = std::max(t_max, lengths[s]);
-        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
-    }
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, (size_t)1 << 30, &shape, out_batch_error)) return false;
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
-    double *d_y = nullptr, *d_fp = nullptr;
-    uint8_t *d_valid = nullptr;
-    int64_t *d_int = nullptr;
-    int32_t *d_len = nullptr;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_valid, (void *)d_int, (void *)d_len}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    const size_t ld = shape.ld, T = shape.T;
+    const bool any_mask = shape.any_mask;
+    Scratch scratch;
     std::vector<int64_t> oi(QUALITY_N_INT * ld);
     std::vector<double> of(QUALITY_N_FP * ld);
     try {
         if (!device_ready(out_batch_error)) return false;
         std::vector<double> yb(T * ld, 0.0);
         std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
-        std::vector<int32_t> len(ld, 0);
-        for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
-            const uint64_t *m = validity ? validity[s] : nullptr;
-            for (size_t t = 0; t < lengths[s]; t++) {
-                yb[t * ld + s] = values[s][t];
-                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
-            }
-        }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
-        d_int = dalloc<int64_t>(QUALITY_N_INT * ld); d_fp = dalloc<double>(QUALITY_N_FP * ld);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
+        pack_time_major(yb.data(), ld, values, lengths, n_series);
+        if (any_mask) pack_validity(vb.data(), ld, validity, lengths, n_series);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld);
+        int64_t *d_int = scratch.get<int64_t>(QUALITY_N_INT * ld);
+        double *d_fp = scratch.get<double>(QUALITY_N_FP * ld);
+        uint8_t *d_valid = nullptr;
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (any_mask) {
-            d_valid = dalloc<uint8_t>(T * ld);
+            d_valid = scratch.get<uint8_t>(T * ld);
             HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
         }
-        if (!anofox_hip_quality_device(d_y, d_valid, ld, d_len, n_series, T, d_fp, d_int, nullptr, out_batch_error)) {
-            release(false);
-            return false;
-        }
+        if (!anofox_hip_quality_device(d_y, d_valid, ld, d_len, n_series, T, d_fp, d_int, nullptr, out_batch_error)) return false;
         HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -4114,7 +4001,7 @@ bool anofox_hip_quality_batch(const double *const *values, const uint64_t *const
 
 bool anofox_ts_data_quality(const double *values, const uint64_t *validity, size_t length, DataQualityResult *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     const double *v[1] = {values};
     const uint64_t *m[1] = {validity};
@@ -4139,103 +4026,72 @@ static_assert(sizeof(AnofoxHipSeasonality) == 128 && offsetof(AnofoxHipSeasonali
 bool anofox_hip_seasonality_device(const double *y, const uint8_t *valid, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
                                    int max_period, int32_t *out_int, double *out_fp, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !out_fp || !out_int) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
-    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, (size_t)1 << 30, out_error)) return false;
     if (n_series == 0) return true;
     if (!device_ready(out_error)) return false;
     SeasonalityArgs a{};
     a.y = y; a.valid = valid; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = (int)t_rows;
     a.max_period = max_period; a.out_int = out_int; a.out_fp = out_fp;
     hipStream_t st = (hipStream_t)stream;
-    double *work = nullptr;
+    Scratch scratch;
     try {
-        (void)hipGetLastError();
-        const size_t need = seasonality_work_doubles(a.n_series, a.t_rows);
-        if (need) work = dalloc<double>(need);
-        a.work = work;
-        launch_seasonality(a, st);
-        LAUNCHCHECK("seasonality");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(work, true);
-    } catch (const HipFail &f) {
-        dev_free(work, false);
-        report_hip_failure(out_error, f);
-        return false;
+        const bool ok = launch_and_wait("seasonality", st, out_error, [&] {
+            const size_t need = seasonality_work_doubles(a.n_series, a.t_rows);
+            if (need) a.work = scratch.get<double>(need);
+            launch_seasonality(a, st);
+        });
+        if (ok) scratch.settled();
+        return ok;
     } catch (const std::runtime_error &e) {
-        dev_free(work, false);
         set_error(out_error, COMPUTATION_ERROR, e.what());
         return false;
     }
-    return true;
 }
 
 bool anofox_hip_seasonality_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
                                   int max_period, AnofoxHipSeasonality *out_results, int32_t *out_status, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_series > 0 && (!values || !lengths || !out_results)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    size_t t_max = 0;
-    bool any_mask = false;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        t_max = std::max(t_max, lengths[s]);
-        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
-    }
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, (size_t)1 << 30, &shape, out_batch_error)) return false;
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
-    double *d_y = nullptr, *d_fp = nullptr;
-    uint8_t *d_valid = nullptr;
-    int32_t *d_int = nullptr, *d_len = nullptr;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_valid, (void *)d_int, (void *)d_len}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    const size_t ld = shape.ld, T = shape.T;
+    const bool any_mask = shape.any_mask;
+    Scratch scratch;
     std::vector<int32_t> oi(SEASONALITY_N_INT * ld);
     std::vector<double> of(SEASONALITY_N_FP * ld);
     try {
         if (!device_ready(out_batch_error)) return false;
         std::vector<double> yb(T * ld, 0.0);
         std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
-        std::vector<int32_t> len(ld, 0);
-        for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
-            const uint64_t *m = validity ? validity[s] : nullptr;
-            for (size_t t = 0; t < lengths[s]; t++) {
-                yb[t * ld + s] = values[s][t];
-                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
-            }
-        }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
-        d_int = dalloc<int32_t>(SEASONALITY_N_INT * ld); d_fp = dalloc<double>(SEASONALITY_N_FP * ld);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
+        pack_time_major(yb.data(), ld, values, lengths, n_series);
+        if (any_mask) pack_validity(vb.data(), ld, validity, lengths, n_series);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld);
+        int32_t *d_int = scratch.get<int32_t>(SEASONALITY_N_INT * ld);
+        double *d_fp = scratch.get<double>(SEASONALITY_N_FP * ld);
+        uint8_t *d_valid = nullptr;
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (any_mask) {
-            d_valid = dalloc<uint8_t>(T * ld);
+            d_valid = scratch.get<uint8_t>(T * ld);
             HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
         }
-        if (!anofox_hip_seasonality_device(d_y, d_valid, ld, d_len, n_series, T, max_period, d_int, d_fp, nullptr, out_batch_error)) {
-            release(false);
-            return false;
-        }
+        if (!anofox_hip_seasonality_device(d_y, d_valid, ld, d_len, n_series, T, max_period, d_int, d_fp, nullptr, out_batch_error)) return false;
         HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -4283,7 +4139,7 @@ static bool seasonality_periods(const AnofoxHipSeasonality &r, int **out, Anofox
 
 bool anofox_ts_detect_seasonality(const double *values, size_t length, int max_period, int **out_periods, size_t *out_n_periods, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_periods || !out_n_periods) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     AnofoxHipSeasonality r;
     if (!seasonality_single(values, length, max_period, &r, out_error)) return false;
@@ -4296,7 +4152,7 @@ bool anofox_ts_analyze_seasonality(const int64_t *timestamps, size_t timestamps_
                                    SeasonalityResult *out_result, AnofoxError *out_error)
 {
     (void)timestamps; (void)timestamps_len;                  // ignored, as the reference ignores them
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     AnofoxHipSeasonality r;
     if (!seasonality_single(values, length, max_period, &r, out_error)) return false;
@@ -4357,16 +4213,12 @@ bool anofox_hip_prepare_device(const double *y, const uint8_t *valid, const int6
                                uint8_t *valid_out, int64_t *dates_out, int32_t *len_out, int64_t *out_int, double *out_fp, void *stream,
                                AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !options || !len_out || !out_int || !out_fp) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
-    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
-    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30) || t_out > (size_t)(1u << 30)) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_series, "n_series", std::max(t_rows, t_out), (size_t)1 << 30, out_error)) return false;
     if (!prep_options_ok(options, struct_size, out_error)) return false;
     if (options->gaps && !dates) { set_error(out_error, INVALID_INPUT, "Invalid input: the gaps stage needs dates"); return false; }
     if (y_out) {
@@ -4389,16 +4241,7 @@ bool anofox_hip_prepare_device(const double *y, const uint8_t *valid, const int6
     a.t_out = t_out; a.y_out = y_out; a.valid_out = y_out ? valid_out : nullptr; a.dates_out = y_out ? dates_out : nullptr;
     a.len_out = len_out; a.out_int = out_int; a.out_fp = out_fp;
     hipStream_t st = (hipStream_t)stream;
-    try {
-        (void)hipGetLastError();
-        launch_dataprep(a, st);
-        LAUNCHCHECK("dataprep");
-        HIPCHECK(hipStreamSynchronize(st));
-    } catch (const HipFail &f) {
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    return launch_and_wait("dataprep", st, out_error, [&] { launch_dataprep(a, st); });
 }
 
 void anofox_hip_free_prepared(AnofoxHipPrepared *results, size_t n_series)
@@ -4415,21 +4258,17 @@ bool anofox_hip_prepare_batch(const double *const *values, const uint64_t *const
                               size_t n_series, const AnofoxHipPrepOptions *options, size_t struct_size, AnofoxHipPrepared *out_results,
                               AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (!options || (n_series > 0 && (!values || !lengths || !out_results))) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
     if (!prep_options_ok(options, struct_size, out_batch_error)) return false;
-    size_t t_max = 0, n_dated = 0, n_nonempty = 0;
-    bool any_mask = false;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)PREP_MAX_ROWS) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        t_max = std::max(t_max, lengths[s]);
-        any_mask = any_mask || (validity && validity[s] && lengths[s] > 0);
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, (size_t)PREP_MAX_ROWS, &shape, out_batch_error)) return false;
+    size_t n_dated = 0, n_nonempty = 0;
+    for (size_t s = 0; s < n_series; s++)
         if (lengths[s] > 0) { n_nonempty++; if (dates && dates[s]) n_dated++; }
-    }
     if (n_dated != 0 && n_dated != n_nonempty) {
         set_error(out_batch_error, INVALID_INPUT, "Invalid input: dates must be given for every series or for none");
         return false;
@@ -4441,18 +4280,9 @@ bool anofox_hip_prepare_batch(const double *const *values, const uint64_t *const
     }
     for (size_t s = 0; s < n_series; s++) std::memset(&out_results[s], 0, sizeof out_results[s]);
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
-    double *d_y = nullptr, *d_fp = nullptr, *d_yo = nullptr;
-    uint8_t *d_valid = nullptr, *d_vo = nullptr;
-    int64_t *d_dates = nullptr, *d_int = nullptr, *d_do = nullptr;
-    int32_t *d_len = nullptr, *d_lo = nullptr;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_yo, (void *)d_valid, (void *)d_vo, (void *)d_dates, (void *)d_int, (void *)d_do,
-                        (void *)d_len, (void *)d_lo}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    const size_t ld = shape.ld, T = shape.T;
+    const bool any_mask = shape.any_mask;
+    Scratch scratch;
     std::vector<int64_t> oi(PREP_N_INT * ld);
     std::vector<double> of(PREP_N_FP * ld), yo;
     std::vector<uint8_t> vo;
@@ -4464,11 +4294,10 @@ bool anofox_hip_prepare_batch(const double *const *values, const uint64_t *const
         std::vector<double> yb(T * ld, 0.0);
         std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
         std::vector<int64_t> db(dated ? T * ld : 0, 0);
-        std::vector<int32_t> len(ld, 0);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
         std::vector<size_t> order;
         for (size_t s = 0; s < n_series; s++) {
             const size_t n = lengths[s];
-            len[s] = (int32_t)n;
             const uint64_t *m = validity ? validity[s] : nullptr;
             const int64_t *d = dated ? dates[s] : nullptr;
             order.resize(n);
@@ -4477,37 +4306,37 @@ bool anofox_hip_prepare_batch(const double *const *values, const uint64_t *const
             for (size_t t = 0; t < n; t++) {
                 const size_t i = order[t];
                 yb[t * ld + s] = values[s][i];
-                if (m) vb[t * ld + s] = (uint8_t)((m[i >> 6] >> (i & 63)) & 1);
+                if (m) vb[t * ld + s] = (uint8_t)valid_bit(m, i);
                 if (d) db[t * ld + s] = d[i];
             }
         }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld); d_lo = dalloc<int32_t>(ld);
-        d_int = dalloc<int64_t>(PREP_N_INT * ld); d_fp = dalloc<double>(PREP_N_FP * ld);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld), *d_lo = scratch.get<int32_t>(ld);
+        int64_t *d_int = scratch.get<int64_t>(PREP_N_INT * ld), *d_dates = nullptr, *d_do = nullptr;
+        double *d_fp = scratch.get<double>(PREP_N_FP * ld);
+        uint8_t *d_valid = nullptr;
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (any_mask) {
-            d_valid = dalloc<uint8_t>(T * ld);
+            d_valid = scratch.get<uint8_t>(T * ld);
             HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
         }
         if (dated) {
-            d_dates = dalloc<int64_t>(T * ld);
+            d_dates = scratch.get<int64_t>(T * ld);
             HIPCHECK(hipMemcpy(d_dates, db.data(), T * ld * sizeof(int64_t), hipMemcpyHostToDevice));
         }
         // count, size the output block, run
         if (!anofox_hip_prepare_device(d_y, d_valid, d_dates, ld, d_len, n_series, T, options, struct_size, 0, nullptr, nullptr, nullptr, d_lo,
-                                       d_int, d_fp, nullptr, out_batch_error)) {
-            release(false);
+                                       d_int, d_fp, nullptr, out_batch_error))
             return false;
-        }
         HIPCHECK(hipMemcpy(lo.data(), d_lo, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < n_series; s++) t_out = std::max(t_out, (size_t)lo[s]);
-        d_yo = dalloc<double>(t_out * ld); d_vo = dalloc<uint8_t>(t_out * ld);
-        if (dated) d_do = dalloc<int64_t>(t_out * ld);
+        double *d_yo = scratch.get<double>(t_out * ld);
+        uint8_t *d_vo = scratch.get<uint8_t>(t_out * ld);
+        if (dated) d_do = scratch.get<int64_t>(t_out * ld);
         if (!anofox_hip_prepare_device(d_y, d_valid, d_dates, ld, d_len, n_series, T, options, struct_size, t_out, d_yo, d_vo, d_do, d_lo, d_int,
-                                       d_fp, nullptr, out_batch_error)) {
-            release(false);
+                                       d_fp, nullptr, out_batch_error))
             return false;
-        }
         yo.resize(t_out * ld); vo.resize(t_out * ld);
         HIPCHECK(hipMemcpy(lo.data(), d_lo, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -4518,9 +4347,8 @@ bool anofox_hip_prepare_batch(const double *const *values, const uint64_t *const
             dto.resize(t_out * ld);
             HIPCHECK(hipMemcpy(dto.data(), d_do, dto.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         }
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -4568,7 +4396,7 @@ static bool prep_single(const double *values, const uint64_t *validity, const in
 static bool prep_fill_values(const double *values, const uint64_t *validity, size_t length, int fill, double fill_value, double **out_values,
                              AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_values) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     AnofoxHipPrepOptions o{};
     o.fill = fill; o.fill_value = fill_value;
@@ -4598,7 +4426,7 @@ bool anofox_ts_fill_nulls_interpolate(const double *values, const uint64_t *vali
 static bool prep_fill_masked(const double *values, const uint64_t *validity, size_t length, int fill, FilledValuesResult *out_result,
                              AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     AnofoxHipPrepOptions o{};
     o.fill = fill;
@@ -4623,7 +4451,7 @@ bool anofox_ts_fill_nulls_backward(const double *values, const uint64_t *validit
 bool anofox_ts_fill_gaps(const int64_t *dates, const double *values, const uint64_t *validity, size_t length, int64_t frequency_micros,
                          FrequencyType frequency_type, GapFillResult *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!dates || !values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (frequency_type == FIXED && frequency_micros <= 0) {
         set_error(out_error, INVALID_FREQUENCY, "Frequency must be positive for fixed intervals");
@@ -4733,7 +4561,7 @@ bool anofox_hip_periods_device(const double *y, size_t ld, const int32_t *length
                                double max_period, size_t n_grid, double *figures, int32_t *index, int32_t *status, void *stream,
                                AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!y || !lengths || !figures || !index || !status) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
@@ -4742,11 +4570,7 @@ bool anofox_hip_periods_device(const double *y, size_t ld, const int32_t *length
         set_error(out_error, INVALID_INPUT, "Invalid input: unknown period detection method " + std::to_string(method));
         return false;
     }
-    if (ld < n_series) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_series"); return false; }
-    if (n_series > (size_t)INT32_MAX || t_rows > (size_t)INT32_MAX) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, (size_t)INT32_MAX, out_error)) return false;
     if (method != PERIODS_SAZED && n_grid > (size_t)INT32_MAX) {
         set_error(out_error, INVALID_INPUT, "Invalid input: more than 2147483647 frequencies or candidates");
         return false;
@@ -4767,27 +4591,19 @@ bool anofox_hip_periods_device(const double *y, size_t ld, const int32_t *length
         a.n_grid = n_grid > 0 ? (int64_t)n_grid : (method == PERIODS_LOMB_SCARGLE ? 1000 : 50);
     }
     hipStream_t st = (hipStream_t)stream;
-    double *work = nullptr;
-    try {
-        (void)hipGetLastError();
-        if (a.work_stride && a.work_blocks > 0) work = dalloc<double>(a.work_stride * (size_t)a.work_blocks);
-        a.work = work;
+    Scratch scratch;
+    const bool ok = launch_and_wait("periods", st, out_error, [&] {
+        if (a.work_stride && a.work_blocks > 0) a.work = scratch.get<double>(a.work_stride * (size_t)a.work_blocks);
         launch_periods(a, st);
-        LAUNCHCHECK("periods");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(work, true);
-    } catch (const HipFail &f) {
-        dev_free(work, false);
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_periods_batch(const double *const *values, const size_t *lengths, size_t n_series, int method, double min_period, double max_period,
                               size_t n_grid, double *out_figures, int32_t *out_index, AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_series > 0 && (!values || !lengths || !out_figures)) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
@@ -4796,47 +4612,32 @@ bool anofox_hip_periods_batch(const double *const *values, const size_t *lengths
         set_error(out_batch_error, INVALID_INPUT, "Invalid input: unknown period detection method " + std::to_string(method));
         return false;
     }
-    size_t t_max = 0;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)INT32_MAX) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        t_max = std::max(t_max, lengths[s]);
-    }
+    BlockShape shape;
+    if (!series_shape(values, nullptr, lengths, n_series, (size_t)INT32_MAX, &shape, out_batch_error)) return false;
     if (n_series == 0) return true;
-    const size_t ld = (n_series + 63) / 64 * 64, T = std::max<size_t>(t_max, 1);
-    double *d_y = nullptr, *d_fp = nullptr;
-    int32_t *d_len = nullptr, *d_idx = nullptr, *d_st = nullptr;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_fp, (void *)d_len, (void *)d_idx, (void *)d_st}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    const size_t ld = shape.ld, T = shape.T;
+    Scratch scratch;
     std::vector<double> fp(PERIODS_N_FP * ld);
     std::vector<int32_t> idx(n_series), status(n_series);
     try {
         if (!device_ready(out_batch_error)) return false;
         std::vector<double> yb(T * ld, 0.0);
-        std::vector<int32_t> len(ld, 0);
-        for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
-            for (size_t t = 0; t < lengths[s]; t++) yb[t * ld + s] = values[s][t];
-        }
-        d_y = dalloc<double>(T * ld); d_len = dalloc<int32_t>(ld);
-        d_fp = dalloc<double>(PERIODS_N_FP * ld); d_idx = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
+        pack_time_major(yb.data(), ld, values, lengths, n_series);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld);
+        double *d_fp = scratch.get<double>(PERIODS_N_FP * ld);
+        int32_t *d_idx = scratch.get<int32_t>(ld), *d_st = scratch.get<int32_t>(ld);
         HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (!anofox_hip_periods_device(d_y, ld, d_len, n_series, T, method, min_period, max_period, n_grid, d_fp, d_idx, d_st, nullptr,
-                                       out_batch_error)) {
-            release(false);
+                                       out_batch_error))
             return false;
-        }
         HIPCHECK(hipMemcpy(fp.data(), d_fp, fp.size() * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(idx.data(), d_idx, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(status.data(), d_st, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
@@ -4844,7 +4645,7 @@ bool anofox_hip_periods_batch(const double *const *values, const size_t *lengths
     const int used = method == PERIODS_LOMB_SCARGLE ? 4 : (method == PERIODS_AIC ? 5 : 3);
     for (size_t s = 0; s < n_series; s++) {
         const bool ok = status[s] == PERIODS_OK;
-        if (out_errors) { out_errors[s].code = SUCCESS; std::memset(out_errors[s].message, 0, sizeof out_errors[s].message); }
+        if (out_errors) clear_error(&out_errors[s]);
         if (!ok && out_errors) set_error(&out_errors[s], COMPUTATION_ERROR, periods_series_error(method, status[s], lengths[s]));
         for (int j = 0; j < PERIODS_N_FP; j++) out_figures[(size_t)j * n_series + s] = (ok && j < used) ? fp[(size_t)j * ld + s] : nan;
         if (out_index) out_index[s] = ok ? idx[s] : -1;
@@ -4855,7 +4656,7 @@ bool anofox_hip_periods_batch(const double *const *values, const size_t *lengths
 bool anofox_ts_lomb_scargle(const double *values, size_t length, double min_period, double max_period, size_t n_frequencies,
                             LombScargleResultFFI *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     double fig[PERIODS_N_FP];
     if (!periods_single(PERIODS_LOMB_SCARGLE, values, length, min_period, max_period, n_frequencies, fig, out_error)) return false;
@@ -4867,7 +4668,7 @@ bool anofox_ts_lomb_scargle(const double *values, size_t length, double min_peri
 bool anofox_ts_aic_period(const double *values, size_t length, double min_period, double max_period, size_t n_candidates,
                           AicPeriodResultFFI *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     double fig[PERIODS_N_FP];
     if (!periods_single(PERIODS_AIC, values, length, min_period, max_period, n_candidates, fig, out_error)) return false;
@@ -4879,7 +4680,7 @@ bool anofox_ts_aic_period(const double *values, size_t length, double min_period
 bool anofox_ts_sazed_period(const double *values, size_t length, size_t min_period, size_t max_period, size_t zero_pad_factor,
                             SazedPeriodResultFFI *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     double fig[PERIODS_N_FP];
     // periods beyond 2^53 act like any period beyond the series' length, so the conversion to double loses nothing that matters
@@ -4893,7 +4694,7 @@ bool anofox_ts_detect_periods_flat(const double *values, size_t length, const ch
                                    const double *expected_periods, size_t n_expected, double tolerance, FlatMultiPeriodResult *out_result,
                                    AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     (void)max_period;                                              // detect_periods_internal passes it to fft / acf / auto only
     std::string name;
@@ -5050,7 +4851,7 @@ bool metrics_validate(size_t n_actual, size_t n_forecast, AnofoxError *err)
 bool metrics_two(int figure, const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double *out_result,
                  AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !forecast || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!metrics_validate(actual_len, forecast_len, out_error)) return false;
     return metrics_single(figure, actual, actual_len, forecast, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.5, out_result, out_error);
@@ -5059,7 +4860,7 @@ bool metrics_two(int figure, const double *actual, size_t actual_len, const doub
 bool metrics_three(int figure, const char *third_name, const double *actual, size_t actual_len, const double *forecast, size_t forecast_len,
                    const double *third, size_t third_len, double *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !forecast || !third || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!metrics_validate(actual_len, forecast_len, out_error)) return false;
     if (actual_len != third_len) {                                 // metrics.rs:168-173, 238-243
@@ -5078,7 +4879,7 @@ bool anofox_hip_metrics_device(const double *actual, const double *forecast, con
                                size_t stride_t, const int32_t *lengths, size_t n_groups, size_t t_rows, uint32_t figures_mask, double quantile,
                                bool drop_nan, double *figures, size_t ld, int32_t *status, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !lengths || !figures || !status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!metrics_check_request(figures_mask, forecast, second, lower, upper, quantiles, n_levels, levels, out_error)) return false;
     if ((figures_mask >> MF_QUANTILE_LOSS & 1u) && !metrics_unit_interval(quantile)) {
@@ -5089,11 +4890,7 @@ bool anofox_hip_metrics_device(const double *actual, const double *forecast, con
     if (figures_mask >> MF_MQLOSS & 1u)
         for (size_t k = 0; k < n_levels; k++)
             if (!metrics_unit_interval(levels[k])) { set_error(out_error, INVALID_INPUT, METRICS_QUANTILE_TEXT); return false; }
-    if (ld < n_groups) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is smaller than n_groups"); return false; }
-    if (n_groups > (size_t)INT32_MAX || t_rows > (size_t)INT32_MAX) {
-        set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
+    if (!block_args_ok(ld, n_groups, "n_groups", t_rows, (size_t)INT32_MAX, out_error)) return false;
     if (n_groups == 0) return true;
     if (!device_ready(out_error)) return false;
     MetricsArgs a{};
@@ -5110,16 +4907,7 @@ bool anofox_hip_metrics_device(const double *actual, const double *forecast, con
         if (it != kv.end()) a.staging = std::atoi(it->second.c_str());
     }
     hipStream_t st = (hipStream_t)stream;
-    try {
-        (void)hipGetLastError();
-        launch_metrics(a, st);
-        LAUNCHCHECK("metrics");
-        HIPCHECK(hipStreamSynchronize(st));
-    } catch (const HipFail &f) {
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    return launch_and_wait("metrics", st, out_error, [&] { launch_metrics(a, st); });
 }
 
 bool anofox_hip_metrics_batch(const double *const *actual, const double *const *forecast, const double *const *second, const double *const *lower,
@@ -5127,7 +4915,7 @@ bool anofox_hip_metrics_batch(const double *const *actual, const double *const *
                               const size_t *lengths, size_t n_groups, uint32_t figures_mask, double quantile, bool drop_nan,
                               double *out_figures, AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_groups > 0 && (!actual || !lengths || !out_figures)) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!metrics_check_request(figures_mask, forecast, second, lower, upper, quantiles, n_levels, levels, out_batch_error)) return false;
     const size_t nq = (quantiles && levels) ? n_levels : 0;
@@ -5167,39 +4955,31 @@ bool anofox_hip_metrics_batch(const double *const *actual, const double *const *
         const bool use_q = nq > 0 && (mask >> MF_MQLOSS & 1u);
         const size_t n_blocks = 5 + (use_q ? nq : 0);
         std::vector<double *> d_in(6, nullptr);                    // actual .. upper, and every level's block in one (level k at k * T * ld)
-        double *d_fig = nullptr;
-        int32_t *d_len = nullptr, *d_st = nullptr;
-        auto release = [&](bool quiesced) {
-            for (double *q : d_in) { dev_free(q, quiesced); quiesced = true; }
-            dev_free(d_fig, quiesced); dev_free(d_len, true); dev_free(d_st, true);
-        };
+        Scratch scratch;
         try {
             if (!device_ready(out_batch_error)) return false;
             std::vector<double> blk(T * ld);
-            if (use_q) d_in[5] = dalloc<double>(nq * T * ld);
+            if (use_q) d_in[5] = scratch.get<double>(nq * T * ld);
             for (size_t b = 0; b < n_blocks; b++) {
                 const double *const *col = b < 5 ? src[b] : quantiles[b - 5];
                 if (!col) continue;
                 std::fill(blk.begin(), blk.end(), 0.0);
-                for (size_t s = 0; s < n_groups; s++)
-                    for (size_t t = 0; t < (size_t)len[s]; t++) blk[t * ld + s] = col[s][t];
-                double *dst = b < 5 ? (d_in[b] = dalloc<double>(T * ld)) : d_in[5] + (b - 5) * T * ld;
+                pack_time_major(blk.data(), ld, col, len.data(), n_groups);        // (len: 0 for a group that fails alone)
+                double *dst = b < 5 ? (d_in[b] = scratch.get<double>(T * ld)) : d_in[5] + (b - 5) * T * ld;
                 HIPCHECK(hipMemcpy(dst, blk.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
             }
-            d_fig = dalloc<double>((size_t)METRICS_N_FIG * ld); d_len = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+            double *d_fig = scratch.get<double>((size_t)METRICS_N_FIG * ld);
+            int32_t *d_len = scratch.get<int32_t>(ld), *d_st = scratch.get<int32_t>(ld);
             HIPCHECK(hipMemcpy(d_fig, fig.data(), fig.size() * sizeof(double), hipMemcpyHostToDevice));
             HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
             if (!anofox_hip_metrics_device(d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], use_q ? d_in[5] : nullptr, T * ld, levels, use_q ? nq : 0, 1,
                                            ld, d_len, n_groups, T, mask, ql_bad ? 0.5 : quantile, drop_nan, d_fig, ld, d_st, nullptr,
-                                           out_batch_error)) {
-                release(false);
+                                           out_batch_error))
                 return false;
-            }
             HIPCHECK(hipMemcpy(fig.data(), d_fig, fig.size() * sizeof(double), hipMemcpyDeviceToHost));
             HIPCHECK(hipMemcpy(status.data(), d_st, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
-            release(true);
+            scratch.settled();
         } catch (const HipFail &f) {
-            release(false);
             report_hip_failure(out_batch_error, f);
             return false;
         }
@@ -5210,8 +4990,7 @@ bool anofox_hip_metrics_batch(const double *const *actual, const double *const *
         for (int k = 0; k < METRICS_N_FIG; k++)
             out_figures[(size_t)k * n_groups + s] = (!empty && (mask >> k & 1u)) ? fig[(size_t)k * ld + s] : nan;
         if (!out_errors) continue;
-        out_errors[s].code = SUCCESS;
-        std::memset(out_errors[s].message, 0, sizeof out_errors[s].message);
+        clear_error(&out_errors[s]);
         if (null_level[s] >= 0) set_error(&out_errors[s], COMPUTATION_ERROR, "Invalid input: Null pointer at quantile index " + std::to_string(null_level[s]));
         else if (empty && (figures_mask & ~(1u << MF_COVERAGE))) set_error(&out_errors[s], COMPUTATION_ERROR, METRICS_EMPTY_TEXT);   // coverage of nothing is NaN, no error
         else if (!empty && (ql_bad || mql_bad)) set_error(&out_errors[s], COMPUTATION_ERROR, METRICS_QUANTILE_TEXT);
@@ -5245,7 +5024,7 @@ bool anofox_ts_mase(const double *actual, size_t actual_len, const double *forec
 bool anofox_ts_quantile_loss(const double *actual, size_t actual_len, const double *forecast, size_t forecast_len, double quantile,
                              double *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !forecast || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!metrics_validate(actual_len, forecast_len, out_error)) return false;
     if (!metrics_unit_interval(quantile)) { set_error(out_error, COMPUTATION_ERROR, METRICS_QUANTILE_TEXT); return false; }
@@ -5256,7 +5035,7 @@ bool anofox_ts_quantile_loss(const double *actual, size_t actual_len, const doub
 bool anofox_ts_mqloss(const double *actual, size_t actual_len, const double *const *quantiles, size_t n_levels, const double *levels,
                       double *out_result, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !quantiles || !levels || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (n_levels == 0) { set_error(out_error, INVALID_INPUT, "Must have at least one quantile level"); return false; }
     if (n_levels > (size_t)METRICS_MAX_LEVELS) {                   // the backend's limit
@@ -5279,7 +5058,7 @@ bool anofox_ts_mqloss(const double *actual, size_t actual_len, const double *con
 bool anofox_ts_coverage(const double *actual, size_t actual_len, const double *lower, const double *upper, double *out_result,
                         AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !lower || !upper || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (actual_len == 0) { *out_result = std::numeric_limits<double>::quiet_NaN(); return true; }       // metrics.rs:350-352
     return metrics_single(MF_COVERAGE, actual, actual_len, nullptr, nullptr, lower, upper, nullptr, nullptr, 0, 0.5, out_result, out_error);
@@ -5338,16 +5117,6 @@ bool conformal_check_method(int method, AnofoxError *err)
     return false;
 }
 
-bool conformal_check_block(size_t n_groups, size_t t_rows, size_t ld, AnofoxError *err)
-{
-    if (ld < n_groups) { set_error(err, INVALID_INPUT, "Invalid input: ld is smaller than n_groups"); return false; }
-    if (n_groups > (size_t)INT32_MAX || t_rows > (size_t)(1u << 30)) {
-        set_error(err, INVALID_INPUT, "Invalid input: the block is too large");
-        return false;
-    }
-    return true;
-}
-
 } // namespace
 } // extern "C++"
 
@@ -5356,13 +5125,13 @@ bool anofox_hip_conformal_learn_device(const double *residual, const double *act
                                        const double *alphas, size_t n_alphas, int method, double *scores_lower, double *scores_upper,
                                        size_t ld, double *sorted, int32_t *n_kept, int32_t *status, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if ((!residual && !(actual && forecast)) || !lengths || !scores_lower || !scores_upper || !status) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
     if (!conformal_check_levels(alphas, n_alphas, true, out_error) || !conformal_check_method(method, out_error)) return false;
-    if (!conformal_check_block(n_groups, t_rows, ld, out_error)) return false;
+    if (!block_args_ok(ld, n_groups, "n_groups", t_rows, (size_t)1 << 30, out_error)) return false;
     if (n_groups == 0) return true;
     if (!device_ready(out_error)) return false;
     ConformalLearnArgs a{};
@@ -5376,21 +5145,13 @@ bool anofox_hip_conformal_learn_device(const double *residual, const double *act
     a.work_stride = conformal_work_stride(t_rows);
     a.work_waves = a.work_stride ? conformal_work_waves((int)n_groups) : 0;
     hipStream_t st = (hipStream_t)stream;
-    uint64_t *work = nullptr;
-    try {
-        (void)hipGetLastError();
-        if (a.work_stride && a.work_waves > 0) work = dalloc<uint64_t>(a.work_stride * (size_t)a.work_waves);
-        a.work = work;
+    Scratch scratch;
+    const bool ok = launch_and_wait("conformal_learn", st, out_error, [&] {
+        if (a.work_stride && a.work_waves > 0) a.work = scratch.get<uint64_t>(a.work_stride * (size_t)a.work_waves);
         launch_conformal_learn(a, st);
-        LAUNCHCHECK("conformal_learn");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(work, true);
-    } catch (const HipFail &f) {
-        dev_free(work, false);
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_conformal_apply_device(const double *forecast, const double *difficulty, size_t stride_s, size_t stride_t,
@@ -5398,14 +5159,14 @@ bool anofox_hip_conformal_apply_device(const double *forecast, const double *dif
                                        const double *scores_upper, size_t ld, size_t n_alphas, int method, double *lower, double *upper,
                                        size_t stride_q, int32_t *status, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!forecast || !scores_lower || !scores_upper || !lower || !upper || !status) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
     if (!conformal_check_levels(nullptr, n_alphas, false, out_error) || !conformal_check_method(method, out_error)) return false;
     if (method == CONFORMAL_ADAPTIVE && !difficulty) { set_error(out_error, INVALID_INPUT, CONFORMAL_NEED_DIFFICULTY_TEXT); return false; }
-    if (!conformal_check_block(n_groups, h_rows, ld, out_error)) return false;
+    if (!block_args_ok(ld, n_groups, "n_groups", h_rows, (size_t)1 << 30, out_error)) return false;
     if (h_rows == 0) { set_error(out_error, INVALID_INPUT, CONFORMAL_NO_FORECAST_TEXT); return false; }
     if (n_groups == 0) return true;
     if (!device_ready(out_error)) return false;
@@ -5416,29 +5177,20 @@ bool anofox_hip_conformal_apply_device(const double *forecast, const double *dif
     a.method = method; a.n_alphas = (int)n_alphas;
     a.lower = lower; a.upper = upper; a.stride_q = stride_q; a.status = status;
     hipStream_t st = (hipStream_t)stream;
-    try {
-        (void)hipGetLastError();
-        launch_conformal_apply(a, st);
-        LAUNCHCHECK("conformal_apply");
-        HIPCHECK(hipStreamSynchronize(st));
-    } catch (const HipFail &f) {
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    return launch_and_wait("conformal_apply", st, out_error, [&] { launch_conformal_apply(a, st); });
 }
 
 bool anofox_hip_conformal_evaluate_device(const double *actual, const double *lower, const double *upper, size_t stride_s, size_t stride_t,
                                           const int32_t *lengths, size_t n_groups, size_t t_rows, double alpha, double *figures, size_t ld,
                                           int32_t *status, void *stream, AnofoxError *out_error)
 {
-    if (out_error) { out_error->code = SUCCESS; std::memset(out_error->message, 0, sizeof out_error->message); }
+    clear_error(out_error);
     if (!actual || !lower || !upper || !lengths || !figures || !status) {
         set_error(out_error, NULL_POINTER, "Null pointer argument");
         return false;
     }
     if (!conformal_check_levels(&alpha, 1, true, out_error)) return false;
-    if (!conformal_check_block(n_groups, t_rows, ld, out_error)) return false;
+    if (!block_args_ok(ld, n_groups, "n_groups", t_rows, (size_t)1 << 30, out_error)) return false;
     if (n_groups == 0) return true;
     if (!device_ready(out_error)) return false;
     ConformalEvalArgs a{};
@@ -5446,16 +5198,7 @@ bool anofox_hip_conformal_evaluate_device(const double *actual, const double *lo
     a.len = lengths; a.n_groups = (int)n_groups; a.t_rows = t_rows; a.alpha = alpha;
     a.figures = figures; a.ld = ld; a.status = status;
     hipStream_t st = (hipStream_t)stream;
-    try {
-        (void)hipGetLastError();
-        launch_conformal_evaluate(a, st);
-        LAUNCHCHECK("conformal_evaluate");
-        HIPCHECK(hipStreamSynchronize(st));
-    } catch (const HipFail &f) {
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    return launch_and_wait("conformal_evaluate", st, out_error, [&] { launch_conformal_evaluate(a, st); });
 }
 
 void anofox_hip_free_conformal(AnofoxHipConformal *results, size_t n_groups)
@@ -5473,7 +5216,7 @@ bool anofox_hip_conformal_batch(const double *const *residuals, const uint64_t *
                                 size_t n_groups, const double *alphas, size_t n_alphas, int method, int strategy, bool want_sorted,
                                 AnofoxHipConformal *out_results, AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    if (out_batch_error) { out_batch_error->code = SUCCESS; std::memset(out_batch_error->message, 0, sizeof out_batch_error->message); }
+    clear_error(out_batch_error);
     if (n_groups > 0 && (!residuals || !residual_lengths || !out_results || (forecasts && !forecast_lengths))) {
         set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
         return false;
@@ -5511,14 +5254,7 @@ bool anofox_hip_conformal_batch(const double *const *residuals, const uint64_t *
     const bool adaptive = method == CONFORMAL_ADAPTIVE;
     std::vector<double> sl(K * ld), su(K * ld), sorted, lower, upper;
     std::vector<int32_t> len(ld, 0), hlen(ld, 0), kept(n_groups, 0), st_learn(n_groups, CONFORMAL_OK), st_apply(n_groups, CONFORMAL_OK);
-    double *d_r = nullptr, *d_sorted = nullptr, *d_sl = nullptr, *d_su = nullptr, *d_f = nullptr, *d_d = nullptr, *d_lo = nullptr, *d_up = nullptr;
-    uint8_t *d_valid = nullptr;
-    int32_t *d_len = nullptr, *d_hlen = nullptr, *d_kept = nullptr, *d_st = nullptr;
-    auto release = [&](bool quiesced) {
-        dev_free(d_r, quiesced);
-        dev_free(d_sorted, true); dev_free(d_sl, true); dev_free(d_su, true); dev_free(d_f, true); dev_free(d_d, true); dev_free(d_lo, true);
-        dev_free(d_up, true); dev_free(d_valid, true); dev_free(d_len, true); dev_free(d_hlen, true); dev_free(d_kept, true); dev_free(d_st, true);
-    };
+    Scratch scratch;
     try {
         if (!device_ready(out_batch_error)) return false;
         // time-major blocks [T x ld] and [H x ld]
@@ -5527,26 +5263,23 @@ bool anofox_hip_conformal_batch(const double *const *residuals, const uint64_t *
         bool any_mask = false;
         for (size_t s = 0; s < n_groups; s++) any_mask = any_mask || (residual_validity && residual_validity[s] && residual_lengths[s] > 0);
         if (any_mask) vb.assign(T * ld, 1);
-        for (size_t s = 0; s < n_groups; s++) {
-            len[s] = (int32_t)residual_lengths[s];
-            for (size_t t = 0; t < residual_lengths[s]; t++) blk[t * ld + s] = residuals[s][t];
-            if (any_mask && residual_validity[s])
-                for (size_t t = 0; t < residual_lengths[s]; t++) vb[t * ld + s] = (uint8_t)((residual_validity[s][t / 64] >> (t % 64)) & 1ull);
-        }
-        d_r = dalloc<double>(T * ld); d_sl = dalloc<double>(K * ld); d_su = dalloc<double>(K * ld);
-        d_len = dalloc<int32_t>(ld); d_kept = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+        for (size_t s = 0; s < n_groups; s++) len[s] = (int32_t)residual_lengths[s];
+        pack_time_major(blk.data(), ld, residuals, residual_lengths, n_groups);
+        if (any_mask) pack_validity(vb.data(), ld, residual_validity, residual_lengths, n_groups);
+        double *d_r = scratch.get<double>(T * ld), *d_sl = scratch.get<double>(K * ld), *d_su = scratch.get<double>(K * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld), *d_kept = scratch.get<int32_t>(ld), *d_st = scratch.get<int32_t>(ld);
+        uint8_t *d_valid = nullptr;
+        double *d_sorted = nullptr;
         HIPCHECK(hipMemcpy(d_r, blk.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
         if (any_mask) {
-            d_valid = dalloc<uint8_t>(T * ld);
+            d_valid = scratch.get<uint8_t>(T * ld);
             HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
         }
-        if (want_sorted) d_sorted = dalloc<double>(T * ld);
+        if (want_sorted) d_sorted = scratch.get<double>(T * ld);
         if (!anofox_hip_conformal_learn_device(d_r, nullptr, nullptr, d_valid, 1, ld, d_len, n_groups, T, alphas, K, method, d_sl, d_su, ld,
-                                               d_sorted, d_kept, d_st, nullptr, out_batch_error)) {
-            release(false);
+                                               d_sorted, d_kept, d_st, nullptr, out_batch_error))
             return false;
-        }
         HIPCHECK(hipMemcpy(sl.data(), d_sl, K * ld * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(su.data(), d_su, K * ld * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(kept.data(), d_kept, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -5558,40 +5291,34 @@ bool anofox_hip_conformal_batch(const double *const *residuals, const uint64_t *
         if (forecasts && H > 0) {
             std::vector<double> fb(H * ld, 0.0), db;
             if (adaptive) db.assign(H * ld, 1.0);
-            for (size_t s = 0; s < n_groups; s++) {
-                hlen[s] = (int32_t)forecast_lengths[s];
-                for (size_t t = 0; t < forecast_lengths[s]; t++) {
-                    fb[t * ld + s] = forecasts[s][t];
-                    if (adaptive) db[t * ld + s] = difficulty[s][t];
-                }
-            }
-            d_f = dalloc<double>(H * ld); d_lo = dalloc<double>(K * H * ld); d_up = dalloc<double>(K * H * ld); d_hlen = dalloc<int32_t>(ld);
+            for (size_t s = 0; s < n_groups; s++) hlen[s] = (int32_t)forecast_lengths[s];
+            pack_time_major(fb.data(), ld, forecasts, forecast_lengths, n_groups);
+            if (adaptive) pack_time_major(db.data(), ld, difficulty, forecast_lengths, n_groups);
+            double *d_f = scratch.get<double>(H * ld), *d_lo = scratch.get<double>(K * H * ld), *d_up = scratch.get<double>(K * H * ld), *d_d = nullptr;
+            int32_t *d_hlen = scratch.get<int32_t>(ld);
             HIPCHECK(hipMemcpy(d_f, fb.data(), H * ld * sizeof(double), hipMemcpyHostToDevice));
             HIPCHECK(hipMemcpy(d_hlen, hlen.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
             if (adaptive) {
-                d_d = dalloc<double>(H * ld);
+                d_d = scratch.get<double>(H * ld);
                 HIPCHECK(hipMemcpy(d_d, db.data(), H * ld * sizeof(double), hipMemcpyHostToDevice));
             }
             if (!anofox_hip_conformal_apply_device(d_f, d_d, 1, ld, d_hlen, n_groups, H, d_sl, d_su, ld, K, method, d_lo, d_up, H * ld, d_st,
-                                                   nullptr, out_batch_error)) {
-                release(false);
+                                                   nullptr, out_batch_error))
                 return false;
-            }
             lower.resize(K * H * ld); upper.resize(K * H * ld);
             HIPCHECK(hipMemcpy(lower.data(), d_lo, lower.size() * sizeof(double), hipMemcpyDeviceToHost));
             HIPCHECK(hipMemcpy(upper.data(), d_up, upper.size() * sizeof(double), hipMemcpyDeviceToHost));
             HIPCHECK(hipMemcpy(st_apply.data(), d_st, n_groups * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         return false;
     }
     auto copy_out = [](size_t n) { return (double *)std::malloc(std::max<size_t>(n, 1) * sizeof(double)); };
     for (size_t s = 0; s < n_groups; s++) {
         AnofoxError *e = out_errors ? &out_errors[s] : nullptr;
-        if (e) { e->code = SUCCESS; std::memset(e->message, 0, sizeof e->message); }
+        clear_error(e);
         const size_t h = forecasts ? forecast_lengths[s] : 0;
         // the order of the source's checks: conformal_learn first (no residual; the difficulty of the calibration set is not part of
         // this entry), then conformal_apply (no forecast, then the difficulty)
@@ -5628,13 +5355,12 @@ namespace {
 
 const char *const CONFORMAL_ALPHA_V1_TEXT = "Invalid input: Alpha must be between 0 and 1 (exclusive)";      // conformal.rs:123-127
 
-void conformal_init(AnofoxError *e) { if (e) { e->code = SUCCESS; std::memset(e->message, 0, sizeof e->message); } }
 
 size_t conformal_count_valid(const uint64_t *validity, size_t n)
 {
     if (!validity) return n;
     size_t c = 0;
-    for (size_t t = 0; t < n; t++) c += (size_t)((validity[t / 64] >> (t % 64)) & 1ull);
+    for (size_t t = 0; t < n; t++) c += (size_t)valid_bit(validity, t);
     return c;
 }
 
@@ -5675,34 +5401,27 @@ bool conformal_apply_one(const double *forecasts, const double *difficulty, size
     const size_t ld = 64;
     std::vector<double> sl(K * ld, 0.0), su(K * ld, 0.0);
     for (size_t k = 0; k < K; k++) { sl[k * ld] = scores_lower[k]; su[k * ld] = scores_upper[k]; }
-    double *d_f = nullptr, *d_d = nullptr, *d_sl = nullptr, *d_su = nullptr, *d_lo = nullptr, *d_up = nullptr;
-    int32_t *d_st = nullptr;
-    auto release = [&](bool quiesced) {
-        dev_free(d_f, quiesced);
-        dev_free(d_d, true); dev_free(d_sl, true); dev_free(d_su, true); dev_free(d_lo, true); dev_free(d_up, true); dev_free(d_st, true);
-    };
+    Scratch scratch;
     try {
         if (!device_ready(out_error)) return false;
-        d_f = dalloc<double>(h); d_sl = dalloc<double>(K * ld); d_su = dalloc<double>(K * ld);
-        d_lo = dalloc<double>(K * h); d_up = dalloc<double>(K * h); d_st = dalloc<int32_t>(ld);
+        double *d_f = scratch.get<double>(h), *d_sl = scratch.get<double>(K * ld), *d_su = scratch.get<double>(K * ld), *d_d = nullptr;
+        double *d_lo = scratch.get<double>(K * h), *d_up = scratch.get<double>(K * h);
+        int32_t *d_st = scratch.get<int32_t>(ld);
         HIPCHECK(hipMemcpy(d_f, forecasts, h * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_sl, sl.data(), K * ld * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_su, su.data(), K * ld * sizeof(double), hipMemcpyHostToDevice));
         if (method == CONFORMAL_ADAPTIVE) {
-            d_d = dalloc<double>(h);
+            d_d = scratch.get<double>(h);
             HIPCHECK(hipMemcpy(d_d, difficulty, h * sizeof(double), hipMemcpyHostToDevice));
         }
         // one group, series-major: its steps are neighbours
-        if (!anofox_hip_conformal_apply_device(d_f, d_d, h, 1, nullptr, 1, h, d_sl, d_su, ld, K, method, d_lo, d_up, h, d_st, nullptr, out_error)) {
-            release(false);
+        if (!anofox_hip_conformal_apply_device(d_f, d_d, h, 1, nullptr, 1, h, d_sl, d_su, ld, K, method, d_lo, d_up, h, d_st, nullptr, out_error))
             return false;
-        }
         HIPCHECK(hipMemcpy(lower.data(), d_lo, K * h * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(upper.data(), d_up, K * h * sizeof(double), hipMemcpyDeviceToHost));
         HIPCHECK(hipMemcpy(&status, d_st, sizeof(int32_t), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_error, f);
         return false;
     }
@@ -5714,29 +5433,21 @@ bool conformal_evaluate_one(const double *actuals, const double *lower, const do
                             AnofoxError *out_error)
 {
     const size_t ld = 64;
-    double *d_a = nullptr, *d_l = nullptr, *d_u = nullptr, *d_fig = nullptr;
-    int32_t *d_len = nullptr, *d_st = nullptr;
-    auto release = [&](bool quiesced) {
-        dev_free(d_a, quiesced);
-        dev_free(d_l, true); dev_free(d_u, true); dev_free(d_fig, true); dev_free(d_len, true); dev_free(d_st, true);
-    };
+    Scratch scratch;
     try {
         if (!device_ready(out_error)) return false;
         const int32_t len = (int32_t)n;
-        d_a = dalloc<double>(n); d_l = dalloc<double>(n); d_u = dalloc<double>(n);
-        d_fig = dalloc<double>(CONFORMAL_N_EVAL * ld); d_len = dalloc<int32_t>(ld); d_st = dalloc<int32_t>(ld);
+        double *d_a = scratch.get<double>(n), *d_l = scratch.get<double>(n), *d_u = scratch.get<double>(n);
+        double *d_fig = scratch.get<double>(CONFORMAL_N_EVAL * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld), *d_st = scratch.get<int32_t>(ld);
         HIPCHECK(hipMemcpy(d_a, actuals, n * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_l, lower, n * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_u, upper, n * sizeof(double), hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(d_len, &len, sizeof len, hipMemcpyHostToDevice));
-        if (!anofox_hip_conformal_evaluate_device(d_a, d_l, d_u, n, 1, d_len, 1, n, alpha, d_fig, ld, d_st, nullptr, out_error)) {
-            release(false);
-            return false;
-        }
+        if (!anofox_hip_conformal_evaluate_device(d_a, d_l, d_u, n, 1, d_len, 1, n, alpha, d_fig, ld, d_st, nullptr, out_error)) return false;
         for (int k = 0; k < CONFORMAL_N_EVAL; k++) HIPCHECK(hipMemcpy(&fig[k], d_fig + (size_t)k * ld, sizeof(double), hipMemcpyDeviceToHost));
-        release(true);
+        scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_error, f);
         return false;
     }
@@ -5826,7 +5537,7 @@ void anofox_free_prediction_intervals(PredictionIntervalsFFI *r)
 bool anofox_ts_conformal_quantile(const double *residuals, const uint64_t *validity, size_t length, double alpha, double *out_result,
                                   AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!residuals) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (!out_result) { set_error(out_error, NULL_POINTER, "Null output pointer"); return false; }
     if (conformal_count_valid(validity, length) == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
@@ -5841,7 +5552,7 @@ bool anofox_ts_conformal_quantile(const double *residuals, const uint64_t *valid
 bool anofox_ts_conformal_intervals(const double *forecasts, size_t length, double conformity_score, double **out_lower, double **out_upper,
                                    AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!forecasts || !out_lower || !out_upper) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     std::vector<double> lo, up;
     int32_t status;
@@ -5860,7 +5571,7 @@ bool anofox_ts_conformal_intervals(const double *forecasts, size_t length, doubl
 bool anofox_ts_conformal_predict(const double *residuals, const uint64_t *residuals_validity, size_t residuals_length, const double *forecasts,
                                  size_t forecasts_length, double alpha, ConformalResultFFI *out_result, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!residuals || !forecasts || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     return conformal_predict_one(residuals, residuals_validity, residuals_length, forecasts, nullptr, forecasts_length, alpha, CONFORMAL_SYMMETRIC,
                                  "split_conformal", out_result, out_error);
@@ -5870,7 +5581,7 @@ bool anofox_ts_conformal_predict_adaptive(const double *residuals, const uint64_
                                           const double *forecasts, const double *difficulty, size_t forecasts_length, double alpha,
                                           ConformalResultFFI *out_result, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!residuals || !forecasts || !difficulty || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     for (size_t t = 0; t < forecasts_length; t++)                  // before the quantile's own checks (conformal.rs:315-323)
         if (difficulty[t] <= 0.0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_DIFFICULTY_TEXT); return false; }
@@ -5882,7 +5593,7 @@ bool anofox_ts_conformal_predict_asymmetric(const double *residuals, const uint6
                                             const double *forecasts, size_t forecasts_length, double alpha, ConformalResultFFI *out_result,
                                             AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!residuals || !forecasts || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     return conformal_predict_one(residuals, residuals_validity, residuals_length, forecasts, nullptr, forecasts_length, alpha, CONFORMAL_ASYMMETRIC,
                                  "asymmetric_conformal", out_result, out_error);
@@ -5892,7 +5603,7 @@ bool anofox_ts_conformal_predict_multi(const double *residuals, const uint64_t *
                                        const double *forecasts, size_t forecasts_length, const double *alphas, size_t n_alphas,
                                        ConformalMultiResultFFI *out_result, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!residuals || !forecasts || !alphas || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (conformal_too_many(n_alphas, out_error)) return false;
     if (n_alphas == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_NO_ALPHA_TEXT); return false; }
@@ -5924,7 +5635,7 @@ bool anofox_ts_conformal_predict_multi(const double *residuals, const uint64_t *
 
 bool anofox_ts_mean_interval_width(const double *lower, const double *upper, size_t length, double *out_result, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!lower || !upper || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (length == 0) { *out_result = std::numeric_limits<double>::quiet_NaN(); return true; }          // conformal.rs:461-463
     double fig[CONFORMAL_N_EVAL];
@@ -5937,7 +5648,7 @@ bool anofox_ts_conformal_learn(const double *residuals, const uint64_t *residual
                                size_t n_alphas, ConformalMethodFFI method, ConformalStrategyFFI strategy, const double *difficulty,
                                CalibrationProfileFFI *out_profile, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!residuals || !alphas || !out_profile) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (conformal_too_many(n_alphas, out_error) || !conformal_check_method((int)method, out_error)) return false;
     if ((int)strategy < 0 || (int)strategy > 2) {
@@ -6002,7 +5713,7 @@ bool anofox_ts_conformal_learn(const double *residuals, const uint64_t *residual
 bool anofox_ts_conformal_apply(const double *forecasts, size_t n_forecasts, const CalibrationProfileFFI *profile, const double *difficulty,
                                PredictionIntervalsFFI *out_intervals, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!forecasts || !profile || !out_intervals) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     const size_t K = profile->n_levels, h = n_forecasts;
     const int method = (int)profile->method;
@@ -6057,7 +5768,7 @@ bool anofox_ts_conformal_apply(const double *forecasts, size_t n_forecasts, cons
 bool anofox_ts_conformal_coverage(const double *actuals, const double *lower, const double *upper, size_t length, double *out_coverage,
                                   AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!actuals || !lower || !upper || !out_coverage) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (length == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
     double fig[CONFORMAL_N_EVAL];
@@ -6069,7 +5780,7 @@ bool anofox_ts_conformal_coverage(const double *actuals, const double *lower, co
 bool anofox_ts_conformal_evaluate(const double *actuals, const double *lower, const double *upper, size_t length, double alpha,
                                   ConformalEvaluationFFI *out_eval, AnofoxError *out_error)
 {
-    conformal_init(out_error);
+    clear_error(out_error);
     if (!actuals || !lower || !upper || !out_eval) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
     if (length == 0) { set_error(out_error, COMPUTATION_ERROR, CONFORMAL_EMPTY_TEXT); return false; }
     if (!conformal_alpha_ok(alpha)) {                              // winkler_score's check, after coverage has succeeded (conformal.rs:1123-1128)
@@ -6112,7 +5823,6 @@ std::string exog_cap_message(size_t k)
     return "Computation error: ARIMAX takes at most " + std::to_string(EXOG_MAX_REGRESSORS) + " exogenous regressors, got " + std::to_string(k);
 }
 
-void clear_error(AnofoxError *e) { if (e) { e->code = SUCCESS; std::memset(e->message, 0, sizeof e->message); } }
 
 // host regressors -> the batch's own device blocks, through one pinned staging block per regressor slice (cells past a series' end: 0.0)
 void batch_pack_exog_host(AnofoxHipBatch *b, const double *const *xreg, const double *const *future_xreg, const size_t *lengths, size_t k)
@@ -6464,25 +6174,18 @@ bool anofox_hip_backtest_expand_device(const double *y, size_t ld_src, const int
     }
     if (!device_ready(out_error)) return false;
     hipStream_t st = (hipStream_t)stream;
-    BacktestFoldPos *d_tab = nullptr;
-    try {
-        (void)hipGetLastError();
-        d_tab = dalloc<BacktestFoldPos>(n_folds);
+    Scratch scratch;
+    const bool ok = launch_and_wait("backtest expand", st, out_error, [&] {
+        BacktestFoldPos *d_tab = scratch.get<BacktestFoldPos>(n_folds);
         if (n_folds) HIPCHECK(hipMemcpyAsync(d_tab, tab.data(), n_folds * sizeof(BacktestFoldPos), hipMemcpyHostToDevice, st));
         BacktestArgs a{};
         a.y = y; a.ld_src = ld_src; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
         a.folds = d_tab; a.n_folds = (int)std::max<size_t>(n_folds, 1); a.n_pairs = (int)np; a.ld_pairs = ld_pairs;
         a.t_train = t_train; a.y_out = y_out; a.len_pairs = len_pairs; a.n_test = n_test;
         launch_backtest_expand(a, st);
-        LAUNCHCHECK("backtest expand");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(d_tab, true);
-    } catch (const HipFail &f) {
-        dev_free(d_tab, false);
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_backtest_collect_device(const double *y, size_t ld_src, size_t n_series, size_t t_rows, const AnofoxHipFold *folds,
@@ -6508,10 +6211,9 @@ bool anofox_hip_backtest_collect_device(const double *y, size_t ld_src, size_t n
     if (n_folds == 0) return true;
     if (!device_ready(out_error)) return false;
     hipStream_t st = (hipStream_t)stream;
-    BacktestFoldPos *d_tab = nullptr;
-    try {
-        (void)hipGetLastError();
-        d_tab = dalloc<BacktestFoldPos>(n_folds);
+    Scratch scratch;
+    const bool ok = launch_and_wait("backtest collect", st, out_error, [&] {
+        BacktestFoldPos *d_tab = scratch.get<BacktestFoldPos>(n_folds);
         HIPCHECK(hipMemcpyAsync(d_tab, tab.data(), n_folds * sizeof(BacktestFoldPos), hipMemcpyHostToDevice, st));
         BacktestArgs a{};
         a.y = y; a.ld_src = ld_src; a.n_series = (int)n_series; a.t_rows = t_rows;
@@ -6520,15 +6222,9 @@ bool anofox_hip_backtest_collect_device(const double *y, size_t ld_src, size_t n
         a.actual = actual; a.error = error; a.abs_error = abs_error; a.valid = valid; a.n_rows = n_rows;
         a.metric = backtest_metric_code(metric); a.scores = scores;
         launch_backtest_collect(a, st);
-        LAUNCHCHECK("backtest collect");
-        HIPCHECK(hipStreamSynchronize(st));
-        dev_free(d_tab, true);
-    } catch (const HipFail &f) {
-        dev_free(d_tab, false);
-        report_hip_failure(out_error, f);
-        return false;
-    }
-    return true;
+    });
+    if (ok) scratch.settled();
+    return ok;
 }
 
 bool anofox_hip_backtest_batch(const double *const *values, const size_t *lengths, size_t n_series, const ForecastOptions *options,
@@ -6538,27 +6234,16 @@ bool anofox_hip_backtest_batch(const double *const *values, const size_t *length
 {
     clear_error(out_batch_error);
     if (!options || (n_series > 0 && (!values || !lengths))) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-    size_t t_train = 1, np = 0, ld_pairs = 64, T = 1;
+    size_t t_train = 1, np = 0, ld_pairs = 64;
     if (!anofox_hip_backtest_sizes(folds, n_folds, n_series, &t_train, &np, &ld_pairs, out_batch_error)) return false;
-    for (size_t s = 0; s < n_series; s++) {
-        if (lengths[s] > 0 && !values[s]) { set_error(out_batch_error, NULL_POINTER, "Null pointer argument"); return false; }
-        if (lengths[s] > (size_t)(1u << 30)) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: a series is too long"); return false; }
-        T = std::max(T, lengths[s]);
-    }
+    BlockShape shape;
+    if (!series_shape(values, nullptr, lengths, n_series, (size_t)1 << 30, &shape, out_batch_error)) return false;
     if (options->horizon < 1) { set_error(out_batch_error, INVALID_INPUT, "Invalid input: horizon must be at least 1"); return false; }
     if (np == 0) return true;
-    const size_t h = (size_t)options->horizon, nh = np * h, ld_src = (n_series + 63) / 64 * 64;
+    const size_t h = (size_t)options->horizon, nh = np * h, ld_src = shape.ld, T = shape.T;
     AnofoxHipBatch *b = nullptr;
     if (!anofox_hip_batch_create(np, t_train, options, &b, out_batch_error)) return false;      // e.g. "ETS:AAA": INVALID_MODEL, no rows
-    double *d_src = nullptr, *d_exp = nullptr, *d_fp = nullptr, *d_work = nullptr;
-    int32_t *d_len = nullptr, *d_int = nullptr;
     bool ok = true;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_src, (void *)d_exp, (void *)d_fp, (void *)d_work, (void *)d_len, (void *)d_int}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
     // ONE arena of results, so that one copy brings them back: yhat, lower, upper, actual, the scores, then error and abs_error
     // (fp64), then n_rows, status, model_code [np] and, not copied, len_pairs and n_test [ld_pairs] (int32)
     const size_t n_fp_back = 4 * nh + n_folds;
@@ -6566,18 +6251,17 @@ bool anofox_hip_backtest_batch(const double *const *values, const size_t *length
     try {
         DeviceGuard guard(b->dev);
         hipStream_t st = b->own_stream;
+        Scratch scratch;
+        double *d_src = scratch.get<double>(T * ld_src), *d_exp = nullptr;
+        int32_t *d_len = scratch.get<int32_t>(ld_src);
         {
             std::vector<double> yb(T * ld_src, 0.0);
-            std::vector<int32_t> len(ld_src, 0);
-            for (size_t s = 0; s < n_series; s++) {
-                len[s] = (int32_t)lengths[s];
-                for (size_t t = 0; t < lengths[s]; t++) yb[t * ld_src + s] = values[s][t];
-            }
-            d_src = dalloc<double>(T * ld_src); d_len = dalloc<int32_t>(ld_src);
+            const std::vector<int32_t> len = block_lengths(lengths, n_series, ld_src);
+            pack_time_major(yb.data(), ld_src, values, lengths, n_series);
             HIPCHECK(hipMemcpy(d_src, yb.data(), T * ld_src * sizeof(double), hipMemcpyHostToDevice));
             HIPCHECK(hipMemcpy(d_len, len.data(), ld_src * sizeof(int32_t), hipMemcpyHostToDevice));
         }
-        try { d_exp = dalloc<double>(t_train * ld_pairs); }
+        try { d_exp = scratch.get<double>(t_train * ld_pairs); }
         catch (const HipFail &f) {
             if (!f.oom) throw;
             set_error(out_batch_error, COMPUTATION_ERROR, "Computation error: the expanded backtest block of " + std::to_string(t_train) + " x " +
@@ -6585,9 +6269,9 @@ bool anofox_hip_backtest_batch(const double *const *values, const size_t *length
             ok = false;
         }
         if (ok) {
-            d_fp = dalloc<double>(n_fp_back + (3 * np + 1) / 2);
-            d_int = dalloc<int32_t>(2 * ld_pairs);
-            d_work = dalloc<double>(2 * nh);
+            double *d_fp = scratch.get<double>(n_fp_back + (3 * np + 1) / 2);
+            int32_t *d_int = scratch.get<int32_t>(2 * ld_pairs);
+            double *d_work = scratch.get<double>(2 * nh);
             int32_t *d_rows = (int32_t *)(d_fp + n_fp_back), *d_stat = d_rows + np, *d_code = d_rows + 2 * np, *d_lenp = d_int, *d_ntest = d_int + ld_pairs;
             double *d_yh = d_fp, *d_lo = d_fp + nh, *d_hi = d_fp + 2 * nh, *d_act = d_fp + 3 * nh, *d_sc = d_fp + 4 * nh, *d_err = d_work,
                    *d_abs = d_work + nh;
@@ -6610,9 +6294,8 @@ bool anofox_hip_backtest_batch(const double *const *values, const size_t *length
                 HIPCHECK(hipMemcpy(back.data(), d_fp, back.size() * sizeof(double), hipMemcpyDeviceToHost));
             }
         }
-        release(ok);
+        if (ok) scratch.settled();
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_batch_error, f);
         anofox_hip_batch_destroy(b);
         return false;
@@ -6668,9 +6351,9 @@ bool hierarchy_mask_range(const uint64_t *m, size_t n, size_t *t0, size_t *t1)
     if (n == 0) return false;
     if (!m) { *t0 = 0; *t1 = n - 1; return true; }
     size_t a = 0, b = n;
-    while (a < n && !((m[a >> 6] >> (a & 63)) & 1)) a++;
+    while (a < n && !valid_bit(m, a)) a++;
     if (a == n) return false;
-    while (!((m[(b - 1) >> 6] >> ((b - 1) & 63)) & 1)) b--;
+    while (!valid_bit(m, b - 1)) b--;
     *t0 = a; *t1 = b - 1;
     return true;
 }
@@ -6836,36 +6519,23 @@ bool anofox_hip_hierarchy_batch(const double *const *values, const uint64_t *con
     const size_t cells = t_out * ld_out, back_bytes = cells * 8 + ld_out * 8 + ld_out * 4 + cells;
     double *d_y = nullptr;
     uint8_t *d_valid = nullptr, *d_present = nullptr, *d_back = nullptr;
-    int32_t *d_len = nullptr, *d_plan = nullptr;
-    int64_t *d_first = nullptr;
-    auto release = [&](bool quiesced) {
-        for (void *q : {(void *)d_y, (void *)d_valid, (void *)d_present, (void *)d_back, (void *)d_len, (void *)d_plan, (void *)d_first}) {
-            dev_free(q, quiesced);
-            quiesced = true;
-        }
-    };
+    Scratch scratch;
     std::vector<uint8_t> back(back_bytes);
     bool ok = true;
     try {
         std::vector<double> yb(T * ld, 0.0);
         std::vector<uint8_t> vb(any_valid ? T * ld : 0, 1), pb(any_present ? T * ld : 0, 1);
-        std::vector<int32_t> len(ld, 0);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
         std::vector<int64_t> fst(ld, 0);
-        for (size_t s = 0; s < n_series; s++) {
-            len[s] = (int32_t)lengths[s];
-            fst[s] = first ? first[s] : 0;
-            const uint64_t *m = validity ? validity[s] : nullptr, *p = present ? present[s] : nullptr;
-            for (size_t t = 0; t < lengths[s]; t++) {
-                yb[t * ld + s] = values[s][t];
-                if (m) vb[t * ld + s] = (uint8_t)((m[t >> 6] >> (t & 63)) & 1);
-                if (p) pb[t * ld + s] = (uint8_t)((p[t >> 6] >> (t & 63)) & 1);
-            }
-        }
+        for (size_t s = 0; s < n_series; s++) fst[s] = first ? first[s] : 0;
+        pack_time_major(yb.data(), ld, values, lengths, n_series);
+        if (any_valid) pack_validity(vb.data(), ld, validity, lengths, n_series);
+        if (any_present) pack_validity(pb.data(), ld, present, lengths, n_series);
         try {
-            d_y = dalloc<double>(T * ld);
-            if (any_valid) d_valid = dalloc<uint8_t>(T * ld);
-            if (any_present) d_present = dalloc<uint8_t>(T * ld);
-            d_back = dalloc<uint8_t>(back_bytes);
+            d_y = scratch.get<double>(T * ld);
+            if (any_valid) d_valid = scratch.get<uint8_t>(T * ld);
+            if (any_present) d_present = scratch.get<uint8_t>(T * ld);
+            d_back = scratch.get<uint8_t>(back_bytes);
         } catch (const HipFail &f) {
             if (!f.oom) throw;
             set_error(out_error, COMPUTATION_ERROR, "Computation error: the source block of " + std::to_string(T) + " x " + std::to_string(ld) +
@@ -6874,7 +6544,9 @@ bool anofox_hip_hierarchy_batch(const double *const *values, const uint64_t *con
             ok = false;
         }
         if (ok) {
-            d_len = dalloc<int32_t>(ld); d_first = dalloc<int64_t>(ld); d_plan = dalloc<int32_t>(n_out + 1 + nnz);
+            int32_t *d_len = scratch.get<int32_t>(ld);
+            int64_t *d_first = scratch.get<int64_t>(ld);
+            int32_t *d_plan = scratch.get<int32_t>(n_out + 1 + nnz);
             HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
             if (any_valid) HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
             if (any_present) HIPCHECK(hipMemcpy(d_present, pb.data(), T * ld, hipMemcpyHostToDevice));
@@ -6892,9 +6564,8 @@ bool anofox_hip_hierarchy_batch(const double *const *values, const uint64_t *con
             if (ok) HIPCHECK(hipMemcpy(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost));      // waits for the null stream
             else HIPCHECK(hipDeviceSynchronize());
         }
-        release(true);
+        scratch.settled();                                                 // (either way the device has been waited for)
     } catch (const HipFail &f) {
-        release(false);
         report_hip_failure(out_error, f);
         return false;
     }

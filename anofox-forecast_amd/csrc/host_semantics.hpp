@@ -184,6 +184,14 @@ inline void set_error(AnofoxError *e, int code, const std::string &msg)
     e->message[n] = 0;
 }
 
+// what every entry does first: SUCCESS and an all-zero message, so that a caller may compare the whole struct
+inline void clear_error(AnofoxError *e)
+{
+    if (!e) return;
+    e->code = SUCCESS;
+    std::memset(e->message, 0, sizeof e->message);
+}
+
 // ComputeFoldBoundaries (ts_backtest_native.cpp:623-711): position-based fold boundaries over the number of distinct dates of the
 // whole input, all inclusive.  Writes the first `capacity` folds to `out` (may be null) and returns how many there are.  The
 // reference's unsigned arithmetic is kept where it matters: no training window starts before position 0, and a fold whose test

@@ -213,6 +213,23 @@ def test_device_keyed_caches_on_four_fake_devices(sanitizer):
         assert r.returncode == 0 and r.stdout.startswith("resources_mt: ok"), (r.stdout, r.stderr[-3000:])
 
 
+def test_scratch_owner_and_series_packer_under_sanitizers():
+    """csrc/host_scratch.hpp -- the owner of a call's device scratch, the series packer and the shape function shared by the entry
+    families of host_api.hip -- compiled against tests/c_abi/fake_hip.h (one "device" of 8 MB) and run under ASan + UBSan
+    (tests/c_abi/scratch_san.cpp): every block is freed exactly once, without a device-wide wait after settled() and with exactly
+    one otherwise, also when a HipFail passes through the owner or the allocator refuses a call's third block; the packed cells
+    match a plain loop across a mask word edge; the shape function refuses with the entries' codes and texts.  No GPU test can
+    reach these paths.  Test infrastructure: the product never sees the fake."""
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "scratch_san")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+                               os.path.join(ROOT, "tests", "c_abi", "scratch_san.cpp"), "-o", exe])
+        env = dict(os.environ, FAKE_HIP_DEVICES="1", FAKE_HIP_DEVICE_MB="8")
+        env.pop("ANOFOX_HIP_CACHE_GB", None)
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0 and r.stdout.startswith("scratch_san: ok"), (r.stdout, r.stderr[-3000:])
+
+
 def test_duckdb_macro_binding_parses():
     """binding/ts_macros_hip.cpp (the macro that sends ts_forecast_by to the batch route) needs nothing but DuckDB's API:
     `g++ -fsyntax-only` against the declaration-only stand-in tests/c_abi/duckdb_stub/ (test infrastructure, written from DuckDB's
