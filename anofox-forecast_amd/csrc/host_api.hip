@@ -39,6 +39,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 
 #include "host_resources.hpp"     // HipFail / HIPCHECK, the tunables, DeviceGuard, the device / pinned / stream caches, the device list
 #include "host_scratch.hpp"       // Scratch (a call's device blocks), the shape and packing of a batch of series, the _device entry's checks and launch
+#include "host_parts.hpp"         // how an auto-detected batch is cut into device batches (PartPlan), and how a batch's results reach the caller's arrays
 
 struct Plan {
     ModelType model;
@@ -2503,12 +2504,7 @@ bool anofox_hip_batch_fetch(AnofoxHipBatch *b, ForecastResult *out_results, Anof
 
 void anofox_free_forecast_result(ForecastResult *r)
 {
-    if (!r) return;
-    std::free(r->point_forecasts); r->point_forecasts = nullptr;
-    std::free(r->lower_bounds); r->lower_bounds = nullptr;
-    std::free(r->upper_bounds); r->upper_bounds = nullptr;
-    std::free(r->fitted_values); r->fitted_values = nullptr;
-    std::free(r->residuals); r->residuals = nullptr;
+    if (r) free_result_arrays(*r);
 }
 
 bool anofox_hip_batch_inspect(AnofoxHipBatch *b, AnofoxHipInspection *out, double *fitted, double *seasonal, size_t seasonal_stride,
@@ -2648,438 +2644,348 @@ bool anofox_hip_batch_arima_fit(AnofoxHipBatch *b, AnofoxHipArimaFit *out, Anofo
     return true;
 }
 
-// one plan, one device batch: create, pack, run, fetch (the whole of the batch entry unless periods are auto-detected)
+// ---------------------------------------------------------------------------------------------
+// The batch entry on one device.  Every route -- one period given, merged periods, a part on a worker's reused batch, a single
+// pooled series, a batch with regressors -- creates its device batch its own way (they differ in what a refused option block
+// means) and then shares run_batch below and the deliver step of host_parts.hpp.
+// ---------------------------------------------------------------------------------------------
+extern "C++" {
+
+using Clock = std::chrono::steady_clock;
+static double ms_between(Clock::time_point a, Clock::time_point z) { return std::chrono::duration<double, std::milli>(z - a).count(); }
+
+struct BatchPhases { Clock::time_point packed, ran, fetched; };       // when the phases of run_batch ended (ANOFOX_HIP_TIMING lines)
+
+// Pack -> `between` (what a caller uploads beside the series: the per-column periods of a merged batch, the regressors of an
+// exog batch) -> run -> fetch, on a batch that exists.  false: *e says why ("device batch failed" when no step did) and whatever
+// the fetch had allocated is freed again; res must hold b->n zeroed or fetched results.
+template <class Between>
+static bool run_batch(AnofoxHipBatch *b, const double *const *values, const uint64_t *const *validity, const size_t *lengths, ForecastResult *res,
+                      AnofoxError *errs, AnofoxError *e, BatchPhases *phases, Between &&between)
+{
+    clear_error(e);
+    bool ok = anofox_hip_batch_pack_host(b, values, validity, lengths, e);
+    const auto packed = Clock::now();
+    if (ok) {
+        try { between(); }
+        catch (const HipFail &f) { report_hip_failure(e, f); ok = false; }
+        catch (const std::exception &x) { set_error(e, INTERNAL_ERROR, std::string("Internal error: ") + x.what()); ok = false; }
+    }
+    ok = ok && anofox_hip_batch_run(b, nullptr, e);
+    if (ok && b->tun.timing) (void)hipStreamSynchronize(b->last_stream);        // (the run's time, not the fetch's)
+    const auto ran = Clock::now();
+    ok = ok && anofox_hip_batch_fetch(b, res, errs);
+    if (phases) *phases = BatchPhases{packed, ran, Clock::now()};
+    if (!ok) {
+        if (e->code == SUCCESS) set_error(e, INTERNAL_ERROR, "Internal error: device batch failed");
+        free_results(res, b->n);
+    }
+    return ok;
+}
+
+// One plan, one device batch: create, pack, run, fetch (the whole of the batch entry unless periods are auto-detected).  The
+// caller's arrays go straight through: no per-series copy, the fetch writes into out_results.
 static bool forecast_batch_uniform(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
                                    const ForecastOptions *options, const int *horizons, ForecastResult *out_results,
                                    AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
     ForecastOptions opt = *options;
-    int hmax = options->horizon;
-    if (horizons) for (size_t s = 0; s < n_series; s++) hmax = std::max(hmax, horizons[s]);
-    opt.horizon = hmax;
     size_t t_max = 0;
-    for (size_t s = 0; s < n_series; s++) t_max = std::max(t_max, lengths[s]);
+    for (size_t s = 0; s < n_series; s++) {
+        t_max = std::max(t_max, lengths[s]);
+        if (horizons) opt.horizon = std::max(opt.horizon, horizons[s]);
+    }
     AnofoxHipBatch *b = nullptr;
     AnofoxError e;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     if (!anofox_hip_batch_create(n_series, t_max, &opt, &b, &e)) {
-        if (e.code == INVALID_INPUT) {
-            // an option block the core rejects (seasonal_period on a non-seasonal model, bad ETS notation or pool) is a
-            // PER-SERIES error there, raised after the length checks (forecast.rs:516-565): a series that is too short
-            // reports InsufficientData first, and a batch made only of such series does not abort the statement
-            if (out_errors)
-                for (size_t s = 0; s < n_series; s++) {
-                    if (lengths[s] == 0) set_error(&out_errors[s], INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0");
-                    else if (lengths[s] < 3)
-                        set_error(&out_errors[s], INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(lengths[s]));
-                    else out_errors[s] = e;
-                }
-            return true;
-        }
+        // (a rejected option block is every long-enough series' own error: a batch made only of short series does not abort the statement)
+        if (e.code == INVALID_INPUT) { option_error_per_series(out_errors, lengths, n_series, e); return true; }
         if (out_batch_error) *out_batch_error = e;
         if (out_errors) for (size_t s = 0; s < n_series; s++) out_errors[s] = e;
         return false;
     }
     const bool timing = b->tun.timing;     // ANOFOX_HIP_TIMING: phase times of the batch entry on stderr
-    const auto t1 = std::chrono::steady_clock::now();
-    bool ok = anofox_hip_batch_pack_host(b, values, validity, lengths, &e);
-    const auto t2 = std::chrono::steady_clock::now();
-    ok = ok && anofox_hip_batch_run(b, nullptr, &e);
-    if (ok && timing) (void)hipStreamSynchronize(b->last_stream);
-    const auto t3 = std::chrono::steady_clock::now();
-    ok = ok && anofox_hip_batch_fetch(b, out_results, out_errors);
-    const auto t4 = std::chrono::steady_clock::now();
-    if (!ok) {
-        if (e.code == SUCCESS) set_error(&e, INTERNAL_ERROR, "Internal error: device batch failed");
-        if (out_batch_error) *out_batch_error = e;
-    } else if (horizons) {
-        // per-series horizon: forecasts are prefix-consistent, so truncate (ts_cv_forecast_native.cpp:676-677)
-        for (size_t s = 0; s < n_series; s++)
-            if (out_results[s].point_forecasts && horizons[s] >= 0 && (size_t)horizons[s] < out_results[s].n_forecasts) {
-                out_results[s].n_forecasts = (size_t)horizons[s];
-                if (horizons[s] == 0) {
-                    std::free(out_results[s].point_forecasts); std::free(out_results[s].lower_bounds); std::free(out_results[s].upper_bounds);
-                    out_results[s].point_forecasts = out_results[s].lower_bounds = out_results[s].upper_bounds = nullptr;
-                }
-            }
-    }
+    const auto t1 = Clock::now();
+    BatchPhases ph;
+    const bool ok = run_batch(b, values, validity, lengths, out_results, out_errors, &e, &ph, [] {});
+    if (!ok) { if (out_batch_error) *out_batch_error = e; }
+    else if (horizons) for (size_t s = 0; s < n_series; s++) truncate_to_horizon(out_results[s], horizons[s]);
     anofox_hip_batch_destroy(b);
-    if (timing) {
-        auto ms = [](auto a, auto z) { return std::chrono::duration<double, std::milli>(z - a).count(); };
+    if (timing)
         std::fprintf(stderr, "[anofox-hip] batch of %zu: create %.1f ms, pack + H2D %.1f ms, run %.1f ms, fetch %.1f ms, destroy %.1f ms\n", n_series,
-                     ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, std::chrono::steady_clock::now()));
-    }
+                     ms_between(t0, t1), ms_between(t1, ph.packed), ms_between(ph.packed, ph.ran), ms_between(ph.ran, ph.fetched), ms_between(ph.fetched, Clock::now()));
     return ok;
 }
 
-// the batch entry on the calling thread's current device
+namespace {
+
+// the caller's arrays of one batch call
+struct BatchCall {
+    const double *const *values; const uint64_t *const *validity; const size_t *lengths; size_t n_series;
+    const ForecastOptions *options; const int *horizons; ForecastResult *out_results; AnofoxError *out_errors;
+};
+
+// The first failure among the batches that run side by side for one call speaks for the call.
+struct FirstError {
+    std::mutex mu; bool ok = true; AnofoxError first;
+    FirstError() { clear_error(&first); }
+    void fail(const AnofoxError &e)
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (ok) first = e;
+        ok = false;
+    }
+    void fail(const std::string &msg) { AnofoxError e; clear_error(&e); set_error(&e, INTERNAL_ERROR, msg); fail(e); }
+};
+
+// The host threads of one call: joined before the call returns, whatever the way out.
+struct ThreadJoiner {
+    std::vector<std::thread> threads;
+    ~ThreadJoiner() { join(); }
+    void join() { for (auto &t : threads) if (t.joinable()) t.join(); }
+    // false: the host's thread limit (EAGAIN) -- the caller does the work on its own thread
+    template <class Work> bool start(const Work &work) { try { threads.emplace_back(work); return true; } catch (const std::system_error &) { return false; } }
+};
+
+// What a host thread that works for a call runs under: the call's device (a per-thread setting) and the ARIMA method that was in
+// force when the call came in.  Nothing may leave a worker thread.
+template <class Body> void call_worker(int device, int method, FirstError &errors, Body &&body)
+{
+    ArimaMethodScope method_scope(method);
+    try {
+        (void)hipSetDevice(device);
+        body();
+    } catch (const std::exception &e) { errors.fail(std::string("Internal error: ") + e.what()); }
+    catch (...) { errors.fail("Internal error: worker failed"); }
+}
+
+const double EMPTY_SERIES = 0.0;        // what a padding column points at (length 0)
+
+// The series behind the columns of one device batch -- src[j] is the caller's series of column j, PAD_COLUMN an empty one -- and
+// the room for their results.
+struct Columns {
+    std::vector<size_t> src, len;
+    std::vector<const double *> v;
+    std::vector<const uint64_t *> m;
+    std::vector<ForecastResult> res;
+    std::vector<AnofoxError> errs;
+    size_t t_max = 0;           // the longest series
+    int h_max = 0;              // the largest horizon: the call's, or a series' own
+
+    void gather(const BatchCall &c)
+    {
+        const size_t n = src.size();
+        v.resize(n); m.resize(n); len.resize(n); res.resize(n); errs.resize(n);
+        t_max = 0;
+        h_max = c.options->horizon;
+        for (size_t j = 0; j < n; j++) {
+            const size_t s = src[j];
+            const bool pad = s == PAD_COLUMN;
+            v[j] = pad ? &EMPTY_SERIES : c.values[s];
+            m[j] = pad || !c.validity ? nullptr : c.validity[s];
+            len[j] = pad ? 0 : c.lengths[s];
+            std::memset(&res[j], 0, sizeof(ForecastResult));
+            clear_error(&errs[j]);
+            t_max = std::max(t_max, len[j]);
+            if (!pad && c.horizons) h_max = std::max(h_max, c.horizons[s]);
+        }
+    }
+    const uint64_t *const *masks(const BatchCall &c) const { return c.validity ? m.data() : nullptr; }
+    void deliver(const BatchCall &c) { deliver_results(res.data(), errs.data(), src.data(), src.size(), c.horizons, c.options->horizon, c.out_results, c.out_errors); }
+};
+
+// the option block of a batch that names its period: forecast() sees the same period either way (forecast.rs:527-539)
+ForecastOptions part_options(const ForecastOptions *options, int period, int horizon)
+{
+    ForecastOptions o = *options;
+    o.auto_detect_seasonality = false;
+    o.seasonal_period = period > 1 ? period : 0;           // 0 with detection off: period 1
+    o.horizon = horizon;
+    return o;
+}
+
+// the period a model uses for a series whose detected period is `period`
+int used_period(ModelType model, int period)
+{
+    switch (model) {
+    case M_Naive: case M_RandomWalkDrift: case M_ARIMA: case M_SES: case M_SESOptimized: case M_Holt: return 1;
+    case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: return 1;
+    case M_AutoARIMA: return period > ETS_MAX_PERIOD ? ETS_MAX_PERIOD + 1 : (period > 1 ? period : 1);      // (forecast.rs:528-537, 1448-1452: any detected period is seasonal)
+    default: return period;
+    }
+}
+
+std::vector<int> detect_used_periods(const BatchCall &c, ModelType model, bool timing)
+{
+    const auto t0 = Clock::now();
+    const std::vector<int> raw = detect_periods_host_series(c.values, c.validity, c.lengths, c.n_series);
+    std::vector<int> period(c.n_series, 1);
+    for (size_t s = 0; s < c.n_series; s++) period[s] = c.lengths[s] < 3 ? 1 : used_period(model, raw[s] > 0 ? raw[s] : 1);
+    if (timing) std::fprintf(stderr, "[anofox-hip] period detection of %zu series: %.1f ms\n", c.n_series, ms_between(t0, Clock::now()));
+    return period;
+}
+
+// AutoETS and the seasonal smoothing family: the small parts of a ring class run as ONE batch (138 tiny batches x 25 spec chains
+// on 16 hardware queues were latency bound end to end).  AutoARIMA: every detected period is seasonal (forecast.rs:528-537,
+// 1448-1452) -- ~400 distinct ones on the M5 shape, each a latency-bound batch of its own (13 sweeps with a host round trip
+// apiece: 8.2 s for the 30,490 series) -- so the periods above 24 (ring of seasonal lags in the HBM scratch) run as ONE batch
+// with the period per series (arima.hip pass variant 6).
+MergeRule merge_rule(const Plan &plan, const Tunables &tun)
+{
+    if (!tun.merge_periods) return MergeRule::None;
+    if (plan.model == M_AutoARIMA) return MergeRule::AutoArima;
+    const bool seasonal_ets = plan.model == M_AutoETS || plan.model == M_HoltWinters || plan.model == M_SeasonalES || plan.model == M_SeasonalESOptimized ||
+                              (plan.model == M_ETS && plan.ets_spec_id >= 0 && spec_season(plan.ets_spec_id) != 0);
+    return seasonal_ets ? MergeRule::EtsLike : MergeRule::None;
+}
+
+// a part as a device batch of its own through the plain path, which also reports what is wrong with the option block
+void run_part(const BatchCall &c, const Part &part, FirstError &errors)
+{
+    Columns col;
+    col.src = part.series;
+    col.gather(c);
+    const ForecastOptions o = part_options(c.options, part.period, col.h_max);
+    AnofoxError be;
+    const bool ok = forecast_batch_uniform(col.v.data(), col.masks(c), col.len.data(), col.src.size(), &o, nullptr, col.res.data(), col.errs.data(), &be);
+    col.deliver(c);             // (after a failure: the per-series errors, no arrays)
+    if (!ok) errors.fail(be);
+}
+
+// the parts of one ring class as ONE batch whose 64-column blocks each have their own period
+void run_merged(const BatchCall &c, const MergedBatch &batch, bool timing, FirstError &errors)
+{
+    MergedColumns mc = merged_columns(batch);
+    Columns col;
+    col.src = std::move(mc.src);
+    col.gather(c);
+    const size_t nc = col.src.size();
+    const ForecastOptions o = part_options(c.options, mc.m_max, col.h_max);
+    AnofoxHipBatch *mb = nullptr;
+    AnofoxError be;
+    clear_error(&be);
+    const auto t0 = Clock::now();
+    bool ok = anofox_hip_batch_create(nc, col.t_max, &o, &mb, &be);
+    const auto t1 = Clock::now();
+    BatchPhases ph{t1, t1, t1};
+    if (ok) {
+        ok = run_batch(mb, col.v.data(), col.masks(c), col.len.data(), col.res.data(), col.errs.data(), &be, &ph, [&] {
+            mc.period.resize(mb->ld, mc.period.back());
+            mb->d_m_col = dalloc<int32_t>(mb->ld);
+            HIPCHECK(hipMemcpy(mb->d_m_col, mc.period.data(), mb->ld * sizeof(int32_t), hipMemcpyHostToDevice));
+            mb->merged_m_max = mc.m_max;
+            for (size_t j = 0; j < nc; j++) mb->h_period[j] = mc.period[j];     // what the host-side fitted values use
+        });
+        anofox_hip_batch_destroy(mb);
+    } else if (be.code == SUCCESS) set_error(&be, INTERNAL_ERROR, "Internal error: device batch failed");
+    if (timing)
+        std::fprintf(stderr, "[anofox-hip] merged batch: %zu parts with periods %d..%d in %zu columns: %.1f ms (create %.1f, pack %.1f, run %.1f, fetch + destroy %.1f)\n",
+                     batch.size(), batch.front().period, mc.m_max, nc, ms_between(t0, Clock::now()), ms_between(t0, t1), ms_between(t1, ph.packed),
+                     ms_between(ph.packed, ph.ran), ms_between(ph.ran, Clock::now()));
+    if (ok) col.deliver(c);
+    else errors.fail(be);
+}
+
+// The small parts, pulled from a shared counter.  A worker keeps ONE device batch for all its parts (creating and destroying a
+// batch costs ~30 ms of allocator calls that serialise across threads -- as much as the part's own run): capacity = the largest
+// small part, short parts are padded with empty series, the period is set before every pack.
+void run_small_parts(const BatchCall &c, const std::vector<Part> &small, std::atomic<size_t> &next, size_t t_cap, int h_cap, bool timing,
+                     Clock::time_point t_start, FirstError &errors)
+{
+    if (small.empty()) return;
+    const size_t cap = small.front().series.size();
+    AnofoxHipBatch *wb = nullptr;
+    Columns col;
+    for (size_t g = next.fetch_add(1); g < small.size(); g = next.fetch_add(1)) {
+        const Part &part = small[g];
+        AnofoxError be;
+        if (!wb) {
+            const ForecastOptions o = part_options(c.options, part.period, h_cap);
+            if (!anofox_hip_batch_create(cap, t_cap, &o, &wb, &be)) { wb = nullptr; run_part(c, part, errors); continue; }   // the plain path reports it
+        }
+        wb->opt.seasonal_period = part.period > 1 ? part.period : 0;
+        col.src = part.series;
+        col.src.resize(cap, PAD_COLUMN);
+        col.gather(c);
+        const auto tw0 = Clock::now();
+        const bool ok = run_batch(wb, col.v.data(), col.masks(c), col.len.data(), col.res.data(), col.errs.data(), &be, nullptr, [] {});
+        if (timing)
+            std::fprintf(stderr, "[anofox-hip] small part: period %d, %zu series: %.1f ms (started at %.1f ms)\n", part.period, part.series.size(),
+                         ms_between(tw0, Clock::now()), ms_between(t_start, tw0));
+        if (ok) col.deliver(c);
+        else errors.fail(be);
+    }
+    if (wb) anofox_hip_batch_destroy(wb);
+}
+
+} // namespace
+} // extern "C++"
+
+// The batch entry on the calling thread's current device.  Per-series period detection (params := MAP{}): every distinct period a
+// model uses is its own run of the pipeline, latency bound and tiny (~140 distinct periods per thousand M5-like series).  Detect
+// the periods, plan how the batch is cut (host_parts.hpp) and run the pieces side by side from a few host threads, each as a
+// batch that names its period(s) -- forecast() sees the same period either way (forecast.rs:527-539), so the results are unchanged.
 static bool forecast_batch_one_device(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
                                       const ForecastOptions *options, const int *horizons, ForecastResult *out_results,
                                       AnofoxError *out_errors, AnofoxError *out_batch_error)
 {
-    // Per-series period detection (params := MAP{}): every distinct period a model uses is its own run of the pipeline,
-    // latency bound and tiny (~140 distinct periods per thousand M5-like series).  Detect the periods here, split the batch
-    // by used period and run the parts side by side from a few host threads, each part as an ordinary batch that names
-    // its period -- forecast() sees the same period either way (forecast.rs:527-539), so the results are unchanged.
     Plan plan;
     AnofoxError pe;
-    const int method_in_force = arima_method_in_force();       // ... for the worker threads below
     const bool detect = options->auto_detect_seasonality && options->seasonal_period == 0 && n_series >= 2;
     if (!detect || !make_plan(options, plan, &pe))
         return forecast_batch_uniform(values, validity, lengths, n_series, options, horizons, out_results, out_errors, out_batch_error);
+    const BatchCall c{values, validity, lengths, n_series, options, horizons, out_results, out_errors};
     try {
         EvictionDeferral park_evictions;                 // several batches run side by side below
-        auto used_period = [&](int period) {
-            switch (plan.model) {
-            case M_Naive: case M_RandomWalkDrift: case M_ARIMA: case M_SES: case M_SESOptimized: case M_Holt: return 1;
-            case M_CrostonClassic: case M_CrostonSBA: case M_TSB: case M_ADIDA: case M_IMAPA: return 1;
-            case M_AutoARIMA: return period > ETS_MAX_PERIOD ? ETS_MAX_PERIOD + 1 : (period > 1 ? period : 1);      // (forecast.rs:528-537, 1448-1452: any detected period is seasonal)
-            default: return period;
-            }
-        };
-        std::vector<int> period(n_series, 1);
-        {
-            const auto td0 = std::chrono::steady_clock::now();
-            const std::vector<int> raw = detect_periods_host_series(values, validity, lengths, n_series);
-            for (size_t s = 0; s < n_series; s++) period[s] = lengths[s] < 3 ? 1 : used_period(raw[s] > 0 ? raw[s] : 1);
-            if (Tunables::from_env().timing)
-                std::fprintf(stderr, "[anofox-hip] period detection of %zu series: %.1f ms\n", n_series,
-                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count());
-        }
-        std::map<int, std::vector<size_t>> groups;
-        for (size_t s = 0; s < n_series; s++) groups[period[s]].push_back(s);
-        std::vector<std::pair<int, std::vector<size_t>>> parts(groups.begin(), groups.end());
-        std::sort(parts.begin(), parts.end(), [](const auto &x, const auto &y) { return x.second.size() > y.second.size(); });
-        std::mutex err_mu;
-        bool all_ok = true;
-        AnofoxError first_err;
-        first_err.code = SUCCESS;
-        auto run_part = [&](const std::pair<int, std::vector<size_t>> &part) {
-            const std::vector<size_t> &idx = part.second;
-            const size_t k = idx.size();
-            std::vector<const double *> v(k);
-            std::vector<const uint64_t *> m(k);
-            std::vector<size_t> len(k);
-            std::vector<int> hz(k);
-            for (size_t j = 0; j < k; j++) {
-                v[j] = values[idx[j]]; m[j] = validity ? validity[idx[j]] : nullptr; len[j] = lengths[idx[j]];
-                if (horizons) hz[j] = horizons[idx[j]];
-            }
-            ForecastOptions o = *options;
-            o.auto_detect_seasonality = false;
-            o.seasonal_period = part.first > 1 ? part.first : 0;           // 0 with detection off: period 1
-            std::vector<ForecastResult> res(k);
-            std::vector<AnofoxError> errs(k);
-            for (auto &e : errs) { e.code = SUCCESS; e.message[0] = 0; }
-            AnofoxError be;
-            const bool ok = forecast_batch_uniform(v.data(), validity ? m.data() : nullptr, len.data(), k, &o, horizons ? hz.data() : nullptr,
-                                                   res.data(), errs.data(), &be);
-            for (size_t j = 0; j < k; j++) {
-                out_results[idx[j]] = res[j];
-                if (out_errors) out_errors[idx[j]] = errs[j];
-            }
-            if (!ok) {
-                std::lock_guard<std::mutex> lock(err_mu);
-                if (all_ok) first_err = be;
-                all_ok = false;
-            }
-        };
-        // AutoETS: the small parts with periods 2..48 run as ONE batch whose columns are grouped by period in blocks of 64 (the
-        // kernels read the period per block): 138 tiny batches x 25 spec chains on 16 hardware queues were latency bound end to end
         const Tunables tun = Tunables::from_env();
-        // AutoARIMA (round 4): every detected period is seasonal now (forecast.rs:528-537, 1448-1452) -- ~400 distinct ones on the M5
-        // shape, each a latency-bound batch of its own (13 sweeps with a host round trip apiece: 8.2 s for the 30,490 series).  The
-        // periods above 24 (ring of seasonal lags in the HBM scratch) run as ONE batch with the period per series (arima.hip pass
-        // variant 6); the periods up to 24 keep their compile-time / LDS-ring kernels, one batch each.
-        const bool arima_merge = tun.merge_periods && plan.model == M_AutoARIMA;
-        const bool do_merge = arima_merge || (tun.merge_periods && (plan.model == M_AutoETS || plan.model == M_HoltWinters || plan.model == M_SeasonalES || plan.model == M_SeasonalESOptimized ||
-                                                (plan.model == M_ETS && plan.ets_spec_id >= 0 && spec_season(plan.ets_spec_id) != 0)));
-            // one merged batch per ring class (seasonal ring in LDS up to 64, in an HBM scratch above; the scratch is sized by the
-            // class's largest period, hence a few classes)
-            using Part = std::pair<int, std::vector<size_t>>;
-            std::mutex merged_mu;
-            auto run_merged = [&](std::vector<Part> &take) -> bool {
-                std::sort(take.begin(), take.end(), [](const Part &x, const Part &y) { return x.first < y.first; });
-                static const double dummy_v = 0.0;
-                std::vector<const double *> v;
-                std::vector<const uint64_t *> mk;
-                std::vector<size_t> len, src;                       // src: index of the caller's series, or SIZE_MAX for padding
-                std::vector<int32_t> mcol;
-                size_t t_cap = 0;
-                int h_cap = options->horizon, m_max = 0;
-                for (const auto &part : take) {
-                    for (size_t idx : part.second) {
-                        v.push_back(values[idx]); mk.push_back(validity ? validity[idx] : nullptr); len.push_back(lengths[idx]); src.push_back(idx);
-                        mcol.push_back(part.first);
-                        t_cap = std::max(t_cap, lengths[idx]);
-                        if (horizons) h_cap = std::max(h_cap, horizons[idx]);
-                    }
-                    while (v.size() % 64) { v.push_back(&dummy_v); mk.push_back(nullptr); len.push_back(0); src.push_back(SIZE_MAX); mcol.push_back(part.first); }
-                    m_max = std::max(m_max, part.first);
-                }
-                const size_t nc = v.size();
-                ForecastOptions o = *options;
-                o.auto_detect_seasonality = false;
-                o.seasonal_period = m_max;
-                o.horizon = h_cap;
-                AnofoxHipBatch *mb = nullptr;
-                AnofoxError be;
-                be.code = SUCCESS; be.message[0] = 0;
-                std::vector<ForecastResult> res(nc);
-                std::vector<AnofoxError> errs(nc);
-                for (size_t j = 0; j < nc; j++) { std::memset(&res[j], 0, sizeof(ForecastResult)); errs[j].code = SUCCESS; errs[j].message[0] = 0; }
-                const auto tm0 = std::chrono::steady_clock::now();
-                bool ok = anofox_hip_batch_create(nc, t_cap, &o, &mb, &be);
-                auto tm1 = std::chrono::steady_clock::now(), tm2 = tm1, tm3 = tm1;
-                if (ok) {
-                    ok = anofox_hip_batch_pack_host(mb, v.data(), validity ? mk.data() : nullptr, len.data(), &be);
-                    tm2 = std::chrono::steady_clock::now();
-                    if (ok) {
-                        try {
-                            mcol.resize(mb->ld, mcol.empty() ? 1 : mcol.back());
-                            mb->d_m_col = dalloc<int32_t>(mb->ld);
-                            HIPCHECK(hipMemcpy(mb->d_m_col, mcol.data(), mb->ld * sizeof(int32_t), hipMemcpyHostToDevice));
-                            mb->merged_m_max = m_max;
-                            for (size_t j = 0; j < nc; j++) mb->h_period[j] = mcol[j];     // what the host-side fitted values use
-                        } catch (const HipFail &f) { report_hip_failure(&be, f); ok = false; }
-                    }
-                    ok = ok && anofox_hip_batch_run(mb, nullptr, &be);
-                    tm3 = std::chrono::steady_clock::now();
-                    ok = ok && anofox_hip_batch_fetch(mb, res.data(), errs.data());
-                    anofox_hip_batch_destroy(mb);
-                }
-                if (tun.timing) {
-                    auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-                    std::fprintf(stderr, "[anofox-hip] merged batch: %zu parts with periods %d..%d in %zu columns: %.1f ms (create %.1f, pack %.1f, run %.1f, fetch + destroy %.1f)\n",
-                                 take.size(), take.front().first, m_max, nc, ms(tm0, std::chrono::steady_clock::now()), ms(tm0, tm1), ms(tm1, tm2), ms(tm2, tm3),
-                                 ms(tm3, std::chrono::steady_clock::now()));
-                }
-                if (!ok) {
-                    if (be.code == SUCCESS) set_error(&be, INTERNAL_ERROR, "Internal error: device batch failed");
-                    for (size_t j = 0; j < nc; j++) anofox_free_forecast_result(&res[j]);
-                    std::lock_guard<std::mutex> lock(merged_mu);
-                    if (out_batch_error && out_batch_error->code == SUCCESS) *out_batch_error = be;
-                    return false;
-                }
-                for (size_t j = 0; j < nc; j++) {
-                    if (src[j] == SIZE_MAX) { anofox_free_forecast_result(&res[j]); continue; }
-                    ForecastResult &r = res[j];
-                    const int hs = horizons ? horizons[src[j]] : options->horizon;      // forecasts are prefix-consistent: truncate
-                    if (r.point_forecasts && hs >= 0 && (size_t)hs < r.n_forecasts) {
-                        r.n_forecasts = (size_t)hs;
-                        if (hs == 0) {
-                            std::free(r.point_forecasts); std::free(r.lower_bounds); std::free(r.upper_bounds);
-                            r.point_forecasts = r.lower_bounds = r.upper_bounds = nullptr;
-                        }
-                    }
-                    out_results[src[j]] = r;
-                    if (out_errors) out_errors[src[j]] = errs[j];
-                }
-                return true;
-            };
-            // (the LDS ring of a round kernel is sized by the batch's largest period, for every wave: periods up to 64 in one batch
-            //  left three waves per CU -- a tenth of the uniform batch's rate per series -- so a merged batch keeps periods above 16
-            //  in the HBM ring, which streams like y; more, finer classes only multiply the streams that share the hardware queues)
-            static const int CLASS_HI[] = {ETS_MERGED_LDS_PERIOD, ETS_MAX_PERIOD};
-            std::vector<Part> keep;
-            std::vector<std::vector<Part>> take(sizeof CLASS_HI / sizeof CLASS_HI[0]);
-            for (auto &part : parts) {
-                int c = -1;
-                if (arima_merge) { if (part.first > 24 && part.first <= ETS_MAX_PERIOD && part.second.size() < 2048) c = 1; }
-                else if (do_merge && part.first >= 2 && part.second.size() < 2048)
-                    for (size_t k = 0; k < take.size(); k++) if (part.first <= CLASS_HI[k]) { c = (int)k; break; }
-                (c >= 0 ? take[(size_t)c] : keep).push_back(std::move(part));
-            }
-            // The HBM-ring class is cut where its ring scratch (workgroups of the widest launch x largest period x 512 B per seasonal
-            // spec; the widest launch is the speculative driver's 16 problems per workgroup, or one wave per problem for the last
-            // 2,048) would pass 2 GiB per spec: many rare long periods otherwise ask for tens of GB.
-            {
-                std::vector<std::vector<Part>> cut;
-                auto scratch_of = [](size_t cols, int m_hi) { return (double)std::max<size_t>((cols + 15) / 16, std::min<size_t>(cols, 2048)) * (double)m_hi * 512.0; };
-                for (auto &cls : take) {
-                    std::sort(cls.begin(), cls.end(), [](const Part &x, const Part &y) { return x.first < y.first; });
-                    std::vector<Part> cur;
-                    size_t cols = 0;
-                    for (auto &part : cls) {
-                        const size_t pc = (part.second.size() + 63) / 64 * 64;
-                        if (!cur.empty() && part.first > ETS_MERGED_LDS_PERIOD && scratch_of(cols + pc, part.first) > 2.0 * 1073741824.0) {
-                            cut.push_back(std::move(cur));
-                            cur.clear();
-                            cols = 0;
-                        }
-                        cols += pc;
-                        cur.push_back(std::move(part));
-                    }
-                    if (!cur.empty()) cut.push_back(std::move(cur));
-                }
-                take = std::move(cut);
-            }
-            // the classes side by side (each is latency bound by its slowest fit and far from filling the chip)
-            std::vector<std::vector<Part> *> todo;
-            for (auto &cls : take) {
-                if (cls.size() >= 2) todo.push_back(&cls);
-                else for (auto &part : cls) keep.push_back(std::move(part));
-            }
-            std::atomic<bool> merged_ok{true};
-            int cur_dev_m = 0;
-            (void)hipGetDevice(&cur_dev_m);
-            // one host thread per LDS-ring batch, one for the HBM-ring batches (one after the other: they share the ring scratch)
-            auto run_cls = [&](std::vector<std::vector<Part> *> group) {
-                ArimaMethodScope method_scope(method_in_force);
-                try {
-                    (void)hipSetDevice(cur_dev_m);
-                    for (auto *cls : group) if (!run_merged(*cls)) merged_ok = false;
-                } catch (...) { merged_ok = false; }                // nothing may leave a worker thread
-            };
-            // ... and beside the parts that stay separate (below); joined before this function returns, whatever the way out
-            std::vector<std::thread> cls_threads;
-            struct Joiner { std::vector<std::thread> &t; ~Joiner() { for (auto &x : t) if (x.joinable()) x.join(); } } cls_joiner{cls_threads};
-            std::vector<std::vector<Part> *> grp_hbm;
-            // (a class whose thread cannot be created -- EAGAIN under the host's thread limit -- runs here, before the parts)
-            auto start_cls = [&](std::vector<std::vector<Part> *> group) {
-                try { cls_threads.emplace_back(run_cls, group); }
-                catch (const std::system_error &) { run_cls(group); }
-            };
-            for (auto *cls : todo) {
-                if (cls->back().first <= ETS_MERGED_LDS_PERIOD) start_cls(std::vector<std::vector<Part> *>{cls});
-                else grp_hbm.push_back(cls);
-            }
-            if (!grp_hbm.empty()) start_cls(grp_hbm);
-            parts = std::move(keep);
-            std::sort(parts.begin(), parts.end(), [](const Part &x, const Part &y) { return x.second.size() > y.second.size(); });
+        const PartPlan parts = plan_parts(parts_by_period(detect_used_periods(c, plan.model, tun.timing)), merge_rule(plan, tun),
+                                          PartLimits{ETS_MERGED_LDS_PERIOD, ETS_MAX_PERIOD});
         if (tun.timing) {
             std::string desc;
-            for (auto &part : parts) desc += " " + std::to_string(part.first) + "x" + std::to_string(part.second.size());
+            for (const auto *list : {&parts.big, &parts.small})
+                for (const Part &part : *list) desc += " " + std::to_string(part.period) + "x" + std::to_string(part.series.size());
             std::fprintf(stderr, "[anofox-hip] remaining parts (period x series):%s\n", desc.c_str());
         }
-        // the big parts fill the chip on their own and hold the most memory: one at a time on this thread (below), beside the small
-        // ones, which run side by side on the workers (a small part is a chain of latency-bound launches: it hardly slows a big one)
-        size_t first_small = 0;
-        while (first_small < parts.size() && parts[first_small].second.size() >= 2048) first_small++;
-        // A worker keeps ONE device batch for all its parts (creating and destroying a batch costs ~30 ms of allocator calls
-        // that serialise across threads -- as much as the part's own run): capacity = the largest small part, short parts are
-        // padded with empty series, the period is set before every pack.
-        const size_t cap = first_small < parts.size() ? parts[first_small].second.size() : 0;
-        size_t t_cap = 0;
+        FirstError errors;
+        const int method = arima_method_in_force();
+        int device = 0;
+        (void)hipGetDevice(&device);
+        size_t t_cap = 0;                                // what a worker's reused batch must hold
         int h_cap = options->horizon;
         for (size_t s = 0; s < n_series; s++) { t_cap = std::max(t_cap, lengths[s]); if (horizons) h_cap = std::max(h_cap, horizons[s]); }
-        std::atomic<size_t> next{first_small};
-        const auto t_small0 = std::chrono::steady_clock::now();
-        int cur_dev = 0;
-        (void)hipGetDevice(&cur_dev);                      // the device is a per-thread setting: the workers inherit the caller's
-        auto work_body = [&]() {
-            (void)hipSetDevice(cur_dev);
-            AnofoxHipBatch *wb = nullptr;
-            static const double dummy = 0.0;
-            std::vector<const double *> v(cap, &dummy);
-            std::vector<const uint64_t *> m(cap, nullptr);
-            std::vector<size_t> len(cap, 0);
-            std::vector<ForecastResult> res(cap);
-            std::vector<AnofoxError> errs(cap);
-            for (size_t g = next.fetch_add(1); g < parts.size(); g = next.fetch_add(1)) {
-                const std::vector<size_t> &idx = parts[g].second;
-                const size_t k = idx.size();
-                AnofoxError be;
-                be.code = SUCCESS; be.message[0] = 0;
-                if (!wb) {
-                    ForecastOptions o = *options;
-                    o.auto_detect_seasonality = false;
-                    o.seasonal_period = parts[g].first > 1 ? parts[g].first : 0;
-                    o.horizon = h_cap;
-                    if (!anofox_hip_batch_create(cap, t_cap, &o, &wb, &be)) { wb = nullptr; run_part(parts[g]); continue; }   // the plain path reports it
-                }
-                wb->opt.seasonal_period = parts[g].first > 1 ? parts[g].first : 0;
-                for (size_t j = 0; j < cap; j++) {
-                    if (j < k) { v[j] = values[idx[j]]; m[j] = validity ? validity[idx[j]] : nullptr; len[j] = lengths[idx[j]]; }
-                    else { v[j] = &dummy; m[j] = nullptr; len[j] = 0; }
-                    std::memset(&res[j], 0, sizeof(ForecastResult));
-                    errs[j].code = SUCCESS; errs[j].message[0] = 0;
-                }
-                const auto tw0 = std::chrono::steady_clock::now();
-                const bool ok = anofox_hip_batch_pack_host(wb, v.data(), validity ? m.data() : nullptr, len.data(), &be) &&
-                                anofox_hip_batch_run(wb, nullptr, &be) && anofox_hip_batch_fetch(wb, res.data(), errs.data());
-                if (tun.timing)
-                    std::fprintf(stderr, "[anofox-hip] small part: period %d, %zu series: %.1f ms (started at %.1f ms)\n", parts[g].first, k,
-                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count(),
-                                 std::chrono::duration<double, std::milli>(tw0 - t_small0).count());
-                if (!ok) {
-                    if (be.code == SUCCESS) set_error(&be, INTERNAL_ERROR, "Internal error: device batch failed");
-                    for (size_t j = 0; j < cap; j++) anofox_free_forecast_result(&res[j]);      // whatever the fetch had allocated
-                    std::lock_guard<std::mutex> lock(err_mu);
-                    if (all_ok) first_err = be;
-                    all_ok = false;
-                    continue;
-                }
-                for (size_t j = 0; j < k; j++) {
-                    ForecastResult &r = res[j];
-                    const int hs = horizons ? horizons[idx[j]] : options->horizon;      // forecasts are prefix-consistent: truncate
-                    if (r.point_forecasts && hs >= 0 && (size_t)hs < r.n_forecasts) {
-                        r.n_forecasts = (size_t)hs;
-                        if (hs == 0) {
-                            std::free(r.point_forecasts); std::free(r.lower_bounds); std::free(r.upper_bounds);
-                            r.point_forecasts = r.lower_bounds = r.upper_bounds = nullptr;
-                        }
-                    }
-                    out_results[idx[j]] = r;
-                    if (out_errors) out_errors[idx[j]] = errs[j];
-                }
-            }
-            if (wb) anofox_hip_batch_destroy(wb);
+        std::atomic<size_t> next_small{0}, next_big{0};
+        const auto t_small0 = Clock::now();
+        // The big parts fill the chip on their own and hold the most memory: up to four side by side (one is throttled by whatever
+        // else runs; one after the other they were the critical path of the call), largest first, each a batch of its own.
+        auto big_work = [&] {
+            call_worker(device, method, errors, [&] { for (size_t g = next_big.fetch_add(1); g < parts.big.size(); g = next_big.fetch_add(1)) run_part(c, parts.big[g], errors); });
         };
-        auto work = [&]() {
-            ArimaMethodScope method_scope(method_in_force);
-            try { work_body(); }
-            catch (const std::exception &e) {           // nothing may leave a worker thread
-                std::lock_guard<std::mutex> lock(err_mu);
-                if (all_ok) set_error(&first_err, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
-                all_ok = false;
-            } catch (...) {
-                std::lock_guard<std::mutex> lock(err_mu);
-                if (all_ok) set_error(&first_err, INTERNAL_ERROR, "Internal error: worker failed");
-                all_ok = false;
-            }
+        // The small parts run side by side on the workers.  (A small part is a chain of latency-bound launches with host round trips
+        // in between -- AutoARIMA: ~13 sweeps of advance / read-back / fit, ~0.2 s whatever its size -- so the number of parts in
+        // flight is what the call's duration divides by; it hardly slows a big one.)
+        auto small_work = [&] {
+            call_worker(device, method, errors, [&] { run_small_parts(c, parts.small, next_small, t_cap, h_cap, tun.timing, t_small0, errors); });
         };
-        // (a small part is a chain of latency-bound launches with host round trips in between -- AutoARIMA: ~13 sweeps of advance /
-        //  read-back / fit, ~0.2 s whatever its size -- so the number of parts in flight is what the call's duration divides by)
         const size_t part_threads = (size_t)std::max(1, tun.part_threads);
-        const unsigned n_thr = (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), part_threads, parts.size() - first_small}));
-        std::vector<std::thread> pool;
-        struct PoolJoiner { std::vector<std::thread> &t; ~PoolJoiner() { for (auto &x : t) if (x.joinable()) x.join(); } } pool_joiner{pool};
-        const bool have_big = first_small > 0;
-        // (workers pull parts from a shared counter: the ones that cannot be created are not missed, this thread takes what is left)
-        for (unsigned i = have_big ? 0 : 1; i < n_thr; i++) {
-            try { pool.emplace_back(work); } catch (const std::system_error &) { break; }
+        const size_t n_small_thr = std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), part_threads, parts.small.size()}));
+        const size_t n_big_thr = std::min<size_t>(parts.big.size(), 4);
+
+        ThreadJoiner threads;
+        // The merged batches of a group one after the other; the groups side by side (each is latency bound by its slowest fit and
+        // far from filling the chip) and beside the parts that stay separate.
+        for (const std::vector<MergedBatch> &group : parts.merged_groups) {
+            auto work = [&, g = &group] { call_worker(device, method, errors, [&] { for (const MergedBatch &batch : *g) run_merged(c, batch, tun.timing, errors); }); };
+            if (!threads.start(work)) work();            // (a group that finds no thread runs here, before the parts)
         }
-        if (have_big) {
-            // the big parts: up to four side by side (one is throttled by whatever else runs; one after the other they were the
-            // critical path of the call), each on its own thread, largest first
-            std::atomic<size_t> next_big{0};
-            auto big_work = [&]() {
-                ArimaMethodScope method_scope(method_in_force);
-                (void)hipSetDevice(cur_dev);
-                try {
-                    for (size_t g = next_big.fetch_add(1); g < first_small; g = next_big.fetch_add(1)) run_part(parts[g]);
-                } catch (...) {                          // nothing may leave a worker thread
-                    std::lock_guard<std::mutex> lock(err_mu);
-                    if (all_ok) set_error(&first_err, INTERNAL_ERROR, "Internal error: worker failed (out of host memory)");
-                    all_ok = false;
-                }
-            };
-            const size_t n_big_thr = std::min<size_t>(first_small, 4);
-            for (size_t i = 1; i < n_big_thr; i++) {
-                try { pool.emplace_back(big_work); } catch (const std::system_error &) { break; }
-            }
-            big_work();
-            work();                          // (nothing left unless the small parts' workers could not be started)
-        } else work();
-        for (auto &t : pool) t.join();
-        for (auto &t : cls_threads) if (t.joinable()) t.join();
-        if (!merged_ok) {
-            if (out_batch_error && out_batch_error->code == SUCCESS) set_error(out_batch_error, INTERNAL_ERROR, "Internal error: device batch failed");
-            return false;
-        }
-        if (!all_ok && out_batch_error) *out_batch_error = first_err;
-        return all_ok;
+        // (workers pull parts from shared counters: the ones that cannot be started are not missed, this thread takes what is left)
+        for (size_t i = n_big_thr ? 0 : 1; i < n_small_thr; i++) if (!threads.start(small_work)) break;
+        for (size_t i = 1; i < n_big_thr; i++) if (!threads.start(big_work)) break;
+        if (n_big_thr) big_work();
+        small_work();
+        threads.join();
+        if (!errors.ok && out_batch_error) *out_batch_error = errors.first;
+        return errors.ok;
     } catch (const std::exception &e) {
         set_error(out_batch_error, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
         return false;
@@ -3205,7 +3111,7 @@ bool anofox_hip_batch_run_many(AnofoxHipBatch *const *batches, size_t n_batches,
     std::vector<char> ok(n_batches, 1);
     auto one = [&](size_t i) {
         AnofoxError e;
-        e.code = SUCCESS; e.message[0] = 0;
+        clear_error(&e);
         try { ok[i] = anofox_hip_batch_run(batches[i], nullptr, &e) ? 1 : 0; }
         catch (...) { ok[i] = 0; set_error(&e, INTERNAL_ERROR, "Internal error: batch run failed"); }
         if (out_errors) out_errors[i] = e;
@@ -3219,12 +3125,9 @@ bool anofox_hip_batch_run_many(AnofoxHipBatch *const *batches, size_t n_batches,
 static bool forecast_one_pooled(const double *values, const uint64_t *validity, size_t length, const ForecastOptions *options, const ForecastOptions &key,
                                 ForecastResult *out_result, AnofoxError *out_error)
 {
-    AnofoxError e;
-    e.code = SUCCESS;
-    std::memset(e.message, 0, sizeof e.message);
-    AnofoxError se;
-    se.code = SUCCESS;
-    std::memset(se.message, 0, sizeof se.message);
+    AnofoxError e, se;
+    clear_error(&e);
+    clear_error(&se);
     const double *vals[1] = {values};
     const uint64_t *valid[1] = {validity};
     size_t lens[1] = {length};
@@ -3248,10 +3151,7 @@ static bool forecast_one_pooled(const double *values, const uint64_t *validity, 
             return false;
         }
     }
-    const bool ok = anofox_hip_batch_pack_host(b, vals, validity ? valid : nullptr, lens, &e) && anofox_hip_batch_run(b, nullptr, &e) &&
-                    anofox_hip_batch_fetch(b, &r, &se);
-    if (!ok) {
-        if (e.code == SUCCESS) set_error(&e, INTERNAL_ERROR, "Internal error: device batch failed");
+    if (!run_batch(b, vals, validity ? valid : nullptr, lens, &r, &se, &e, nullptr, [] {})) {
         anofox_hip_batch_destroy(b);                            // a batch that failed is not reused
         if (out_error) *out_error = e;
         return false;
@@ -3294,11 +3194,7 @@ bool anofox_ts_forecast(const double *values, const uint64_t *validity, size_t l
         ModelType mt;
         if (!parse_model(mname, mt)) { set_error(out_error, INVALID_MODEL, "Invalid model: Unknown model: '" + mname + "'"); return false; }
         if (options->horizon < 0) { set_error(out_error, PANIC_CAUGHT, "Panic in Rust code"); return false; }
-        if (length == 0) { set_error(out_error, INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0"); return false; }
-        if (length < 3) {
-            set_error(out_error, INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(length));
-            return false;
-        }
+        if (series_too_short(out_error, length)) return false;
     }
     // the option block is the key (every byte of it: callers memset it first, ts_forecast_scalar.cpp:440)
     ForecastOptions key;                       // normalised copy: padding and the bytes behind a string's NUL do not take part
@@ -3399,9 +3295,9 @@ bool anofox_ts_forecast(const double *values, const uint64_t *validity, size_t l
             for (size_t j = 0; j < k; j++) { v[j] = grp->reqs[j]->values; m[j] = grp->reqs[j]->validity; len[j] = grp->reqs[j]->length; any_mask |= m[j] != nullptr; }
             std::vector<ForecastResult> res(k);
             std::vector<AnofoxError> errs(k);
-            for (size_t j = 0; j < k; j++) { std::memset(&res[j], 0, sizeof(ForecastResult)); errs[j].code = SUCCESS; errs[j].message[0] = 0; }
+            for (size_t j = 0; j < k; j++) { std::memset(&res[j], 0, sizeof(ForecastResult)); clear_error(&errs[j]); }
             AnofoxError be;
-            be.code = SUCCESS; be.message[0] = 0;
+            clear_error(&be);
             bool ok = false;
             try {
                 ok = forecast_batch_one_device(v.data(), any_mask ? m.data() : nullptr, len.data(), k, options, nullptr, res.data(), errs.data(), &be);
@@ -5963,14 +5859,11 @@ bool anofox_ts_forecast_exog_batch(const double *const *values, const uint64_t *
         clear_error(out_errors ? &out_errors[s] : nullptr);
     }
     auto fail_all = [&](int code, const std::string &msg) {
-        set_error(out_batch_error, code, msg);
-        if (out_errors)
-            for (size_t s = 0; s < n_series; s++) {
-                // the length checks come before the model's own (forecast.rs:780-789)
-                if (lengths[s] == 0) set_error(&out_errors[s], INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0");
-                else if (lengths[s] < 3) set_error(&out_errors[s], INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(lengths[s]));
-                else set_error(&out_errors[s], code, msg);
-            }
+        AnofoxError fe;
+        clear_error(&fe);
+        set_error(&fe, code, msg);
+        if (out_batch_error) *out_batch_error = fe;
+        option_error_per_series(out_errors, lengths, n_series, fe);        // the length checks come before the model's own
         return false;
     };
     if (options->horizon < 0) return fail_all(PANIC_CAUGHT, "Panic in Rust code");
@@ -5999,15 +5892,10 @@ bool anofox_ts_forecast_exog_batch(const double *const *values, const uint64_t *
     AnofoxError e;
     clear_error(&e);
     if (!anofox_hip_batch_create(n_series, t_max, &opt, &b, &e)) return fail_all(e.code, e.message);
-    bool ok = anofox_hip_batch_pack_host(b, values, validity, lengths, &e);
-    if (ok) {
+    bool ok = run_batch(b, values, validity, lengths, out_results, out_errors, &e, nullptr, [&] {
         DeviceGuard guard(b->dev);
-        try { batch_pack_exog_host(b, xreg, future_xreg, lengths, K); }
-        catch (const HipFail &f) { report_hip_failure(&e, f); ok = false; }
-        catch (const std::exception &x) { set_error(&e, INTERNAL_ERROR, std::string("Internal error: ") + x.what()); ok = false; }
-    }
-    ok = ok && anofox_hip_batch_run(b, nullptr, &e);
-    ok = ok && anofox_hip_batch_fetch(b, out_results, out_errors);
+        batch_pack_exog_host(b, xreg, future_xreg, lengths, K);
+    });
     if (ok && (out_coefficients || out_used)) {
         std::vector<double> b0(n_series), beta(n_series * K);
         ok = anofox_hip_batch_exog_coefficients(b, b0.data(), beta.data(), out_used, &e);
@@ -6055,8 +5943,7 @@ bool anofox_ts_forecast_exog(const double *values, const uint64_t *validity, siz
             if ((!r.values && r.n_values > 0) || (!r.future_values && r.n_future > 0)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
         }
     }
-    if (length == 0) { set_error(out_error, INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0"); return false; }
-    if (length < 3) { set_error(out_error, INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(length)); return false; }
+    if (series_too_short(out_error, length)) return false;
     ForecastOptions opt;
     std::memset(&opt, 0, sizeof opt);
     std::memcpy(opt.model, options->model, sizeof opt.model);

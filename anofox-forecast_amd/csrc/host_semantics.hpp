@@ -192,6 +192,25 @@ inline void clear_error(AnofoxError *e)
     std::memset(e->message, 0, sizeof e->message);
 }
 
+// the length checks every forecast entry makes first (forecast.rs:514-524, 780-789): true when the series is too short, *e says so
+inline bool series_too_short(AnofoxError *e, size_t length)
+{
+    if (length >= 3) return false;
+    if (length == 0) set_error(e, INSUFFICIENT_DATA, "Insufficient data: need at least 1 observations, got 0");
+    else set_error(e, INSUFFICIENT_DATA, "Insufficient data: need at least 3 observations, got " + std::to_string(length));
+    return true;
+}
+
+// An option block the core rejects (seasonal_period on a non-seasonal model, bad ETS notation or pool, an exogenous model it
+// does not run) is a PER-SERIES error there, raised after the length checks (forecast.rs:516-565, 780-789): a series that is too
+// short reports InsufficientData first.
+inline void option_error_per_series(AnofoxError *out_errors, const size_t *lengths, size_t n_series, const AnofoxError &e)
+{
+    if (!out_errors) return;
+    for (size_t s = 0; s < n_series; s++)
+        if (!series_too_short(&out_errors[s], lengths[s])) out_errors[s] = e;
+}
+
 // ComputeFoldBoundaries (ts_backtest_native.cpp:623-711): position-based fold boundaries over the number of distinct dates of the
 // whole input, all inclusive.  Writes the first `capacity` folds to `out` (may be null) and returns how many there are.  The
 // reference's unsigned arithmetic is kept where it matters: no training window starts before position 0, and a fold whose test

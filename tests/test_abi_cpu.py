@@ -230,6 +230,22 @@ def test_scratch_owner_and_series_packer_under_sanitizers():
         assert r.returncode == 0 and r.stdout.startswith("scratch_san: ok"), (r.stdout, r.stderr[-3000:])
 
 
+def test_part_plan_and_result_delivery_under_sanitizers():
+    """csrc/host_parts.hpp -- how the batch entry cuts an auto-detected batch into merged batches, big parts and small parts, and how
+    the results of a device batch are cut to each series' horizon and scattered to the caller's arrays -- compiled on its own (no
+    HIP, not even a stand-in) and run under ASan + UBSan (tests/c_abi/parts_san.cpp): the plan of seeded period vectors equals a
+    brute-force restatement under the ETS-like rule, the AutoARIMA rule and without merging (every series once, parts padded to
+    whole 64-column blocks at their end only, ring classes never mixed, the 2 GiB cut of the HBM-ring class exactly where the next
+    part would cross it, parts of 2,048 series never merged, lone parts returned); the leak check proves that truncation to horizon
+    0, padding columns and a failed run free every array exactly once.  The GPU suite reaches these rules only through forecasts."""
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "parts_san")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+                               os.path.join(ROOT, "tests", "c_abi", "parts_san.cpp"), "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and r.stdout.startswith("parts_san: ok"), (r.stdout, r.stderr[-3000:])
+
+
 def test_duckdb_macro_binding_parses():
     """binding/ts_macros_hip.cpp (the macro that sends ts_forecast_by to the batch route) needs nothing but DuckDB's API:
     `g++ -fsyntax-only` against the declaration-only stand-in tests/c_abi/duckdb_stub/ (test infrastructure, written from DuckDB's

@@ -752,10 +752,15 @@ def test_batches_of_empty_series(env):
             _compare(api, O, lib, [np.array([])] * k, model, 5, **kw)
 
 
-def test_merged_periods_with_nulls_horizons_and_fitted(env):
-    """The merged batch keeps the per-series extras: NULLs are interpolated before detection, per-series horizons truncate
-    (the cross-validation caller), fitted values and residuals use the series' own period."""
+@pytest.mark.parametrize("tune", [None, "merge_periods=0", "merge_periods=0;part_threads=1"], ids=["merged", "split", "split-one-worker"])
+def test_merged_periods_with_nulls_horizons_and_fitted(env, monkeypatch, tune):
+    """The auto-detected batch keeps the per-series extras on every route: NULLs are interpolated before detection, per-series
+    horizons truncate (the cross-validation caller), fitted values and residuals use the series' own period.  Merged (the
+    default), split into one batch per period on the part workers (merge_periods=0), and split with ONE worker, which reuses one
+    padded device batch for every part (part_threads=1)."""
     api, O, lib, synth = env
+    if tune is None: monkeypatch.delenv("ANOFOX_HIP_TUNE", raising=False)
+    else: monkeypatch.setenv("ANOFOX_HIP_TUNE", tune)
     rng = np.random.default_rng(23)
     series, valids, hz = [], [], []
     for p, reps in ((4, 2), (7, 3), (9, 2), (26, 2), (66, 2), (90, 1)):
