@@ -839,6 +839,65 @@ def _ts_detect_changepoints_bocpd(values, hazard_lambda=250.0, include_probabili
     return out
 
 
+# PELT (L2 cost): anofox_hip_pelt_batch and the mirror of the two list scalars over anofox_ts_detect_changepoints
+def pelt_batch(series, min_size=2, penalty=0.0, valids=None):
+    """anofox_hip_pelt_batch over a list of 1-D arrays: PELT with the L2 cost, one min_size and one penalty for the call (a penalty
+    that is not > 0 means 2 ln n of each series).  valids[i] (None: all valid) marks the NULLs of series i, which are DROPPED
+    before the detection.  Per series a dict: changepoints (ascending positions in the series without its NULLs), n_changepoints,
+    cost, and flags (bool, one per kept value)."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    total = int(lens.sum()) if n else 0
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks, kept = None, [int(m) for m in lens]
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+        kept = [int(np.count_nonzero(np.asarray(v, dtype=bool))) if v is not None else int(m) for v, m in zip(valids, lens)]
+    flag = np.zeros(max(total, 1), dtype=np.uint8)
+    cnt = np.zeros(max(n, 1), dtype=np.int32)
+    cost = np.zeros(max(n, 1), dtype=np.float64)
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_pelt_batch(vals, masks, lens.ctypes.data, n, int(min_size), float(penalty), flag.ctypes.data, cnt.ctypes.data,
+                                 cost.ctypes.data, None, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out, off = [], 0
+    for i in range(n):
+        fl = flag[off:off + kept[i]].astype(bool)
+        out.append({"changepoints": [int(k) for k in np.flatnonzero(fl)], "n_changepoints": int(cnt[i]), "cost": float(cost[i]),
+                    "flags": fl})
+        off += int(lens[i])
+    return out
+
+
+def _ts_detect_changepoints_pelt(values, min_size=None, penalty=None):
+    """The two list scalars TsDetectChangepointsFunction / TsDetectChangepointsWithParamsFunction (ts_changepoints.cpp:53-213) over
+    anofox_ts_detect_changepoints.  The reference compiles them but registers neither (RegisterTsDetectChangepointsFunction is a
+    no-op), so the name is this package's own; the C entry is the contract.  None for a NULL list and for fewer than 2 non-NULL
+    values (NULL elements are dropped, ExtractListAsDouble); a NULL min_size is 2, a NULL penalty 0.0 (= 2 ln n).  Else the STRUCT
+    as a dict: changepoints, n_changepoints, cost."""
+    if values is None:
+        return None
+    vals = np.array([float(v) for v in values if v is not None and v is not np.ma.masked], dtype=np.float64)
+    if len(vals) < 2:
+        return None
+    L = _lib.load()
+    res = _lib.ChangepointResult()
+    C.memset(C.byref(res), 0, C.sizeof(res))
+    err = _lib.AnofoxError()
+    if not L.anofox_ts_detect_changepoints(vals.ctypes.data, len(vals), 2 if min_size is None else int(min_size),
+                                           0.0 if penalty is None else float(penalty), C.byref(res), C.byref(err)):
+        return None
+    k = res.n_changepoints
+    out = {"changepoints": [int(res.changepoints[i]) for i in range(k)] if res.changepoints else [], "n_changepoints": int(k),
+           "cost": float(res.cost)}
+    L.anofox_free_changepoint_result(C.byref(res))
+    return out
+
+
 def _stod(text):
     """std::stod: leading whitespace, the longest numeric prefix, trailing text ignored; None where it throws (no conversion, or a
     decimal out of the double range)."""

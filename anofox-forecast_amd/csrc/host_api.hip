@@ -3665,6 +3665,160 @@ void anofox_free_bocpd_result(BocpdResult *result)
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// Changepoints by the optimal-partitioning recurrence, L2 cost (changepoint.rs detect_changepoints, "PELT"; pelt.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+bool anofox_hip_pelt_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, int min_size, double penalty,
+                            uint8_t *flags, int32_t *counts, double *cost, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!y || !lengths || !flags || !counts || !cost) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, PELT_MAX_ROWS, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    PeltArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.min_size = std::max<int64_t>((int64_t)min_size, 1);                    // the FFI wrapper: min_size.max(1) (lib.rs:3012)
+    a.penalty = penalty;
+    a.flag = flags; a.count = counts; a.cost = cost;
+    a.resident = pelt_resident(t_rows);
+    a.work_stride = pelt_work_stride(t_rows);
+    a.work_groups = a.work_stride ? pelt_work_groups((int)n_series) : 0;
+    // `if penalty > 0.0` (lib.rs:3009): NaN, zero and negative values take the default 2 ln n (changepoint.rs:118), rounded as the
+    // host's libm rounds it -- what the source's f64::ln calls -- so it is a table by length, not a device logarithm
+    // (kept per host thread and only ever extended, so that the batch-of-one entry does not pay t_rows logarithms per call)
+    static thread_local std::vector<double> log_tab;
+    const bool default_pen = !(penalty > 0.0);
+    if (default_pen)
+        for (size_t n = log_tab.size(); n <= t_rows; n++) log_tab.push_back(std::log((double)n) * 2.0);
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const bool ok = launch_and_wait("pelt", st, out_error, [&] {
+        if (default_pen) {
+            double *d_tab = scratch.get<double>(t_rows + 1);
+            HIPCHECK(hipMemcpyAsync(d_tab, log_tab.data(), (t_rows + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+            a.pen_tab = d_tab;
+        }
+        if (a.work_stride && a.work_groups > 0) a.work = scratch.get<double>(a.work_stride * (size_t)a.work_groups);
+        launch_pelt(a, st);
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_pelt_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series, int min_size,
+                           double penalty, uint8_t *out_flags, int32_t *out_n_changepoints, double *out_cost, AnofoxError *out_errors,
+                           AnofoxError *out_batch_error)
+{
+    clear_error(out_batch_error);
+    if (n_series > 0 && (!values || !lengths || !out_n_changepoints || !out_cost)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, PELT_MAX_ROWS, &shape, out_batch_error)) return false;
+    if (shape.total > 0 && !out_flags) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (n_series == 0) return true;
+    // a NULL value is DROPPED before the series is packed, as ExtractListAsDouble does for the scalar (ts_changepoints.cpp:45-50)
+    std::vector<std::vector<double>> kept(n_series);
+    std::vector<const double *> rows(n_series);
+    std::vector<size_t> packed(n_series);
+    size_t T = 1;
+    for (size_t s = 0; s < n_series; s++) {
+        const uint64_t *m = validity ? validity[s] : nullptr;
+        rows[s] = values[s];
+        packed[s] = lengths[s];
+        if (m && lengths[s] > 0) {
+            kept[s].reserve(lengths[s]);
+            for (size_t t = 0; t < lengths[s]; t++)
+                if (valid_bit(m, t)) kept[s].push_back(values[s][t]);
+            rows[s] = kept[s].data();
+            packed[s] = kept[s].size();
+        }
+        T = std::max(T, packed[s]);
+    }
+    const size_t ld = shape.ld;
+    Scratch scratch;
+    std::vector<int32_t> cnt(n_series);
+    std::vector<uint8_t> flag;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        pack_time_major(yb.data(), ld, rows.data(), packed.data(), n_series);
+        const std::vector<int32_t> len = block_lengths(packed.data(), n_series, ld);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld), *d_cnt = scratch.get<int32_t>(ld);
+        double *d_cost = scratch.get<double>(ld);
+        uint8_t *d_flag = scratch.get<uint8_t>(T * ld);
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!anofox_hip_pelt_device(d_y, ld, d_len, n_series, T, min_size, penalty, d_flag, d_cnt, d_cost, nullptr, out_batch_error))
+            return false;
+        flag.resize(T * ld);
+        HIPCHECK(hipMemcpy(cnt.data(), d_cnt, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(out_cost, d_cost, n_series * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(flag.data(), d_flag, T * ld * sizeof(uint8_t), hipMemcpyDeviceToHost));
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    // flags by position in the PACKED series; the positions a series lost to its NULLs (the tail of its range) are 0
+    size_t off = 0;
+    for (size_t s = 0; s < n_series; s++) {
+        if (out_errors) clear_error(&out_errors[s]);
+        out_n_changepoints[s] = cnt[s];
+        for (size_t t = 0; t < lengths[s]; t++) out_flags[off + t] = t < packed[s] ? flag[t * ld + s] : 0;
+        off += lengths[s];
+    }
+    return true;
+}
+
+bool anofox_ts_detect_changepoints(const double *values, size_t length, int min_size, double penalty, ChangepointResult *out_result,
+                                   AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    std::vector<uint8_t> fl(std::max<size_t>(length, 1));
+    int32_t n_cp = 0;
+    double cost = 0.0;
+    AnofoxError berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    if (!anofox_hip_pelt_batch(v, nullptr, len, 1, min_size, penalty, fl.data(), &n_cp, &cost, nullptr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    out_result->changepoints = nullptr;
+    out_result->n_changepoints = (size_t)n_cp;
+    out_result->cost = cost;
+    if (n_cp > 0) {
+        out_result->changepoints = (size_t *)std::malloc((size_t)n_cp * sizeof(size_t));
+        if (!out_result->changepoints) {
+            out_result->n_changepoints = 0;
+            set_error(out_error, ALLOCATION_ERROR, "Failed to allocate changepoint result");
+            return false;
+        }
+        size_t k = 0;
+        for (size_t t = 0; t < length && k < (size_t)n_cp; t++)
+            if (fl[t]) out_result->changepoints[k++] = t;
+    }
+    return true;
+}
+
+void anofox_free_changepoint_result(ChangepointResult *result)
+{
+    if (!result) return;
+    std::free(result->changepoints);
+    result->changepoints = nullptr;
+    result->n_changepoints = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Per-series statistics (stats.rs compute_ts_stats_with_dates_and_type; stats.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(TsStatsResult) == 296 && offsetof(TsStatsResult, n_zeros_start) == 64 && offsetof(TsStatsResult, mean) == 96 &&

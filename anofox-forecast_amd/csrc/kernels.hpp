@@ -218,6 +218,27 @@ struct ChangepointArgs {
 };
 void launch_bocpd(const ChangepointArgs &, hipStream_t);
 
+// Changepoints by the optimal-partitioning recurrence with the L2 cost (changepoint.rs detect_changepoints, "PELT"; pelt.hip)
+constexpr int PELT_RESIDENT = 2048;      // rows of the longest series whose arrays live in LDS; longer ones use the global workspace
+constexpr size_t PELT_MAX_ROWS = (size_t)1 << 16;     // rows of a block: n^3 / 6 pair-steps per series; bounds the workspace (940 MB) and the penalty table
+struct PeltArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // rows of the flag block; a longer series is cut to it
+    int64_t min_size;            // max(min_size, 1)
+    double penalty;              // used when pen_tab is null
+    const double *pen_tab;       // [t_rows + 1] 2 ln n as the host's libm rounds it (the default penalty), or null
+    uint8_t *flag;               // [t_rows x ld] 1 at a changepoint, else 0; rows t >= len stay untouched
+    int32_t *count;              // [n_series] changepoints
+    double *cost;                // [n_series] f[n]; 0.0 for a series of fewer than 2 min_size rows
+    int resident;                // pelt_resident(t_rows): rows the LDS of the launch holds
+    double *work;                // [work_groups x work_stride] or null when t_rows <= PELT_RESIDENT
+    size_t work_stride; int work_groups;
+};
+int pelt_resident(size_t t_rows);
+size_t pelt_work_stride(size_t t_rows);  // doubles per workspace slice (0: no workspace needed)
+int pelt_work_groups(int n_series);
+void launch_pelt(const PeltArgs &, hipStream_t);
+
 // Per-series statistics (stats.rs compute_ts_stats_with_dates_and_type; stats.hip)
 constexpr int STATS_RESIDENT = 2048;     // rows of the longest series that is sorted in LDS; longer ones use the global workspace
 constexpr int STATS_WORK_WAVES = 1024;   // waves (and workspace slices) that walk the longer series

@@ -126,6 +126,36 @@ def quality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | 
     return {"scores": scores, "figures": figures}
 
 
+def pelt_block(y: torch.Tensor, lengths: torch.Tensor, min_size: int = 2, penalty: float = 0.0, *, n_series: int | None = None,
+               stream: torch.cuda.Stream | None = None):
+    """anofox_hip_pelt_device on torch tensors: the PELT changepoints (L2 cost) of every series of a block, nothing read back.
+
+    y [t_rows, ld] fp64, lengths int32 [>= n_series], on one HIP device, contiguous.  One min_size and one penalty for the block; a
+    penalty that is not > 0 means 2 ln n of each series.
+
+    Returns device tensors (flags, counts, cost): flags uint8 [t_rows, ld], 1 at a changepoint and 0 elsewhere (rows beyond a
+    series' length and columns s >= n_series hold 0 too: the block is allocated zeroed), counts int32 [ld] (-1 in columns
+    s >= n_series) and cost fp64 [ld] (NaN there)."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    flags = torch.zeros((t_rows, ld), dtype=torch.uint8, device=dev)
+    counts = torch.full((ld,), -1, dtype=torch.int32, device=dev)
+    cost = torch.full((ld,), float("nan"), dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_pelt_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, int(min_size), float(penalty), flags.data_ptr(),
+                                  counts.data_ptr(), cost.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_pelt_device failed: [{err.code}] {err.message.decode()}")
+    return flags, counts, cost
+
+
 def seasonality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | None = None, max_period: int = 0, *,
                       n_series: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
     """anofox_hip_seasonality_device on torch tensors: the ts_analyze_seasonality figures of every series of a block, no host copy.

@@ -113,6 +113,14 @@ class BocpdResult(C.Structure):
     ]
 
 
+class ChangepointResult(C.Structure):
+    _fields_ = [
+        ("changepoints", C.POINTER(C.c_size_t)),
+        ("n_changepoints", C.c_size_t),
+        ("cost", C.c_double),
+    ]
+
+
 class TsStatsResult(C.Structure):
     """include/anofox_fcst_hip.h TsStatsResult: 36 figures and has_date_metrics (296 bytes)."""
     _fields_ = ([(n, C.c_size_t) for n in ("length", "n_nulls", "n_nan", "n_zeros", "n_positive", "n_negative", "n_unique_values")]
@@ -373,6 +381,7 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_mstl_decomposition", "anofox_free_mstl_result", "anofox_hip_mstl_decompose_batch", "anofox_hip_mstl_decompose_device",
     "anofox_ts_forecast_exog", "anofox_ts_forecast_exog_batch", "anofox_hip_batch_set_exog_device", "anofox_hip_batch_exog_coefficients",
     "anofox_ts_detect_changepoints_bocpd", "anofox_free_bocpd_result", "anofox_hip_changepoints_batch", "anofox_hip_changepoints_device",
+    "anofox_ts_detect_changepoints", "anofox_free_changepoint_result", "anofox_hip_pelt_batch", "anofox_hip_pelt_device",
     "anofox_ts_stats", "anofox_ts_stats_with_dates", "anofox_ts_stats_with_dates_and_type", "anofox_free_ts_stats_result",
     "anofox_hip_stats_batch", "anofox_hip_stats_device",
     "anofox_ts_data_quality", "anofox_hip_quality_batch", "anofox_hip_quality_device",
@@ -502,6 +511,15 @@ def load():
     L.anofox_hip_changepoints_device.restype = C.c_bool
     L.anofox_hip_changepoints_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_detect_changepoints.restype = C.c_bool
+    L.anofox_ts_detect_changepoints.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, P(ChangepointResult), P(AnofoxError)]
+    L.anofox_free_changepoint_result.argtypes = [P(ChangepointResult)]
+    L.anofox_hip_pelt_batch.restype = C.c_bool
+    L.anofox_hip_pelt_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_pelt_device.restype = C.c_bool
+    L.anofox_hip_pelt_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     L.anofox_ts_stats.restype = C.c_bool
     L.anofox_ts_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(TsStatsResult), P(AnofoxError)]
     L.anofox_ts_stats_with_dates.restype = C.c_bool

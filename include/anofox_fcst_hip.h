@@ -266,6 +266,35 @@ bool anofox_ts_detect_changepoints_bocpd(const double *values,
 
 void anofox_free_bocpd_result(struct BocpdResult *result);
 
+/*
+ * Result of the PELT changepoint detection (layout of the reference's anofox_fcst_ffi.h).  `changepoints` is malloc()ed by the
+ * callee and released by anofox_free_changepoint_result; it is NULL when there are none.
+ */
+typedef struct ChangepointResult {
+    size_t *changepoints; /* [n_changepoints] ascending, or NULL */
+    size_t n_changepoints;
+    double cost;          /* f[n] of the recurrence; 0.0 for a series of fewer than 2 * min_size values */
+} ChangepointResult;
+
+/*
+ * Changepoints of ONE series by the reference's detect_changepoints with the L2 cost ("PELT"; as written there it prunes nothing,
+ * so it is the exact optimal partitioning): f[0] = -pen, f[t] = min over tau of (f[tau] + cost(tau, t)) + pen with
+ * tau <= t - ms, tau == 0 or tau >= ms, cost = the sum of squared deviations of [tau, t) from its mean; the FIRST minimum in
+ * ascending tau wins; the changepoints are the backtrack from n, `cost` is f[n].  ms = max(min_size, 1); a series of fewer than
+ * 2 ms values has no changepoints and cost 0.0.  penalty > 0 is taken as given; anything else (0, negative, NaN) means
+ * 2 ln(length).  The results equal the reference's BIT FOR BIT: every sum is its serial chain, no operation is fused.
+ * Non-finite values are not special-cased: they follow the arithmetic (a NaN candidate is never the minimum; a step without a
+ * finite candidate gets f = +inf).  NULL `values` or `out_result`: NULL_POINTER.  Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_detect_changepoints(const double *values,
+                                   size_t length,
+                                   int min_size,
+                                   double penalty,
+                                   struct ChangepointResult *out_result,
+                                   struct AnofoxError *out_error);
+
+void anofox_free_changepoint_result(struct ChangepointResult *result);
+
 /* How a frequency is counted in the date figures of the statistics (the reference's FrequencyType). */
 typedef enum FrequencyType {
     FIXED = 0,     /* a fixed number of microseconds */
@@ -672,6 +701,53 @@ bool anofox_hip_changepoints_device(const double *y,
                                     int32_t *counts,
                                     void *stream,
                                     struct AnofoxError *out_error);
+
+/*
+ * PELT of `n_series` series with one min_size and one penalty, in one GPU pass (per series the semantics and the bits of
+ * anofox_ts_detect_changepoints; a default penalty is 2 ln of EACH series' own packed length).  `validity` may be NULL.  A NULL
+ * value is DROPPED before the series is packed, as the reference's list scalar drops it (ExtractListAsDouble) -- unlike
+ * anofox_hip_changepoints_batch, which counts it as 0.0 the way ITS table function does.  With total = the sum of `lengths`,
+ * series i owns [off_i, off_i + lengths[i]) of out_flags[total] (0 / 1), indexed by position in the PACKED series: flag k of
+ * series i is its k-th non-NULL value, and the positions a series lost to its NULLs, at the end of its range, are 0.
+ * out_n_changepoints[i] and out_cost[i] are the count and f[n].  No series fails alone: out_errors[i] (may be NULL) is always
+ * cleared.  At most 65,536 values per series.  The return value is false only for batch-level failures (NULL pointers, a series
+ * too long, no GPU), also reported through `out_batch_error`.  Runs on the calling thread's current device
+ * (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_pelt_batch(const double *const *values,
+                           const uint64_t *const *validity,
+                           const size_t *lengths,
+                           size_t n_series,
+                           int min_size,
+                           double penalty,
+                           uint8_t *out_flags,
+                           int32_t *out_n_changepoints,
+                           double *out_cost,
+                           struct AnofoxError *out_errors,
+                           struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows), lengths[n_series] (int32) and the outputs
+ * are device pointers.  flags (uint8) is [t_rows x ld]: rows t < lengths[s] are written 0 / 1, rows t >= lengths[s] are left
+ * untouched; counts (int32) and cost (fp64) are [n_series].  A length above t_rows is cut to t_rows; a series of fewer than
+ * 2 * max(min_size, 1) rows gets count 0, cost 0.0 and zero flags; there is no per-series error.  t_rows <= 65,536.  One workgroup
+ * per series: its arrays live in LDS up to 2,048 rows (the launch sizes the LDS from min(t_rows, 2,048)), in a global workspace
+ * of the call beyond (28 bytes x (t_rows + 1) x min(n_series, 512), allocated whenever t_rows > 2,048, however few series are
+ * that long: 29 MB at 2,049 rows, 940 MB at the row limit); the same bits either way, on every run and through every entry.  Runs on `stream` (NULL: the null stream)
+ * and returns after it has finished.
+ */
+bool anofox_hip_pelt_device(const double *y,
+                            size_t ld,
+                            const int32_t *lengths,
+                            size_t n_series,
+                            size_t t_rows,
+                            int min_size,
+                            double penalty,
+                            uint8_t *flags,
+                            int32_t *counts,
+                            double *cost,
+                            void *stream,
+                            struct AnofoxError *out_error);
 
 /*
  * Statistics of `n_series` series in one GPU pass (per series the semantics of anofox_ts_stats_with_dates_and_type).  Replaces

@@ -3,7 +3,7 @@
 // hipcc --offload-arch=gfx950 -O3 -o op_rates op_rates.hip && ./op_rates
 #include <hip/hip_runtime.h>
 #include <cstdio>
-enum { OP_FMA, OP_RCP, OP_DIV, OP_RNDNE, OP_CVT, OP_SQRT, OP_MUL, OP_FIXUP, OP_FMAS, OP_SCALE, N_OPS };
+enum { OP_FMA, OP_RCP, OP_DIV, OP_RNDNE, OP_CVT, OP_SQRT, OP_MUL, OP_FIXUP, OP_FMAS, OP_SCALE, OP_SMA, N_OPS };
 template <int OP>
 __device__ __forceinline__ double op(double x, double a, double b)
 {
@@ -17,6 +17,11 @@ __device__ __forceinline__ double op(double x, double a, double b)
     if (OP == OP_FIXUP) return __builtin_amdgcn_div_fixup(x, a, b);
     if (OP == OP_FMAS) return __builtin_amdgcn_div_fmas(x, a, b, true);
     if (OP == OP_SCALE) return __builtin_amdgcn_div_scale(x, a, true, nullptr) + b;
+    if (OP == OP_SMA) {                                                          // v_add (sub) + v_mul + v_add, each on the last:
+#pragma clang fp contract(off)                                                   // never one fma, whatever the command line says
+        const double d = x - a;
+        return d * d + b;
+    }
     return x;
 }
 template <int OP>
@@ -63,5 +68,6 @@ int main()
     run<OP_FIXUP>("div_fixup", f);
     run<OP_FMAS>("div_fmas", f);
     run<OP_SCALE>("div_scale + add", f);
+    run<OP_SMA>("sub + mul + add", f);
     return 0;
 }
