@@ -1398,6 +1398,138 @@ anofox_fcst_ts_data_quality_agg = ts_data_quality_agg      # ts_data_quality_agg
 
 
 # --------------------------------------------------------------------------------------------
+# features: anofox_hip_features_batch and the mirrors of ts_features_by (_ts_features_native), ts_features_agg / ts_features,
+# ts_features_table and ts_features_list
+# --------------------------------------------------------------------------------------------
+_FEATURE_DUMMY = tuple(float(i) for i in range(1, 11))      # the series the operators take their columns from
+
+
+def features_batch(series, valids=None):
+    """anofox_hip_features_batch over a list of 1-D arrays: one GPU pass for all series.  `valids[i]` (booleans, False = NULL) may be
+    None per series, as may the list; NULL values are dropped.  Returns {"names": the 117 names in byte order, "features": fp64
+    [n, 117] (NaN where the source inserts nothing), "present": bool [n, 117], "status": int32 [n] (0; 1 no value; 2 a NaN among
+    the values: only `length` is written)}."""
+    L = _lib.load()
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    masks = None
+    if valids is not None:
+        ms = [validity_mask(v) if v is not None else None for v in valids]
+        masks = (C.c_void_p * max(n, 1))(*[m.ctypes.data if m is not None and len(m) else None for m in ms])
+    feats = np.full((max(n, 1), _lib.N_FEATURES), np.nan, dtype=np.float64)
+    words = np.zeros((max(n, 1), 2), dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    berr = _lib.AnofoxError()
+    ok = L.anofox_hip_features_batch(vals, masks, lens.ctypes.data, n, feats.ctypes.data, words.ctypes.data, status.ctypes.data, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    idx = np.arange(_lib.N_FEATURES)
+    present = ((words[:n, idx // 64] >> (idx % 64).astype(np.uint64)) & np.uint64(1)).astype(bool)
+    return {"names": _lib.feature_names(), "features": feats[:n], "present": present, "status": status[:n]}
+
+
+def ts_features_single(values):
+    """anofox_ts_features: {name: value} of the features the source inserts, in byte order of the names."""
+    L = _lib.load()
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    res, err = _lib.FeaturesResult(), _lib.AnofoxError()
+    if not L.anofox_ts_features(v.ctypes.data if len(v) else _EMPTY_SERIES_ADDR, len(v), C.byref(res), C.byref(err)):
+        raise InvalidInputException(err.message.decode(errors="replace"))
+    out = {res.feature_names[i].decode(): float(res.features[i]) for i in range(res.n_features)}
+    L.anofox_free_features_result(C.byref(res))
+    return out
+
+
+_feature_columns_cache = []
+
+
+def ts_features_columns():
+    """The columns of the operators: the names anofox_ts_features returns for the series 1 .. 10 (GetFeatureNames of
+    ts_features_native.cpp and ts_features_agg.cpp) -- 116, autocorrelation_lag10 needs eleven values."""
+    if not _feature_columns_cache:
+        _feature_columns_cache.append(tuple(ts_features_single(_FEATURE_DUMMY)))
+    return _feature_columns_cache[0]
+
+
+def _feature_rows(series):
+    """Per series the operator's row over ts_features_columns(): NaN where the single entry returns no such feature or fails (a NaN
+    among the values fails here and leaves `length` only)."""
+    cols = ts_features_columns()
+    r = features_batch(series)
+    at = [r["names"].index(c) for c in cols]
+    rows = np.where(r["present"][:, at], r["features"][:, at], np.nan) if len(series) else np.zeros((0, len(cols)))
+    return cols, rows, r["status"]
+
+
+def ts_features_by(group, date, value):
+    """ts_features_by(source, group_col, date_col, value_col) = _ts_features_native (ts_features_native.cpp): rows with a NULL date are
+    dropped, a NULL value is NaN (:246), groups come in first-arrival order, each group's (timestamp, value) pairs are sorted, and
+    the columns are those of the series 1 .. 10.  All groups go to the GPU in one features_batch call instead of one FFI call per
+    group.  Returns {"id": groups, <116 names>: lists of float}."""
+    dates = np.asarray(date)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.array([d is None for d in dates], dtype=bool)
+    vals, vnull = _changepoint_values(value)
+    vals = np.where(vnull, np.nan, vals)
+    grp = np.asarray(group, dtype=object)
+    keep = np.nonzero(~null_date)[0]
+    us = _to_micros(dates[keep], _date_kind(dates)) if len(keep) else np.zeros(0, dtype=np.int64)
+    order, rows = [], {}
+    for j, i in enumerate(keep):
+        key = "__NULL__" if grp[i] is None else str(grp[i])
+        if key not in rows:
+            rows[key] = (grp[i], [])
+            order.append(key)
+        rows[key][1].append(j)
+    series = []
+    for key in order:
+        j = np.array(rows[key][1])
+        v, t = vals[keep][j], us[j]
+        series.append(v[np.lexsort((v, t))] if not np.isnan(v).any() else v)
+    cols, table, _ = _feature_rows(series)
+    out = {"id": [rows[k][0] for k in order]}
+    for c, name in enumerate(cols):
+        out[name] = [float(x) for x in table[:, c]]
+    return out
+
+
+def ts_features_agg(ts, value):
+    """The aggregate ts_features_agg(ts, value) / ts_features(ts, value) over ONE group (ts_features_agg.cpp): rows with a NULL
+    timestamp or value are dropped, the rest ordered by (timestamp, value); a STRUCT (dict) of the 116 columns, NaN where the source
+    inserts nothing; None when no row is left or the wrapper fails (a NaN among the values)."""
+    dates = np.asarray(ts)
+    vals, vnull = _changepoint_values(value)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), dtype=bool)
+    keep = np.nonzero(~(null_date | vnull))[0]
+    if len(keep) == 0:
+        return None
+    us = _to_micros(dates[keep], _date_kind(dates))
+    v = vals[keep]
+    cols, table, status = _feature_rows([v[np.lexsort((v, us))] if not np.isnan(v).any() else v])
+    if status[0] != _lib.FEATURES_OK:
+        return None
+    return {name: float(table[0, c]) for c, name in enumerate(cols)}
+
+
+def ts_features_table(date, value):
+    """The macro ts_features_table(source, date_col, value_col) (ts_macros.cpp:1644-): ts_features_agg over the whole table, its STRUCT
+    spread into one row of columns (lists of one element; None where the aggregate is NULL)."""
+    r = ts_features_agg(date, value)
+    return {name: [None if r is None else r[name]] for name in ts_features_columns()}
+
+
+def ts_features_list():
+    """ts_features_list() (ts_features.cpp): the 117 names in the order of the source's list_features."""
+    return _lib.feature_list()
+
+
+ts_features = ts_features_agg                              # ts_features_agg.cpp:424-429
+anofox_fcst_ts_features_agg = ts_features_agg
+anofox_fcst_ts_features_by = ts_features_by
+
+
+# --------------------------------------------------------------------------------------------
 # seasonality analysis: anofox_hip_seasonality_batch and the mirrors of ts_detect_seasonality and ts_analyze_seasonality
 # --------------------------------------------------------------------------------------------
 def seasonality_batch(series, valids=None, max_period=0):

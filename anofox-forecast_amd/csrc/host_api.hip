@@ -4065,6 +4065,229 @@ bool anofox_ts_data_quality(const double *values, const uint64_t *validity, size
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// The 117 features per series (features.rs extract_features; features.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(FeaturesResult) == 24 && offsetof(FeaturesResult, feature_names) == 8 && offsetof(FeaturesResult, n_features) == 16,
+              "FeaturesResult layout");
+static_assert(ANOFOX_HIP_N_FEATURES == FEATURES_N && ANOFOX_HIP_FEATURES_MAX_ROWS == FEATURES_MAX_ROWS, "the header's feature constants");
+static const char *const FEATURES_TOO_LONG_TEXT = "Invalid input: a series has more than 65536 rows, the limit of the feature kernels";
+
+// the names in byte order (the rows of the kernels) and in the order of the source's list_features
+static const char *const FEATURE_NAMES_SORTED[FEATURES_N] = {
+#define X(id, name, pos) name,
+#include "feature_names.inc"
+#undef X
+};
+static const int FEATURE_LIST_POS[FEATURES_N] = {
+#define X(id, name, pos) pos,
+#include "feature_names.inc"
+#undef X
+};
+
+// the thresholds dEk (d = 1 .. 9, k = 0 .. 308) as strtod rounds them, ascending: Rust's shortest round-trip to_string() of v >= 1
+// starts with d exactly when strtod("dEk") <= v < strtod("(d+1)Ek")
+static const std::vector<double> &benford_thresholds()
+{
+    static const std::vector<double> table = [] {
+        std::vector<double> t;
+        t.reserve(FEATURES_BENFORD);
+        char text[16];
+        for (int k = 0; k < 309; k++)
+            for (int d = 1; d <= 9; d++) {
+                std::snprintf(text, sizeof text, "%de%d", d, k);
+                t.push_back(std::strtod(text, nullptr));
+            }
+        return t;
+    }();
+    return table;
+}
+
+static char *c_string_copy(const std::string &s)
+{
+    char *p = (char *)std::malloc(s.size() + 1);
+    if (p) std::memcpy(p, s.c_str(), s.size() + 1);
+    return p;
+}
+
+bool anofox_hip_features_families_device(const double *y, const uint8_t *valid, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
+                                         unsigned families, double *out_fp, int64_t *out_int, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!y || !lengths || !out_fp || !out_int) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (t_rows > FEATURES_MAX_ROWS) { set_error(out_error, INVALID_INPUT, FEATURES_TOO_LONG_TEXT); return false; }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, FEATURES_MAX_ROWS, out_error)) return false;
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    FeaturesArgs a{};
+    a.y = y; a.valid = valid; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.out_fp = out_fp; a.out_int = out_int;
+    a.tile = features_tile(t_rows);
+    a.work_stride = features_work_stride(t_rows);
+    a.work_waves = a.work_stride ? features_work_waves((int)n_series) : 0;
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const std::vector<double> &table = benford_thresholds();
+    const bool ok = launch_and_wait("features", st, out_error, [&] {
+        double *d_table = scratch.get<double>(FEATURES_BENFORD);
+        HIPCHECK(hipMemcpyAsync(d_table, table.data(), FEATURES_BENFORD * sizeof(double), hipMemcpyHostToDevice, st));
+        a.benford = d_table;
+        if (a.work_stride && a.work_waves > 0) a.work = scratch.get<uint64_t>(2 * a.work_stride * (size_t)a.work_waves);
+        launch_features(a, st, (int)(families & ((1u << FEATURES_FAMILIES) - 1u)));
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_features_device(const double *y, const uint8_t *valid, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows,
+                                double *out_fp, int64_t *out_int, void *stream, AnofoxError *out_error)
+{
+    return anofox_hip_features_families_device(y, valid, ld, lengths, n_series, t_rows, (1u << FEATURES_FAMILIES) - 1u, out_fp, out_int, stream,
+                                               out_error);
+}
+
+bool anofox_hip_features_batch(const double *const *values, const uint64_t *const *validity, const size_t *lengths, size_t n_series,
+                               double *out_features, uint64_t *out_present, int32_t *out_status, AnofoxError *out_batch_error)
+{
+    clear_error(out_batch_error);
+    if (n_series > 0 && (!values || !lengths || !out_features || !out_present)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++)
+        if (lengths[s] > FEATURES_MAX_ROWS) { set_error(out_batch_error, INVALID_INPUT, FEATURES_TOO_LONG_TEXT); return false; }
+    BlockShape shape;
+    if (!series_shape(values, validity, lengths, n_series, FEATURES_MAX_ROWS, &shape, out_batch_error)) return false;
+    if (n_series == 0) return true;
+    const size_t ld = shape.ld, T = shape.T;
+    const bool any_mask = shape.any_mask;
+    Scratch scratch;
+    std::vector<int64_t> oi(FEATURES_N_INT * ld);
+    std::vector<double> of((size_t)FEATURES_N * ld);
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        std::vector<double> yb(T * ld, 0.0);
+        std::vector<uint8_t> vb(any_mask ? T * ld : 0, 1);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld);
+        pack_time_major(yb.data(), ld, values, lengths, n_series);
+        if (any_mask) pack_validity(vb.data(), ld, validity, lengths, n_series);
+        double *d_y = scratch.get<double>(T * ld);
+        int32_t *d_len = scratch.get<int32_t>(ld);
+        int64_t *d_int = scratch.get<int64_t>(FEATURES_N_INT * ld);
+        double *d_fp = scratch.get<double>((size_t)FEATURES_N * ld);
+        uint8_t *d_valid = nullptr;
+        HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d_len, len.data(), ld * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (any_mask) {
+            d_valid = scratch.get<uint8_t>(T * ld);
+            HIPCHECK(hipMemcpy(d_valid, vb.data(), T * ld, hipMemcpyHostToDevice));
+        }
+        if (!anofox_hip_features_device(d_y, d_valid, ld, d_len, n_series, T, d_fp, d_int, nullptr, out_batch_error)) return false;
+        HIPCHECK(hipMemcpy(oi.data(), d_int, oi.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(of.data(), d_fp, of.size() * sizeof(double), hipMemcpyDeviceToHost));
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    for (size_t s = 0; s < n_series; s++) {
+        for (int i = 0; i < FEATURES_N; i++) out_features[s * FEATURES_N + i] = of[(size_t)i * ld + s];
+        out_present[2 * s] = (uint64_t)oi[0 * ld + s];
+        out_present[2 * s + 1] = (uint64_t)oi[1 * ld + s];
+        if (out_status) out_status[s] = (int32_t)oi[2 * ld + s];
+    }
+    return true;
+}
+
+bool anofox_ts_features(const double *values, size_t length, FeaturesResult *out_result, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (length == 0) { set_error(out_error, COMPUTATION_ERROR, "Insufficient data: need at least 1 observations, got 0"); return false; }
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    std::vector<double> f(FEATURES_N);
+    uint64_t present[2] = {0, 0};
+    int32_t status = 0;
+    if (!anofox_hip_features_batch(v, nullptr, len, 1, f.data(), present, &status, out_error)) return false;
+    if (status == (int32_t)FEATURES_NAN) { set_error(out_error, COMPUTATION_ERROR, QUALITY_NAN_TEXT); return false; }
+    const size_t n = (size_t)(__builtin_popcountll(present[0]) + __builtin_popcountll(present[1]));
+    out_result->n_features = n;
+    out_result->features = nullptr;
+    out_result->feature_names = nullptr;
+    if (n == 0) return true;
+    double *fp = (double *)std::malloc(n * sizeof(double));
+    char **names = (char **)std::calloc(n, sizeof(char *));
+    if (!fp || !names) {
+        std::free(fp); std::free(names);
+        out_result->n_features = 0;
+        set_error(out_error, ALLOCATION_ERROR, "Allocation failed");
+        return false;
+    }
+    size_t j = 0;
+    for (int i = 0; i < FEATURES_N; i++)
+        if ((present[i >> 6] >> (i & 63)) & 1ull) {
+            fp[j] = f[i];
+            names[j++] = c_string_copy(FEATURE_NAMES_SORTED[i]);
+        }
+    out_result->features = fp;
+    out_result->feature_names = names;
+    return true;
+}
+
+void anofox_free_features_result(FeaturesResult *result)
+{
+    if (!result) return;
+    if (result->feature_names)
+        for (size_t i = 0; i < result->n_features; i++) std::free(result->feature_names[i]);
+    std::free(result->feature_names);
+    std::free(result->features);
+    result->features = nullptr;
+    result->feature_names = nullptr;
+    result->n_features = 0;
+}
+
+bool anofox_ts_features_list(char **out_names, size_t *out_count)
+{
+    if (!out_names || !out_count) return false;
+    char **names = (char **)std::calloc(FEATURES_N, sizeof(char *));
+    if (!names) return false;
+    for (int i = 0; i < FEATURES_N; i++) names[FEATURE_LIST_POS[i]] = c_string_copy(FEATURE_NAMES_SORTED[i]);
+    *out_count = FEATURES_N;
+    *out_names = (char *)names;                               // (the reference's cast: the caller reads a char ** out of it)
+    return true;
+}
+
+bool anofox_ts_validate_feature_params(const char *const *param_names, size_t n_params, char ***out_warnings, size_t *out_n_warnings)
+{
+    if (!param_names || !out_warnings || !out_n_warnings) return false;
+    std::vector<std::string> warnings;
+    for (size_t i = 0; i < n_params; i++) {
+        if (!param_names[i]) continue;
+        bool known = false;
+        for (int f = 0; f < FEATURES_N && !known; f++) known = std::strcmp(param_names[i], FEATURE_NAMES_SORTED[f]) == 0;
+        if (!known) warnings.push_back(std::string("Unknown feature parameter key '") + param_names[i] + "' - this parameter will be ignored");
+    }
+    *out_n_warnings = warnings.size();
+    *out_warnings = nullptr;
+    if (warnings.empty()) return true;
+    char **w = (char **)std::calloc(warnings.size(), sizeof(char *));
+    if (!w) return false;
+    for (size_t i = 0; i < warnings.size(); i++) w[i] = c_string_copy(warnings[i]);
+    *out_warnings = w;
+    return true;
+}
+
+void anofox_free_warnings(char **warnings, size_t n_warnings)
+{
+    if (!warnings) return;
+    for (size_t i = 0; i < n_warnings; i++) std::free(warnings[i]);
+    std::free(warnings);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Seasonality analysis per series (seasonality.rs detect_seasonality / analyze_seasonality / compute_trend_strength; seasonality.hip)
 // ------------------------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(SeasonalityResult) == 40 && offsetof(SeasonalityResult, n_periods) == 8 && offsetof(SeasonalityResult, primary_period) == 16 &&

@@ -396,6 +396,31 @@ size_t quality_work_stride(size_t t_rows);       // words per workspace slice (0
 int quality_work_waves(int n_series);
 void launch_quality(const QualityArgs &, hipStream_t);
 
+// The 117 features per series (features.rs extract_features; features.hip): five kernels, one per family, each over every column of
+// a time-major block.  Rows of out_fp and presence bits are in the byte order of the names (feature_names.inc).
+constexpr int FEATURES_RESIDENT = 2048;      // rows of the longest series whose values live in LDS; longer ones use the global workspace
+constexpr int FEATURES_WORK_WAVES = 256;     // waves (and workspace slices) that walk the longer series
+constexpr size_t FEATURES_MAX_ROWS = (size_t)1 << 16;    // rows of a block: bounds the O(n^2) families and the workspace (256 MiB)
+constexpr int FEATURES_N = 117, FEATURES_N_INT = 3;
+constexpr int FEATURES_BENFORD = 9 * 309;    // the thresholds dEk, ascending
+constexpr int64_t FEATURES_OK = 0, FEATURES_EMPTY = 1, FEATURES_NAN = 2;
+constexpr int FEATURES_CHAINS = 0, FEATURES_SORT = 1, FEATURES_SCAN = 2, FEATURES_MATCH = 3, FEATURES_DFT = 4, FEATURES_FAMILIES = 5;
+struct FeaturesArgs {
+    const double *y; const uint8_t *valid;       // [t_rows x ld]; valid may be null
+    size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    double *out_fp;              // [FEATURES_N x ld]; NaN where the source inserts nothing
+    int64_t *out_int;            // [FEATURES_N_INT x ld] presence bits 0..63, presence bits 64..116, status (written by the chains kernel)
+    const double *benford;       // [FEATURES_BENFORD] correctly rounded thresholds (the scan kernel)
+    int tile;                    // words of the LDS kernels: a power of two, 64 .. FEATURES_RESIDENT
+    uint64_t *work;              // [work_waves x 2 work_stride] or null when t_rows <= FEATURES_RESIDENT
+    size_t work_stride; int work_waves;
+};
+int features_tile(size_t t_rows);
+size_t features_work_stride(size_t t_rows);      // words per half of a workspace slice (0: no workspace needed)
+int features_work_waves(int n_series);
+void launch_features(const FeaturesArgs &, hipStream_t, int families = (1 << FEATURES_FAMILIES) - 1);   // bit f: run family f
+
 // Seasonality analysis per series (seasonality.rs detect_seasonality, analyze_seasonality, compute_trend_strength; seasonality.hip):
 // the up to five strongest autocorrelation peaks, their strengths and the trend strength of every column of a time-major block
 constexpr int SEASONALITY_LDS_ROWS = 5120;   // rows of the longest block whose working buffers live in LDS (63,504 bytes of it)

@@ -8,7 +8,7 @@
 // walks t in the source's order, so each of its sums has the source's order of additions.  The mean and the sums of squares are
 // the source's sequential sums as well (every lane adds them redundantly from LDS).
 //
-// What differs from the source is the evaluation of the elementary functions only: sin / cos are per_sincos below (two-term
+// What differs from the source is the evaluation of the elementary functions only: sin / cos are per_sincos of det_trig.hpp (two-term
 // Cody-Waite reduction by fused multiply-adds, exact in its first step, then fdlibm's kernels on [-pi/4, pi/4]: below one ulp for
 // every argument a series that fits in memory can produce), ln / exp are det_math.hpp's, the power (1 - p)^M of the false-alarm
 // probability is exp(M ln(1 - p)), atan2 is the device library's.  SAZED evaluates the phase exactly: the padded length L is a
@@ -27,6 +27,7 @@
 // order of NaN powers inside SAZED's median, which the source leaves to its sort.
 #include "kernels.hpp"
 #include "det_math.hpp"
+#include "det_trig.hpp"
 
 namespace anofox {
 
@@ -34,38 +35,6 @@ namespace {
 
 constexpr double PER_PI = 3.14159265358979323846;
 constexpr double PER_EPS = 2.2204460492503131e-16;     // f64::EPSILON
-
-// sin and cos of x.  k = nearest integer to x 2/pi; x - k p1 is exact (both are multiples of ulp(p1) and the difference is below 1),
-// the second step leaves a head and a tail for the kernels.  |k| <= 2^52 is accepted; pi/2 - p1 - p2 = 1.5e-33, so the reduction
-// error k 1.5e-33 stays below 1e-17 for every |x| < 1e16.
-__device__ __forceinline__ void per_sincos(double x, double &s, double &c)
-{
-    const double two_over_pi = 6.36619772367581382433e-01;
-    const double p1 = 1.57079632679489655800e+00, p2 = 6.12323399573676603587e-17, p3 = -1.49738490485916983766e-33;
-    if (!(fabs(x) < 0x1p52)) { s = c = __builtin_nan(""); return; }
-    const double k = __builtin_rint(x * two_over_pi);
-    const double r0 = fma(-k, p1, x);
-    const double y0 = fma(-k, p2, r0);
-    const double y1 = fma(-k, p3, fma(-k, p2, r0 - y0));
-    const double z = y0 * y0;
-    // fdlibm __kernel_sin(y0, y1, 1)
-    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
-                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-    const double v = z * y0;
-    const double rs = fma(z, fma(z, fma(z, fma(z, S6, S5), S4), S3), S2);
-    const double sn = y0 - ((z * (0.5 * y1 - v * rs) - y1) - v * S1);
-    // fdlibm __kernel_cos(y0, y1)
-    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
-                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    const double w = z * z;
-    const double rc = z * fma(z, fma(z, C3, C2), C1) + (w * w) * fma(z, fma(z, C6, C5), C4);
-    const double hz = 0.5 * z, w1 = 1.0 - hz;
-    const double cs = w1 + (((1.0 - w1) - hz) + (z * rc - y0 * y1));
-    const int q = (int)((long long)k & 3);
-    const double a = (q & 1) ? cs : sn, b = (q & 1) ? sn : cs;
-    s = (q & 2) ? -a : a;
-    c = ((q + 1) & 2) ? -b : b;
-}
 
 __device__ __forceinline__ int per_wave_sum(int v)
 {

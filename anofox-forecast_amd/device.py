@@ -126,6 +126,47 @@ def quality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | 
     return {"scores": scores, "figures": figures}
 
 
+def features_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tensor | None = None, *, n_series: int | None = None,
+                   families=None, out: dict | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_features_device on torch tensors: the 117 features of every series of a block, no host copy.
+
+    y [t_rows, ld] fp64 (t_rows <= lib.FEATURES_MAX_ROWS), valid [t_rows, ld] uint8 or bool (0 = NULL; None: all valid), lengths int32
+    [>= n_series], on one HIP device, contiguous -- what prepare_block returns.  `families`: None for all five kernels, or names out of
+    lib.FEATURES_FAMILIES (only their rows are written; "chains" writes present and status).  `out` may bring "features" and "figures".
+
+    Returns {"features": fp64 [117, ld], rows in the order of lib.feature_names(), NaN where the source inserts nothing; "figures":
+    int64 [3, ld]: the two presence words (bit i % 64 of word i // 64 for feature i) and the status (lib.FEATURES_OK, FEATURES_EMPTY,
+    FEATURES_NAN)}.  Columns s >= n_series hold NaN and -1 (in tensors the call allocates)."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.to(torch.uint8)
+        assert valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous() and tuple(valid.shape) == (t_rows, ld)
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    out = dict(out or {})
+    feats, figures = out.get("features"), out.get("figures")
+    if feats is None:
+        feats = torch.full((_lib.N_FEATURES, ld), float("nan"), dtype=torch.float64, device=dev)
+    if figures is None:
+        figures = torch.full((3, ld), -1, dtype=torch.int64, device=dev)
+    assert feats.dtype == torch.float64 and feats.is_cuda and feats.is_contiguous() and tuple(feats.shape) == (_lib.N_FEATURES, ld)
+    assert figures.dtype == torch.int64 and figures.is_cuda and figures.is_contiguous() and tuple(figures.shape) == (3, ld)
+    mask = sum(1 << _lib.FEATURES_FAMILIES.index(f) for f in set(families)) if families is not None else (1 << len(_lib.FEATURES_FAMILIES)) - 1
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_features_families_device(y.data_ptr(), valid.data_ptr() if valid is not None else None, ld, lengths.data_ptr(), n,
+                                               t_rows, mask, feats.data_ptr(), figures.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_features_device failed: [{err.code}] {err.message.decode()}")
+    return {"features": feats, "figures": figures}
+
+
 def pelt_block(y: torch.Tensor, lengths: torch.Tensor, min_size: int = 2, penalty: float = 0.0, *, n_series: int | None = None,
                stream: torch.cuda.Stream | None = None):
     """anofox_hip_pelt_device on torch tensors: the PELT changepoints (L2 cost) of every series of a block, nothing read back.

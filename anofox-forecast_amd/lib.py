@@ -145,6 +145,18 @@ QUALITY_FIELDS = tuple(n for n, _ in DataQualityResult._fields_)
 QUALITY_OK, QUALITY_NAN = 0, 2
 
 
+class FeaturesResult(C.Structure):
+    """include/anofox_fcst_hip.h FeaturesResult (the reference's layout, 24 bytes): both arrays and the names are malloc'ed by the entry."""
+    _fields_ = [("features", C.POINTER(C.c_double)), ("feature_names", C.POINTER(C.c_char_p)), ("n_features", C.c_size_t)]
+
+
+assert C.sizeof(FeaturesResult) == 24
+N_FEATURES = 117                         # ANOFOX_HIP_N_FEATURES
+FEATURES_MAX_ROWS = 1 << 16              # ANOFOX_HIP_FEATURES_MAX_ROWS
+FEATURES_OK, FEATURES_EMPTY, FEATURES_NAN = 0, 1, 2
+FEATURES_FAMILIES = ("chains", "sort", "scan", "match", "dft")      # bit i of `families` of anofox_hip_features_families_device
+
+
 class SeasonalityResult(C.Structure):
     """include/anofox_fcst_hip.h SeasonalityResult (the reference's layout, 40 bytes): detected_periods is malloc'ed by the entry."""
     _fields_ = [("detected_periods", C.POINTER(C.c_int)), ("n_periods", C.c_size_t), ("primary_period", C.c_int),
@@ -385,6 +397,8 @@ EXPORTED_SYMBOLS = [
     "anofox_ts_stats", "anofox_ts_stats_with_dates", "anofox_ts_stats_with_dates_and_type", "anofox_free_ts_stats_result",
     "anofox_hip_stats_batch", "anofox_hip_stats_device",
     "anofox_ts_data_quality", "anofox_hip_quality_batch", "anofox_hip_quality_device",
+    "anofox_ts_features", "anofox_free_features_result", "anofox_ts_features_list", "anofox_ts_validate_feature_params",
+    "anofox_free_warnings", "anofox_hip_features_batch", "anofox_hip_features_device", "anofox_hip_features_families_device",
     "anofox_ts_detect_seasonality", "anofox_ts_analyze_seasonality", "anofox_free_seasonality_result", "anofox_free_int_array",
     "anofox_hip_seasonality_batch", "anofox_hip_seasonality_device",
     "anofox_ts_lomb_scargle", "anofox_ts_aic_period", "anofox_ts_sazed_period", "anofox_ts_detect_periods_flat",
@@ -538,6 +552,24 @@ def load():
     L.anofox_ts_data_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(DataQualityResult), P(AnofoxError)]
     L.anofox_hip_quality_batch.restype = C.c_bool
     L.anofox_hip_quality_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_features.restype = C.c_bool
+    L.anofox_ts_features.argtypes = [C.c_void_p, C.c_size_t, P(FeaturesResult), P(AnofoxError)]
+    L.anofox_free_features_result.restype = None
+    L.anofox_free_features_result.argtypes = [P(FeaturesResult)]
+    L.anofox_ts_features_list.restype = C.c_bool
+    L.anofox_ts_features_list.argtypes = [P(C.c_void_p), P(C.c_size_t)]
+    L.anofox_ts_validate_feature_params.restype = C.c_bool
+    L.anofox_ts_validate_feature_params.argtypes = [C.c_void_p, C.c_size_t, P(C.c_void_p), P(C.c_size_t)]
+    L.anofox_free_warnings.restype = None
+    L.anofox_free_warnings.argtypes = [C.c_void_p, C.c_size_t]
+    L.anofox_hip_features_batch.restype = C.c_bool
+    L.anofox_hip_features_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_features_device.restype = C.c_bool
+    L.anofox_hip_features_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_features_families_device.restype = C.c_bool
+    L.anofox_hip_features_families_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     L.anofox_hip_quality_device.restype = C.c_bool
     L.anofox_hip_quality_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                             C.c_void_p, P(AnofoxError)]
@@ -824,3 +856,34 @@ def shard_range(n_series, n_shards, shard):
     lo, hi = C.c_size_t(), C.c_size_t()
     load().anofox_hip_shard_range(n_series, n_shards, shard, C.byref(lo), C.byref(hi))
     return lo.value, hi.value
+
+
+def feature_list():
+    """anofox_ts_features_list: the 117 feature names in the order of the source's list_features (host only)."""
+    L = load()
+    names, count = C.c_void_p(), C.c_size_t()
+    if not L.anofox_ts_features_list(C.byref(names), C.byref(count)):
+        raise RuntimeError("anofox_ts_features_list failed")
+    arr = C.cast(names, C.POINTER(C.c_char_p))
+    out = [arr[i].decode() for i in range(count.value)]
+    L.anofox_free_warnings(names, count.value)
+    return out
+
+
+def feature_names():
+    """The 117 names in byte order: the order of anofox_ts_features, of out_features and of the presence bits."""
+    return sorted(feature_list(), key=lambda s: s.encode())
+
+
+def validate_feature_params(keys):
+    """anofox_ts_validate_feature_params: one warning per key that is no feature name (host only)."""
+    L = load()
+    keys = [k.encode() for k in keys]
+    arr = (C.c_char_p * max(len(keys), 1))(*keys)
+    warnings, count = C.c_void_p(), C.c_size_t()
+    if not L.anofox_ts_validate_feature_params(arr, len(keys), C.byref(warnings), C.byref(count)):
+        raise RuntimeError("anofox_ts_validate_feature_params failed")
+    w = C.cast(warnings, C.POINTER(C.c_char_p))
+    out = [w[i].decode() for i in range(count.value)]
+    L.anofox_free_warnings(warnings, count.value)
+    return out

@@ -385,6 +385,57 @@ bool anofox_ts_data_quality(const double *values,
                             struct AnofoxError *out_error);
 
 /*
+ * Feature extraction result (layout of the reference's anofox_fcst_ffi.h: two pointers and a size_t, sizeof == 24).  `features`,
+ * `feature_names` and every name are malloc'ed by the entry and released by anofox_free_features_result.
+ */
+typedef struct FeaturesResult {
+    double *features;
+    char **feature_names;
+    size_t n_features;
+} FeaturesResult;
+
+#define ANOFOX_HIP_N_FEATURES 117
+#define ANOFOX_HIP_FEATURES_MAX_ROWS 65536
+
+/*
+ * The features of ONE series, the reference's extract_features (features.rs) behind its FFI wrapper: only the features the source
+ * inserts (skewness and kurtosis need a deviation above DBL_EPSILON, the change features two values, a lag feature enough rows,
+ * fft_coefficient_i a series longer than i), sorted by name in byte order.  Every sum runs left to right from 0.0 as the source's,
+ * so counts, flags, locations, order statistics, sums and what one division or square root derives from them equal the reference's
+ * bit for bit; the four entropies and lempel_ziv_complexity (ln) and the fft coefficients and spectral figures (sin / cos) agree to
+ * a tolerance.  The source sums sum_of_reoccurring_values, sum_of_reoccurring_datapoints and the terms of
+ * permutation_entropy in hash order; here the order is ascending over the distinct bit patterns (total order) and the lexicographic
+ * order of the patterns.  length == 0: false, COMPUTATION_ERROR "Insufficient data: need at least 1 observations, got 0".  A NaN
+ * among the values: false, COMPUTATION_ERROR "Invalid input: a value is NaN" (the source leaves its sorted figures to its sort's
+ * internals).  More than 65,536 values: false, INVALID_INPUT, the text names the limit.  NULL `values` or `out_result`:
+ * NULL_POINTER.  +-inf are ordinary values.  Runs on the GPU as a batch of one.
+ */
+bool anofox_ts_features(const double *values,
+                        size_t length,
+                        struct FeaturesResult *out_result,
+                        struct AnofoxError *out_error);
+
+void anofox_free_features_result(struct FeaturesResult *result);
+
+/*
+ * The 117 names in the order of the source's list_features.  As the reference's: *out_names receives a malloc'ed array of
+ * *out_count malloc'ed strings (cast to char *); anofox_free_warnings(names, count) releases it.  Host only.
+ */
+bool anofox_ts_features_list(char **out_names, size_t *out_count);
+
+/*
+ * One warning "Unknown feature parameter key '<key>' - this parameter will be ignored" per key that is no feature name (NULL keys
+ * are skipped).  *out_warnings is malloc'ed (NULL when there is none) and released by anofox_free_warnings.  false for a NULL
+ * argument.  Host only.
+ */
+bool anofox_ts_validate_feature_params(const char *const *param_names,
+                                       size_t n_params,
+                                       char ***out_warnings,
+                                       size_t *out_n_warnings);
+
+void anofox_free_warnings(char **warnings, size_t n_warnings);
+
+/*
  * Seasonality analysis of one series (layout of the reference's anofox_fcst_ffi.h: a pointer, a size_t, an int, two doubles; sizeof ==
  * 40, primary_period at 16, seasonal_strength at 24).  detected_periods is malloc'ed by the entry (NULL when n_periods == 0) and
  * released by anofox_free_seasonality_result.
@@ -823,6 +874,61 @@ bool anofox_hip_quality_device(const double *y,
                                int64_t *out_int,
                                void *stream,
                                struct AnofoxError *out_error);
+
+/*
+ * The features of `n_series` series in one GPU pass (per series the semantics of anofox_ts_features).  Replaces the reference's one
+ * FFI call per group (_ts_features_native).  `validity` may be NULL, and so may validity[i] (all valid); NULL values are dropped.
+ * out_features is fp64 [n_series x 117], series-major, the features in byte order of their names (the order of the single entry;
+ * feature_names.inc); a feature the source does not insert is NaN there and its bit in out_present (uint64 [n_series x 2], bit
+ * i % 64 of word i / 64 for feature i) is 0.  out_status is int32 [n_series] (may be NULL): 0; 1 for a series without a value
+ * (every feature NaN, no bit); 2 for a series with a NaN among its values (`length` is written and is its only bit, every other
+ * feature is NaN).  The return value is false only for batch-level failures (NULL pointers, no GPU, a series above 65,536 values),
+ * also reported through `out_batch_error`.  Runs on the calling thread's current device.
+ */
+bool anofox_hip_features_batch(const double *const *values,
+                               const uint64_t *const *validity,
+                               const size_t *lengths,
+                               size_t n_series,
+                               double *out_features,
+                               uint64_t *out_present,
+                               int32_t *out_status,
+                               struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows <= 65,536), `valid` (uint8 [t_rows x ld], 0 =
+ * NULL; may be NULL), lengths[n_series] (int32; a length above t_rows is cut to it); the outputs are device pointers.  out_fp is
+ * fp64 [117 x ld], row i the feature i; out_int is int64 [3 x ld]: the two presence words and the status.  Columns s >= n_series
+ * are left untouched.  Five kernels, one per family (in-order chains, sort, counting scans, template matching, DFT), one wavefront
+ * per series: a series of at most 2,048 rows lives in LDS, a longer one in a workspace in global memory that the call allocates
+ * (slower, the same figures).  The same bits on every run and through every entry.  Runs on `stream` (NULL: the null stream) and
+ * returns after it has finished.
+ */
+bool anofox_hip_features_device(const double *y,
+                                const uint8_t *valid,
+                                size_t ld,
+                                const int32_t *lengths,
+                                size_t n_series,
+                                size_t t_rows,
+                                double *out_fp,
+                                int64_t *out_int,
+                                void *stream,
+                                struct AnofoxError *out_error);
+
+/*
+ * anofox_hip_features_device restricted to the families whose bit is set in `families` (bit 0 chains -- it writes out_int --, 1 sort,
+ * 2 counting scans, 3 template matching, 4 DFT): the rows of the other families are left untouched.  For tests and timing.
+ */
+bool anofox_hip_features_families_device(const double *y,
+                                         const uint8_t *valid,
+                                         size_t ld,
+                                         const int32_t *lengths,
+                                         size_t n_series,
+                                         size_t t_rows,
+                                         unsigned families,
+                                         double *out_fp,
+                                         int64_t *out_int,
+                                         void *stream,
+                                         struct AnofoxError *out_error);
 
 /*
  * The seasonality analysis of one series of a batch: sizeof == 128, no pointer.  Entries k >= n_periods of the arrays are 0.
