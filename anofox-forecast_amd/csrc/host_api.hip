@@ -40,6 +40,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_resources.hpp"     // HipFail / HIPCHECK, the tunables, DeviceGuard, the device / pinned / stream caches, the device list
 #include "host_scratch.hpp"       // Scratch (a call's device blocks), the shape and packing of a batch of series, the _device entry's checks and launch
 #include "host_parts.hpp"         // how an auto-detected batch is cut into device batches (PartPlan), and how a batch's results reach the caller's arrays
+#include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
 struct Plan {
     ModelType model;
@@ -166,8 +167,8 @@ struct AnofoxHipBatch {
     size_t classic_ybuf_cols = 0;
     std::vector<void *> retired;  // blocks a run outgrew while kernels may still read them: handed back when the batch is destroyed
                                   // (freeing them on the spot needs a device-wide synchronisation, which couples every host thread's batch)
-    int merged_m_max = 0;         // ... and its largest period (sizes)
     int32_t *d_m_col = nullptr;   // merged batch of several seasonal periods (auto-detected): period of every column, constant within 64 columns
+    int merged_m_max = 0;         // ... and its largest period (sizes)
     int spec2_below_md = 2048; // per spec: the last problems run one per wave, two iterations per pass (0 = never); damped multiplicative
                                // trend.  Measured on the 30-spec M5 batch (tools/spec2_sweep.sh): 0 / 256 / 1024 / 2048 / 4096 / 8192 -> 579 / 575 / 565 / 562 / 594 / 736 ms
     int spec2_below = 1024;    // same, other specs (single-spec ETS(A,A,A) fit: 22.5 -> 18.2 ms; all specs at 2048 / 4096: 588 / 673 ms)
@@ -883,16 +884,14 @@ void compact_storage_decide(AnofoxHipBatch *b, bool pending, hipStream_t st, int
     else if (b->h_misfit[0] == 0u) b->y_type = YT_F32;
 }
 
+// The host side of every ETS / AutoETS fit.  WHAT runs where and when is decided by plan_fit_schedule (host_fit_schedule.hpp) from
+// plain values; this function looks the launchers up, builds the per-slot arguments, sizes the scratches from the plan and walks
+// the plan once.
+static_assert(N_GROUP_CLASSES == FIT_GROUP_CLASSES && GROUP_DAMPED_MUL == 0 && GROUP_GENERAL == 1 && GROUP_ADDITIVE == 2, "host_fit_schedule.hpp names the group classes by number");
 void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const int32_t *d_len, int m, bool skip_constant,
                       hipStream_t st)
 {
-    const size_t n = b->n, ld = b->ld;
-    // Round budgets (streamed passes per launch).  Geometric, so every round retires roughly half of the
-    // still-running problems and the compaction + gather in between stays a few percent of the passes.
-    // iteration budgets of the rounds (the last one runs everything left to completion); ANOFOX_HIP_TUNE budgets=... overrides
-    const std::vector<int> &BUDGET = b->tun.budgets;
-    const int n_rounds = (int)BUDGET.size();
-    const int n_lanes = std::min<int>(N_AUX_STREAMS, b->n_slots_cap);
+    const size_t n = b->n, ld = b->ld, n_spec = specs.size();
     // fork: aux streams wait for everything queued on `st` so far
     HIPCHECK(hipEventRecord(b->ev_fit0, st));
     // several periods in one block (columns grouped by period in blocks of 64): the round kernels read the period PER LANE, so the
@@ -904,41 +903,41 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
     const void *ybase = yt == YT_F32 ? (const void *)b->d_yc32 : (yt == YT_U16 ? (const void *)b->d_yc16 : (const void *)b->d_y);
     const int ybytes = yt == YT_F32 ? 4 : (yt == YT_U16 ? 2 : 8);
     const int lds_limit = merged ? ETS_MERGED_LDS_PERIOD : ETS_LDS_PERIOD;      // largest period whose seasonal ring stays in LDS
-    // ONE spec (ETS with an explicit model, fitted or with given parameters): its launches go on the run's own stream -- no fork, no
-    // join.  A cross-stream event wait is cheap when the host has just synchronised and expensive inside a pipeline of runs: twenty
-    // fixed-parameter steps enqueued back to back took 1.4 ms each with the fork / join against 0.5 ms with a host wait in between.
-    const bool inline_stream = specs.size() == 1;
-    const int n_fork = inline_stream ? 0 : n_lanes;      // streams that carry work: one per spec
-    auto spec_stream = [&](int idx) -> hipStream_t { return inline_stream ? st : b->aux[idx]; };
-    // enqueue order: most expensive specs first, dealt round-robin over the streams, so the long
-    // multiplicative / damped / seasonal fits start together instead of queueing behind each other
-    std::vector<size_t> order(specs.size());
-    for (size_t i = 0; i < order.size(); i++) order[i] = i;
-    // (relative wave-time of one fitted problem of each spec, measured on the M5 shape with the wave trace -- profiles/r06_wave_residency_base.txt:
-    //  resident wave-milliseconds per spec over a 30,490-series step, in thousands; the damped multiplicative-trend specs lead, and
-    //  among them the additive-season one needs the most iterations, not the one with the longest step)
-    auto cost = [&](int id) {
-        static const int measured[30] = {/* A,N,* */ 3, 8, 14, /* A,A,* */ 7, 13, 27, /* A,Ad,* */ 17, 29, 41, /* A,M,* */ 14, 26, 22, /* A,Md,* */ 63, 92, 84,
-                                         /* M,N,* */ 7, 0, 15, /* M,A,* */ 18, 0, 29, /* M,Ad,* */ 33, 0, 48, /* M,M,* */ 16, 0, 28, /* M,Md,* */ 65, 0, 95};
-        return (id >= 0 && id < 30 && measured[id] > 0) ? measured[id] : 1;
-    };
-    // expected work of a spec on THIS batch: a spec with a multiplicative component only runs on the strictly positive series
-    auto work = [&](int id) {
-        const double live = (b->live_all >= 0 && spec_has_mult(id)) ? (double)b->live_pos : (b->live_all >= 0 ? (double)b->live_all : 1.0);
-        return (double)cost(id) * (live + 1.0);
-    };
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return work(specs[x]) > work(specs[y]); });
-    // one stream per spec (the runtime maps them onto the hardware queues; two explicit pairing schemes -- dedicated
-    // queues for the heaviest specs, heaviest-with-lightest -- both measured 14 % slower on the 30-spec batch)
-    std::vector<int> stream_of(order.size());
-    for (size_t oi = 0; oi < order.size(); oi++) stream_of[oi] = (int)(oi % (size_t)n_lanes);
-    std::vector<FitArgs> args(order.size());
-    std::vector<FitLaunchers> fns(order.size());
-    for (size_t oi = 0; oi < order.size(); oi++) {
-        const size_t k = order[oi];
+    // the launchers of every spec and class, and the schedule's input: what the decisions read, as values
+    std::vector<FitLaunchers> fns_of(n_spec);
+    GroupLaunchFn group_fn[N_GROUP_CLASSES];
+    FitScheduleInput in;
+    in.n = n; in.ld = ld; in.t_max = b->t_max; in.m = m;
+    for (size_t k = 0; k < n_spec; k++) {
+        const int id = specs[k], ms = spec_season(id) != 0 ? m : 1;
+        fns_of[k] = ets_fit_launcher(id, (merged && ms != 1) ? (ms > lds_limit ? ETS_PERLANE_HBM : ETS_PERLANE_LDS) : ms, yt);
+        if (!fns_of[k].round_seq || !fns_of[k].round_spec || !fns_of[k].round_auto || !fns_of[k].final) throw HipFail{"no kernel for ETS spec id " + std::to_string(id)};
+        in.specs.push_back(FitSpec{id, spec_has_mult(id), spec_trend_idx(id) == 4, spec_season(id) != 0, fns_of[k].round_k4 && fns_of[k].round_auto_k4,
+                                   fns_of[k].nm_scratch_per_wg, ets_group_class(id)});
+    }
+    for (int c = 0; c < N_GROUP_CLASSES; c++) { group_fn[c] = ets_group_launcher(c, m, yt); in.group_launcher[c] = group_fn[c] != nullptr; }
+    in.live_pos = b->live_pos; in.live_all = b->live_all; in.use_pos = b->use_pos; in.none_pos = b->none_pos;
+    in.fixed_params = b->fixed_params; in.merged = merged; in.fp64 = yt == YT_F64; in.use_gather = b->use_gather; in.gather_budget = b->gather_budget;
+    in.seq_rounds = b->seq_rounds; in.seq_rounds_env = b->seq_rounds_env;
+    in.spec_below = b->spec_below; in.spec_below_md = b->spec_below_md; in.spec2_below = b->spec2_below; in.spec2_below_md = b->spec2_below_md;
+    in.n_lanes = std::min<int>(N_AUX_STREAMS, b->n_slots_cap);
+    {
+        const Tunables &t = b->tun;
+        in.budgets = t.budgets; in.k4 = t.k4; in.k4_top = t.k4_top; in.k4_top_below = t.k4_top_below;
+        in.fill_policy = t.fill_policy; in.fill_target = t.fill_target; in.fill_late_div = t.fill_late_div; in.fill_s2_div = t.fill_s2_div;
+        in.top_boost_n = t.top_boost_n; in.top_boost_pct = t.top_boost_pct; in.prio_top = t.prio_top;
+        in.group_launch = t.group_launch; in.group_split = t.group_split; in.dm_head_rounds = t.dm_head_rounds; in.gather_cols = t.gather_cols;
+    }
+    in.lim = FitLimits{NM_BLOCK, NM_K, GROUP_MAX_SLOTS, N_AUX_STREAMS, TINY_BATCH_PROBLEMS, lds_limit, 2 * 1024 * 64};
+    const FitSchedule plan = plan_fit_schedule(in);
+    if (!plan.error.empty()) throw HipFail{plan.error};
+    auto spec_stream = [&](size_t oi) -> hipStream_t { return plan.inline_stream ? st : b->aux[plan.stream_of[oi]]; };
+    std::vector<FitArgs> args(n_spec);
+    std::vector<FitLaunchers> fns(n_spec);
+    for (size_t oi = 0; oi < n_spec; oi++) {
+        const size_t k = plan.order[oi];
         const int id = specs[k];
-        const int q = (int)(oi % (size_t)n_lanes);
-        auto &lane = b->lanes[q];
+        auto &lane = b->lanes[plan.lane_of[oi]];
         const int se = spec_season(id), ti = spec_trend_idx(id);
         const int tt = ti == 0 ? 0 : (ti <= 2 ? 1 : 2);
         FitArgs &a = args[oi];
@@ -962,376 +961,85 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
         a.st = lane.st;
         a.ring_scratch = nullptr;
         a.m_col = b->d_m_col;
-        if (b->sd_in_final && order.size() == 1) { a.mean = b->d_mean; a.sd_out = b->d_sd; }
+        if (b->sd_in_final && n_spec == 1) { a.mean = b->d_mean; a.sd_out = b->d_sd; }
         a.lane_stats = b->d_lane_stats ? b->d_lane_stats + 2 * k : nullptr;
         a.wave_trace = b->d_wave_trace;
-        fns[oi] = ets_fit_launcher(id, (merged && se != 0) ? (a.m > lds_limit ? ETS_PERLANE_HBM : ETS_PERLANE_LDS) : a.m, yt);
-        if (!fns[oi].round_seq || !fns[oi].round_spec || !fns[oi].round_auto || !fns[oi].final) throw HipFail{"no kernel for ETS spec id " + std::to_string(id)};
+        fns[oi] = fns_of[k];
     }
-    // Periods above the LDS limit keep the seasonal ring of every lane in HBM: one area per (spec, workgroup of the widest
-    // launch = the speculative driver's 16 problems per workgroup)
+    // Periods above the LDS limit keep the seasonal ring of every lane in HBM: one area per (spec, workgroup of the widest launch)
     {
         size_t n_long = 0;
-        for (size_t oi = 0; oi < order.size(); oi++) if (args[oi].m > lds_limit) n_long++;
+        for (size_t oi = 0; oi < n_spec; oi++) if (args[oi].m > lds_limit) n_long++;
         if (n_long) {
-            // (a tiny batch runs EVERY problem on a wave of its own whatever the thresholds say: found in round 6 as the intermittent
-            //  "Memory access fault by GPU" of test_two_level_speculation_is_bit_identical[20] -- 24 series, spec2_below = 20: 24 one-wave
-            //  workgroups on a scratch sized for 20, four rings written past its end; never with the default thresholds, which are
-            //  larger than any tiny batch.  docs/history/r06_round_log.md section E)
-            const bool tiny_batch = (uint64_t)n * order.size() <= (uint64_t)TINY_BATCH_PROBLEMS;
-            const size_t wg = std::max<size_t>((n + 15) / 16, std::min<size_t>(n, tiny_batch ? n : (size_t)std::max(b->spec2_below, b->spec2_below_md)));
-            const size_t per_spec = wg * (size_t)m * 64u;
+            const size_t per_spec = plan.scratch_workgroups * (size_t)m * 64u;
             if ((double)n_long * (double)per_spec * 8.0 > 64.0 * 1073741824.0)
                 throw HipFail{"seasonal period " + std::to_string(m) + " on " + std::to_string(n) + " series needs more than 64 GiB of ring scratch: shard the batch"};
             double *base = ensure_ring(b, n_long * per_spec);
             size_t k = 0;
-            for (size_t oi = 0; oi < order.size(); oi++) if (args[oi].m > lds_limit) { args[oi].ring_scratch = base + (k++) * per_spec; args[oi].ring_scratch_doubles = per_spec; }
+            for (size_t oi = 0; oi < n_spec; oi++) if (args[oi].m > lds_limit) { args[oi].ring_scratch = base + (k++) * per_spec; args[oi].ring_scratch_doubles = per_spec; }
         }
     }
     // Specs whose round kernels keep the Nelder-Mead simplex out of LDS: a global scratch per stream, one slice per workgroup of the
-    // widest launch (four lanes per problem for every series, or one wave per problem for the last spec2_below / a tiny batch)
-    {
-        const bool tiny_batch = (uint64_t)n * order.size() <= (uint64_t)TINY_BATCH_PROBLEMS;
-        const size_t wg = std::max<size_t>((n + 15) / 16, std::min<size_t>(n, tiny_batch ? n : (size_t)std::max(b->spec2_below, b->spec2_below_md)));
-        for (size_t oi = 0; oi < order.size(); oi++) {
-            if (!fns[oi].nm_scratch_per_wg) continue;
-            auto &lane = b->lanes[oi % (size_t)n_lanes];
-            const size_t need = (wg + 8) * fns[oi].nm_scratch_per_wg;         // (+ the waves that round a launch up to whole workgroups)
-            if (lane.nm_scratch_doubles < need) {
-                if (lane.nm_scratch) b->retired.push_back(lane.nm_scratch);
-                lane.nm_scratch = nullptr; lane.nm_scratch_doubles = 0;
-                lane.nm_scratch = dalloc<double>(need);
-                lane.nm_scratch_doubles = need;
-            }
-            args[oi].nm_scratch = lane.nm_scratch; args[oi].nm_scratch_doubles = lane.nm_scratch_doubles;
+    // widest launch
+    for (size_t oi = 0; oi < n_spec; oi++) {
+        if (!fns[oi].nm_scratch_per_wg) continue;
+        auto &lane = b->lanes[plan.lane_of[oi]];
+        const size_t need = (plan.scratch_workgroups + 8) * fns[oi].nm_scratch_per_wg;         // (+ the waves that round a launch up to whole workgroups)
+        if (lane.nm_scratch_doubles < need) {
+            if (lane.nm_scratch) b->retired.push_back(lane.nm_scratch);
+            lane.nm_scratch = nullptr; lane.nm_scratch_doubles = 0;
+            lane.nm_scratch = dalloc<double>(need);
+            lane.nm_scratch_doubles = need;
         }
+        args[oi].nm_scratch = lane.nm_scratch; args[oi].nm_scratch_doubles = lane.nm_scratch_doubles;
     }
-    // Round-major submission: round r of every spec is enqueued before round r+1 of any, each spec on its
-    // own stream, so that all specs advance together and the hardware queues never hold a long spec behind
-    // another one.  Early rounds run the sequential driver (least arithmetic while problems outnumber
-    // lanes), late rounds the speculative one (shortest critical path for the stragglers).
-    // specs that are inadmissible for EVERY series of the group (a multiplicative component, no strictly positive series: the raw
-    // M5 counts) get their per-series outputs from one small kernel and no launch chain at all -- 19 of the 25 chains of the
-    // intermittent batch used to be compaction / gather / round launches over empty lists, queueing in front of the live ones
-    std::vector<char> dead(order.size(), 0);
-    if (b->none_pos && !b->fixed_params)
-        for (size_t oi = 0; oi < order.size(); oi++)
-            if (args[oi].need_positive) dead[oi] = 1;         // (their outputs: below, once the streams have forked)
-    // additive-class specs, one lane per problem: four trial points per pass (K4).  Their pass is memory bound (6-10 instructions per
-    // 8-byte load): against the sequential driver K4 is one pass per iteration instead of ~1.7, against four lanes per problem it is
-    // the same bytes through a quarter of the load instructions (512 instead of 128 bytes each)
-    std::vector<char> k4(order.size(), 0);
-    {
-        bool all_additive = true;           // (-1: only when the general-class specs see under half of the series)
-        for (size_t oi = 0; oi < order.size(); oi++)
-            if (!dead[oi] && spec_has_mult(specs[order[oi]]) && !(b->live_all > 0 && b->live_pos >= 0 && 2 * (int64_t)b->live_pos < (int64_t)b->live_all))
-                all_additive = false;
-        // ... and enough of them to fill the chip one lane per problem: two K4 waves per SIMD
-        int64_t additive_live = 0;
-        for (size_t oi = 0; oi < order.size(); oi++)
-            if (!dead[oi] && !spec_has_mult(specs[order[oi]])) additive_live += b->live_all >= 0 ? (int64_t)b->live_all : (int64_t)n;
-        // ... or (round 5) the batch oversubscribes the chip whatever its mix: with the general-class steps a third shorter (error-correction
-        // form) the 25-spec batch of strictly positive series is no longer bound by fp64 issue alone, and the additive specs' ~41 % fewer
-        // passes are worth their arithmetic -- 477.6 -> 450.9 ms on the 30,490-series batch, same box (profiles/r05_tune_sweep.txt).  One
-        // lane per problem fills two waves per SIMD from 131,072 live problems on; below four times that the chains' latency decides
-        int64_t all_live = 0;
-        for (size_t oi = 0; oi < order.size(); oi++)
-            if (!dead[oi]) all_live += (spec_has_mult(specs[order[oi]]) && b->live_pos >= 0) ? (int64_t)b->live_pos : (b->live_all >= 0 ? (int64_t)b->live_all : (int64_t)n);
-        // (round 6) ... as long as the run streams the fp64 block.  K4 buys 41 % fewer passes with four times the arithmetic: a trade for a
-        // pass bound by its BYTES.  Over a compact copy (2 or 4 bytes per observation) the additive pass is bound by its instructions like
-        // every other, and K4 loses: intermittent M5 batch 58.0 -> 53.8 ms, 125k x 1,024 99.9 -> 75.5 ms, 125k x 256 with all 25 specs
-        // 148-156 -> 141-142 ms, the 25-spec M5 batch unchanged (profiles/r06_k4_shapes.txt)
-        const bool on = b->tun.k4 > 0 || (b->tun.k4 < 0 && yt == YT_F64 && ((all_additive && additive_live >= 131072) || all_live >= 524288));
-        for (size_t oi = 0; oi < order.size(); oi++)
-            k4[oi] = on && !dead[oi] && !b->fixed_params && !spec_has_mult(specs[order[oi]]) && fns[oi].round_k4 && fns[oi].round_auto_k4;
-    }
-    // Mid-size batches (round 6): fewer than 524,288 live problems (below that the first rounds run four lanes per problem for EVERY
-    // spec) but so many that four lanes for everybody oversubscribe the resident lanes more than eight times -- the 15,245-series
-    // shard of a 2-GPU M5 job: 381k problems, 1.5 M lanes on 131k.  There the first round's lanes are dealt by expected work: specs
-    // in cost order get four lanes per problem while the total stays under fill_target x the resident lanes, the rest start one
-    // lane per problem (the least arithmetic) and switch to four lanes when 1 / fill_late_div of their problems are left; one wave
-    // per problem at 1 / fill_s2_div.  Measured (profiles/r06_shard_policy.txt, shard of a 2-rank job alone on one GPU): 314 -> 280 ms.
-    // SMALLER batches keep four lanes for everybody: the 7,623- and 3,812-series shards (4 / 8 ranks) are bound by their longest
-    // chain from the first round, and dealing them fewer lanes makes it longer (204 -> 246-320 ms, 173 -> 187-215 ms) -- the chip
-    // absorbs three to six times its resident lanes of speculative work better than a chain absorbs 1.7 passes per iteration.
-    // Same trajectories whatever the driver (test_schedule_variants_are_bit_identical).
-    std::vector<char> fill_spec4(order.size(), 0);
-    bool fill_mode = false;
-    {
-        int64_t lanes = 0;
-        std::vector<int64_t> live_of(order.size(), 0);
-        for (size_t oi = 0; oi < order.size(); oi++) {
-            if (dead[oi]) continue;
-            live_of[oi] = (spec_has_mult(specs[order[oi]]) && b->live_pos >= 0) ? (int64_t)b->live_pos : (b->live_all >= 0 ? (int64_t)b->live_all : (int64_t)n);
-            lanes += live_of[oi];
+    // the gather blocks the plan asks for (none without the gather)
+    for (size_t oi = 0; oi < n_spec; oi++) {
+        auto &lane = b->lanes[plan.lane_of[oi]];
+        size_t cols = plan.gather_cols[oi];
+        if (cols == 0 || (lane.ybuf && lane.ybuf_cols >= cols)) continue;             // (a larger block from an earlier run serves as well)
+        if (lane.ybuf) {
+            HIPCHECK(hipDeviceSynchronize());                                          // an earlier run of this batch may still read the old block
+            dev_free(lane.ybuf, true);
+            lane.ybuf = nullptr; lane.ybuf_cols = 0;
         }
-        const int64_t resident = 2 * 1024 * 64;
-        const bool tiny_batch = (uint64_t)n * order.size() <= (uint64_t)TINY_BATCH_PROBLEMS;
-        fill_mode = b->tun.fill_policy > 0 && !tiny_batch && !b->fixed_params && order.size() > 1 && b->seq_rounds_env < 0 && b->seq_rounds == 0 &&
-                    lanes * 4 > 8 * resident;
-        if (fill_mode) {
-            const int64_t target = resident * (int64_t)b->tun.fill_target / 100;
-            for (size_t oi = 0; oi < order.size(); oi++) {                  // `order` is by expected work, most first
-                if (dead[oi] || k4[oi]) continue;
-                if (lanes + 3 * live_of[oi] <= target) { fill_spec4[oi] = 1; lanes += 3 * live_of[oi]; }
+        while (cols >= 64) {
+            try { lane.ybuf = dalloc<double>(std::max<size_t>(b->t_max, 1) * cols); lane.ybuf_cols = cols; break; }
+            catch (const HipFail &f) {
+                if (!f.oom) throw;
+                cols = cols / 2 / 64 * 64;                 // a co-resident allocator holds memory: half the columns, in the end none
+                if (cols < 1024) cols = 0;
             }
         }
     }
-    if (b->use_gather && !b->fixed_params) {
-        // gather blocks of the specs that have something to fit: as many columns as the spec can ever have running (the strictly
-        // positive series for a spec with a multiplicative component), scaled down together if that exceeds the budget
-        const size_t T = std::max<size_t>(b->t_max, 1);
-        std::vector<size_t> need(order.size(), 0);
-        double total = 0.0;
-        for (size_t oi = 0; oi < order.size(); oi++) {
-            if (dead[oi]) continue;
-            size_t c = (b->use_pos && args[oi].need_positive && b->live_pos >= 0) ? (size_t)b->live_pos : n;
-            need[oi] = std::min(ld, (c + 63) / 64 * 64);
-            total += (double)need[oi] * (double)T * 8.0;
+    // what round r of slot oi runs on: its step of the plan, and the series list and block its lane holds by then
+    auto set_round = [&](FitArgs &a, const size_t oi, const int r) {
+        const RoundStep &s = plan.steps[oi][(size_t)r];
+        const auto &lane = b->lanes[plan.lane_of[oi]];
+        a.first_round = (r == 0);
+        a.wave_trace_tag = ((unsigned long long)specs[plan.order[oi]] << 32) | ((unsigned long long)r << 16);
+        a.wave_prio = s.wave_prio;
+        a.budget = s.budget; a.budget_seq = s.budget_seq; a.spec_below = s.spec_below; a.spec2_below = s.spec2_below;
+        a.y_round = a.y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr; a.gathered = 0;
+        if (s.source == SRC_POSITIVE) {
+            // mixed batch: this spec is admissible for the strictly positive series only -- its first round runs on their dense list
+            // (built once per group) instead of sweeping every wave for a few live lanes
+            a.series_of = b->d_pos_map; a.n_active = b->d_pos_cnt;
+            if (b->d_ypos) { a.y_round = b->d_ypos; a.gathered = 1; a.gather_cap = (int)ld; }
+        } else if (s.source == SRC_COMPACTED) {
+            a.series_of = lane.map[r & 1]; a.n_active = lane.cnt + (r % 3);
+            if (b->use_gather && lane.ybuf) { a.y_round = lane.ybuf; a.ld_round = lane.ybuf_cols; a.gathered = 1; a.gather_cap = (int)lane.ybuf_cols; }
         }
-        const double scale = total > b->gather_budget ? b->gather_budget / total : 1.0;
-        for (size_t oi = 0; oi < order.size(); oi++) {
-            if (dead[oi]) continue;
-            auto &lane = b->lanes[oi % (size_t)n_lanes];
-            size_t cols = scale < 1.0 ? (size_t)((double)need[oi] * scale) / 64 * 64 : need[oi];
-            if (b->tun.gather_cols > 0) cols = std::min<size_t>(need[oi], (size_t)b->tun.gather_cols / 64 * 64);
-            if (cols < need[oi] && cols < 1024 && b->tun.gather_cols <= 0) cols = 0;      // (a block for a few hundred stragglers is not worth its launches)
-            if (lane.ybuf && lane.ybuf_cols >= cols) continue;                            // (a larger block from an earlier run serves as well)
-            if (lane.ybuf) {
-                HIPCHECK(hipDeviceSynchronize());                                          // an earlier run of this batch may still read the old block
-                dev_free(lane.ybuf, true);
-                lane.ybuf = nullptr; lane.ybuf_cols = 0;
-            }
-            while (cols >= 64) {
-                try { lane.ybuf = dalloc<double>(T * cols); lane.ybuf_cols = cols; break; }
-                catch (const HipFail &f) {
-                    if (!f.oom) throw;
-                    cols = cols / 2 / 64 * 64;                 // a co-resident allocator holds memory: half the columns, in the end none
-                    if (cols < 1024) cols = 0;
-                }
-            }
-        }
-    }
-    // a handful of series: one launch per spec, every problem on a wave of its own (two iterations per pass) to completion -- one
-    // series through AutoETS was 12 rounds x 3 launches x 25 specs
-    const bool tiny = (uint64_t)n * order.size() <= (uint64_t)TINY_BATCH_PROBLEMS;
-    const int total_rounds = b->fixed_params ? 0 : (tiny ? 1 : n_rounds);
-    // Group schedule (tune group_launch, the default): the live specs are dealt by class into at most four groups -- the damped
-    // multiplicative-trend specs (the step's critical path: two groups of similar expected work, on the priority streams), the other
-    // general-class specs and the additive class -- and round r of a group is ONE launch of its class's group kernel
-    // (ets_group_kernel.hpp) on the group's stream, behind one compaction and one gather launch for all its slots.  So the fit needs
-    // four streams whatever GPU_MAX_HW_QUEUES the host exports: with one stream per spec, 25 chains shared the runtime's default of
-    // four hardware queues (453 ms per step on the M5 batch, 372 ms with 16 queues; the group schedule: 377 and 376 ms,
-    // profiles/group_schedule_ab.txt).  Every argument of every round is known here, so the [round][slot] table goes to the device
-    // in one copy at the start of the run.  The per-spec schedule stays for one spec, a tiny batch (one launch per spec), given
-    // parameters and merged batches of several periods (per-lane period variants, which have no group kernels).
-    enum { RK_SEQ, RK_SPEC, RK_SPEC2, RK_AUTO, RK_K4, RK_AUTO_K4 };
-    std::vector<int> group_of(order.size(), -1);
-    std::vector<std::vector<size_t>> groups;         // slots (order indices) of each group, heaviest first
-    std::vector<int> group_stream;                   // the aux stream of each group
-    std::vector<GroupLaunchFn> group_fn;
-    std::vector<size_t> slot_of(order.size(), 0);    // column of the slot in a round's row of the table
-    size_t n_slots = 0;
-    bool grouped = b->tun.group_launch > 0 && !inline_stream && !tiny && !merged && !b->fixed_params && total_rounds > 0;
-    if (grouped) {
-        GroupLaunchFn fn[N_GROUP_CLASSES];
-        for (int c = 0; c < N_GROUP_CLASSES; c++) fn[c] = ets_group_launcher(c, m, yt);
-        std::vector<size_t> of_class[N_GROUP_CLASSES];
-        for (size_t oi = 0; oi < order.size() && grouped; oi++) {
-            if (dead[oi]) continue;
-            const int c = ets_group_class(specs[order[oi]]);
-            if (c < 0 || !fn[c] || fns[oi].nm_scratch_per_wg != 0) grouped = false;
-            else of_class[c].push_back(oi);
-        }
-        if (grouped) {
-            auto add = [&](const std::vector<size_t> &sl, int c) {
-                if (sl.empty()) return;
-                if (sl.size() > (size_t)GROUP_MAX_SLOTS) throw HipFail{"launch_fit_slots: more specs in one group than GROUP_MAX_SLOTS"};
-                groups.push_back(sl); group_fn.push_back(fn[c]);
-            };
-            // one class in two groups (tune group_split: 1 the damped-M class, 2 the other general-class specs), each spec (heaviest
-            // first) to the half with less expected work so far
-            auto add_split = [&](const std::vector<size_t> &sl, int c) {
-                std::vector<size_t> half[2];
-                double w[2] = {0.0, 0.0};
-                for (size_t oi : sl) {
-                    const int j = w[1] < w[0] ? 1 : 0;
-                    half[j].push_back(oi); w[j] += work(specs[order[oi]]);
-                }
-                add(half[0], c); add(half[1], c);
-            };
-            if (b->tun.group_split == 1) add_split(of_class[GROUP_DAMPED_MUL], GROUP_DAMPED_MUL);
-            else add(of_class[GROUP_DAMPED_MUL], GROUP_DAMPED_MUL);
-            if (b->tun.group_split == 2) add_split(of_class[GROUP_GENERAL], GROUP_GENERAL);
-            else add(of_class[GROUP_GENERAL], GROUP_GENERAL);
-            add(of_class[GROUP_ADDITIVE], GROUP_ADDITIVE);
-            grouped = !groups.empty();
-        }
-        if (grouped) {
-            // streams: the damped-M group (when there is one) on the first, which is the priority stream where the set has one; the
-            // others from the far end of the set, which never is
-            for (size_t g = 0; g < groups.size(); g++) {
-                const bool dm = spec_trend_idx(specs[order[groups[g][0]]]) == 4;
-                group_stream.push_back(dm ? (int)g : N_AUX_STREAMS - 1 - (int)g);      // (the damped-M groups come first)
-                for (size_t oi : groups[g]) { group_of[oi] = (int)g; stream_of[oi] = group_stream[g]; slot_of[oi] = n_slots++; }
-            }
-            // the specs with nothing to fit only get their outputs written: on the first group's stream
-            for (size_t oi = 0; oi < order.size(); oi++) if (dead[oi]) stream_of[oi] = group_stream[0];
-        }
-    }
-    // the table: pass 1 (emit = false) of the round loop below fills h_group_tab[r * n_slots + slot] and the slots' workgroup counts
-    bool emit = true;
-    std::vector<int> slot_blocks, slot_k4;
-    GroupCompactArgs gc{};          // pass 2: what enqueue_round collects of a group's slots for the group's compaction and gather
-    GroupGatherArgs gg{};
-    int gg_cols = 0;
-    auto run_round = [&](const size_t oi, const int kind, const FitArgs &a, hipStream_t sq, const int r) {
-        if (!grouped) {
-            const FitLaunchFn f = kind == RK_SEQ ? fns[oi].round_seq : kind == RK_SPEC ? fns[oi].round_spec : kind == RK_SPEC2 ? fns[oi].round_spec2 :
-                                  kind == RK_AUTO ? fns[oi].round_auto : kind == RK_K4 ? fns[oi].round_k4 : fns[oi].round_auto_k4;
-            f(a, sq);
-            return;
-        }
-        if (emit) return;                         // (the group launch carries it)
-        // the slot runs the device-side choice (SPEC 3) with the thresholds set so that it lands on the driver the host picked
-        FitArgs t = a;
-        if (kind == RK_SEQ || kind == RK_K4) { t.spec_below = -1; t.spec2_below = -1; t.budget_seq = t.budget; }
-        else if (kind == RK_SPEC) { t.spec_below = 0x7fffffff; t.spec2_below = -1; }
-        else if (kind == RK_SPEC2) throw HipFail{"launch_fit_slots: the one-wave-per-problem round of a tiny batch has no group form"};
-        // workgroups: those of the spec's own round_auto launch (ets_round_launch, SPEC 3) -- the same as its sequential (n / 64) or
-        // speculative (n / 16) launch under the thresholds above
-        const int g_seq = (int)((n + NM_BLOCK - 1) / NM_BLOCK);
-        const int g_spec = (int)((std::min<int64_t>((int64_t)n, std::max(t.spec_below, 0)) + NM_BLOCK / NM_K - 1) / (NM_BLOCK / NM_K));
-        const int g_spec2 = (int)std::min<int64_t>((int64_t)n, std::max(t.spec2_below, 0));
-        const int blocks = std::max(g_seq, std::max(g_spec, g_spec2));
-        if (t.ring_scratch != nullptr && (size_t)blocks * (size_t)t.m * NM_BLOCK > t.ring_scratch_doubles)
-            throw HipFail{"launch_fit_slots: the seasonal-ring scratch does not cover a group slot"};
-        const size_t cell = (size_t)r * n_slots + slot_of[oi];
-        b->h_group_tab[cell] = t;
-        slot_blocks[cell] = blocks;
-        slot_k4[cell] = (kind == RK_K4 || kind == RK_AUTO_K4) ? 1 : 0;
     };
-    auto enqueue_round = [&](const int r, const size_t oi) {
-            if (dead[oi]) return;
-            const int q = (int)(oi % (size_t)n_lanes);
-            auto &lane = b->lanes[q];
-            hipStream_t sq = spec_stream(stream_of[oi]);
-            FitArgs &a = args[oi];
-            const bool spec_mode = r >= b->seq_rounds;
-            a.first_round = (r == 0);
-            a.wave_trace_tag = ((unsigned long long)specs[order[oi]] << 32) | ((unsigned long long)r << 16);
-            a.wave_prio = (int)oi < b->tun.prio_top ? std::max(1, 3 - (int)oi) : 0;
-            a.spec_below = -1; a.spec2_below = -1;
-            a.gathered = 0;
-            if (tiny) {
-                a.y_round = b->d_y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr;
-                a.budget = 1 << 30; a.budget_seq = a.budget;
-                run_round(oi, RK_SPEC2, a, sq, r);
-                b->fit_launches++;
-                return;
-            }
-            if (r == 0 && b->use_pos && a.need_positive) {
-                // mixed batch: this spec is admissible for the strictly positive series only -- its first round runs on
-                // their dense list (built once per group) instead of sweeping every wave for a few live lanes
-                if (emit)
-                    hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sq, (int)n, d_len, b->d_notpos,
-                                       a.status, lane.st.done, lane.st.passes, lane.st.evals, lane.st.iters);
-                a.series_of = b->d_pos_map; a.n_active = b->d_pos_cnt;
-                if (b->d_ypos) { a.y_round = b->d_ypos; a.ld_round = ld; a.gathered = 1; a.gather_cap = (int)ld; }
-                else { a.y_round = b->d_y; a.ld_round = ld; }
-            } else if (r == 0) {
-                a.y_round = a.y; a.ld_round = ld; a.series_of = nullptr; a.n_active = nullptr;
-            } else {
-                const int32_t *prev_map = (r == 1) ? nullptr : lane.map[(r - 1) & 1];
-                const int32_t *prev_cnt = (r == 1) ? nullptr : lane.cnt + ((r - 1) % 3);
-                if (emit && !grouped && r == 1) HIPCHECK(hipMemsetAsync(lane.cnt, 0, 3 * sizeof(int32_t), sq));      // then the counters rotate: no more memsets
-                if (emit && !grouped) launch_compact(prev_map, prev_cnt, (int)n, lane.st.done, lane.map[r & 1], lane.cnt + (r % 3), sq, lane.cnt + ((r + 1) % 3));
-                if (emit && grouped) {          // (the group's one compaction launch: enqueue_group_round)
-                    const int k = gc.n_slots++;
-                    gc.prev[k] = prev_map; gc.n_prev[k] = prev_cnt; gc.done[k] = lane.st.done;
-                    gc.next[k] = lane.map[r & 1]; gc.n_next[k] = lane.cnt + (r % 3); gc.n_clear[k] = lane.cnt + ((r + 1) % 3);
-                }
-                a.series_of = lane.map[r & 1]; a.n_active = lane.cnt + (r % 3);
-                if (b->use_gather && lane.ybuf) {
-                    if (emit && !grouped)
-                        launch_gather_columns(a.y, ld, lane.map[r & 1], lane.cnt + (r % 3), (int)n, (int)b->t_max, lane.ybuf, lane.ybuf_cols, sq,
-                                              (int)lane.ybuf_cols, ybytes);
-                    if (emit && grouped) {      // (and its one gather launch)
-                        const int k = gg.n_slots++;
-                        gg.series_of[k] = lane.map[r & 1]; gg.n_active[k] = lane.cnt + (r % 3);
-                        gg.out[k] = lane.ybuf; gg.ld_out[k] = lane.ybuf_cols; gg.cap[k] = (int)lane.ybuf_cols;
-                        gg_cols = std::max(gg_cols, (int)std::min<size_t>(n, lane.ybuf_cols));
-                    }
-                    a.y_round = lane.ybuf; a.ld_round = lane.ybuf_cols; a.gathered = 1; a.gather_cap = (int)lane.ybuf_cols;
-                } else {
-                    a.y_round = a.y; a.ld_round = ld;
-                }
-            }
-            const int s2 = (spec_trend_idx(specs[order[oi]]) == 4) ? b->spec2_below_md : b->spec2_below;
-            if (fill_mode && !k4[oi]) {
-                const int64_t live_i = (spec_has_mult(specs[order[oi]]) && b->live_pos >= 0) ? (int64_t)b->live_pos : (b->live_all >= 0 ? (int64_t)b->live_all : (int64_t)n);
-                const int s2v = (int)std::max<int64_t>(32, std::min<int64_t>(s2 > 0 ? s2 : 32, live_i / std::max(1, b->tun.fill_s2_div)));
-                a.budget = BUDGET[r]; a.budget_seq = (BUDGET[r] * 7) / 4;
-                if (r == 0) {
-                    if (fill_spec4[oi]) run_round(oi, RK_SPEC, a, sq, r);
-                    else { a.budget = a.budget_seq; run_round(oi, RK_SEQ, a, sq, r); }
-                } else {
-                    a.spec_below = fill_spec4[oi] ? 0x7fffffff : (int)std::max<int64_t>(64, live_i / std::max(1, b->tun.fill_late_div));
-                    a.spec2_below = s2v;
-                    run_round(oi, RK_AUTO, a, sq, r);
-                }
-                if (!grouped) b->fit_launches++;
-                return;
-            }
-            if (k4[oi]) {
-                // additive spec of a memory-bound run: one lane per problem with four trial points per pass wherever four LANES per
-                // problem would otherwise run -- the same bytes per iteration through a quarter of the load instructions (a wave of
-                // four-lane groups moves 128 bytes per load, and it is the CU's address pipeline that such a run saturates) -- as
-                // long as the spec still has more problems than `spec_below`; fewer are a latency problem again: four lanes, then
-                // one wave per problem
-                a.budget = BUDGET[r]; a.budget_seq = BUDGET[r];
-                const int64_t live = b->live_all >= 0 ? b->live_all : (int64_t)n;
-                // The most expensive spec (`k4_top` of them) switches to four lanes per problem EARLIER, at `k4_top_below` live problems
-                // (20,480; every other spec at spec_below = 8,192): its chain ends the step, alone on the chip for the last 10-25 ms of
-                // the intermittent M5 batch with 477 one-lane waves on 1,024 SIMDs -- four lanes per problem are the same arithmetic on
-                // four times the waves.  70.6-71.7 -> 66.1-68.1 ms on that batch (thresholds 14,336-24,576: the same; 12,288 and 32,768:
-                // no gain -- at 32,768 the first round already runs four lanes while all six chains still fill the chip), 125k x 1,024:
-                // 138-142 -> 132-139 ms, batches with general-class specs: unchanged (profiles/r04_ab_experiments.txt).
-                const int sb = ((int)oi < b->tun.k4_top && b->tun.k4_top_below > 0) ? b->tun.k4_top_below : b->spec_below;
-                if (r == 0) run_round(oi, live > sb ? RK_K4 : RK_SPEC, a, sq, r);
-                else {
-                    a.spec_below = sb; a.spec2_below = s2 > 0 ? s2 : -1;
-                    run_round(oi, RK_AUTO_K4, a, sq, r);
-                }
-            } else if (r == 0 || b->seq_rounds_env >= 0 || b->seq_rounds == 0) {
-                // first round (no device count yet) or a forced schedule: the host picks the driver
-                a.budget = spec_mode ? BUDGET[r] : (BUDGET[r] * 7) / 4;     // ~1.7 passes per iteration when sequential
-                if (spec_mode && r > 0 && s2 > 0) {
-                    // ... but the last s2 problems still go one per wave (device-side count), in the same launch
-                    a.spec_below = 0x7fffffff; a.spec2_below = s2; a.budget_seq = a.budget;
-                    run_round(oi, RK_AUTO, a, sq, r);
-                } else
-                    run_round(oi, spec_mode ? RK_SPEC : RK_SEQ, a, sq, r);
-            } else {
-                // later rounds: the device-side count of running problems picks the driver -- sequential (least arithmetic)
-                // while this spec still fills >= 1/8 of the chip, then speculative (one pass per iteration), then two-level
-                // speculative (one problem per wave, two iterations per pass)
-                a.spec_below = (spec_trend_idx(specs[order[oi]]) == 4) ? b->spec_below_md : b->spec_below;
-                a.spec2_below = s2 > 0 ? s2 : -1;
-                if ((int)oi < b->tun.top_boost_n) {         // (experiment: the chains that end the step get their parallelism earlier)
-                    a.spec_below = (int)std::min<int64_t>(0x7fffffff, (int64_t)a.spec_below * b->tun.top_boost_pct / 100);
-                    if (a.spec2_below > 0) a.spec2_below = (int)std::min<int64_t>(0x7fffffff, (int64_t)a.spec2_below * b->tun.top_boost_pct / 100);
-                }
-                // ONE launch: a launch whose workgroups only find out that another driver owns the round still has to be dispatched
-                a.budget_seq = (BUDGET[r] * 7) / 4;
-                a.budget = BUDGET[r];
-                run_round(oi, RK_AUTO, a, sq, r);
-            }
-            if (!grouped) b->fit_launches++;
+    auto retire_nonpositive = [&](const size_t oi, hipStream_t sq) {
+        const auto &lane = b->lanes[plan.lane_of[oi]];
+        hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sq, (int)n, d_len, b->d_notpos,
+                           args[oi].status, lane.st.done, lane.st.passes, lane.st.evals, lane.st.iters);
     };
-    if (grouped) {
-        // pass 1: the table, then one copy of it ahead of everything the group streams run
-        const size_t cells = (size_t)total_rounds * n_slots;
+    if (plan.grouped) {
+        // every argument of every group round is known: the [round][slot] table goes to the device in one copy, ahead of
+        // everything the group streams run
+        const size_t cells = (size_t)plan.total_rounds * plan.n_slots;
         if (b->ev_group_tab) HIPCHECK(hipEventSynchronize(b->ev_group_tab));      // (the previous run's copy has been read)
         else HIPCHECK(hipEventCreateWithFlags(&b->ev_group_tab, hipEventDisableTiming));
         if (b->group_tab_cap < cells) {
@@ -1342,26 +1050,27 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
             b->h_group_tab = (FitArgs *)pin_alloc_bytes(cells * sizeof(FitArgs));
             b->group_tab_cap = cells;
         }
-        slot_blocks.assign(cells, 0); slot_k4.assign(cells, 0);
-        emit = false;
-        for (int r = 0; r < total_rounds; r++) for (size_t oi = 0; oi < order.size(); oi++) enqueue_round(r, oi);
-        emit = true;
+        for (size_t oi = 0; oi < n_spec; oi++) {
+            if (plan.dead[oi]) continue;
+            FitArgs t = args[oi];
+            for (int r = 0; r < plan.total_rounds; r++) { set_round(t, oi, r); b->h_group_tab[(size_t)r * plan.n_slots + plan.slot_of[oi]] = t; }
+        }
         HIPCHECK(hipMemcpyAsync(b->d_group_tab, b->h_group_tab, cells * sizeof(FitArgs), hipMemcpyHostToDevice, st));
         HIPCHECK(hipEventRecord(b->ev_group_tab, st));
         HIPCHECK(hipEventRecord(b->ev_fork, st));
-        for (int q : group_stream) HIPCHECK(hipStreamWaitEvent(b->aux[q], b->ev_fork, 0));
-    } else
-        for (int i = 0; i < n_fork; i++) HIPCHECK(hipStreamWaitEvent(b->aux[i], b->ev_fit0, 0));
-    for (size_t oi = 0; oi < order.size(); oi++)
-        if (dead[oi]) {
+    }
+    for (int q : plan.fork_streams) HIPCHECK(hipStreamWaitEvent(b->aux[q], plan.grouped ? b->ev_fork : b->ev_fit0, 0));
+    // the specs with nothing to fit: their per-series outputs
+    for (size_t oi = 0; oi < n_spec; oi++)
+        if (plan.dead[oi]) {
             const FitArgs &a = args[oi];
-            hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, spec_stream(stream_of[oi]), (int)n, d_len,
+            hipLaunchKernelGGL(retire_nonpositive_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, spec_stream(oi), (int)n, d_len,
                                b->d_notpos, a.status, a.st.done, a.st.passes, a.st.evals, a.st.iters, a.aicc, a.passes, a.evals, a.iters);
         }
     if (b->fixed_params) {
         // given smoothing parameters: no rounds at all -- admissibility + parameters, then the final pass below
-        for (size_t oi = 0; oi < order.size(); oi++) {
-            const int id = specs[order[oi]];
+        for (size_t oi = 0; oi < n_spec; oi++) {
+            const int id = specs[plan.order[oi]];
             FitArgs &a = args[oi];
             // coordinates present in this spec, in optimiser order (alpha, [beta*], [gamma*], [phi])
             double x[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1370,94 +1079,116 @@ void launch_fit_slots(AnofoxHipBatch *b, const std::vector<int> &specs, const in
             if (spec_trend_idx(id) != 0) x[d++] = b->fixed_x[1];
             if (spec_season(id) != 0) x[d++] = b->fixed_x[2];
             if (spec_trend_idx(id) == 2 || spec_trend_idx(id) == 4) x[d++] = b->fixed_x[3];
-            hipLaunchKernelGGL(ets_fixed_setup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, spec_stream(stream_of[oi]), (int)n, ld, d_len,
+            hipLaunchKernelGGL(ets_fixed_setup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, spec_stream(oi), (int)n, ld, d_len,
                                b->d_flags, spec_season(id) != 0 ? 1 : 0, a.m, a.n_param, a.need_positive, d, x[0], x[1], x[2], x[3], a.status,
                                a.st.sim, a.st.evals, a.st.iters, a.st.passes, a.st.done);
         }
         LAUNCHCHECK("ETS fixed-parameter setup");
     }
-    // round r of group g: the slots' compaction and gather (enqueue_round) on the group's stream, then the one group launch
+    // round r of a spec with a launch chain of its own: the compaction and gather of its running problems, then its round launch
+    auto enqueue_round = [&](const int r, const size_t oi) {
+        if (plan.dead[oi]) return;
+        const RoundStep &s = plan.steps[oi][(size_t)r];
+        auto &lane = b->lanes[plan.lane_of[oi]];
+        hipStream_t sq = spec_stream(oi);
+        FitArgs &a = args[oi];
+        set_round(a, oi, r);
+        if (s.source == SRC_POSITIVE) retire_nonpositive(oi, sq);
+        else if (s.source == SRC_COMPACTED) {
+            const int32_t *prev_map = (r == 1) ? nullptr : lane.map[(r - 1) & 1];
+            const int32_t *prev_cnt = (r == 1) ? nullptr : lane.cnt + ((r - 1) % 3);
+            if (r == 1) HIPCHECK(hipMemsetAsync(lane.cnt, 0, 3 * sizeof(int32_t), sq));      // then the counters rotate: no more memsets
+            launch_compact(prev_map, prev_cnt, (int)n, lane.st.done, lane.map[r & 1], lane.cnt + (r % 3), sq, lane.cnt + ((r + 1) % 3));
+            if (a.gathered)
+                launch_gather_columns(a.y, ld, lane.map[r & 1], lane.cnt + (r % 3), (int)n, (int)b->t_max, lane.ybuf, lane.ybuf_cols, sq,
+                                      (int)lane.ybuf_cols, ybytes);
+        }
+        const FitLaunchFn f = s.kind == RK_SEQ ? fns[oi].round_seq : s.kind == RK_SPEC ? fns[oi].round_spec : s.kind == RK_SPEC2 ? fns[oi].round_spec2 :
+                              s.kind == RK_AUTO ? fns[oi].round_auto : s.kind == RK_K4 ? fns[oi].round_k4 : fns[oi].round_auto_k4;
+        f(a, sq);
+        b->fit_launches++;
+    };
+    // round r of group g, on the group's stream: ONE compaction and ONE gather launch for all its slots, then the one group launch
     auto enqueue_group_round = [&](const int r, const size_t g) {
-        hipStream_t sg = b->aux[group_stream[g]];
+        const std::vector<size_t> &slots = plan.groups[g].slots;
+        hipStream_t sg = b->aux[plan.groups[g].stream];
         if (r == 0) {
             // the slots' rotating counters, cleared once before the first compaction (the per-spec chains' memsets)
             int32_t *zero[GROUP_MAX_SLOTS] = {};
-            for (size_t k = 0; k < groups[g].size(); k++) zero[k] = b->lanes[groups[g][k] % (size_t)n_lanes].cnt;
-            launch_group_zero3((int)groups[g].size(), zero, sg);
+            for (size_t k = 0; k < slots.size(); k++) zero[k] = b->lanes[plan.lane_of[slots[k]]].cnt;
+            launch_group_zero3((int)slots.size(), zero, sg);
         }
-        gc = GroupCompactArgs{}; gc.n_series = (int)n;
-        gg = GroupGatherArgs{}; gg.t_max = (int)b->t_max; gg.elem_bytes = ybytes; gg.y = ybase; gg.ld = ld; gg_cols = 0;
-        for (size_t oi : groups[g]) enqueue_round(r, oi);
+        GroupCompactArgs gc{}; gc.n_series = (int)n;
+        GroupGatherArgs gg{}; gg.t_max = (int)b->t_max; gg.elem_bytes = ybytes; gg.y = ybase; gg.ld = ld;
+        int gg_cols = 0;
+        GroupRoundArgs ga{};
+        ga.n_slots = (int)slots.size();
+        for (int k = 0; k < ga.n_slots; k++) {
+            const size_t oi = slots[(size_t)k];
+            const RoundStep &s = plan.steps[oi][(size_t)r];
+            auto &lane = b->lanes[plan.lane_of[oi]];
+            if (s.source == SRC_POSITIVE) retire_nonpositive(oi, sg);
+            else if (s.source == SRC_COMPACTED) {
+                const int c = gc.n_slots++;
+                gc.prev[c] = (r == 1) ? nullptr : lane.map[(r - 1) & 1]; gc.n_prev[c] = (r == 1) ? nullptr : lane.cnt + ((r - 1) % 3); gc.done[c] = lane.st.done;
+                gc.next[c] = lane.map[r & 1]; gc.n_next[c] = lane.cnt + (r % 3); gc.n_clear[c] = lane.cnt + ((r + 1) % 3);
+                if (b->use_gather && lane.ybuf) {
+                    const int j = gg.n_slots++;
+                    gg.series_of[j] = lane.map[r & 1]; gg.n_active[j] = lane.cnt + (r % 3);
+                    gg.out[j] = lane.ybuf; gg.ld_out[j] = lane.ybuf_cols; gg.cap[j] = (int)lane.ybuf_cols;
+                    gg_cols = std::max(gg_cols, (int)std::min<size_t>(n, lane.ybuf_cols));
+                }
+            }
+            ga.spec[k] = specs[plan.order[oi]];
+            ga.k4[k] = s.k4 ? 1 : 0;
+            ga.start[k + 1] = ga.start[k] + s.workgroups;
+        }
         if (gc.n_slots > 0) launch_group_compact(gc, sg);
         if (gg.n_slots > 0) launch_group_gather(gg, gg_cols, sg);
-        GroupRoundArgs ga{};
-        ga.n_slots = (int)groups[g].size();
-        const size_t row = (size_t)r * n_slots + slot_of[groups[g][0]];
-        for (int k = 0; k < ga.n_slots; k++) {
-            const size_t oi = groups[g][(size_t)k];
-            ga.spec[k] = specs[order[oi]];
-            ga.k4[k] = slot_k4[(size_t)r * n_slots + slot_of[oi]];
-            ga.start[k + 1] = ga.start[k] + slot_blocks[(size_t)r * n_slots + slot_of[oi]];
-        }
-        group_fn[g](b->d_group_tab + row, ga, m, sg);
+        group_fn[plan.groups[g].cls](b->d_group_tab + (size_t)r * plan.n_slots + plan.slot_of[slots[0]], ga, m, sg);
         b->fit_launches++;
     };
-    // Head start of the damped multiplicative-trend chains (tune dm_head_rounds, round 5): their fits are the step's critical path -- alone
-    // on the chip one of them takes 185-280 ms of a 450 ms step (profiles/r05_step_anatomy.txt) -- and while all 25 chains start together
-    // their early, full rounds share every SIMD with the cheap specs' waves.  With a head start their first rounds are enqueued alone,
-    // the other specs' streams wait for an event recorded behind them, and fill the chip once those chains thin out.
-    int head = 0;
-    if (grouped && total_rounds > 0 && b->tun.dm_head_rounds > 0 && groups.size() > 1 && group_stream[0] == 0 &&
-        spec_trend_idx(specs[order[groups[0][0]]]) == 4) {
-        // (the same head start for the damped-M group: its first rounds alone, the other groups' streams wait behind them)
-        head = std::min(b->tun.dm_head_rounds, total_rounds);
-        for (int r = 0; r < head; r++) enqueue_group_round(r, 0);
+    // the head start of the damped multiplicative-trend chains: their first rounds, then the other streams wait behind them
+    if (plan.head_rounds > 0) {
+        for (int r = 0; r < plan.head_rounds; r++) {
+            if (plan.grouped) enqueue_group_round(r, 0);
+            else for (size_t oi = 0; oi < n_spec; oi++) if (plan.head[oi]) enqueue_round(r, oi);
+        }
         LAUNCHCHECK("ETS fit head rounds");
-        HIPCHECK(hipEventRecord(b->ev_join[0], b->aux[0]));
-        for (size_t g = 1; g < groups.size(); g++) HIPCHECK(hipStreamWaitEvent(b->aux[group_stream[g]], b->ev_join[0], 0));
-    } else if (!grouped && !tiny && !inline_stream && total_rounds > 0 && b->tun.dm_head_rounds > 0) {
-        std::vector<size_t> dm, rest;
-        for (size_t oi = 0; oi < order.size(); oi++)
-            if (!dead[oi]) (spec_trend_idx(specs[order[oi]]) == 4 ? dm : rest).push_back(oi);
-        if (!dm.empty() && !rest.empty()) {
-            head = std::min(b->tun.dm_head_rounds, total_rounds);
-            for (int r = 0; r < head; r++) for (size_t oi : dm) enqueue_round(r, oi);
-            LAUNCHCHECK("ETS fit head rounds");
-            for (size_t oi : dm) HIPCHECK(hipEventRecord(b->ev_join[stream_of[oi]], spec_stream(stream_of[oi])));
-            for (size_t oi : rest) for (size_t od : dm) HIPCHECK(hipStreamWaitEvent(spec_stream(stream_of[oi]), b->ev_join[stream_of[od]], 0));
+        if (plan.grouped) {
+            HIPCHECK(hipEventRecord(b->ev_join[0], b->aux[0]));
+            for (size_t g = 1; g < plan.groups.size(); g++) HIPCHECK(hipStreamWaitEvent(b->aux[plan.groups[g].stream], b->ev_join[0], 0));
+        } else {
+            for (size_t od = 0; od < n_spec; od++) if (plan.head[od]) HIPCHECK(hipEventRecord(b->ev_join[plan.stream_of[od]], spec_stream(od)));
+            for (size_t oi = 0; oi < n_spec; oi++) {
+                if (plan.dead[oi] || plan.head[oi]) continue;
+                for (size_t od = 0; od < n_spec; od++) if (plan.head[od]) HIPCHECK(hipStreamWaitEvent(spec_stream(oi), b->ev_join[plan.stream_of[od]], 0));
+            }
         }
     }
-    for (int r = 0; r < total_rounds; r++) {
-        if (grouped) {
-            for (size_t g = 0; g < groups.size(); g++) if (!(r < head && g == 0)) enqueue_group_round(r, g);
+    for (int r = 0; r < plan.total_rounds; r++) {
+        const bool ahead = r < plan.head_rounds;          // (the head slots' round is already enqueued)
+        if (plan.grouped) {
+            for (size_t g = 0; g < plan.groups.size(); g++) if (!(ahead && plan.head[plan.groups[g].slots[0]])) enqueue_group_round(r, g);
         } else
-            for (size_t oi = 0; oi < order.size(); oi++) {
-                if (r < head && spec_trend_idx(specs[order[oi]]) == 4) continue;      // (already enqueued)
-                enqueue_round(r, oi);
-            }
+            for (size_t oi = 0; oi < n_spec; oi++) if (!(ahead && plan.head[oi])) enqueue_round(r, oi);
         LAUNCHCHECK("ETS fit round");
     }
     // fixed parameters: the one streamed pass IS the workload -- the fit events bracket exactly that launch, on its stream
-    if (b->fixed_params && order.size() == 1) HIPCHECK(hipEventRecord(b->ev_fit0, spec_stream(stream_of[0])));
-    for (size_t oi = 0; oi < order.size(); oi++) if (!dead[oi]) fns[oi].final(args[oi], spec_stream(stream_of[oi]));
-    if (b->fixed_params && order.size() == 1) HIPCHECK(hipEventRecord(b->ev_fit1, spec_stream(stream_of[0])));
+    if (b->fixed_params && n_spec == 1) HIPCHECK(hipEventRecord(b->ev_fit0, spec_stream(0)));
+    for (size_t oi = 0; oi < n_spec; oi++) if (!plan.dead[oi]) fns[oi].final(args[oi], spec_stream(oi));
+    if (b->fixed_params && n_spec == 1) HIPCHECK(hipEventRecord(b->ev_fit1, spec_stream(0)));
     LAUNCHCHECK("ETS final pass");
-    if (grouped)
-        for (int q : group_stream) {
-            HIPCHECK(hipEventRecord(b->ev_join[q], b->aux[q]));
-            HIPCHECK(hipStreamWaitEvent(st, b->ev_join[q], 0));
-        }
-    else
-        for (int i = 0; i < n_fork; i++) {
-            HIPCHECK(hipEventRecord(b->ev_join[i], b->aux[i]));
-            HIPCHECK(hipStreamWaitEvent(st, b->ev_join[i], 0));
-        }
-    if (!(b->fixed_params && order.size() == 1)) HIPCHECK(hipEventRecord(b->ev_fit1, st));
+    for (int q : plan.fork_streams) {
+        HIPCHECK(hipEventRecord(b->ev_join[q], b->aux[q]));
+        HIPCHECK(hipStreamWaitEvent(st, b->ev_join[q], 0));
+    }
+    if (!(b->fixed_params && n_spec == 1)) HIPCHECK(hipEventRecord(b->ev_fit1, st));
     b->timed_fit = true;
-    b->n_problems += (uint64_t)specs.size() * n;
-    b->insp_args = args; b->insp_fns = fns; b->insp_stream = stream_of; b->insp_m = m;
-    b->insp_spec.resize(order.size());
-    for (size_t oi = 0; oi < order.size(); oi++) b->insp_spec[oi] = specs[order[oi]];
+    b->n_problems += (uint64_t)n_spec * n;
+    b->insp_args = args; b->insp_fns = fns; b->insp_stream = plan.stream_of; b->insp_m = m;
+    b->insp_spec.resize(n_spec);
+    for (size_t oi = 0; oi < n_spec; oi++) b->insp_spec[oi] = specs[plan.order[oi]];
     b->insp_ok = true;
 }
 

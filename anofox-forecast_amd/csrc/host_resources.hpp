@@ -49,7 +49,6 @@ struct Tunables {
     int spec2_below = 1024;     // tune spec2_below[_md]: one wave per problem, two iterations per pass, for the last problems
     int spec2_below_md = 2048;  //   (tools/spec2_sweep.sh: 0 / 256 / 1024 / 2048 / 4096 / 8192 -> 579 / 575 / 565 / 562 / 594 / 736 ms on the 30-spec M5 batch)
     int k4 = -1;                // tune k4: additive-class specs run one lane per problem with all four trial points of an iteration in ONE
-    int k4_top = 1, k4_top_below = 20480;   // tune k4_top, k4_top_below: see host_api.hip run_fit (0 = like every other spec)
                                 //   pass (ets_fit_kernel.hpp K4) wherever one or four LANES per problem would run.  -1 (default): when the run is
                                 //   memory bound and fills the chip that way -- the general-class specs see under half of the series AND the
                                 //   additive specs have >= 131,072 live problems together (two K4 waves per SIMD), or (round 5) the batch has
@@ -57,21 +56,23 @@ struct Tunables {
                                 //   Measured: intermittent M5 batch 86.3 -> 70.4 ms, 125k x 1,024 batch 181 -> 136-140 ms, 1M x 1,024 1,200 -> 853 ms;
                                 //   beside the 19 general-class specs of the strictly positive batch it is time-neutral (fewer passes, the step is
                                 //   bound by fp64 issue), and ONE additive spec on 30,490 series is slower with it (20.5 against 17.9 ms: 477 waves)
+    int k4_top = 1, k4_top_below = 20480;   // tune k4_top, k4_top_below: the k4_top most expensive K4 specs switch to four lanes per problem at k4_top_below
+                                //   live problems instead of spec_below (host_fit_schedule.hpp, the K4 steps of plan_fit_schedule; 0 = like every other spec)
     std::string wave_trace;     // tune wave_trace=<file>: developer instrument -- one record per wave of the ETS round kernels (FitArgs::wave_trace), written by anofox_hip_batch_lane_stats
     int compact = -1;           // tune compact: compact storage of the streamed block (host_api.hip compact_storage_begin): -1 auto, 0 never, 1 float at most, 2 narrowest exact type whatever the batch size
-    // batches that do NOT oversubscribe the chip one lane per problem (launch_fit_slots, round 6): speculation is dealt by expected work
+    // batches that do NOT oversubscribe the chip one lane per problem (host_fit_schedule.hpp, round 6): speculation is dealt by expected work
     int fill_policy = 1;        // tune fill_policy: 0 = rounds 1-5 (every spec four lanes per problem from the first round), 1 = by chip fill
     int fill_target = 150;      // tune fill_target: lanes the first round may occupy, in percent of the resident lanes (2 waves x 1,024 SIMDs x 64)
     int fill_late_div = 2;      // tune fill_late_div: a spec that started one lane per problem switches to four lanes at 1 / this of its problems
     int fill_s2_div = 16;       // tune fill_s2_div: ... and any spec to one wave per problem at 1 / this of its problems (at most spec2_below)
     int top_boost_n = 0, top_boost_pct = 200;   // tune top_boost_n / top_boost_pct: the N heaviest chains switch to four lanes / one wave per problem at pct % of the class thresholds
-    int prio_top = 0;           // tune prio_top: the N chains with the most expected work run their waves at raised issue priority (3, 2, 1, 1, ...: launch_fit_slots)
-    int group_launch = 1;       // tune group_launch: 1 = the specs of a class run each round in ONE launch (at most 4 streams: launch_fit_slots);
+    int prio_top = 0;           // tune prio_top: the N chains with the most expected work run their waves at raised issue priority (3, 2, 1, 1, ...: host_fit_schedule.hpp)
+    int group_launch = 1;       // tune group_launch: 1 = the specs of a class run each round in ONE launch (at most 4 streams: host_fit_schedule.hpp);
                                 //   0 = one stream and one launch chain per spec (the earlier schedule, for A/B runs and tests)
     int group_split = 1;        // tune group_split: the class dealt by expected work into two groups (four streams in all): 1 the damped
                                 //   multiplicative-trend specs (the step's critical path), 2 the other general-class specs, 0 none.  M5 batch,
                                 //   4 queues: 377 / 412 / 418 ms (profiles/group_schedule_ab.txt)
-    int dm_head_rounds = 0;     // tune dm_head_rounds: rounds the damped multiplicative-trend chains run before the other specs' streams start (launch_fit_slots)
+    int dm_head_rounds = 0;     // tune dm_head_rounds: rounds the damped multiplicative-trend chains run before the other specs' streams start (host_fit_schedule.hpp)
     bool merge_periods = true;  // tune merge_periods: auto-detected periods run as merged batches (0: one batch per period)
     int part_threads = 16;      // tune part_threads: host threads that run the small per-period parts of an auto-detected batch side by side
     int pack_threads = 0;       // ANOFOX_HIP_PACK_THREADS: host threads of the packer (0: all, at most 32)
@@ -492,7 +493,7 @@ void stream_set_destroy(StreamSet *s)
     for (auto &e : s->ev_join) if (e) (void)hipEventDestroy(e);
     delete s;
 }
-// The group schedule (launch_fit_slots, the default) runs a fit on at most four streams, so it needs no more than the HIP runtime's
+// The group schedule (host_fit_schedule.hpp, the default) runs a fit on at most four streams, so it needs no more than the HIP runtime's
 // default of 4 hardware queues (GPU_MAX_HW_QUEUES).  The one-stream-per-spec schedule (tune group_launch=0, A/B runs only) puts up to 25
 // streams side by side, and streams that share a queue serialise: for it, the first stream set says ONCE on stderr when the variable
 // is missing or below 16 -- only when the host has asked for the library's diagnostics (ANOFOX_HIP_TIMING).  The library does not touch
@@ -516,7 +517,7 @@ StreamSet *stream_set_take()
     HIPCHECK(hipGetDevice(&dev));
     warn_hw_queues_once();
     StreamPool &p = stream_pool();
-    // The first streams of a device's FIRST set carry the most expensive specs of a fit (launch_fit_slots: the damped multiplicative-
+    // The first streams of a device's FIRST set carry the most expensive specs of a fit (host_fit_schedule.hpp: the damped multiplicative-
     // trend groups, or the specs ordered by work) and get the highest priority: the command processor then dispatches their workgroups
     // first whenever slots free up, the cheap specs fill in behind.  The group schedule uses two of them, whatever GPU_MAX_HW_QUEUES
     // says.  For the one-stream-per-spec schedule, longest chains first:

@@ -246,6 +246,22 @@ def test_part_plan_and_result_delivery_under_sanitizers():
         assert r.returncode == 0 and r.stdout.startswith("parts_san: ok"), (r.stdout, r.stderr[-3000:])
 
 
+def test_fit_schedule_under_sanitizers():
+    """csrc/host_fit_schedule.hpp -- the schedule of an ETS / AutoETS fit, decided from plain values before anything is enqueued:
+    order, streams, retired specs, K4, the fill policy, the group partition, the head start, and the driver, budgets, thresholds and
+    workgroups of every (round, spec) -- compiled on its own (no HIP, not even a stand-in) and run under ASan + UBSan
+    (tests/c_abi/fit_schedule_san.cpp): over seeded inputs from 1 to 125,000 series, every spec pool, period class and schedule knob
+    the GPU tests set, the plan equals a restatement of the rules, and NO step launches more workgroups than the ring and simplex
+    scratches are sized for (the recorded GPU memory fault of a 24-series batch with spec2_below = 20 was such a step).  The GPU
+    suite reaches these rules only through forecasts."""
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "fit_schedule_san")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               os.path.join(ROOT, "tests", "c_abi", "fit_schedule_san.cpp"), "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and r.stdout.startswith("fit_schedule_san: ok"), (r.stdout, r.stderr[-3000:])
+
+
 def test_duckdb_macro_binding_parses():
     """binding/ts_macros_hip.cpp (the macro that sends ts_forecast_by to the batch route) needs nothing but DuckDB's API:
     `g++ -fsyntax-only` against the declaration-only stand-in tests/c_abi/duckdb_stub/ (test infrastructure, written from DuckDB's

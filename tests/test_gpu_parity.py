@@ -486,6 +486,18 @@ def test_schedule_variants_are_bit_identical(env, monkeypatch, seq_rounds, gathe
     _compare(api, O, lib, series, "ETS", 12, ets_model="MAdM", seasonal_period=7)
 
 
+@pytest.mark.parametrize("tune", ["dm_head_rounds=2", "dm_head_rounds=2;group_launch=0", "top_boost_n=2", "prio_top=3"])
+def test_head_start_boost_and_priority_are_bit_identical(env, monkeypatch, tune):
+    """The head start of the damped multiplicative-trend chains (grouped and one chain per spec), the earlier thresholds of the
+    heaviest chains and the raised wave priority move launches, thresholds and issue order, never an iterate: the same 130 ragged
+    series as test_schedule_variants_are_bit_identical reproduce the oracle under each of them."""
+    api, O, lib, synth = env
+    monkeypatch.setenv("ANOFOX_HIP_TUNE", tune)
+    Y = synth.gen_series(synth.SEED_M5, 5000, 130, 160, 7, positive=True)
+    series = [Y[s, : 160 - (s % 5) * 9] for s in range(130)]          # ragged lengths
+    _compare(api, O, lib, series, "AutoETS", 12, seasonal_period=7)
+
+
 def _device_run(lib, Y, lens, model, h, tune, monkeypatch, **kw):
     """One device-resident run (block 3 of the header) under an ANOFOX_HIP_TUNE setting: forecasts, model codes, status, run statistics."""
     import torch

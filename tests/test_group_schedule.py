@@ -1,4 +1,4 @@
-"""Group rounds (launch_fit_slots, ANOFOX_HIP_TUNE group_launch): the specs of a class run each round in one launch of their class's
+"""Group rounds (host_fit_schedule.hpp decides them, launch_fit_slots enqueues them; ANOFOX_HIP_TUNE group_launch): the specs of a class run each round in one launch of their class's
 group kernel, on at most four streams.  Each problem's Nelder-Mead trajectory does not depend on which launch or lane runs it, so the
 group schedule and the one-stream-per-spec schedule (group_launch=0) give the same bits, and so does every GPU_MAX_HW_QUEUES setting."""
 import os
