@@ -3798,6 +3798,123 @@ def ts_validate_separator(ids, separator="|"):
     return {"separator": sep, "is_valid": not conflicts, "n_conflicts": len(conflicts), "conflicting_values": conflicts, "message": message}
 
 
+def reconcile_batch(column_of, forecast, method="ols", weights=None):
+    """anofox_hip_reconcile_batch: column_of int32 [n_groupings, n_series] as for hierarchy_batch; forecast fp64 series-major [n_out, h],
+    one row per output column of that plan; method in lib.RECONCILE_METHODS; weights fp64 [n_out] for "wls_var".  The bottom column of a
+    series is the column whose only member it is; every other column with members is reconciled against the bottoms and comes back
+    as the serial sum of its members' reconciled forecasts, in plan order from +0.0 (DESIGN.md section 3 "Reconciliation").
+
+    Returns ({"y": fp64 [n_out, h]; "row_status": int32 [h] -- 0 done, 2 a base forecast of that step is not finite and its columns are
+    NaN}, error)."""
+    L = _lib.load()
+    code = _lib.reconcile_method(method)
+    co = np.ascontiguousarray(column_of, dtype=np.int32)
+    co = co.reshape(1, -1) if co.ndim == 1 else co
+    G, n = co.shape
+    f = np.ascontiguousarray(forecast, dtype=np.float64)
+    f = f.reshape(len(f), -1) if f.ndim != 2 else f
+    n_out, h = f.shape
+    planned = int(co.max()) + 1 if co.size and co.max() >= 0 else 0
+    if n_out != planned:
+        raise ValueError(f"reconcile_batch: the forecast block has {n_out} rows, the plan has {planned} output columns")
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and len(w) != n_out:
+        raise ValueError(f"reconcile_batch: {len(w)} weights for {n_out} output columns")
+    out = {"y": np.full((n_out, h), np.nan), "row_status": np.zeros(h, dtype=np.int32)}
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_reconcile_batch(co.ctypes.data, G, n, f.ctypes.data, h, code, None if w is None else w.ctypes.data, out["y"].ctypes.data,
+                                      out["row_status"].ctypes.data, C.byref(err))
+    return out, {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+
+
+def _reconcile_level(parts, keyword):
+    """The level of a key of BuildUniqueId: the number of leading parts that are kept -- the keyword stands from there on."""
+    level = len(parts)
+    while level > 0 and parts[level - 1] == keyword:
+        level -= 1
+    return level
+
+
+def _reconcile_columns(unique_ids, sep, keyword):
+    """The keys of ts_aggregate_hierarchy's output -> (names sorted in byte order, leaves, column_of [N + 1, n_leaf]).  A key with the
+    keyword from part L on holds every leaf whose first L parts match; the leaves, numbered in byte order, are the series."""
+    names = sorted(set(unique_ids), key=lambda u: u.encode("utf-8"))
+    split = {u: (u.split(sep) if sep else [u]) for u in names}
+    widths = sorted({len(p) for p in split.values()})
+    if len(widths) > 1:
+        odd = [u for u in names if len(split[u]) != widths[-1]]
+        raise InvalidInputException(f"ts_reconcile_hierarchy: the ids do not have the same number of parts under separator {sep!r}: {odd[:5]}")
+    N = widths[0] if widths else 0
+    leaves = [u for u in names if _reconcile_level(split[u], keyword) == N]
+    column = {u: c for c, u in enumerate(names)}
+    column_of = np.full((N + 1, len(leaves)), -1, dtype=np.int32)
+    for s, u in enumerate(leaves):
+        for level in range(N + 1):
+            column_of[level, s] = column.get(_hierarchy_unique_id(split[u], level, sep, keyword), -1)
+    held = set(column_of.reshape(-1).tolist())
+    orphans = [u for u in names if column[u] not in held]
+    if orphans:
+        raise InvalidInputException(f"ts_reconcile_hierarchy: no leaf lies beneath the aggregate ids {orphans[:5]}")
+    return names, leaves, column_of
+
+
+def ts_reconcile_hierarchy(unique_id, date, forecast, params=None, date_name="date", forecast_name="forecast", info=None):
+    """Makes the forecasts of a key hierarchy coherent: the rows that ts_aggregate_hierarchy -> ts_forecast_by produce, one forecast
+    per (unique_id, date).  The reference has no such function; the name and the contract are this package's.
+
+    params: method ("bottom_up", "ols" -- the default --, "wls_struct", "wls_var"), separator and aggregate_keyword as for
+    ts_aggregate_hierarchy, weights (wls_var: a mapping unique_id -> positive weight, e.g. the error variance of that id's model).
+    Membership is read from the keys: an id with the keyword from part L on holds every leaf whose first L parts match.  The leaves,
+    in byte order of their ids, are the series; every aggregate comes back as the serial sum of its leaves' reconciled forecasts in
+    that order.  Returns unique_id, <date_name>, <forecast_name>, sorted by (unique_id bytes, date).  InvalidInputException, naming the
+    ids: a leaf with a NULL forecast, an aggregate without a leaf beneath it, ids whose dates differ."""
+    p = params or {}
+    sep, keyword = _hierarchy_params(p)
+    method = str(p["method"]) if p.get("method") is not None else "ols"
+    if method not in _lib.RECONCILE_METHODS:
+        raise InvalidInputException(f"ts_reconcile_hierarchy: unknown method {method!r}; one of {sorted(_lib.RECONCILE_METHODS)}")
+    dates = np.asarray(date)
+    kind = _date_kind(dates)
+    us = _to_micros(dates, kind)
+    uids = _hierarchy_strings(unique_id, len(dates))
+    val = np.ma.filled(np.ma.asarray(forecast, dtype=object), None) if np.ma.isMaskedArray(forecast) else np.asarray(forecast, dtype=object)
+    if len(val) != len(dates):
+        raise InvalidInputException("every column of the input table must have the same number of rows")
+    names, leaves, column_of = _reconcile_columns(uids, sep, keyword)
+    column = {u: c for c, u in enumerate(names)}
+    by_id = {u: {} for u in names}
+    for u, d, v in zip(uids, us, val):
+        by_id[u][int(d)] = v
+    missing = [u for u in leaves if any(v is None for v in by_id[u].values())]
+    if missing:
+        raise InvalidInputException(f"ts_reconcile_hierarchy: the leaf ids {missing[:5]} have no forecast at some date")
+    grid = sorted(by_id[names[0]]) if names else []
+    differ = [u for u in names if sorted(by_id[u]) != grid]
+    if differ:
+        raise InvalidInputException(f"ts_reconcile_hierarchy: the dates of the ids {differ[:5]} differ from those of {names[0]!r}")
+    block = np.array([[np.nan if by_id[u][d] is None else float(by_id[u][d]) for d in grid] for u in names], dtype=np.float64).reshape(len(names), len(grid))
+    weights = None
+    if method == "wls_var":
+        given = p.get("weights") or {}
+        lacking = [u for u in names if u not in given]
+        if lacking:
+            raise InvalidInputException(f"ts_reconcile_hierarchy: wls_var needs a weight for the ids {lacking[:5]}")
+        weights = np.array([float(given[u]) for u in names])
+    if len(names) and len(grid):
+        res, err = reconcile_batch(column_of, block, method, weights)
+        if not err["ok"]:
+            if err["code"] == 2:
+                raise InvalidInputException(f"ts_reconcile_hierarchy: {err['message']}")
+            raise RuntimeError(f"anofox_hip_reconcile_batch failed: [{err['code']}] {err['message']}")
+        block = res["y"]
+        if info is not None:
+            info["row_status"] = res["row_status"]
+            info["column_of"] = column_of
+    return {"unique_id": np.array([u for u in names for _ in grid], dtype=object),
+            date_name: _from_micros(np.array([d for _ in names for d in grid], dtype=np.int64), kind, dates.dtype),
+            forecast_name: np.array(block, dtype=np.float64).reshape(-1)}
+
+
 anofox_fcst_ts_aggregate_hierarchy = ts_aggregate_hierarchy
 anofox_fcst_ts_combine_keys = ts_combine_keys
 anofox_fcst_ts_split_keys = ts_split_keys

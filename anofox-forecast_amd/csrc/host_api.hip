@@ -40,6 +40,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_resources.hpp"     // HipFail / HIPCHECK, the tunables, DeviceGuard, the device / pinned / stream caches, the device list
 #include "host_scratch.hpp"       // Scratch (a call's device blocks), the shape and packing of a batch of series, the _device entry's checks and launch
 #include "host_parts.hpp"         // how an auto-detected batch is cut into device batches (PartPlan), and how a batch's results reach the caller's arrays
+#include "host_reconcile_plan.hpp" // the host-only planner of the reconciliation entries (bottom columns, aggregates, the transposed plan)
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
 struct Plan {
@@ -6577,6 +6578,225 @@ bool anofox_hip_hierarchy_batch(const double *const *values, const uint64_t *con
     std::memcpy(out_lengths, lo, n_out * sizeof(int32_t));
     if (out_present) std::memcpy(out_present, back.data() + cells * 8 + ld_out * 8 + ld_out * 4, cells);
     return true;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Reconciliation of the forecasts of a hierarchy (DESIGN.md section 3 "Reconciliation"; reconcile.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// what the two device entries share: the sizes, then the plan pointers where there is something to read through them
+bool reconcile_plan_args(const int32_t *col_offsets, const int32_t *members, size_t n_out, size_t nnz, size_t n_series, const int32_t *bottom_col,
+                         const int32_t *agg_cols, size_t n_agg, const int32_t *leaf_offsets, const int32_t *leaf_aggs, size_t n_leaf,
+                         const double *weights, ReconcilePlan *p, AnofoxError *err)
+{
+    if (n_out > (size_t)INT32_MAX || nnz > (size_t)INT32_MAX || n_series > (size_t)INT32_MAX || n_leaf > (size_t)INT32_MAX) {
+        set_error(err, INVALID_INPUT, "Invalid input: n_out, nnz, n_series and n_leaf are limited to 2^31 - 1");
+        return false;
+    }
+    if (n_agg > (size_t)ANOFOX_HIP_RECONCILE_MAX_AGG) {
+        set_error(err, INVALID_INPUT, "Invalid input: n_agg " + std::to_string(n_agg) + " exceeds the limit of " +
+                  std::to_string(ANOFOX_HIP_RECONCILE_MAX_AGG) + " aggregate columns");
+        return false;
+    }
+    if ((n_out > 0 && !col_offsets) || (nnz > 0 && !members) || (n_series > 0 && (!bottom_col || !leaf_offsets)) || (n_agg > 0 && !agg_cols) ||
+        (n_leaf > 0 && !leaf_aggs)) {
+        set_error(err, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    p->col_offsets = col_offsets; p->members = members; p->n_out = (int)n_out; p->nnz = (int)nnz; p->n_series = (int)n_series;
+    p->bottom_col = bottom_col; p->agg_cols = agg_cols; p->n_agg = (int)n_agg;
+    p->leaf_offsets = leaf_offsets; p->leaf_aggs = leaf_aggs; p->n_leaf = (int)n_leaf; p->weights = weights;
+    return true;
+}
+
+bool reconcile_method_ok(int32_t method, bool allow_bottom_up, AnofoxError *err)
+{
+    if (method < (allow_bottom_up ? RECONCILE_BOTTOM_UP : RECONCILE_OLS) || method > RECONCILE_WLS_VAR) {
+        set_error(err, INVALID_INPUT, allow_bottom_up ? "Invalid input: method must be 0 (bottom_up), 1 (ols), 2 (wls_struct) or 3 (wls_var)"
+                                                      : "Invalid input: a factor exists for method 1 (ols), 2 (wls_struct) or 3 (wls_var) only");
+        return false;
+    }
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+static_assert(ANOFOX_RECONCILE_BOTTOM_UP == RECONCILE_BOTTOM_UP && ANOFOX_RECONCILE_WLS_VAR == RECONCILE_WLS_VAR, "reconciliation method codes");
+
+bool anofox_hip_reconcile_plan(const int32_t *col_offsets, const int32_t *members, size_t n_out, size_t n_series, size_t *n_agg, size_t *n_leaf,
+                               int32_t *bottom_col, int32_t *agg_cols, int32_t *leaf_offsets, int32_t *leaf_aggs, double *struct_weights,
+                               AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    const ReconcilePlanResult r = reconcile_plan_host(col_offsets, members, n_out, n_series, (size_t)ANOFOX_HIP_RECONCILE_MAX_AGG, n_agg, n_leaf,
+                                                      bottom_col, agg_cols, leaf_offsets, leaf_aggs, struct_weights, &message);
+    if (r == RECONCILE_PLAN_NULL) set_error(out_error, NULL_POINTER, "Null pointer argument");
+    else if (r == RECONCILE_PLAN_INVALID) set_error(out_error, INVALID_INPUT, message);
+    return r == RECONCILE_PLAN_OK;
+}
+
+bool anofox_hip_reconcile_factor_device(const int32_t *col_offsets, const int32_t *members, size_t n_out, size_t nnz, size_t n_series,
+                                        const int32_t *bottom_col, const int32_t *agg_cols, size_t n_agg, const int32_t *leaf_offsets,
+                                        const int32_t *leaf_aggs, size_t n_leaf, int32_t method, const double *weights, double *factor,
+                                        size_t ld_a, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!reconcile_method_ok(method, false, out_error)) return false;
+    ReconcileFactorArgs a{};
+    if (!reconcile_plan_args(col_offsets, members, n_out, nnz, n_series, bottom_col, agg_cols, n_agg, leaf_offsets, leaf_aggs, n_leaf,
+                             method == RECONCILE_OLS ? nullptr : weights, &a.p, out_error))
+        return false;
+    if (method != RECONCILE_OLS && n_out > 0 && !weights) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_agg > 0 && !factor) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (ld_a < n_agg) { set_error(out_error, INVALID_INPUT, "Invalid input: ld_a is smaller than n_agg"); return false; }
+    if (!device_ready(out_error)) return false;
+    a.L = factor; a.ld_a = ld_a;
+    a.trailing = RECONCILE_TRAILING_MFMA;                          // the faster tile on the 12,350-row system (profiles/reconcile_m5.txt)
+    {                                                              // developer knob of tools/time_reconcile.py: 0 plain FMA tile, 1 MFMA
+        const std::map<std::string, std::string> kv = Tunables::tune_map();
+        auto it = kv.find("reconcile_trailing");
+        if (it != kv.end()) a.trailing = std::atoi(it->second.c_str()) == 0 ? RECONCILE_TRAILING_FMA : RECONCILE_TRAILING_MFMA;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    int32_t info[2] = {RECONCILE_NONE, RECONCILE_NONE};
+    const bool ok = launch_and_wait("reconcile factor", st, out_error, [&] {
+        a.info = scratch.get<int32_t>(2);
+        launch_reconcile_factor(a, st);
+        HIPCHECK(hipMemcpyAsync(info, a.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    });
+    if (!ok) return false;
+    scratch.settled();
+    if (info[0] != RECONCILE_NONE) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the weight of column " + std::to_string(info[0]) + " is not finite and positive");
+        return false;
+    }
+    if (info[1] != RECONCILE_NONE) {
+        set_error(out_error, COMPUTATION_ERROR, "Computation error: the pivot of row " + std::to_string(info[1]) + " of the reconciliation system is not positive");
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_reconcile_apply_device(const double *base, size_t stride_s, size_t stride_t, size_t n_rows, const int32_t *col_offsets,
+                                       const int32_t *members, size_t n_out, size_t nnz, size_t n_series, const int32_t *bottom_col,
+                                       const int32_t *agg_cols, size_t n_agg, const int32_t *leaf_offsets, const int32_t *leaf_aggs, size_t n_leaf,
+                                       int32_t method, const double *weights, const double *factor, size_t ld_a, double *work, double *out,
+                                       int32_t *row_status, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!reconcile_method_ok(method, true, out_error)) return false;
+    ReconcileApplyArgs a{};
+    const bool solve = method != RECONCILE_BOTTOM_UP && n_agg > 0;
+    if (!reconcile_plan_args(col_offsets, members, n_out, nnz, n_series, bottom_col, agg_cols, n_agg, leaf_offsets, leaf_aggs, n_leaf,
+                             (method == RECONCILE_OLS || method == RECONCILE_BOTTOM_UP) ? nullptr : weights, &a.p, out_error))
+        return false;
+    if (n_rows > (size_t)INT32_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: n_rows is limited to 2^31 - 1"); return false; }
+    if (n_rows > 0 && (!row_status || (n_out > 0 && (!base || !out)))) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (solve && !factor) { set_error(out_error, INVALID_INPUT, "Invalid input: methods 1 to 3 need the factor of anofox_hip_reconcile_factor_device"); return false; }
+    if (solve && n_rows > 0 && !work) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (solve && method != RECONCILE_OLS && !weights) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (solve && ld_a < n_agg) { set_error(out_error, INVALID_INPUT, "Invalid input: ld_a is smaller than n_agg"); return false; }
+    if (n_rows == 0) return true;
+    if (!device_ready(out_error)) return false;
+    a.method = method; a.base = base; a.out = out; a.stride_s = stride_s; a.stride_t = stride_t; a.n_rows = n_rows;
+    a.L = factor; a.ld_a = ld_a; a.work = work; a.row_status = row_status;
+    try {
+        (void)hipGetLastError();
+        launch_reconcile_apply(a, (hipStream_t)stream);
+        LAUNCHCHECK("reconcile apply");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_reconcile_batch(const int32_t *column_of, size_t n_groupings, size_t n_series, const double *forecast, size_t h, int32_t method,
+                                const double *weights, double *out, int32_t *out_row_status, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!reconcile_method_ok(method, true, out_error)) return false;
+    size_t n_out = 0, nnz = 0, n_agg = 0, n_leaf = 0;
+    if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, nullptr, nullptr, out_error)) return false;
+    std::vector<int32_t> offs(n_out + 1), memb(std::max<size_t>(nnz, 1));
+    if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, offs.data(), memb.data(), out_error)) return false;
+    if (!anofox_hip_reconcile_plan(offs.data(), memb.data(), n_out, n_series, &n_agg, &n_leaf, nullptr, nullptr, nullptr, nullptr, nullptr, out_error))
+        return false;
+    std::vector<int32_t> bottom(std::max<size_t>(n_series, 1)), aggs(std::max<size_t>(n_agg, 1)), loffs(n_series + 1), laggs(std::max<size_t>(n_leaf, 1));
+    std::vector<double> w(std::max<size_t>(n_out, 1), 1.0);
+    if (!anofox_hip_reconcile_plan(offs.data(), memb.data(), n_out, n_series, &n_agg, &n_leaf, bottom.data(), aggs.data(), loffs.data(), laggs.data(),
+                                   w.data(), out_error))
+        return false;
+    if (n_out > 0 && h > 0 && (!forecast || !out || !out_row_status)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (method == RECONCILE_WLS_VAR) {
+        if (n_out > 0 && !weights) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        for (size_t c = 0; c < n_out; c++) w[c] = weights[c];
+    }
+    if (n_out == 0 || h == 0) return true;
+    if (!device_ready(out_error)) return false;
+    const bool solve = method != RECONCILE_BOTTOM_UP && n_agg > 0;
+    // ONE arena of int32 plan arrays: offsets, members, bottom_col, agg_cols, leaf_offsets, leaf_aggs
+    const size_t n_int = (n_out + 1) + nnz + n_series + n_agg + (n_series + 1) + n_leaf, cells = n_out * h;
+    const size_t bytes = n_int * 4 + (2 * cells + n_out + (solve ? n_agg * n_agg + h * n_agg : 0)) * 8 + h * 4;
+    Scratch scratch;
+    bool ok = true;
+    try {
+        int32_t *d_int = nullptr, *d_status = nullptr;
+        double *d_base = nullptr, *d_out = nullptr, *d_w = nullptr, *d_L = nullptr, *d_work = nullptr;
+        try {
+            d_int = scratch.get<int32_t>(n_int);
+            d_base = scratch.get<double>(cells);
+            d_out = scratch.get<double>(cells);
+            d_w = scratch.get<double>(n_out);
+            d_status = scratch.get<int32_t>(h);
+            if (solve) { d_L = scratch.get<double>(n_agg * n_agg); d_work = scratch.get<double>(h * n_agg); }
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the plan, two blocks of " + std::to_string(n_out) + " x " + std::to_string(h) +
+                      " values and the factor of " + std::to_string(n_agg) + " x " + std::to_string(n_agg) + " values need " + std::to_string(bytes) +
+                      " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            std::vector<int32_t> plan;
+            plan.reserve(n_int);
+            plan.insert(plan.end(), offs.begin(), offs.end());
+            plan.insert(plan.end(), memb.begin(), memb.begin() + nnz);
+            plan.insert(plan.end(), bottom.begin(), bottom.begin() + n_series);
+            plan.insert(plan.end(), aggs.begin(), aggs.begin() + n_agg);
+            plan.insert(plan.end(), loffs.begin(), loffs.end());
+            plan.insert(plan.end(), laggs.begin(), laggs.begin() + n_leaf);
+            const int32_t *d_offs = d_int, *d_memb = d_offs + n_out + 1, *d_bottom = d_memb + nnz, *d_aggs = d_bottom + n_series,
+                          *d_loffs = d_aggs + n_agg, *d_laggs = d_loffs + n_series + 1;
+            HIPCHECK(hipMemcpy(d_int, plan.data(), n_int * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_base, forecast, cells * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_w, w.data(), n_out * sizeof(double), hipMemcpyHostToDevice));
+            if (solve)
+                ok = anofox_hip_reconcile_factor_device(d_offs, d_memb, n_out, nnz, n_series, d_bottom, d_aggs, n_agg, d_loffs, d_laggs, n_leaf, method,
+                                                        d_w, d_L, n_agg, nullptr, out_error);
+            if (ok)
+                ok = anofox_hip_reconcile_apply_device(d_base, h, 1, h, d_offs, d_memb, n_out, nnz, n_series, d_bottom, d_aggs, n_agg, d_loffs, d_laggs,
+                                                       n_leaf, method, d_w, d_L, n_agg, d_work, d_out, d_status, nullptr, out_error);
+            if (ok) {
+                HIPCHECK(hipMemcpy(out, d_out, cells * sizeof(double), hipMemcpyDeviceToHost));          // waits for the null stream
+                HIPCHECK(hipMemcpy(out_row_status, d_status, h * sizeof(int32_t), hipMemcpyDeviceToHost));
+            } else {
+                HIPCHECK(hipDeviceSynchronize());
+            }
+        }
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return ok;
 }
 
 } // extern "C"

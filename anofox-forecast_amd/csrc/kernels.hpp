@@ -491,6 +491,34 @@ struct HierarchyArgs {
 };
 void launch_hierarchy(const HierarchyArgs &, hipStream_t);     // spans, then (y_out != null) the two routes
 
+// Reconciliation of the forecasts of a hierarchy (DESIGN.md section 3 "Reconciliation"; reconcile.hip)
+enum { RECONCILE_BOTTOM_UP = 0, RECONCILE_OLS = 1, RECONCILE_WLS_STRUCT = 2, RECONCILE_WLS_VAR = 3 };
+enum { RECONCILE_TRAILING_FMA = 0, RECONCILE_TRAILING_MFMA = 1 };
+constexpr int32_t RECONCILE_NONE = INT32_MAX;          // ReconcileFactorArgs::info: nothing to report
+struct ReconcilePlan {                                 // everything in device memory
+    const int32_t *col_offsets, *members; int n_out, nnz, n_series;      // the aggregation plan
+    const int32_t *bottom_col;                         // [n_series] the column whose member list is exactly [s]
+    const int32_t *agg_cols; int n_agg;                // [n_agg] ascending: the columns with members that are no bottom column
+    const int32_t *leaf_offsets, *leaf_aggs; int n_leaf;      // the transposed plan: per series the aggregates (indices into agg_cols) that hold it
+    const double *weights;                             // [n_out], null: all 1
+};
+struct ReconcileFactorArgs {
+    ReconcilePlan p;
+    double *L; size_t ld_a;                            // [n_agg x ld_a]: M, then its Cholesky factor, in the lower triangle; the rest is not touched
+    int32_t *info;                                     // [2]: the smallest column with a bad weight, the first row with a pivot that is not positive
+    int trailing;                                      // RECONCILE_TRAILING_*
+};
+struct ReconcileApplyArgs {
+    ReconcilePlan p;
+    int method;
+    const double *base; double *out; size_t stride_s, stride_t, n_rows;  // element (column c, row t) at c * stride_s + t * stride_t
+    const double *L; size_t ld_a;
+    double *work;                                      // [n_rows x n_agg]: the residuals, then lambda
+    int32_t *row_status;                               // [n_rows]
+};
+void launch_reconcile_factor(const ReconcileFactorArgs &, hipStream_t);
+void launch_reconcile_apply(const ReconcileApplyArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

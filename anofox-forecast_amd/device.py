@@ -490,6 +490,112 @@ def aggregate_block(y: torch.Tensor, lengths: torch.Tensor, column_of, *, first:
     return {"y": yo, "present": po, "lengths": len_out, "first": first_out, "t_out": t_out, "n_out": n_out}
 
 
+_RECONCILE_PLAN_KEYS = ("col_offsets", "members", "bottom_col", "agg_cols", "leaf_offsets", "leaf_aggs")
+
+
+def reconcile_plan_device(column_of, n_series: int | None = None, device=None) -> dict:
+    """The reconciliation plan on the device.  column_of: an int array or tensor [n_groupings, n_series] as for aggregate_block, or an
+    aggregation plan {"col_offsets", "members"} (host arrays or tensors) together with n_series.  The planning itself is
+    anofox_hip_hierarchy_plan / anofox_hip_reconcile_plan on the host (a plan is made once and kept); the six int32 arrays and
+    "struct_weights" (fp64 [n_out]) are uploaded.  A plan the planner refuses raises ValueError with its message."""
+    import numpy as np
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if isinstance(column_of, dict):
+        assert n_series is not None, "an aggregation plan needs n_series"
+        n_out = int(column_of.get("n_out", len(column_of["col_offsets"]) - 1))
+        offs = host(column_of["col_offsets"])[:n_out + 1]
+        memb = host(column_of["members"])[:int(offs[n_out]) if n_out else 0]
+        if device is None and isinstance(column_of["col_offsets"], torch.Tensor) and column_of["col_offsets"].is_cuda:
+            device = column_of["col_offsets"].device
+    else:
+        if device is None and isinstance(column_of, torch.Tensor) and column_of.is_cuda:
+            device = column_of.device
+        co = host(column_of)
+        co = co.reshape(-1, co.shape[-1] if n_series is None else int(n_series))
+        n_series = co.shape[1]
+        _n_out, offs, memb = _lib.hierarchy_plan(co)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    p = _lib.reconcile_plan(offs, memb, int(n_series))
+    plan = {k: p[k] for k in ("n_out", "nnz", "n_series", "n_agg", "n_leaf")}
+    for k in _RECONCILE_PLAN_KEYS:
+        plan[k] = torch.from_numpy(np.ascontiguousarray(p[k], dtype=np.int32)).to(dev)
+    plan["struct_weights"] = torch.from_numpy(np.ascontiguousarray(p["struct_weights"])).to(dev)
+    return plan
+
+
+def reconcile_block(forecast: torch.Tensor, column_of, method: str | int = "ols", weights: torch.Tensor | None = None,
+                    series_major: bool = True, factor: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                    stream: torch.cuda.Stream | None = None, *, n_series: int | None = None) -> dict:
+    """anofox_hip_reconcile_factor_device + anofox_hip_reconcile_apply_device on torch tensors: the forecasts of the columns of an
+    aggregation plan made coherent where they lie (DESIGN.md section 3 "Reconciliation").
+
+    forecast fp64, contiguous, on one HIP device: series_major [>= n_out, h] -- the `yhat` of DeviceBatch results as it lies -- or
+    time-major [n_rows, ld >= n_out].  column_of: an int array / tensor [n_groupings, n_series], or a plan of reconcile_plan_device
+    (the "plan" this function returns: make it once).  method in lib.RECONCILE_METHODS; weights fp64 [>= n_out] for "wls_var".
+    factor: the "factor" an earlier call with the same plan, method and weights returned -- one factor serves every block.  out: a
+    tensor of forecast's shape (not forecast itself); only columns < n_out are written.
+
+    Returns {"y", "row_status" int32 [n_rows] (0 done, 2 a base forecast that is not finite: that row's columns are NaN), "factor"
+    (None for "bottom_up" or a plan without aggregates), "plan"}.  The factor call waits for the device; the apply only enqueues."""
+    L = _lib.load()
+    code = _lib.reconcile_method(method)
+    assert forecast.dtype == torch.float64 and forecast.is_cuda and forecast.is_contiguous() and forecast.dim() == 2
+    dev = forecast.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    plan = column_of if isinstance(column_of, dict) and "bottom_col" in column_of else reconcile_plan_device(column_of, n_series, dev)
+    n_out, n_agg = int(plan["n_out"]), int(plan["n_agg"])
+    for k in _RECONCILE_PLAN_KEYS:
+        assert plan[k].dtype == torch.int32 and plan[k].is_cuda and plan[k].is_contiguous(), k
+    if series_major:
+        n_rows, stride_s, stride_t = int(forecast.shape[1]), int(forecast.shape[1]), 1
+        assert int(forecast.shape[0]) >= n_out, "a series-major block has one row per output column"
+    else:
+        n_rows, stride_s, stride_t = int(forecast.shape[0]), 1, int(forecast.shape[1])
+        assert int(forecast.shape[1]) >= n_out, "a time-major block has one column per output column"
+    if out is None:
+        out = forecast.clone()                                  # (columns from n_out on and the padding keep the input's values)
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == tuple(forecast.shape)
+    assert out.data_ptr() != forecast.data_ptr(), "the input may not alias the output"
+    w = None
+    if code == _lib.RECONCILE_METHODS["wls_struct"]:
+        w = plan["struct_weights"]
+    elif code == _lib.RECONCILE_METHODS["wls_var"]:
+        assert weights is not None, "wls_var takes one weight per output column"
+        w = weights
+    if w is not None:
+        assert w.dtype == torch.float64 and w.is_cuda and w.is_contiguous() and w.numel() >= n_out
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    plan_args = (plan["col_offsets"].data_ptr(), plan["members"].data_ptr(), n_out, int(plan["nnz"]), int(plan["n_series"]),
+                 plan["bottom_col"].data_ptr(), plan["agg_cols"].data_ptr(), n_agg, plan["leaf_offsets"].data_ptr(),
+                 plan["leaf_aggs"].data_ptr(), int(plan["n_leaf"]))
+    solve = code != 0 and n_agg > 0
+    err = _lib.AnofoxError()
+    ld_a = 0
+    if solve:
+        if factor is None:
+            factor = torch.zeros((n_agg, n_agg), dtype=torch.float64, device=dev)
+            st.wait_stream(torch.cuda.current_stream(dev))
+            if not L.anofox_hip_reconcile_factor_device(*plan_args, code, ptr(w), factor.data_ptr(), n_agg, C.c_void_p(st.cuda_stream), C.byref(err)):
+                exc = ValueError if err.code == 2 else RuntimeError
+                raise exc(f"anofox_hip_reconcile_factor_device failed: [{err.code}] {err.message.decode()}")
+        assert factor.dtype == torch.float64 and factor.is_cuda and factor.is_contiguous() and factor.dim() == 2
+        assert int(factor.shape[0]) >= n_agg and int(factor.shape[1]) >= n_agg
+        ld_a = int(factor.shape[1])
+    else:
+        factor = None
+    work = torch.empty((n_rows, n_agg), dtype=torch.float64, device=dev) if solve else None
+    row_status = torch.zeros(max(n_rows, 1), dtype=torch.int32, device=dev)
+    ok = L.anofox_hip_reconcile_apply_device(forecast.data_ptr(), stride_s, stride_t, n_rows, *plan_args, code, ptr(w), ptr(factor), ld_a,
+                                             ptr(work), out.data_ptr(), row_status.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_reconcile_apply_device failed: [{err.code}] {err.message.decode()}")
+    if work is not None:
+        work.record_stream(st)
+    return {"y": out, "row_status": row_status[:n_rows], "factor": factor, "plan": plan}
+
+
 class DeviceBatch:
     """anofox_hip_batch_* over torch-owned HBM."""
 

@@ -353,6 +353,8 @@ class AnofoxHipHierarchyOptions(C.Structure):
 
 assert C.sizeof(AnofoxHipHierarchyOptions) == 16
 HIERARCHY_ROUTES = {"auto": 0, "lane": 1, "tile": 2}      # include/anofox_fcst_hip.h ANOFOX_HIERARCHY_ROUTE_*
+RECONCILE_METHODS = {"bottom_up": 0, "ols": 1, "wls_struct": 2, "wls_var": 3}      # include/anofox_fcst_hip.h ANOFOX_RECONCILE_*
+RECONCILE_MAX_AGG = 16384                                 # ANOFOX_HIP_RECONCILE_MAX_AGG
 
 
 assert C.sizeof(ExogenousRegressor) == 32 and C.sizeof(ExogenousData) == 16 and C.sizeof(ForecastOptionsExog) == 192
@@ -418,6 +420,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_backtest_folds", "anofox_hip_backtest_sizes", "anofox_hip_backtest_expand_device", "anofox_hip_backtest_collect_device",
     "anofox_hip_backtest_batch",
     "anofox_hip_hierarchy_plan", "anofox_hip_hierarchy_device", "anofox_hip_hierarchy_batch",
+    "anofox_hip_reconcile_plan", "anofox_hip_reconcile_factor_device", "anofox_hip_reconcile_apply_device", "anofox_hip_reconcile_batch",
 ]
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
@@ -720,6 +723,19 @@ def load():
     L.anofox_hip_hierarchy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                              P(AnofoxHipHierarchyOptions), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
+    # block 7: reconciliation
+    L.anofox_hip_reconcile_plan.restype = C.c_bool
+    L.anofox_hip_reconcile_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, P(C.c_size_t), P(C.c_size_t), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    plan_args = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.anofox_hip_reconcile_factor_device.restype = C.c_bool
+    L.anofox_hip_reconcile_factor_device.argtypes = plan_args + [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_reconcile_apply_device.restype = C.c_bool
+    L.anofox_hip_reconcile_apply_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + plan_args + \
+        [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_reconcile_batch.restype = C.c_bool
+    L.anofox_hip_reconcile_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -819,6 +835,41 @@ def hierarchy_plan(column_of, n_series=None):
     if not L.anofox_hip_hierarchy_plan(co.ctypes.data, G, n, C.byref(n_out), C.byref(nnz), offs.ctypes.data, memb.ctypes.data, C.byref(err)):
         raise ValueError(f"anofox_hip_hierarchy_plan failed: [{err.code}] {err.message.decode()}")
     return n_out.value, offs, memb[:nnz.value]
+
+
+def reconcile_method(method):
+    """The code of a reconciliation method given by name (RECONCILE_METHODS) or by code."""
+    if isinstance(method, str):
+        if method not in RECONCILE_METHODS:
+            raise ValueError(f"unknown reconciliation method {method!r}: one of {sorted(RECONCILE_METHODS)}")
+        return RECONCILE_METHODS[method]
+    return int(method)
+
+
+def reconcile_plan(col_offsets, members, n_series):
+    """anofox_hip_reconcile_plan on an aggregation plan (hierarchy_plan): {"bottom_col" int32 [n_series], "agg_cols" int32 [n_agg],
+    "leaf_offsets" int32 [n_series + 1], "leaf_aggs" int32 [n_leaf], "struct_weights" fp64 [n_out], "n_agg", "n_leaf", "n_out", "nnz",
+    "n_series", "col_offsets", "members"}.  Host only, no device; a plan the entry refuses raises ValueError with its message."""
+    import numpy as np
+    offs = np.ascontiguousarray(col_offsets, dtype=np.int32)
+    memb = np.ascontiguousarray(members, dtype=np.int32)
+    n_out, n = len(offs) - 1, int(n_series)
+    L = load()
+    n_agg, n_leaf, err = C.c_size_t(), C.c_size_t(), AnofoxError()
+    mp = memb.ctypes.data if len(memb) else None
+    if not L.anofox_hip_reconcile_plan(offs.ctypes.data, mp, n_out, n, C.byref(n_agg), C.byref(n_leaf), None, None, None, None, None, C.byref(err)):
+        raise ValueError(f"anofox_hip_reconcile_plan failed: [{err.code}] {err.message.decode()}")
+    bottom = np.zeros(max(n, 1), dtype=np.int32)
+    aggs = np.zeros(max(n_agg.value, 1), dtype=np.int32)
+    loffs = np.zeros(n + 1, dtype=np.int32)
+    laggs = np.zeros(max(n_leaf.value, 1), dtype=np.int32)
+    w = np.zeros(max(n_out, 1))
+    if not L.anofox_hip_reconcile_plan(offs.ctypes.data, mp, n_out, n, C.byref(n_agg), C.byref(n_leaf), bottom.ctypes.data, aggs.ctypes.data,
+                                       loffs.ctypes.data, laggs.ctypes.data, w.ctypes.data, C.byref(err)):
+        raise ValueError(f"anofox_hip_reconcile_plan failed: [{err.code}] {err.message.decode()}")
+    return {"bottom_col": bottom[:n], "agg_cols": aggs[:n_agg.value], "leaf_offsets": loffs, "leaf_aggs": laggs[:n_leaf.value],
+            "struct_weights": w[:n_out], "n_agg": n_agg.value, "n_leaf": n_leaf.value, "n_out": n_out, "nnz": int(offs[n_out]) if n_out else 0,
+            "n_series": n, "col_offsets": offs, "members": memb}
 
 
 def make_prep_options(gaps=False, frequency_micros=0, frequency_type="FIXED", trim="none", fill="none", fill_value=0.0):

@@ -396,6 +396,7 @@ typedef struct FeaturesResult {
 
 #define ANOFOX_HIP_N_FEATURES 117
 #define ANOFOX_HIP_FEATURES_MAX_ROWS 65536
+#define ANOFOX_HIP_RECONCILE_MAX_AGG 16384      /* aggregate columns of a reconciliation plan: bounds the factor at 2 GiB */
 
 /*
  * The features of ONE series, the reference's extract_features (features.rs) behind its FFI wrapper: only the features the source
@@ -2079,6 +2080,130 @@ bool anofox_hip_hierarchy_batch(const double *const *values,
                                 size_t *out_n_out,
                                 size_t *out_t_out,
                                 size_t *out_ld,
+                                struct AnofoxError *out_error);
+
+/* ------------------------------------------------------------------------- */
+/* Block 7: reconciliation of the forecasts of a hierarchy                     */
+/* ------------------------------------------------------------------------- */
+/*
+ * The forecasts of the columns that anofox_hip_hierarchy_device builds do not add up; these entries make them coherent.  The
+ * reference has no such function: the contract is the published method (Hyndman et al. 2011, OLS; Wickramasuriya et al. 2019, MinT
+ * with a diagonal W) in its constraint form.  A plan is col_offsets / members as anofox_hip_hierarchy_plan returns them.  The BOTTOM
+ * column of series s is the one column whose member list is exactly [s]; every other column with members is an AGGREGATE; a column
+ * without members is copied through and takes no part.  A[i][s] = how often s occurs among the members of aggregate i (a series
+ * listed twice counts twice), w > 0 one weight per column.  For one row of base forecasts yhat:
+ *   1. r_i = yhat_i - (((0.0 + yhat_b(m0)) + yhat_b(m1)) + ...) over the members of i in plan order;
+ *   2. M = diag(w_a) + A diag(w_b) A^T (n_agg x n_agg, symmetric positive definite), lambda = M^-1 r by Cholesky;
+ *   3. btilde_s = yhat_b(s) + w_b(s) * (((0.0 + lambda_i0) + lambda_i1) + ...) over the aggregates that hold s, ascending, once per
+ *      occurrence;
+ *   4. the bottom columns receive btilde, aggregate column i the chain ((0.0 + btilde(m0)) + btilde(m1)) + ... in plan order.
+ * Step 4 makes the output coherent to the bit: every aggregate is what anofox_hip_hierarchy_device computes from the bottoms.
+ */
+enum { ANOFOX_RECONCILE_BOTTOM_UP = 0,      /* lambda = 0: the bottoms keep their bits, no factor */
+       ANOFOX_RECONCILE_OLS = 1,            /* w = 1 */
+       ANOFOX_RECONCILE_WLS_STRUCT = 2,     /* w_c = the member entries of column c (struct_weights of the plan) */
+       ANOFOX_RECONCILE_WLS_VAR = 3 };      /* the caller's weights, e.g. a per-column error variance */
+
+/*
+ * The reconciliation plan of an aggregation plan.  Host only.  *n_agg and *n_leaf (the entries of leaf_aggs: the member entries of
+ * all aggregates) are always written; with bottom_col NULL that is all (the sizing call; then every output array must be NULL).
+ * Otherwise: bottom_col int32 [n_series]; agg_cols int32 [n_agg] ascending; leaf_offsets int32 [n_series + 1] and leaf_aggs int32
+ * [n_leaf], the transposed plan: for series s the indices into agg_cols of the aggregates that hold it, ascending, once per
+ * occurrence; struct_weights fp64 [n_out]: the member entries of each column (may be NULL).
+ * INVALID_INPUT, each naming what it found: a member outside [0, n_series), a series without a bottom column, a series with two,
+ * offsets that do not ascend from 0, n_agg above ANOFOX_HIP_RECONCILE_MAX_AGG.
+ */
+bool anofox_hip_reconcile_plan(const int32_t *col_offsets,
+                               const int32_t *members,
+                               size_t n_out,
+                               size_t n_series,
+                               size_t *n_agg,
+                               size_t *n_leaf,
+                               int32_t *bottom_col,
+                               int32_t *agg_cols,
+                               int32_t *leaf_offsets,
+                               int32_t *leaf_aggs,
+                               double *struct_weights,
+                               struct AnofoxError *out_error);
+
+/*
+ * The Cholesky factor L (lower) of M for method 1, 2 or 3, into factor fp64 [n_agg x ld_a], ld_a >= n_agg.  All arrays in device
+ * memory; nnz = col_offsets[n_out], n_leaf as the planner returned it.  weights fp64 [n_out]: NULL for method 1, the planner's
+ * struct_weights for method 2, the caller's for method 3.  Only the lower triangle is written: the strict upper part and the
+ * columns from n_agg on keep what they held.  The call returns after the factor is finished.  A factor is a value: one factor
+ * serves every block of the same plan and weights.  Every sum has a fixed order; the same inputs give the same bits.
+ * INVALID_INPUT: an unknown method or method 0, ld_a < n_agg, n_agg above the limit, a weight of a column with members that is not
+ * finite and positive (names the column).  COMPUTATION_ERROR: a pivot that is not positive (names the row).
+ */
+bool anofox_hip_reconcile_factor_device(const int32_t *col_offsets,
+                                        const int32_t *members,
+                                        size_t n_out,
+                                        size_t nnz,
+                                        size_t n_series,
+                                        const int32_t *bottom_col,
+                                        const int32_t *agg_cols,
+                                        size_t n_agg,
+                                        const int32_t *leaf_offsets,
+                                        const int32_t *leaf_aggs,
+                                        size_t n_leaf,
+                                        int32_t method,
+                                        const double *weights,
+                                        double *factor,
+                                        size_t ld_a,
+                                        void *stream,
+                                        struct AnofoxError *out_error);
+
+/*
+ * Reconciles n_rows rows of a device-resident block: element (column c, row t) of base and of out lies at c * stride_s + t *
+ * stride_t, as anofox_hip_metrics_device takes its blocks -- a time-major block (stride_s 1, stride_t ld) and the series-major
+ * [n_out x h] layout of anofox_hip_batch_device_results (stride_s h, stride_t 1) give the same bits.  Only columns < n_out and rows
+ * < n_rows of out are written; base may not alias out.  factor / ld_a from anofox_hip_reconcile_factor_device and weights as given
+ * there (both NULL for method 0); work fp64 [n_rows x n_agg] is the caller's scratch (NULL for method 0 or n_agg 0).
+ * row_status int32 [n_rows]: 0 done; 2 a base forecast that is not finite in a column with members -- every bottom and aggregate
+ * column of that row is NaN then, never a silent answer; the other rows are not affected.  An empty column is copied, whatever it
+ * holds.  The call only enqueues on `stream` and does not wait on the host.
+ * INVALID_INPUT: an unknown method, a factor missing for method 1-3, ld_a < n_agg, n_agg above the limit, sizes above 2^31 - 1.
+ */
+bool anofox_hip_reconcile_apply_device(const double *base,
+                                       size_t stride_s,
+                                       size_t stride_t,
+                                       size_t n_rows,
+                                       const int32_t *col_offsets,
+                                       const int32_t *members,
+                                       size_t n_out,
+                                       size_t nnz,
+                                       size_t n_series,
+                                       const int32_t *bottom_col,
+                                       const int32_t *agg_cols,
+                                       size_t n_agg,
+                                       const int32_t *leaf_offsets,
+                                       const int32_t *leaf_aggs,
+                                       size_t n_leaf,
+                                       int32_t method,
+                                       const double *weights,
+                                       const double *factor,
+                                       size_t ld_a,
+                                       double *work,
+                                       double *out,
+                                       int32_t *row_status,
+                                       void *stream,
+                                       struct AnofoxError *out_error);
+
+/*
+ * The same for host buffers: column_of as for anofox_hip_hierarchy_plan, forecast and out fp64 series-major [n_out x h] (n_out as
+ * that plan sizes it), weights fp64 [n_out] for method 3 (ignored otherwise; method 2 takes the plan's), out_row_status int32 [h].
+ * The call plans, uploads, factors, applies and reads back once.  The planner's errors come first and need no device.  A failed
+ * device allocation is a COMPUTATION_ERROR that names the size.  One device; fp64 only.
+ */
+bool anofox_hip_reconcile_batch(const int32_t *column_of,
+                                size_t n_groupings,
+                                size_t n_series,
+                                const double *forecast,
+                                size_t h,
+                                int32_t method,
+                                const double *weights,
+                                double *out,
+                                int32_t *out_row_status,
                                 struct AnofoxError *out_error);
 
 #ifdef __cplusplus
