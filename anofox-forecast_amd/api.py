@@ -3915,6 +3915,186 @@ def ts_reconcile_hierarchy(unique_id, date, forecast, params=None, date_name="da
             forecast_name: np.array(block, dtype=np.float64).reshape(-1)}
 
 
+# --------------------------------------------------------------------------------------------
+# the choice of a method per series from backtest scores (include/anofox_fcst_hip.h block 8).  The reference's guides compare models
+# with a UNION ALL of one backtest statement per method and an AVG per model (docs/guides/02-model-selection.md "Comparing Models",
+# docs/guides/03-cross-validation.md "Model Comparison"); it has no operator that chooses per series: the names are this package's
+# --------------------------------------------------------------------------------------------
+def select_batch(series, methods, folds, metric="rmse", mode="pick", fallback=-1):
+    """anofox_hip_select_batch: `series` (sorted, without NULLs), `methods` a list of ForecastOptions of one horizon, `folds` the table
+    of backtest_fold_bounds.  One pack, ONE expand, one backtest batch per method on the shared block, the score of every (method,
+    series) over that series' backtest cells, then -- mode "pick" -- the choice, one sub-batch per method that won something and the
+    scatter, or -- "mean" / "median" / "inverse_score" -- every method on the whole block and the combination.
+
+    Returns ({"winner": int32 [n]; "best_score": fp64 [n]; "scores": fp64 [M, n]; "yhat", "lower", "upper": fp64 [n, h]; "status": int32
+    [n]; "model_name": list [n] ("" unless status is 0; the mode's name for an ensemble); "backtest_yhat", "backtest_actual": fp64
+    [n_pairs, h], NaN where a row does not exist; "n_rows": int32 [n_pairs]}, batch_error)."""
+    L = _lib.load()
+    n, F, M = len(series), len(folds), len(methods)
+    h = max(int(methods[0].horizon), 0) if M else 0
+    arrs = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+    tab = _lib.make_folds(folds)
+    table = _lib.make_options_table(methods)
+    n_pairs = n * F
+    out = {"winner": np.full(n, -1, dtype=np.int32), "best_score": np.full(n, np.nan), "scores": np.full((M, n), np.nan),
+           "yhat": np.full((n, h), np.nan), "lower": np.full((n, h), np.nan), "upper": np.full((n, h), np.nan),
+           "status": np.full(n, _lib.INTERNAL_ERROR, dtype=np.int32), "backtest_yhat": np.full((n_pairs, h), np.nan),
+           "backtest_actual": np.full((n_pairs, h), np.nan), "n_rows": np.zeros(n_pairs, dtype=np.int32)}
+    names = ((C.c_char * 64) * max(n, 1))()
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_select_batch(ptrs, lens, n, table, M, tab, F, str(metric).encode(), str(mode).encode(), int(fallback),
+                                   out["winner"].ctypes.data, out["best_score"].ctypes.data, out["scores"].ctypes.data, out["yhat"].ctypes.data,
+                                   out["lower"].ctypes.data, out["upper"].ctypes.data, out["status"].ctypes.data, names,
+                                   out["backtest_yhat"].ctypes.data, out["backtest_actual"].ctypes.data, out["n_rows"].ctypes.data, C.byref(err))
+    out["model_name"] = [names[s].value.decode() for s in range(n)]
+    return out, {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+
+
+def _select_groups(group, date, target, what):
+    """The groups of a table in first-appearance order, each sorted by date (stable): rows with a NULL date are dropped, a NULL target is
+    an error (the selection entries take no NULLs: fill them first, ts_fill_nulls_*_by).  -> (keys, series, last date per key, dates'
+    kind, all dates in microseconds, the kept rows, the dates' dtype)."""
+    dates = np.asarray(date)
+    kind = _date_kind(dates)
+    us = _to_micros(dates, kind)
+    grp = np.asarray(group, dtype=object)
+    val = np.ma.filled(np.ma.asarray(target, dtype=object), None) if np.ma.isMaskedArray(target) else np.asarray(target, dtype=object)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), bool)
+    order, rows = [], {}
+    for i in range(len(grp)):
+        if null_date[i]:
+            continue
+        if val[i] is None or val[i] != val[i]:
+            raise InvalidInputException(f"{what}: the target holds NULLs (row {i}); the selection entries take none -- fill them first")
+        k = "__NULL__" if grp[i] is None else grp[i]
+        if k not in rows:
+            rows[k] = []
+            order.append(k)
+        rows[k].append(i)
+    series, last = [], []
+    for k in order:
+        idx = np.array(rows[k])
+        idx = idx[np.argsort(us[idx], kind="stable")]
+        series.append(np.array([float(val[i]) for i in idx], dtype=np.float64))
+        last.append(int(us[idx][-1]))
+    kept = np.array([i for k in order for i in rows[k]], dtype=np.int64)
+    return order, series, last, kind, us, kept, dates.dtype
+
+
+def _select_request(methods, horizon, frequency, folds, params, fallback, us, kept):
+    """The option table, the fold table and the fallback index of ts_forecast_best_by / ts_compare_models_by."""
+    if not methods:
+        raise InvalidInputException("methods: at least one (method, params) pair is needed")
+    pairs = [(m, None) if isinstance(m, str) else (m[0], m[1] if len(m) > 1 else None) for m in methods]
+    binds = [bind(m, horizon, frequency, mp) for m, mp in pairs]
+    table = [options_from_bind(b) for b in binds]
+    p = params or {}
+
+    def as_int(key, default):
+        try:
+            return int(str(p[key])) if p.get(key) is not None else default
+        except ValueError:
+            return default
+    window_type = str(p["window_type"]) if p.get("window_type") is not None else "expanding"
+    clip = str(p.get("clip_horizon", "false")).lower() in ("true", "1", "yes")
+    bounds = _lib.backtest_folds(len(np.unique(us[kept])) if len(kept) else 0, horizon, folds, window_type, as_int("min_train_size", 1),
+                                 as_int("gap", 0), as_int("embargo", 0), as_int("initial_train_size", -1), as_int("skip_length", -1), clip)
+    labels = [b.method for b in binds]
+    if fallback is None:
+        fb = -1
+    elif isinstance(fallback, str):
+        if fallback not in labels:
+            raise InvalidInputException(f"fallback {fallback!r} is none of the methods {labels}")
+        fb = labels.index(fallback)
+    else:
+        fb = int(fallback)
+    return binds, table, bounds, labels, fb
+
+
+def ts_forecast_best_by(group, date, target, methods, horizon, frequency, folds=5, params=None, metric="rmse", mode="pick", fallback=None,
+                        group_name="id", date_name="ds", info=None):
+    """ts_forecast_by with the method chosen per group from walk-forward backtest scores, all of it on the device (select_batch).
+
+    methods: a list of (method, params) pairs (params as for ts_forecast_by; a bare method name is allowed); folds and `params`
+    (window_type, min_train_size, gap, embargo, initial_train_size, skip_length, clip_horizon) shape the backtest as in
+    ts_backtest_native; metric one of lib.SELECT_CRITERIA; mode "pick" or an ensemble ("mean", "median", "inverse_score"); fallback: the
+    method (name or index) of a group without an admissible score, None: such a group yields no rows.
+
+    The columns and the row order are those of ts_forecast_by, plus selected_method and cv_score.  In an ensemble mode selected_method
+    is the mode's name, model_name the comma-joined member names, cv_score NaN, and the interval columns are NaN (intervals of an
+    ensemble come from conformal calibration of its backtest forecasts).  `info` (a dict) receives the select_batch result."""
+    order, series, last, kind, us, kept, dtype = _select_groups(group, date, target, "ts_forecast_best_by")
+    binds, table, bounds, labels, fb = _select_request(methods, horizon, frequency, folds, params, fallback, us, kept)
+    if mode not in _lib.SELECT_MODES:
+        raise InvalidInputException(f"unknown mode {mode!r}; one of {sorted(_lib.SELECT_MODES)}")
+    out = {group_name: [], "forecast_step": [], date_name: [], "yhat": [], "yhat_lower": [], "yhat_upper": [], "model_name": [],
+           "selected_method": [], "cv_score": []}
+    if series:
+        res, berr = select_batch(series, table, bounds, metric, mode, fb)
+        if not berr["ok"]:
+            if berr["code"] in (_lib.INVALID_MODEL, _lib.INVALID_INPUT):
+                raise InvalidInputException(berr["message"])
+            raise RuntimeError(f"anofox_hip_select_batch failed: [{berr['code']}] {berr['message']}")
+        if info is not None:
+            info.update(res)
+            info["methods"], info["folds"] = labels, bounds
+        f = binds[0].frequency
+        for s, k in enumerate(order):
+            if res["status"][s] != 0:
+                continue                      # the group yields no rows, as in ts_forecast_by
+            pick = mode == "pick"
+            w = int(res["winner"][s])
+            for i in range(int(horizon)):
+                out[group_name].append(None if k == "__NULL__" else k)
+                out["forecast_step"].append(i + 1)
+                out[date_name].append(compute_forecast_date(last[s], i + 1, f, kind))
+                out["yhat"].append(res["yhat"][s, i])
+                out["yhat_lower"].append(res["lower"][s, i])
+                out["yhat_upper"].append(res["upper"][s, i])
+                out["model_name"].append(res["model_name"][s] if pick else ",".join(labels))
+                out["selected_method"].append(labels[w] if pick else mode)
+                out["cv_score"].append(res["best_score"][s] if pick else np.nan)
+    out["forecast_step"] = np.array(out["forecast_step"], dtype=np.int32)
+    out[date_name] = _from_micros(np.array(out[date_name], dtype=np.int64), kind, dtype)
+    for c in ("yhat", "yhat_lower", "yhat_upper", "cv_score"):
+        out[c] = np.array(out[c], dtype=np.float64)
+    return out
+
+
+def ts_compare_models_by(group, date, target, methods, horizon, frequency, folds=5, params=None, metric="rmse", fallback=None,
+                         group_name="id"):
+    """The guides' model comparison on the device: the long table (group, method, score, is_winner), one row per group and method in
+    first-appearance order of the groups and the order of `methods`, and the number of groups every method won.  The score of a method
+    for a group is `metric` over the existing rows of that group's backtest cells, NaN when it has none.
+
+    Returns ({<group_name>, "method", "score", "is_winner"}, {"method", "wins"})."""
+    order, series, _last, _kind, us, kept, _dtype = _select_groups(group, date, target, "ts_compare_models_by")
+    _binds, table, bounds, labels, fb = _select_request(methods, horizon, frequency, folds, params, fallback, us, kept)
+    M = len(labels)
+    cols = {group_name: [], "method": [], "score": [], "is_winner": []}
+    wins = np.zeros(M, dtype=np.int64)
+    if series:
+        res, berr = select_batch(series, table, bounds, metric, "pick", fb)
+        if not berr["ok"]:
+            if berr["code"] in (_lib.INVALID_MODEL, _lib.INVALID_INPUT):
+                raise InvalidInputException(berr["message"])
+            raise RuntimeError(f"anofox_hip_select_batch failed: [{berr['code']}] {berr['message']}")
+        for s, k in enumerate(order):
+            w = int(res["winner"][s])
+            if w >= 0:
+                wins[w] += 1
+            for m in range(M):
+                cols[group_name].append(None if k == "__NULL__" else k)
+                cols["method"].append(labels[m])
+                cols["score"].append(res["scores"][m, s])
+                cols["is_winner"].append(m == w)
+    cols["score"] = np.array(cols["score"], dtype=np.float64)
+    cols["is_winner"] = np.array(cols["is_winner"], dtype=bool)
+    return cols, {"method": labels, "wins": wins}
+
+
 anofox_fcst_ts_aggregate_hierarchy = ts_aggregate_hierarchy
 anofox_fcst_ts_combine_keys = ts_combine_keys
 anofox_fcst_ts_split_keys = ts_split_keys

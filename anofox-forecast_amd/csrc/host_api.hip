@@ -41,6 +41,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_scratch.hpp"       // Scratch (a call's device blocks), the shape and packing of a batch of series, the _device entry's checks and launch
 #include "host_parts.hpp"         // how an auto-detected batch is cut into device batches (PartPlan), and how a batch's results reach the caller's arrays
 #include "host_reconcile_plan.hpp" // the host-only planner of the reconciliation entries (bottom columns, aggregates, the transposed plan)
+#include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
 struct Plan {
@@ -6797,6 +6798,398 @@ bool anofox_hip_reconcile_batch(const int32_t *column_of, size_t n_groupings, si
         return false;
     }
     return ok;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The choice of a method per series from backtest scores (DESIGN.md section 3 "Selection"; select.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(SELECT_PLAN_MAX_METHODS == (size_t)SELECT_MAX_METHODS && ANOFOX_HIP_SELECT_MAX_METHODS == SELECT_MAX_METHODS, "the limit of methods");
+static_assert(ANOFOX_SELECT_PICK == SELECT_PICK && ANOFOX_SELECT_INVERSE_SCORE == SELECT_INVERSE_SCORE, "selection mode codes");
+
+constexpr double SELECT_MAX_CELLS = 256.0 * 2147483647.0;         // cells of a [rows x horizon] block: the grid of one launch
+
+bool select_plan_report(SelectPlanResult r, const std::string &message, AnofoxError *err)
+{
+    if (r == SELECT_PLAN_NULL) set_error(err, NULL_POINTER, "Null pointer argument");
+    else if (r == SELECT_PLAN_INVALID) set_error(err, INVALID_INPUT, message);
+    return r == SELECT_PLAN_OK;
+}
+
+// a batch that lives as long as this object
+struct BatchOwner {
+    AnofoxHipBatch *b = nullptr;
+    BatchOwner() = default;
+    BatchOwner(const BatchOwner &) = delete;
+    BatchOwner &operator=(const BatchOwner &) = delete;
+    ~BatchOwner() { if (b) anofox_hip_batch_destroy(b); }
+};
+
+// one batch of n columns on a resident block: create, adopt the block, run, wait
+bool select_run_batch(const ForecastOptions *o, size_t n, size_t t_rows, const double *d_y, size_t ld, const int32_t *d_len, BatchOwner *own,
+                      AnofoxError *err)
+{
+    if (!anofox_hip_batch_create(n, t_rows, o, &own->b, err)) return false;
+    if (!anofox_hip_batch_set_device_block(own->b, d_y, ld, d_len, err) || !anofox_hip_batch_run(own->b, nullptr, err)) return false;
+    HIPCHECK(hipStreamSynchronize(own->b->last_stream));
+    own->b->quiesced = true;
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+bool anofox_hip_select_winner_device(const double *scores, size_t ld, const int32_t *score_status, size_t n_methods, size_t n_series,
+                                     int32_t fallback, int32_t *winner, double *best_score, uint8_t *from_fallback, int32_t *offsets,
+                                     int32_t *members, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!select_plan_report(select_counts_check(n_methods, fallback, &message), message, out_error)) return false;
+    if (!offsets || (n_series > 0 && (!scores || !score_status || !winner || !best_score || !from_fallback || !members))) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!block_args_ok(ld, n_series, "n_series", 0, 0, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const bool ok = launch_and_wait("select winner", st, out_error, [&] {
+        if (n_series == 0) {
+            HIPCHECK(hipMemsetAsync(offsets, 0, (n_methods + 1) * sizeof(int32_t), st));
+            return;
+        }
+        SelectWinnerArgs a{};
+        a.scores = scores; a.ld = ld; a.score_status = score_status;
+        a.n_methods = (int)n_methods; a.n_series = (int)n_series; a.fallback = fallback;
+        a.winner = winner; a.best_score = best_score; a.from_fallback = from_fallback;
+        a.n_wg = select_workgroups(n_series);
+        a.counts = scratch.get<int32_t>(select_counts_size(n_series, (int)n_methods));
+        a.offsets = offsets; a.members = members;
+        launch_select_winner(a, st);
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_select_gather_device(const double *y, size_t ld_src, const int32_t *lengths, size_t n_series, size_t t_rows,
+                                     const int32_t *members, size_t off, size_t n_m, double *y_out, size_t ld_m, int32_t *len_out, void *stream,
+                                     AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if ((ld_m > 0 && (!len_out || (t_rows > 0 && !y_out))) || (n_m > 0 && (!y || !lengths || !members))) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!block_args_ok(ld_src, n_series, "n_series", t_rows, (size_t)1 << 30, out_error)) return false;
+    if (ld_m < n_m) { set_error(out_error, INVALID_INPUT, "Invalid input: ld_m is smaller than n_m"); return false; }
+    if (off > n_series || n_m > n_series - off) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: members[off .. off + n_m) lies outside the n_series entries of the partition");
+        return false;
+    }
+    if (ld_m > (size_t)INT32_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: the block is too large"); return false; }
+    if (ld_m == 0) return true;
+    if (!device_ready(out_error)) return false;
+    SelectMoveArgs a{};
+    a.members = members; a.off = off; a.n_m = n_m; a.n_series = (int)n_series;
+    a.y = y; a.ld_src = ld_src; a.len = lengths; a.t_rows = t_rows; a.y_out = y_out; a.ld_m = ld_m; a.len_out = len_out;
+    hipStream_t st = (hipStream_t)stream;
+    return launch_and_wait("select gather", st, out_error, [&] { launch_select_gather(a, st); });
+}
+
+bool anofox_hip_select_scatter_device(const double *yhat_m, const double *lower_m, const double *upper_m, const int32_t *code_m,
+                                      const int32_t *status_m, const int32_t *members, size_t off, size_t n_m, size_t horizon,
+                                      const int32_t *winner, size_t n_series, double *yhat, double *lower, double *upper, int32_t *model_code,
+                                      int32_t *status, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (n_m > 0 && (!members || (yhat && !yhat_m) || (lower && !lower_m) || (upper && !upper_m) || (model_code && !code_m) || (status && !status_m))) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (n_series > (size_t)INT32_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: n_series is limited to 2^31 - 1"); return false; }
+    if (horizon < 1 || horizon > (size_t)(1u << 30) || (double)n_series * (double)horizon >= SELECT_MAX_CELLS) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: horizon must be at least 1 (and n_series x horizon below 2^39)");
+        return false;
+    }
+    if (off > n_series || n_m > n_series - off) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: members[off .. off + n_m) lies outside the n_series entries of the partition");
+        return false;
+    }
+    if (n_series == 0 || (n_m == 0 && !winner)) return true;
+    if (!device_ready(out_error)) return false;
+    SelectMoveArgs a{};
+    a.members = members; a.off = off; a.n_m = n_m; a.n_series = (int)n_series; a.h = (int)horizon;
+    a.yhat_m = yhat_m; a.lower_m = lower_m; a.upper_m = upper_m; a.code_m = code_m; a.status_m = status_m; a.winner = winner;
+    a.yhat = yhat; a.lower = lower; a.upper = upper; a.model_code = model_code; a.status = status;
+    hipStream_t st = (hipStream_t)stream;
+    return launch_and_wait("select scatter", st, out_error, [&] { launch_select_scatter(a, st); });
+}
+
+bool anofox_hip_select_combine_device(const double *const *blocks, size_t n_methods, size_t n_rows, size_t horizon, const int32_t *member_status,
+                                      int32_t mode, const int32_t *winner, const double *weights, size_t ld_w, size_t group_div, double *out,
+                                      int32_t *row_status, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!select_plan_report(select_counts_check(n_methods, -1, &message), message, out_error)) return false;
+    if (mode < SELECT_PICK || mode > SELECT_INVERSE_SCORE) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: mode must be 0 (pick), 1 (mean), 2 (median) or 3 (inverse_score)");
+        return false;
+    }
+    if (!blocks) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (horizon < 1 || horizon > (size_t)(1u << 30) || n_rows > (size_t)INT32_MAX || (double)n_rows * (double)horizon >= SELECT_MAX_CELLS) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: horizon must be at least 1 (and n_rows x horizon below 2^39)");
+        return false;
+    }
+    if (group_div < 1) { set_error(out_error, INVALID_INPUT, "Invalid input: group_div must be at least 1"); return false; }
+    if (n_rows > 0) {
+        bool null = !out || (mode != SELECT_PICK && !member_status) || (mode == SELECT_PICK && !winner) || (mode == SELECT_INVERSE_SCORE && !weights);
+        for (size_t m = 0; m < n_methods; m++) null = null || !blocks[m];
+        if (null) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (mode == SELECT_INVERSE_SCORE && ld_w < (n_rows + group_div - 1) / group_div) {
+            set_error(out_error, INVALID_INPUT, "Invalid input: ld_w is smaller than the number of groups");
+            return false;
+        }
+    }
+    if (n_rows == 0) return true;
+    if (!device_ready(out_error)) return false;
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const bool ok = launch_and_wait("select combine", st, out_error, [&] {
+        const double **d_tab = scratch.get<const double *>(n_methods);
+        HIPCHECK(hipMemcpyAsync(d_tab, blocks, n_methods * sizeof(const double *), hipMemcpyHostToDevice, st));
+        SelectCombineArgs a{};
+        a.blocks = d_tab; a.n_methods = (int)n_methods; a.h = (int)horizon; a.mode = mode;
+        a.n_rows = n_rows; a.group_div = group_div; a.member_status = member_status; a.winner = winner;
+        a.weights = weights; a.ld_w = ld_w; a.out = out; a.row_status = row_status;
+        launch_select_combine(a, st);
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_select_batch(const double *const *values, const size_t *lengths, size_t n_series, const ForecastOptions *methods, size_t n_methods,
+                             const AnofoxHipFold *folds, size_t n_folds, const char *criterion, const char *mode, int32_t fallback,
+                             int32_t *out_winner, double *out_best_score, double *out_scores, double *out_yhat, double *out_lower,
+                             double *out_upper, int32_t *out_status, char (*out_model_names)[64], double *out_backtest_yhat,
+                             double *out_backtest_actual, int32_t *out_n_rows, AnofoxError *out_batch_error)
+{
+    AnofoxError *const err = out_batch_error;
+    clear_error(err);
+    std::string message;
+    if (!select_plan_report(select_counts_check(n_methods, fallback, &message), message, err)) return false;
+    if (!methods || !criterion || !mode || (n_series > 0 && (!values || !lengths))) { set_error(err, NULL_POINTER, "Null pointer argument"); return false; }
+    int figure = -1, mode_code = -1;
+    {
+        int horizons[SELECT_PLAN_MAX_METHODS];
+        for (size_t m = 0; m < n_methods; m++) horizons[m] = methods[m].horizon;
+        if (!select_plan_report(select_request_check(n_methods, horizons, criterion, mode, fallback, &figure, &mode_code, &message), message, err))
+            return false;
+    }
+    size_t t_train = 1, np = 0, ld_pairs = 64;
+    if (!anofox_hip_backtest_sizes(folds, n_folds, n_series, &t_train, &np, &ld_pairs, err)) return false;
+    BlockShape shape;
+    if (!series_shape(values, nullptr, lengths, n_series, (size_t)1 << 30, &shape, err)) return false;
+    for (size_t m = 0; m < n_methods; m++) {                     // an option block anofox_hip_batch_create refuses fails the whole call
+        Plan plan;
+        if (!make_plan(&methods[m], plan, err)) return false;
+    }
+    const size_t M = n_methods, N = n_series, F = n_folds, h = (size_t)methods[0].horizon, nh = np * h, Nh = N * h;
+    if ((double)np * (double)h >= SELECT_MAX_CELLS || F * h > (size_t)INT32_MAX) {
+        set_error(err, INVALID_INPUT, "Invalid input: n_pairs x horizon must stay below 2^39");
+        return false;
+    }
+    if (N == 0) return true;
+    if (!device_ready(err)) return false;
+    const size_t ld_src = shape.ld, T = shape.T, ldN = ld_src;
+    const bool pick = mode_code == SELECT_PICK;
+    // what goes back, in two arenas: fp64 -- yhat, lower, upper [N x h], the selected backtest yhat and actual [np x h], best_score [N],
+    // scores [M x ldN] -- and int32 -- winner, status, model_code, members [N], offsets [M + 1]
+    const size_t n_fp = 3 * Nh + 2 * nh + N + M * ldN, n_int = 4 * N + M + 1;
+    std::vector<double> fp(n_fp);
+    std::vector<int32_t> in(n_int);
+    std::vector<std::string> names(out_model_names ? N : 0);
+    bool ok = true;
+    try {
+        int dev = 0;
+        HIPCHECK(hipGetDevice(&dev));
+        DeviceGuard guard(dev);
+        hipStream_t st = nullptr;
+        Scratch scratch;                                         // (declared before every batch: a batch adopts blocks of it)
+        double *d_src = scratch.get<double>(T * ld_src), *d_exp = nullptr;
+        int32_t *d_len = scratch.get<int32_t>(ld_src);
+        {
+            std::vector<double> yb(T * ld_src, 0.0);
+            const std::vector<int32_t> len = block_lengths(lengths, N, ld_src);
+            pack_time_major(yb.data(), ld_src, values, lengths, N);
+            HIPCHECK(hipMemcpy(d_src, yb.data(), T * ld_src * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld_src * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        try { d_exp = scratch.get<double>(t_train * ld_pairs); }
+        catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(err, COMPUTATION_ERROR, "Computation error: the expanded backtest block of " + std::to_string(t_train) + " x " +
+                      std::to_string(ld_pairs) + " values needs " + std::to_string(t_train * ld_pairs * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            double *d_fp = scratch.get<double>(n_fp);
+            int32_t *d_in = scratch.get<int32_t>(n_int);
+            double *d_yh = d_fp, *d_lo = d_fp + Nh, *d_hi = d_fp + 2 * Nh, *d_sel_yh = d_fp + 3 * Nh, *d_sel_act = d_sel_yh + nh,
+                   *d_best = d_sel_act + nh, *d_scores = d_best + N;
+            int32_t *d_winner = d_in, *d_stat = d_in + N, *d_code = d_in + 2 * N, *d_members = d_in + 3 * N, *d_offsets = d_in + 4 * N;
+            int32_t *d_lenp = scratch.get<int32_t>(ld_pairs), *d_ntest = scratch.get<int32_t>(ld_pairs), *d_rows = scratch.get<int32_t>(std::max<size_t>(np, 1));
+            double *d_bt_yh = scratch.get<double>(M * nh), *d_bt_act = scratch.get<double>(M * nh), *d_work = scratch.get<double>(2 * nh);
+            int32_t *d_bt_stat = scratch.get<int32_t>(M * std::max<size_t>(np, 1)), *d_sstat = scratch.get<int32_t>(M * N);
+            int32_t *d_flen = scratch.get<int32_t>(N);
+            double *d_fig = scratch.get<double>((size_t)METRICS_N_FIG * ldN);
+            uint8_t *d_ff = scratch.get<uint8_t>(N);
+            {
+                const std::vector<int32_t> flen(N, (int32_t)(F * h));
+                HIPCHECK(hipMemcpy(d_flen, flen.data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
+                // a score row that is never written (no fold: nothing to score) is NaN with status 1
+                const std::vector<double> nan_row(M * ldN, std::numeric_limits<double>::quiet_NaN());
+                const std::vector<int32_t> one(M * N, 1);
+                HIPCHECK(hipMemcpy(d_scores, nan_row.data(), M * ldN * sizeof(double), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(d_sstat, one.data(), M * N * sizeof(int32_t), hipMemcpyHostToDevice));
+            }
+            // ---- the backtest of every method on ONE expanded block, scored per series ----
+            if (np > 0)
+                ok = anofox_hip_backtest_expand_device(d_src, ld_src, d_len, N, T, folds, F, t_train, d_exp, ld_pairs, d_lenp, d_ntest, st, err);
+            for (size_t m = 0; ok && np > 0 && m < M; m++) {
+                BatchOwner own;
+                ok = select_run_batch(&methods[m], np, t_train, d_exp, ld_pairs, d_lenp, &own, err) &&
+                     anofox_hip_backtest_collect_device(d_src, ld_src, N, T, folds, F, d_ntest, own.b->d_status, own.b->d_yhat, nullptr, nullptr, h,
+                                                        criterion, d_bt_act + m * nh, d_work, d_work + nh, nullptr, d_rows, nullptr, st, err);
+                if (!ok) break;
+                HIPCHECK(hipMemcpy(d_bt_yh + m * nh, own.b->d_yhat, nh * sizeof(double), hipMemcpyDeviceToDevice));
+                HIPCHECK(hipMemcpy(d_bt_stat + m * np, own.b->d_status, np * sizeof(int32_t), hipMemcpyDeviceToDevice));
+                ok = anofox_hip_metrics_device(d_bt_act + m * nh, d_bt_yh + m * nh, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, F * h, 1, d_flen,
+                                               N, F * h, 1u << figure, 0.5, true, d_fig, ldN, d_sstat + m * N, st, err);
+                if (ok) HIPCHECK(hipMemcpy(d_scores + m * ldN, d_fig + (size_t)figure * ldN, N * sizeof(double), hipMemcpyDeviceToDevice));
+            }
+            // ---- the choice ----
+            if (ok)
+                ok = anofox_hip_select_winner_device(d_scores, ldN, d_sstat, M, N, fallback, d_winner, d_best, d_ff, d_offsets, d_members, st, err);
+            std::vector<int32_t> offs(M + 1, 0), memb(N, 0);
+            if (ok) {
+                HIPCHECK(hipMemcpy(offs.data(), d_offsets, (M + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+                HIPCHECK(hipMemcpy(memb.data(), d_members, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+            }
+            if (ok && pick) {
+                // ---- winners only: one dense sub-batch per method that won something, scattered back to series order ----
+                std::vector<SelectSubBatch> subs;
+                ok = select_plan_report(select_sub_batches(offs.data(), M, N, &subs, &message), message, err);
+                for (size_t k = 0; ok && k < subs.size(); k++) {
+                    const SelectSubBatch &sb = subs[k];
+                    double *d_sub = scratch.get<double>(T * sb.ld_m);
+                    int32_t *d_sublen = scratch.get<int32_t>(sb.ld_m);
+                    BatchOwner own;
+                    ok = anofox_hip_select_gather_device(d_src, ld_src, d_len, N, T, d_members, sb.off, sb.n_m, d_sub, sb.ld_m, d_sublen, st, err) &&
+                         select_run_batch(&methods[sb.method], sb.n_m, T, d_sub, sb.ld_m, d_sublen, &own, err) &&
+                         anofox_hip_select_scatter_device(own.b->d_yhat, own.b->d_lo, own.b->d_hi, own.b->d_model_code, own.b->d_status, d_members, sb.off,
+                                                          sb.n_m, h, nullptr, N, d_yh, d_lo, d_hi, d_code, d_stat, st, err);
+                    if (ok && out_model_names) {
+                        std::vector<int32_t> code(sb.n_m), stat(sb.n_m);
+                        HIPCHECK(hipMemcpy(code.data(), own.b->d_model_code, sb.n_m * sizeof(int32_t), hipMemcpyDeviceToHost));
+                        HIPCHECK(hipMemcpy(stat.data(), own.b->d_status, sb.n_m * sizeof(int32_t), hipMemcpyDeviceToHost));
+                        for (size_t j = 0; j < sb.n_m; j++) {
+                            char name[64];
+                            name[0] = 0;
+                            if (stat[j] == 0) anofox_hip_batch_model_name(own.b, j, code[j], name);
+                            names[(size_t)memb[sb.off + j]] = name;
+                        }
+                    }
+                }
+                if (ok)                                           // the series nobody won
+                    ok = anofox_hip_select_scatter_device(nullptr, nullptr, nullptr, nullptr, nullptr, d_members, 0, 0, h, d_winner, N, d_yh, d_lo, d_hi,
+                                                          d_code, d_stat, st, err);
+            } else if (ok) {
+                // ---- an ensemble: every method on the whole block, combined per cell; no combined intervals (lower and upper are NaN) ----
+                double *d_full = scratch.get<double>(M * Nh);
+                int32_t *d_fstat = scratch.get<int32_t>(M * N);
+                for (size_t m = 0; ok && m < M; m++) {
+                    BatchOwner own;
+                    ok = select_run_batch(&methods[m], N, T, d_src, ld_src, d_len, &own, err);
+                    if (!ok) break;
+                    HIPCHECK(hipMemcpy(d_full + m * Nh, own.b->d_yhat, Nh * sizeof(double), hipMemcpyDeviceToDevice));
+                    HIPCHECK(hipMemcpy(d_fstat + m * N, own.b->d_status, N * sizeof(int32_t), hipMemcpyDeviceToDevice));
+                }
+                if (ok) {
+                    const double *tab[SELECT_MAX_METHODS];
+                    for (size_t m = 0; m < M; m++) tab[m] = d_full + m * Nh;
+                    ok = anofox_hip_select_combine_device(tab, M, N, h, d_fstat, mode_code, d_winner, d_scores, ldN, 1, d_yh, d_stat, st, err);
+                }
+                if (ok) {
+                    const std::vector<double> nan_block(2 * Nh, std::numeric_limits<double>::quiet_NaN());
+                    HIPCHECK(hipMemcpy(d_lo, nan_block.data(), 2 * Nh * sizeof(double), hipMemcpyHostToDevice));
+                    HIPCHECK(hipMemset(d_code, 0, N * sizeof(int32_t)));
+                }
+            }
+            // ---- the picked or combined backtest forecasts, in the layout of the methods' own ----
+            if (ok && np > 0) {
+                const double *tab[SELECT_MAX_METHODS];
+                for (size_t m = 0; m < M; m++) tab[m] = d_bt_yh + m * nh;
+                ok = anofox_hip_select_combine_device(tab, M, np, h, d_bt_stat, mode_code, d_winner, d_scores, ldN, F, d_sel_yh, nullptr, st, err);
+                if (ok && pick) {
+                    for (size_t m = 0; m < M; m++) tab[m] = d_bt_act + m * nh;
+                    ok = anofox_hip_select_combine_device(tab, M, np, h, d_bt_stat, SELECT_PICK, d_winner, nullptr, 0, F, d_sel_act, nullptr, st, err);
+                } else if (ok) {                                  // the test rows of every live pair, whatever became of its forecasts
+                    int32_t *d_zero = scratch.get<int32_t>(np);
+                    HIPCHECK(hipMemset(d_zero, 0, np * sizeof(int32_t)));
+                    ok = anofox_hip_backtest_collect_device(d_src, ld_src, N, T, folds, F, d_ntest, d_zero, d_sel_yh, nullptr, nullptr, h, criterion,
+                                                            d_sel_act, d_work, d_work + nh, nullptr, d_rows, nullptr, st, err);
+                }
+            }
+            if (ok) {
+                HIPCHECK(hipMemcpy(fp.data(), d_fp, n_fp * sizeof(double), hipMemcpyDeviceToHost));
+                HIPCHECK(hipMemcpy(in.data(), d_in, n_int * sizeof(int32_t), hipMemcpyDeviceToHost));
+            } else {
+                HIPCHECK(hipDeviceSynchronize());
+            }
+        }
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(err, f);
+        return false;
+    }
+    if (!ok) {
+        if (err && err->code == SUCCESS) set_error(err, INTERNAL_ERROR, "Internal error: device batch failed");
+        return false;
+    }
+    const double *yh = fp.data(), *lo = yh + Nh, *hi = yh + 2 * Nh, *sel_yh = yh + 3 * Nh, *sel_act = sel_yh + nh, *best = sel_act + nh,
+                 *scores = best + N;
+    const int32_t *winner = in.data(), *stat = winner + N;
+    if (out_winner) std::memcpy(out_winner, winner, N * sizeof(int32_t));
+    if (out_best_score) std::memcpy(out_best_score, best, N * sizeof(double));
+    if (out_scores)
+        for (size_t m = 0; m < M; m++) std::memcpy(out_scores + m * N, scores + m * ldN, N * sizeof(double));
+    if (out_yhat) std::memcpy(out_yhat, yh, Nh * sizeof(double));
+    if (out_lower) std::memcpy(out_lower, lo, Nh * sizeof(double));
+    if (out_upper) std::memcpy(out_upper, hi, Nh * sizeof(double));
+    for (size_t s = 0; s < N; s++) {
+        // pick: the sub-batch's status; an ensemble: the combine's row status (1: no member gave a forecast)
+        const int32_t st_s = pick ? (stat[s] == STATUS_NOT_COMPUTED ? (int32_t)INTERNAL_ERROR : stat[s]) : (stat[s] == 0 ? 0 : (int32_t)INSUFFICIENT_DATA);
+        if (out_status) out_status[s] = st_s;
+        if (out_model_names) {
+            out_model_names[s][0] = 0;
+            if (st_s == 0) std::snprintf(out_model_names[s], 64, "%s", pick ? names[s].c_str() : mode);
+        }
+    }
+    if (out_backtest_yhat && nh) std::memcpy(out_backtest_yhat, sel_yh, nh * sizeof(double));
+    if (out_backtest_actual && nh) std::memcpy(out_backtest_actual, sel_act, nh * sizeof(double));
+    if (out_n_rows)
+        for (size_t p = 0; p < np; p++) {
+            int32_t k = 0;
+            for (size_t i = 0; i < h; i++) k += (sel_yh[p * h + i] == sel_yh[p * h + i] && sel_act[p * h + i] == sel_act[p * h + i]) ? 1 : 0;
+            out_n_rows[p] = k;
+        }
+    return true;
 }
 
 } // extern "C"

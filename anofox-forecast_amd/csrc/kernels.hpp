@@ -519,6 +519,44 @@ struct ReconcileApplyArgs {
 void launch_reconcile_factor(const ReconcileFactorArgs &, hipStream_t);
 void launch_reconcile_apply(const ReconcileApplyArgs &, hipStream_t);
 
+// The choice of a method per series from backtest scores (DESIGN.md section 3 "Selection"; select.hip)
+constexpr int SELECT_MAX_METHODS = 16;                 // the median's values and the partition's counters live in registers / LDS rows of 16
+enum { SELECT_PICK = 0, SELECT_MEAN = 1, SELECT_MEDIAN = 2, SELECT_INVERSE_SCORE = 3 };
+struct SelectWinnerArgs {
+    const double *scores; size_t ld;                   // [n_methods x ld]: method m of series s at m * ld + s
+    const int32_t *score_status;                       // [n_methods x n_series]: 0 = the score counts
+    int n_methods, n_series, fallback;                 // fallback in [-1, n_methods)
+    int32_t *winner; double *best_score; uint8_t *from_fallback;      // [n_series]
+    int32_t *counts; size_t n_wg;                      // [select_counts_size(n_series, n_methods)] scratch; n_wg = select_workgroups(n_series)
+    int32_t *offsets, *members;                        // [n_methods + 1], [n_series]
+};
+struct SelectMoveArgs {                                // gather (block) and scatter (results) by members[off .. off + n_m)
+    const int32_t *members; size_t off, n_m; int n_series;
+    // gather
+    const double *y; size_t ld_src; const int32_t *len; size_t t_rows;
+    double *y_out; size_t ld_m; int32_t *len_out;      // [t_rows x ld_m], [ld_m]
+    // scatter
+    int h;
+    const double *yhat_m, *lower_m, *upper_m; const int32_t *code_m, *status_m;      // the sub-batch: [n_m x h], [n_m]
+    const int32_t *winner;                             // null, or [n_series]: rows of winner -1 become NaN / INSUFFICIENT_DATA
+    double *yhat, *lower, *upper; int32_t *model_code, *status;          // [n_series x h], [n_series]; each may be null
+};
+struct SelectCombineArgs {
+    const double *const *blocks;                       // [n_methods] device pointers, the table itself in device memory: [n_rows x h] each
+    int n_methods, h, mode;                            // SELECT_*
+    size_t n_rows, group_div;                          // row r belongs to group r / group_div
+    const int32_t *member_status;                      // [n_methods x n_rows]
+    const int32_t *winner;                             // SELECT_PICK: [groups]
+    const double *weights; size_t ld_w;                // SELECT_INVERSE_SCORE: the scores [n_methods x ld_w]
+    double *out; int32_t *row_status;                  // [n_rows x h], [n_rows] (may be null)
+};
+size_t select_workgroups(size_t n_series);
+size_t select_counts_size(size_t n_series, int n_methods);
+void launch_select_winner(const SelectWinnerArgs &, hipStream_t);      // winners, the scan of the workgroup counts, the partition
+void launch_select_gather(const SelectMoveArgs &, hipStream_t);
+void launch_select_scatter(const SelectMoveArgs &, hipStream_t);       // the scatter, then (winner != null) the rows nobody won
+void launch_select_combine(const SelectCombineArgs &, hipStream_t);
+
 // ARIMAX: exogenous regressors (fit_exog.hip)
 constexpr int EXOG_MAX_REGRESSORS = 8;   // regressors per call; more fail loudly (COMPUTATION_ERROR)
 constexpr int32_t MODEL_CODE_ARIMAX = 50; // model_code of a series forecast by the ARIMAX path (model_name "ARIMAX")

@@ -314,22 +314,12 @@ def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | 
             "apply_status": apply_status, "sorted": srt}
 
 
-def backtest_block(y: torch.Tensor, lengths: torch.Tensor, opts: _lib.ForecastOptions, folds, *, n_series: int | None = None,
-                   metric: str = "rmse", stream: torch.cuda.Stream | None = None) -> dict:
-    """The walk-forward backtest of a resident block, no host copy: anofox_hip_backtest_expand_device -> DeviceBatch(n_pairs, t_train,
-    opts).set_block -> run -> anofox_hip_backtest_collect_device.
+def backtest_expand_block(y: torch.Tensor, lengths: torch.Tensor, folds, *, n_series: int | None = None,
+                          stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_backtest_expand_device on torch tensors: the training windows of every (series, fold) pair as one block, made once
+    and shared by every method that is backtested on it (backtest_block(..., expanded=...), select_block).
 
-    y [t_rows, ld] fp64 time-major without NULLs, lengths int32 [>= n_series], on one HIP device, contiguous; folds is the table of
-    api.backtest_fold_bounds / lib.backtest_folds ([(fold_id, train_start, train_end, test_start, test_end)], positions inclusive, the
-    same for every series).  Any ForecastOptions block is allowed.  Pair p = s * F + f is series s in fold index f, so every
-    [n_pairs, h] result viewed as [n_series, F * h] is the series-major block of one group per series that conformal_block(...,
-    series_major=True) and anofox_hip_metrics_device(stride_s = F * h, stride_t = 1) take as it lies.
-
-    Returns {"yhat", "lower", "upper" (views of the batch's results), "actual", "error", "abs_error": fp64 [n_pairs, h], NaN in the
-    last three where the row does not exist; "valid": uint8 [n_pairs, h]; "n_rows", "status", "model_code": int32 [n_pairs];
-    "scores": fp64 [F], the fold metric (backtest_metrics.backtest_metric's bits); "len_pairs", "n_test": int32 [ld_pairs]; "train":
-    the expanded block [t_train, ld_pairs]; "batch": the DeviceBatch (model names: batch.model_name(code, p)); "n_pairs",
-    "n_folds", "t_train"}."""
+    Returns {"train": fp64 [t_train, ld_pairs], "len_pairs", "n_test": int32 [ld_pairs], "t_train", "n_pairs", "ld_pairs", "n_folds"}."""
     L = _lib.load()
     assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
     t_rows, ld = int(y.shape[0]), int(y.shape[1])
@@ -341,7 +331,6 @@ def backtest_block(y: torch.Tensor, lengths: torch.Tensor, opts: _lib.ForecastOp
     F = len(folds)
     tab = _lib.make_folds(folds)
     t_train, n_pairs, ld_pairs = _lib.backtest_sizes(tab, F, n)
-    h = int(opts.horizon)
     try:
         train = torch.empty((t_train, ld_pairs), dtype=torch.float64, device=dev)
     except torch.cuda.OutOfMemoryError as e:
@@ -355,6 +344,45 @@ def backtest_block(y: torch.Tensor, lengths: torch.Tensor, opts: _lib.ForecastOp
                                              len_pairs.data_ptr(), n_test.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
     if not ok:
         raise RuntimeError(f"anofox_hip_backtest_expand_device failed: [{err.code}] {err.message.decode()}")
+    return {"train": train, "len_pairs": len_pairs, "n_test": n_test, "t_train": t_train, "n_pairs": n_pairs, "ld_pairs": ld_pairs,
+            "n_folds": F}
+
+
+def backtest_block(y: torch.Tensor, lengths: torch.Tensor, opts: _lib.ForecastOptions, folds, *, n_series: int | None = None,
+                   metric: str = "rmse", stream: torch.cuda.Stream | None = None, expanded: dict | None = None) -> dict:
+    """The walk-forward backtest of a resident block, no host copy: anofox_hip_backtest_expand_device -> DeviceBatch(n_pairs, t_train,
+    opts).set_block -> run -> anofox_hip_backtest_collect_device.
+
+    y [t_rows, ld] fp64 time-major without NULLs, lengths int32 [>= n_series], on one HIP device, contiguous; folds is the table of
+    api.backtest_fold_bounds / lib.backtest_folds ([(fold_id, train_start, train_end, test_start, test_end)], positions inclusive, the
+    same for every series).  Any ForecastOptions block is allowed.  Pair p = s * F + f is series s in fold index f, so every
+    [n_pairs, h] result viewed as [n_series, F * h] is the series-major block of one group per series that conformal_block(...,
+    series_major=True) and anofox_hip_metrics_device(stride_s = F * h, stride_t = 1) take as it lies.
+
+    Returns {"yhat", "lower", "upper" (views of the batch's results), "actual", "error", "abs_error": fp64 [n_pairs, h], NaN in the
+    last three where the row does not exist; "valid": uint8 [n_pairs, h]; "n_rows", "status", "model_code": int32 [n_pairs];
+    "scores": fp64 [F], the fold metric (backtest_metrics.backtest_metric's bits); "len_pairs", "n_test": int32 [ld_pairs]; "train":
+    the expanded block [t_train, ld_pairs]; "batch": the DeviceBatch (model names: batch.model_name(code, p)); "n_pairs",
+    "n_folds", "t_train"}.  `expanded`: what backtest_expand_block returned for the same block and folds -- the expanded block is
+    then shared (several methods on one block: select_block) instead of made again."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    F = len(folds)
+    tab = _lib.make_folds(folds)
+    h = int(opts.horizon)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    if expanded is None:
+        expanded = backtest_expand_block(y, lengths, folds, n_series=n, stream=st)
+    train, len_pairs, n_test = expanded["train"], expanded["len_pairs"], expanded["n_test"]
+    t_train, n_pairs = int(expanded["t_train"]), int(expanded["n_pairs"])
+    assert int(expanded["n_folds"]) == F and n_pairs == n * F, "the expanded block belongs to another block or fold table"
     batch = DeviceBatch(n_pairs, t_train, opts, dev)
     batch.set_block(train, len_pairs)
     batch.run(st)
@@ -594,6 +622,308 @@ def reconcile_block(forecast: torch.Tensor, column_of, method: str | int = "ols"
     if work is not None:
         work.record_stream(st)
     return {"y": out, "row_status": row_status[:n_rows], "factor": factor, "plan": plan}
+
+
+def _check_methods(methods) -> int:
+    """The method table of the selection entries: 1 .. lib.SELECT_MAX_METHODS option blocks that share one horizon >= 1."""
+    M = len(methods)
+    if M < 1:
+        raise ValueError("Invalid input: n_methods is 0, a selection needs at least 1 method")
+    if M > _lib.SELECT_MAX_METHODS:
+        raise ValueError(f"Invalid input: n_methods {M} exceeds the limit of {_lib.SELECT_MAX_METHODS} methods")
+    h = int(methods[0].horizon)
+    if h < 1:
+        raise ValueError(f"Invalid input: horizon must be at least 1, method 0 has {h}")
+    for m, o in enumerate(methods):
+        if int(o.horizon) != h:
+            raise ValueError(f"Invalid input: all methods share one horizon, method {m} has {int(o.horizon)} and method 0 has {h}")
+    return h
+
+
+def combine_block(blocks, mode: str | int, *, status: torch.Tensor | None = None, winner: torch.Tensor | None = None,
+                  weights: torch.Tensor | None = None, group_div: int = 1, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_select_combine_device on torch tensors: M <= 16 blocks [R, h] (fp64, contiguous, one device) combined cell by cell.
+
+    mode "pick" (needs winner int32 [groups]), "mean", "median", "inverse_score" (needs weights fp64 [M, ld_w >= groups]: the SCORES).
+    status int32 [M, R] (None: all 0); a member is live in a cell when its status is 0 and its value there is not NaN.  Row r belongs to
+    group r // group_div.  Returns {"y": fp64 [R, h] (NaN where no member is live), "row_status": int32 [R], 1 where the whole row is
+    NaN}."""
+    L = _lib.load()
+    M = len(blocks)
+    if M < 1 or M > _lib.SELECT_MAX_METHODS:
+        raise ValueError(f"Invalid input: n_methods {M} is outside [1, {_lib.SELECT_MAX_METHODS}] (the limit of {_lib.SELECT_MAX_METHODS} methods)")
+    code = _lib.select_mode(mode)
+    b0 = blocks[0]
+    for b in blocks:
+        assert b.dtype == torch.float64 and b.is_cuda and b.is_contiguous() and b.dim() == 2 and tuple(b.shape) == tuple(b0.shape)
+    R, h = int(b0.shape[0]), int(b0.shape[1])
+    dev = b0.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    if status is None:
+        status = torch.zeros((M, R), dtype=torch.int32, device=dev)
+    assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and tuple(status.shape) == (M, R)
+    groups = (R + int(group_div) - 1) // max(int(group_div), 1)
+    ld_w = 0
+    if winner is not None:
+        assert winner.dtype == torch.int32 and winner.is_cuda and winner.is_contiguous() and winner.numel() >= groups
+    if weights is not None:
+        assert weights.dtype == torch.float64 and weights.is_cuda and weights.is_contiguous() and weights.dim() == 2 and int(weights.shape[0]) == M
+        ld_w = int(weights.shape[1])
+    out = torch.empty((R, h), dtype=torch.float64, device=dev)
+    row_status = torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
+    tab = (C.c_void_p * M)(*[b.data_ptr() for b in blocks])
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_select_combine_device(tab, M, R, h, status.data_ptr(), code, ptr(winner), ptr(weights), ld_w, int(group_div),
+                                            out.data_ptr(), row_status.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        exc = ValueError if err.code == _lib.INVALID_INPUT else RuntimeError
+        raise exc(f"anofox_hip_select_combine_device failed: [{err.code}] {err.message.decode()}")
+    return {"y": out, "row_status": row_status[:R]}
+
+
+def select_winner_block(scores: torch.Tensor, score_status: torch.Tensor, fallback: int = -1, *, n_series: int | None = None,
+                        stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_select_winner_device on torch tensors: scores fp64 [M, ld], score_status int32 [M, n_series] -> {"winner" int32 [n],
+    "best_score" fp64 [n], "from_fallback" uint8 [n], "offsets" int32 [M + 1] and "members" int32 [n] (device tensors; only the first
+    offsets[M] members are written)}.  Nothing is read back."""
+    L = _lib.load()
+    assert scores.dtype == torch.float64 and scores.is_cuda and scores.is_contiguous() and scores.dim() == 2
+    M, ld = int(scores.shape[0]), int(scores.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert score_status.dtype == torch.int32 and score_status.is_cuda and score_status.is_contiguous() and tuple(score_status.shape) == (M, n)
+    dev = scores.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    winner = torch.empty(n, dtype=torch.int32, device=dev)
+    best = torch.empty(n, dtype=torch.float64, device=dev)
+    ff = torch.empty(n, dtype=torch.uint8, device=dev)
+    offsets = torch.zeros(M + 1, dtype=torch.int32, device=dev)
+    members = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_select_winner_device(scores.data_ptr(), ld, score_status.data_ptr(), M, n, int(fallback), winner.data_ptr(),
+                                           best.data_ptr(), ff.data_ptr(), offsets.data_ptr(), members.data_ptr(),
+                                           C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        exc = ValueError if err.code == _lib.INVALID_INPUT else RuntimeError
+        raise exc(f"anofox_hip_select_winner_device failed: [{err.code}] {err.message.decode()}")
+    return {"winner": winner, "best_score": best, "from_fallback": ff, "offsets": offsets, "members": members[:n]}
+
+
+def select_gather_block(y: torch.Tensor, lengths: torch.Tensor, members: torch.Tensor, off: int, n_m: int, *, n_series: int | None = None,
+                        ld_m: int | None = None, out: dict | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_select_gather_device on torch tensors: the columns members[off .. off + n_m) of a time-major block as a dense block
+    {"y": fp64 [t_rows, ld_m], "lengths": int32 [ld_m]} (ld_m: n_m rounded up to 64), which DeviceBatch(n_m, t_rows, opts).set_block
+    takes as it is.  `out` may bring the two tensors."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    assert members.dtype == torch.int32 and members.is_cuda and members.is_contiguous() and members.numel() >= int(off) + int(n_m)
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    out = dict(out or {})
+    ym, lm = out.get("y"), out.get("lengths")
+    if ld_m is None:
+        ld_m = int(ym.shape[1]) if ym is not None else max((int(n_m) + 63) // 64 * 64, 64)
+    if ym is None:
+        ym = torch.empty((t_rows, ld_m), dtype=torch.float64, device=dev)
+    if lm is None:
+        lm = torch.empty(ld_m, dtype=torch.int32, device=dev)
+    assert ym.dtype == torch.float64 and ym.is_cuda and ym.is_contiguous() and tuple(ym.shape) == (t_rows, ld_m)
+    assert lm.dtype == torch.int32 and lm.is_cuda and lm.is_contiguous() and lm.numel() >= ld_m
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_select_gather_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, members.data_ptr(), int(off), int(n_m),
+                                           ym.data_ptr(), ld_m, lm.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        exc = ValueError if err.code == _lib.INVALID_INPUT else RuntimeError
+        raise exc(f"anofox_hip_select_gather_device failed: [{err.code}] {err.message.decode()}")
+    return {"y": ym, "lengths": lm}
+
+
+def select_scatter_block(sub: dict | None, members: torch.Tensor, off: int, n_m: int, out: dict, *, winner: torch.Tensor | None = None,
+                         stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_select_scatter_device on torch tensors: `sub` is a sub-batch's DeviceBatch.results() (None with n_m = 0), `out` holds
+    "yhat", "lower", "upper" [n_series, h] and "model_code", "status" int32 [n_series] (each may be missing); with `winner` the rows of
+    series whose winner is -1 become NaN / code 0 / lib.INSUFFICIENT_DATA.  Returns `out`."""
+    L = _lib.load()
+    some = next(t for t in (out.get("yhat"), out.get("lower"), out.get("upper")) if t is not None)
+    n, h = int(some.shape[0]), int(some.shape[1])
+    dev = some.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    for k in ("yhat", "lower", "upper"):
+        t = out.get(k)
+        assert t is None or (t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (n, h))
+    for k in ("model_code", "status"):
+        t = out.get(k)
+        assert t is None or (t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= n)
+    sub = sub or {}
+    if n_m:
+        for k in ("yhat", "lower", "upper"):
+            assert out.get(k) is None or (sub[k].is_contiguous() and int(sub[k].shape[0]) >= n_m and int(sub[k].shape[1]) == h)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_select_scatter_device(ptr(sub.get("yhat")), ptr(sub.get("lower")), ptr(sub.get("upper")), ptr(sub.get("model_code")),
+                                            ptr(sub.get("status")), ptr(members), int(off), int(n_m), h, ptr(winner), n, ptr(out.get("yhat")),
+                                            ptr(out.get("lower")), ptr(out.get("upper")), ptr(out.get("model_code")), ptr(out.get("status")),
+                                            C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        exc = ValueError if err.code == _lib.INVALID_INPUT else RuntimeError
+        raise exc(f"anofox_hip_select_scatter_device failed: [{err.code}] {err.message.decode()}")
+    return out
+
+
+def score_block(actual: torch.Tensor, forecast: torch.Tensor, metric: str, *, n_groups: int | None = None,
+                stream: torch.cuda.Stream | None = None):
+    """One figure of anofox_hip_metrics_device per row group of two series-major blocks [n_groups, t_rows] (drop_nan: a row in which
+    either block holds a NaN does not count) -> (score fp64 [ld], status int32 [n_groups]: 0, or 1 with a NaN score where no row is
+    left).  With the [n_pairs, h] blocks of backtest_block viewed as [n_series, F * h] this is a method's score per series."""
+    L = _lib.load()
+    if metric not in _lib.SELECT_CRITERIA:
+        raise ValueError(f"Invalid input: unknown criterion '{metric}' (one of {', '.join(_lib.SELECT_CRITERIA)})")
+    fig = _lib.SELECT_CRITERIA.index(metric)
+    assert actual.dtype == torch.float64 and actual.is_cuda and actual.is_contiguous() and actual.dim() == 2
+    assert forecast.dtype == torch.float64 and forecast.is_cuda and forecast.is_contiguous() and tuple(forecast.shape) == tuple(actual.shape)
+    n, t_rows = int(actual.shape[0]), int(actual.shape[1])
+    n = n if n_groups is None else int(n_groups)
+    dev = actual.device
+    ld = max((n + 63) // 64 * 64, 64)
+    figures = torch.full((12, ld), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.ones(max(n, 1), dtype=torch.int32, device=dev)
+    lengths = torch.full((max(n, 1),), t_rows, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_metrics_device(actual.data_ptr(), forecast.data_ptr(), None, None, None, None, 0, None, 0, t_rows, 1, lengths.data_ptr(),
+                                     n, t_rows, 1 << fig, 0.5, True, figures.data_ptr(), ld, status.data_ptr(), C.c_void_p(st.cuda_stream),
+                                     C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_metrics_device failed: [{err.code}] {err.message.decode()}")
+    return figures[fig], status[:n]
+
+
+def select_block(y: torch.Tensor, lengths: torch.Tensor, methods, folds, *, metric: str = "rmse", mode: str = "pick", fallback: int = -1,
+                 n_series: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """Choose the forecast method per series from backtest scores, on a resident block, without a host copy: expand once -> one
+    backtest batch per method on the shared expanded block -> score per series (anofox_hip_metrics_device over each series' F * h
+    backtest cells, drop_nan) -> anofox_hip_select_winner_device -> mode "pick": gather the winners' columns, one sub-batch per method
+    that won something, scatter back; modes "mean" / "median" / "inverse_score": every method on the whole block, combined per cell.
+
+    y [t_rows, ld] fp64 time-major without NULLs, lengths int32 [>= n_series], one HIP device, contiguous; methods: a list of 1 .. 16
+    ForecastOptions of one horizon; folds as for backtest_block; metric one of lib.SELECT_CRITERIA; fallback in [-1, len(methods)): the
+    method of a series without an admissible score (-1: none, its rows are NaN with status lib.INSUFFICIENT_DATA).  An ensemble mode
+    needs ld == n_series rounded up to 64 (the block is run as it lies).
+
+    Returns {"winner" int32 [n], "best_score" fp64 [n], "from_fallback" uint8 [n], "scores" fp64 [M, ld_n], "score_status" int32 [M, n],
+    "offsets" numpy int32 [M + 1] (the one device-to-host read), "members" int32 [n]; the final "yhat", "lower", "upper" fp64 [n, h],
+    "model_code", "status" int32 [n] (an ensemble has no intervals -- lower / upper are NaN, conformal_block on selected_backtest gives
+    them -- model code 0 and status 0 / lib.INSUFFICIENT_DATA); "selected_backtest": {"yhat", "actual" fp64 [n_pairs, h], "valid" uint8
+    [n_pairs, h], "n_rows" int32 [n_pairs]}, the picked or combined backtest forecasts in the layout conformal_block(...,
+    series_major=True) takes viewed as [n, F * h]; "backtests": the per-method backtest_block dicts; "sub_batches": in pick mode
+    [(method, off, n_m, DeviceBatch)] (model names: batch.model_name(code, j) for members[off + j]), else the M whole-block batches;
+    "n_folds", "horizon"}."""
+    L = _lib.load()
+    h = _check_methods(methods)
+    M = len(methods)
+    if metric not in _lib.SELECT_CRITERIA:
+        raise ValueError(f"Invalid input: unknown criterion '{metric}' (one of {', '.join(_lib.SELECT_CRITERIA)})")
+    code = _lib.select_mode(mode)
+    if not -1 <= int(fallback) < M:
+        raise ValueError(f"Invalid input: fallback {int(fallback)} is outside [-1, {M})")
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    F = len(folds)
+    nan = float("nan")
+    # the backtest of every method on ONE expanded block, scored per series
+    expanded = backtest_expand_block(y, lengths, folds, n_series=n, stream=st)
+    n_pairs = int(expanded["n_pairs"])
+    ld_n = max((n + 63) // 64 * 64, 64)
+    scores = torch.full((M, ld_n), nan, dtype=torch.float64, device=dev)
+    score_status = torch.ones((M, n), dtype=torch.int32, device=dev)
+    backtests = []
+    for m, o in enumerate(methods):
+        bt = backtest_block(y, lengths, o, folds, n_series=n, metric=metric, stream=st, expanded=expanded)
+        backtests.append(bt)
+        if n_pairs and n:
+            sc, ss = score_block(bt["actual"].view(n, F * h), bt["yhat"].view(n, F * h), metric, stream=st)
+            scores[m, :n] = sc[:n]
+            score_status[m] = ss
+    chosen = select_winner_block(scores, score_status, fallback, n_series=n, stream=st)
+    winner, members = chosen["winner"], chosen["members"]
+    offsets = chosen["offsets"].cpu().numpy()
+    final = {"yhat": torch.empty((n, h), dtype=torch.float64, device=dev), "lower": torch.empty((n, h), dtype=torch.float64, device=dev),
+             "upper": torch.empty((n, h), dtype=torch.float64, device=dev), "model_code": torch.zeros(n, dtype=torch.int32, device=dev),
+             "status": torch.zeros(n, dtype=torch.int32, device=dev)}
+    subs = []
+    if code == 0:
+        for m, o in enumerate(methods):
+            off, n_m = int(offsets[m]), int(offsets[m + 1] - offsets[m])
+            if n_m == 0:
+                continue
+            g = select_gather_block(y, lengths, members, off, n_m, n_series=n, stream=st)
+            batch = DeviceBatch(n_m, t_rows, o, dev)
+            batch.set_block(g["y"], g["lengths"])
+            batch.run(st)
+            select_scatter_block(batch.results(), members, off, n_m, final, stream=st)
+            subs.append((m, off, n_m, batch))
+        select_scatter_block(None, members, 0, 0, final, winner=winner, stream=st)
+    else:
+        if ld != ld_n:
+            raise ValueError(f"an ensemble mode runs the block as it lies: ld must be {ld_n} (n_series rounded up to 64), got {ld}")
+        fulls, fstat = [], torch.zeros((M, n), dtype=torch.int32, device=dev)
+        for m, o in enumerate(methods):
+            batch = DeviceBatch(n, t_rows, o, dev)
+            batch.set_block(y, lengths)
+            batch.run(st)
+            r = batch.results()
+            fulls.append(r["yhat"])
+            fstat[m] = r["status"]
+            subs.append((m, 0, n, batch))
+        c = combine_block(fulls, code, status=fstat, winner=winner, weights=scores, group_div=1, stream=st)
+        final["yhat"] = c["y"]
+        final["lower"].fill_(nan)
+        final["upper"].fill_(nan)
+        final["status"] = torch.where(c["row_status"] == 0, 0, _lib.INSUFFICIENT_DATA).to(torch.int32)
+    # the picked or combined backtest forecasts, in the pair order of the methods' own
+    if n_pairs:
+        bstat = torch.stack([bt["status"] for bt in backtests]).contiguous()
+        sel_yhat = combine_block([bt["yhat"] for bt in backtests], code, status=bstat, winner=winner, weights=scores, group_div=F,
+                                 stream=st)["y"]
+        if code == 0:
+            sel_actual = combine_block([bt["actual"] for bt in backtests], 0, status=bstat, winner=winner, group_div=F, stream=st)["y"]
+        else:                                                   # the test rows of every live pair, whatever became of its forecasts
+            sel_actual = torch.empty_like(sel_yhat)
+            work = torch.empty((2,) + tuple(sel_yhat.shape), dtype=torch.float64, device=dev)
+            rows = torch.zeros(n_pairs, dtype=torch.int32, device=dev)
+            zero = torch.zeros(n_pairs, dtype=torch.int32, device=dev)
+            err = _lib.AnofoxError()
+            ok = L.anofox_hip_backtest_collect_device(y.data_ptr(), ld, n, t_rows, _lib.make_folds(folds), F, expanded["n_test"].data_ptr(),
+                                                      zero.data_ptr(), sel_yhat.data_ptr(), None, None, h, str(metric).encode(),
+                                                      sel_actual.data_ptr(), work[0].data_ptr(), work[1].data_ptr(), None, rows.data_ptr(),
+                                                      None, C.c_void_p(st.cuda_stream), C.byref(err))
+            if not ok:
+                raise RuntimeError(f"anofox_hip_backtest_collect_device failed: [{err.code}] {err.message.decode()}")
+    else:
+        sel_yhat = torch.empty((0, h), dtype=torch.float64, device=dev)
+        sel_actual = torch.empty((0, h), dtype=torch.float64, device=dev)
+    valid = (~torch.isnan(sel_yhat) & ~torch.isnan(sel_actual)).to(torch.uint8)
+    selected = {"yhat": sel_yhat, "actual": sel_actual, "valid": valid, "n_rows": valid.sum(1).to(torch.int32)}
+    return {"winner": winner, "best_score": chosen["best_score"], "from_fallback": chosen["from_fallback"], "scores": scores,
+            "score_status": score_status, "offsets": offsets, "members": members, **final, "selected_backtest": selected,
+            "backtests": backtests, "sub_batches": subs, "n_folds": F, "horizon": h}
 
 
 class DeviceBatch:

@@ -421,7 +421,14 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_backtest_batch",
     "anofox_hip_hierarchy_plan", "anofox_hip_hierarchy_device", "anofox_hip_hierarchy_batch",
     "anofox_hip_reconcile_plan", "anofox_hip_reconcile_factor_device", "anofox_hip_reconcile_apply_device", "anofox_hip_reconcile_batch",
+    "anofox_hip_select_winner_device", "anofox_hip_select_gather_device", "anofox_hip_select_scatter_device",
+    "anofox_hip_select_combine_device", "anofox_hip_select_batch",
 ]
+
+# include/anofox_fcst_hip.h block 8: the choice of a method per series
+SELECT_MAX_METHODS = 16
+SELECT_MODES = {"pick": 0, "mean": 1, "median": 2, "inverse_score": 3}
+SELECT_CRITERIA = ("mae", "mse", "rmse", "mape", "smape")      # their rows of anofox_hip_metrics_device's figures are 0 .. 4
 
 ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS / ANOFOX_ARIMA_CSS_ML
 
@@ -736,6 +743,24 @@ def load():
     L.anofox_hip_reconcile_batch.restype = C.c_bool
     L.anofox_hip_reconcile_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, P(AnofoxError)]
+    # block 8: the choice of a method per series
+    L.anofox_hip_select_winner_device.restype = C.c_bool
+    L.anofox_hip_select_winner_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_select_gather_device.restype = C.c_bool
+    L.anofox_hip_select_gather_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_select_scatter_device.restype = C.c_bool
+    L.anofox_hip_select_scatter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                   C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_select_combine_device.restype = C.c_bool
+    L.anofox_hip_select_combine_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_select_batch.restype = C.c_bool
+    L.anofox_hip_select_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_char_p, C.c_char_p,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -807,6 +832,23 @@ def backtest_sizes(folds, n_folds, n_series):
     if not load().anofox_hip_backtest_sizes(folds, n_folds, n_series, C.byref(t), C.byref(n), C.byref(ld), C.byref(err)):
         raise ValueError(f"anofox_hip_backtest_sizes failed: [{err.code}] {err.message.decode()}")
     return t.value, n.value, ld.value
+
+
+def make_options_table(methods):
+    """A contiguous ForecastOptions array (the `methods` table of anofox_hip_select_batch) from a list of option blocks."""
+    arr = (ForecastOptions * max(len(methods), 1))()
+    for k, o in enumerate(methods):
+        C.memmove(C.byref(arr[k]), C.byref(o), C.sizeof(ForecastOptions))
+    return arr
+
+
+def select_mode(mode):
+    """The code of a selection mode given by name (SELECT_MODES) or by code."""
+    if isinstance(mode, str):
+        if mode not in SELECT_MODES:
+            raise ValueError(f"unknown selection mode {mode!r}: one of {sorted(SELECT_MODES)}")
+        return SELECT_MODES[mode]
+    return int(mode)
 
 
 def make_hierarchy_options(route="auto", tile_min_members=0):

@@ -2206,6 +2206,169 @@ bool anofox_hip_reconcile_batch(const int32_t *column_of,
                                 int32_t *out_row_status,
                                 struct AnofoxError *out_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 8: the choice of a forecast method per series from backtest scores    */
+/* ------------------------------------------------------------------------- */
+/*
+ * fit -> forecast -> backtest -> score -> CHOOSE -> calibrate.  The reference compares models with one backtest statement per
+ * method and an AVG per model; it has no operator that chooses per series, so the names and the contract are this package's
+ * (DESIGN.md section 3 "Selection"): every result equals a serial restatement bit for bit, and no new floating-point sum is
+ * formed except the combine sums, whose order is the method order.  At most ANOFOX_HIP_SELECT_MAX_METHODS methods per call: more
+ * fail with INVALID_INPUT naming the limit.  Scope: no exogenous regressors, no NULLs in the block, fp64, one device (the calling
+ * thread's current device; anofox_hip_set_devices does not shard these entries).
+ */
+#define ANOFOX_HIP_SELECT_MAX_METHODS 16
+enum { ANOFOX_SELECT_PICK = 0,              /* every series takes the forecast of its winner */
+       ANOFOX_SELECT_MEAN = 1,              /* the live members added in method order from 0.0, divided by their number */
+       ANOFOX_SELECT_MEDIAN = 2,            /* the middle live value; of an even number (a + b) * 0.5 of the two middle ones */
+       ANOFOX_SELECT_INVERSE_SCORE = 3 };   /* sum(w y) / sum(w) with w = 1.0 / score, both sums in method order */
+
+/*
+ * The winner of every series and the stable partition of the series by winner.  scores is fp64 [n_methods x ld] (method m of
+ * series s at m * ld + s: one figure row of anofox_hip_metrics_device per method), score_status int32 [n_methods x n_series].
+ * Method m is admissible for series s when its status is 0 and its score is not NaN; +-inf are ordinary values.  The winner is the
+ * admissible method with the smallest score, the lowest m among equals (-0.0 and +0.0 are equal); without an admissible method it
+ * is `fallback`, an index in [-1, n_methods) (-1: none).  winner int32 [n_series]; best_score fp64 [n_series], NaN when the winner
+ * came from the fallback or is -1; from_fallback uint8 [n_series].  offsets int32 [n_methods + 1] and members int32 [n_series]:
+ * members[offsets[m] .. offsets[m + 1]) are the series method m won, ascending; only the first offsets[n_methods] entries of
+ * members are written, a series with winner -1 appears nowhere.  Everything stays on the device: the caller reads the n_methods + 1
+ * offsets.  Deterministic -- no atomic decides an order -- and correct for every n_series up to 2^31 - 1.  Runs on `stream` (NULL:
+ * the null stream) and returns after it has finished.
+ * INVALID_INPUT, each naming the offender: n_methods 0 or above the limit, fallback outside [-1, n_methods), ld < n_series.
+ */
+bool anofox_hip_select_winner_device(const double *scores,
+                                     size_t ld,
+                                     const int32_t *score_status,
+                                     size_t n_methods,
+                                     size_t n_series,
+                                     int32_t fallback,
+                                     int32_t *winner,
+                                     double *best_score,
+                                     uint8_t *from_fallback,
+                                     int32_t *offsets,
+                                     int32_t *members,
+                                     void *stream,
+                                     struct AnofoxError *out_error);
+
+/*
+ * The columns members[off .. off + n_m) of a time-major block y[t * ld_src + s] (t < t_rows, lengths int32 [n_series]) as a dense
+ * block: y_out[t * ld_m + j] = y[t * ld_src + members[off + j]] and len_out[j] = the length of that series for j < n_m; columns
+ * n_m <= j < ld_m are 0.0 with length 0 (y_out fp64 [t_rows x ld_m], len_out int32 [ld_m]).  With ld_m = n_m rounded up to 64 the
+ * result is what anofox_hip_batch_create(n_m, t_rows, ...) + anofox_hip_batch_set_device_block take.  off and n_m are host values
+ * (the caller has read offsets); a member outside [0, n_series) gives an empty column.  Returns after `stream` has finished.
+ */
+bool anofox_hip_select_gather_device(const double *y,
+                                     size_t ld_src,
+                                     const int32_t *lengths,
+                                     size_t n_series,
+                                     size_t t_rows,
+                                     const int32_t *members,
+                                     size_t off,
+                                     size_t n_m,
+                                     double *y_out,
+                                     size_t ld_m,
+                                     int32_t *len_out,
+                                     void *stream,
+                                     struct AnofoxError *out_error);
+
+/*
+ * The inverse for results: row j of the sub-batch's series-major yhat_m / lower_m / upper_m [n_m x horizon], code_m and status_m
+ * [n_m] (anofox_hip_batch_device_results) goes to row members[off + j] of yhat / lower / upper [n_series x horizon], model_code
+ * and status [n_series]; an output that is NULL is skipped.  With `winner` (int32 [n_series], may be NULL) the rows of every series
+ * whose winner is -1 are written as well: NaN, model code 0, status INSUFFICIENT_DATA.  n_m may be 0.  Returns after `stream` has
+ * finished.
+ */
+bool anofox_hip_select_scatter_device(const double *yhat_m,
+                                      const double *lower_m,
+                                      const double *upper_m,
+                                      const int32_t *code_m,
+                                      const int32_t *status_m,
+                                      const int32_t *members,
+                                      size_t off,
+                                      size_t n_m,
+                                      size_t horizon,
+                                      const int32_t *winner,
+                                      size_t n_series,
+                                      double *yhat,
+                                      double *lower,
+                                      double *upper,
+                                      int32_t *model_code,
+                                      int32_t *status,
+                                      void *stream,
+                                      struct AnofoxError *out_error);
+
+/*
+ * Combines n_methods device blocks [n_rows x horizon] (row r, step i at r * horizon + i; `blocks` is a HOST array of the device
+ * pointers) cell by cell into out [n_rows x horizon].  Row r belongs to group r / group_div: 1 for final forecasts, the number of
+ * folds for the [n_pairs x horizon] backtest blocks.  member_status is int32 [n_methods x n_rows]; member m is live in a cell when
+ * member_status[m * n_rows + r] is 0 and its value there is not NaN.
+ *   mode 0: out = blocks[winner[g]] (winner int32 [groups]; -1: NaN) -- plain indexing, member_status is not consulted;
+ *   mode 1: ((0.0 + y_m0) + y_m1) + ... over the live members in method order, divided by their number;
+ *   mode 2: the live values sorted in the total order of their bit patterns (-0.0 below +0.0): the middle one, or (a + b) * 0.5;
+ *   mode 3: weights fp64 [n_methods x ld_w] holds the SCORES (method m of group g at m * ld_w + g).  A live member whose score is
+ *           not NaN takes part with w = 1.0 / score: out = (((0.0 + w0 * y0) + w1 * y1) + ...) / ((0.0 + w0) + w1 + ...), every
+ *           product rounded before it is added.  If a member that takes part has score 0.0 the cell is instead the plain mean
+ *           (as mode 1) of exactly the members with score 0.0 -- the limit of the weighting.
+ * A cell without a live member is NaN.  row_status int32 [n_rows] (may be NULL): 1 when every cell of the row is NaN, else 0.
+ * Returns after `stream` has finished.  INVALID_INPUT: n_methods 0 or above the limit, an unknown mode, horizon 0, group_div 0,
+ * ld_w smaller than the number of groups.
+ */
+bool anofox_hip_select_combine_device(const double *const *blocks,
+                                      size_t n_methods,
+                                      size_t n_rows,
+                                      size_t horizon,
+                                      const int32_t *member_status,
+                                      int32_t mode,
+                                      const int32_t *winner,
+                                      const double *weights,
+                                      size_t ld_w,
+                                      size_t group_div,
+                                      double *out,
+                                      int32_t *row_status,
+                                      void *stream,
+                                      struct AnofoxError *out_error);
+
+/*
+ * The whole chain for host buffers.  values[i] / lengths[i] as for anofox_hip_backtest_batch; methods is a table of n_methods
+ * option blocks that share one horizon >= 1; folds as for anofox_hip_backtest_batch; criterion is "mae", "mse", "rmse", "mape" or
+ * "smape" (unlike the backtest's fold score, every other name is an error here); mode is "pick", "mean", "median" or
+ * "inverse_score"; fallback in [-1, n_methods).  The call packs once and expands ONCE; every method runs one batch on the shared
+ * expanded block and is scored per series over the existing rows of its n_folds * horizon backtest cells (the bits of
+ * anofox_hip_metrics_device with drop_nan).  "pick" then chooses, partitions, gathers, runs one sub-batch per method that won
+ * something and scatters; the other modes run every method on the whole block and combine (no combined intervals: out_lower and
+ * out_upper are NaN then, and out_model_names holds the mode's name).  Outputs, any of which may be NULL: out_winner int32 [n],
+ * out_best_score fp64 [n], out_scores fp64 [n_methods x n] (method m of series s at m * n + s), out_yhat / out_lower / out_upper
+ * fp64 [n x horizon], out_status int32 [n] (0, the sub-batch's status, or INSUFFICIENT_DATA where nothing was chosen or no member
+ * gave a forecast), out_model_names char [n][64] (empty unless the status is 0), out_backtest_yhat / out_backtest_actual fp64
+ * [n_pairs x horizon] -- the picked or combined backtest forecasts and their test values, NaN where a row does not exist, in
+ * the pair order of anofox_hip_backtest_sizes -- and out_n_rows int32 [n_pairs], the cells of a pair that hold both.
+ * An option block that anofox_hip_batch_create refuses fails the whole call with that error.  INVALID_INPUT, each naming the
+ * offender: n_methods 0 or above the limit, methods of different horizons, a horizon below 1, an unknown criterion or mode, a
+ * fallback out of range.  All argument errors come before the device is touched.
+ */
+bool anofox_hip_select_batch(const double *const *values,
+                             const size_t *lengths,
+                             size_t n_series,
+                             const ForecastOptions *methods,
+                             size_t n_methods,
+                             const AnofoxHipFold *folds,
+                             size_t n_folds,
+                             const char *criterion,
+                             const char *mode,
+                             int32_t fallback,
+                             int32_t *out_winner,
+                             double *out_best_score,
+                             double *out_scores,
+                             double *out_yhat,
+                             double *out_lower,
+                             double *out_upper,
+                             int32_t *out_status,
+                             char (*out_model_names)[64],
+                             double *out_backtest_yhat,
+                             double *out_backtest_actual,
+                             int32_t *out_n_rows,
+                             struct AnofoxError *out_batch_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
