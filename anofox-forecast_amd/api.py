@@ -4095,6 +4095,138 @@ def ts_compare_models_by(group, date, target, methods, horizon, frequency, folds
     return cols, {"method": labels, "wins": wins}
 
 
+# --------------------------------------------------------------------------------------------
+# bootstrap sample paths and their quantiles (include/anofox_fcst_hip.h block 9)
+# --------------------------------------------------------------------------------------------
+def paths_batch(points, pools, levels, n_paths=1000, mode="cumulative", joint=False, seed=0, column_of=None, want_paths=False):
+    """anofox_hip_paths_batch: `points` [n_series, h] point forecasts, `pools` one residual vector per series, `levels` up to 16
+    quantile levels in [0, 1].  One pack, the sample paths (residual bootstrap; mode "cumulative" or "independent"; joint=True: one
+    pool row per path and step for all series), then -- with column_of, int32 [n_groupings, n_series] as for hierarchy_batch -- the
+    paths added up the hierarchy, every cell the serial sum of its members' paths in plan order, then the quantiles of the leaf
+    block or of the aggregated block.
+
+    Returns ({"quantiles": fp64 [n_levels, n_out, h]; "status": int32 [n_out], 0 or lib.PATHS_NAN per output column;
+    "series_status": int32 [n_series] (lib.PATHS_*); "paths": fp64 [n_paths * h, ld] time-major, row p * h + k (want_paths, else
+    None); "n_out", "ld"}, error)."""
+    L = _lib.load()
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim == 1:
+        pts = pts.reshape(len(pools), -1) if len(pools) else pts.reshape(0, 0)
+    n, h = int(pts.shape[0]), int(pts.shape[1])
+    arrs = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1) for p in pools]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else None for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+    al = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    k = len(al)
+    opts = _lib.make_paths_options(mode, joint, seed)
+    co, G = None, 0
+    if column_of is not None:
+        co = np.ascontiguousarray(column_of, dtype=np.int32).reshape(-1, n) if n else np.zeros((0, 0), dtype=np.int32)
+        G = int(co.shape[0])
+    n_out, ld = C.c_size_t(), C.c_size_t()
+    err = _lib.AnofoxError()
+    out = {"quantiles": np.full((k, 0, h), np.nan), "status": np.zeros(0, dtype=np.int32), "series_status": np.zeros(n, dtype=np.int32),
+           "paths": None, "n_out": 0, "ld": 0}
+    report = lambda ok: {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+    args = (pts.ctypes.data, ptrs, lens, n, h, int(n_paths), C.byref(opts), C.sizeof(opts), al.ctypes.data, k,
+            co.ctypes.data if co is not None and co.size else None, G)
+    if not L.anofox_hip_paths_batch(*args, 0, None, None, None, None, C.byref(n_out), C.byref(ld), C.byref(err)):
+        return out, report(False)
+    out["n_out"], out["ld"] = int(n_out.value), int(ld.value)
+    out["quantiles"] = np.full((k, out["n_out"], h), np.nan)
+    out["status"] = np.full(out["n_out"], _lib.INTERNAL_ERROR, dtype=np.int32)
+    if want_paths:
+        out["paths"] = np.full((int(n_paths) * h, out["ld"]), np.nan)
+    ok = L.anofox_hip_paths_batch(*args, out["ld"], out["quantiles"].ctypes.data, out["status"].ctypes.data, out["series_status"].ctypes.data,
+                                  out["paths"].ctypes.data if want_paths else None, C.byref(n_out), C.byref(ld), C.byref(err))
+    return out, report(ok)
+
+
+def ts_forecast_quantiles_by(group, date, target, method, horizon, frequency, levels, residual_folds=10, n_paths=1000, mode="cumulative",
+                             joint=True, seed=0, params=None, group_name="id", date_name="ds", info=None):
+    """ts_forecast_by with quantile forecasts at `levels` from bootstrap sample paths, all of it on the device.
+
+    The residuals are out-of-sample: a backtest with horizon 1 over `residual_folds` rolling folds of the resident block
+    (device.backtest_block) gives every series one one-step error per fold, at the same positions for every series -- so that a
+    joint draw takes the same date for all of them.  The method is then fitted on the whole block (DeviceBatch), paths_block draws
+    n_paths paths around its point forecasts and path_quantiles_block reads the levels off them.  The table's series are expected
+    on a common date grid; the target takes no NULLs (fill them first, ts_fill_nulls_*_by).
+
+    The columns and the row order are those of ts_forecast_by (a group whose fit fails yields no rows), plus one column "q<level>"
+    per level ("q0.05", "q0.5", ...) and paths_status (lib.PATHS_*): a group whose backtest leaves it no residual (PATHS_EMPTY), or
+    not one in every fold (a NaN in its pool: PATHS_NAN), has NaN quantiles and says so there.  `info` (a dict) receives "errors"
+    (the pool, numpy [n_groups, n_folds]), "folds", "status", "series_status", "groups"."""
+    order, series, last, kind, us, kept, dtype = _select_groups(group, date, target, "ts_forecast_quantiles_by")
+    b = bind(method, horizon, frequency, params)
+    opts = options_from_bind(b)
+    opts1 = options_from_bind(bind(method, 1, frequency, params))
+    al = [float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1)]
+    names = ["q%g" % v for v in al]
+    out = {group_name: [], "forecast_step": [], date_name: [], "yhat": [], "yhat_lower": [], "yhat_upper": [], "model_name": []}
+    out.update({c: [] for c in names})
+    out["paths_status"] = []
+    h = int(horizon)
+    if series:
+        import torch
+        from . import device as _device
+        if not torch.cuda.is_available():
+            raise RuntimeError("ts_forecast_quantiles_by needs a HIP device (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n, T = len(series), max(len(s) for s in series)
+        block = _device.pack_time_major(np.stack([np.pad(s, (0, T - len(s))) for s in series]))
+        y = torch.from_numpy(block).to(dev)
+        lens = torch.zeros(block.shape[1], dtype=torch.int32)
+        lens[:n] = torch.tensor([len(s) for s in series], dtype=torch.int32)
+        lens = lens.to(dev)
+        bounds = _lib.backtest_folds(T, 1, int(residual_folds), "expanding")
+        F = len(bounds)
+        try:
+            if F:
+                bt = _device.backtest_block(y, lens, opts1, bounds, n_series=n)
+                pool = bt["error"].view(n, F)
+            else:
+                pool = torch.zeros((n, 0), dtype=torch.float64, device=dev)
+            batch = _device.DeviceBatch(n, T, opts, dev)
+            batch.set_block(y, lens)
+            batch.run()
+            res = batch.results()
+            g = _device.paths_block(res["yhat"], pool, n_paths=int(n_paths), mode=mode, joint=joint, seed=seed, series_major=True,
+                                    pool_series_major=True, n_series=n)
+            q = _device.path_quantiles_block(g["paths"], al, horizon=h, n_paths=int(n_paths), n_cols=n)
+        except ValueError as e:
+            raise InvalidInputException(str(e)) from e
+        quant = q["quantiles"].cpu().numpy()
+        series_status = g["status"].cpu().numpy()
+        col_status = q["status"].cpu().numpy()
+        yhat, lower, upper = (res[c].cpu().numpy() for c in ("yhat", "lower", "upper"))
+        fit_status, codes = res["status"].cpu().numpy(), res["model_code"].cpu().numpy()
+        if info is not None:
+            info.update({"errors": pool.cpu().numpy(), "folds": bounds, "status": col_status, "series_status": series_status, "groups": list(order)})
+        f = b.frequency
+        for s, k in enumerate(order):
+            if fit_status[s] != 0:
+                continue                      # the group yields no rows, as in ts_forecast_by
+            name = batch.model_name(int(codes[s]), s)
+            st_s = int(series_status[s]) if series_status[s] != 0 else int(col_status[s])
+            for i in range(h):
+                out[group_name].append(None if k == "__NULL__" else k)
+                out["forecast_step"].append(i + 1)
+                out[date_name].append(compute_forecast_date(last[s], i + 1, f, kind))
+                out["yhat"].append(yhat[s, i])
+                out["yhat_lower"].append(lower[s, i])
+                out["yhat_upper"].append(upper[s, i])
+                out["model_name"].append(name)
+                for l, c in enumerate(names):
+                    out[c].append(quant[l, s, i])
+                out["paths_status"].append(st_s)
+    out["forecast_step"] = np.array(out["forecast_step"], dtype=np.int32)
+    out[date_name] = _from_micros(np.array(out[date_name], dtype=np.int64), kind, dtype)
+    for c in ["yhat", "yhat_lower", "yhat_upper"] + names:
+        out[c] = np.array(out[c], dtype=np.float64)
+    out["paths_status"] = np.array(out["paths_status"], dtype=np.int32)
+    return out
+
+
 anofox_fcst_ts_aggregate_hierarchy = ts_aggregate_hierarchy
 anofox_fcst_ts_combine_keys = ts_combine_keys
 anofox_fcst_ts_split_keys = ts_split_keys

@@ -42,6 +42,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_parts.hpp"         // how an auto-detected batch is cut into device batches (PartPlan), and how a batch's results reach the caller's arrays
 #include "host_reconcile_plan.hpp" // the host-only planner of the reconciliation entries (bottom columns, aggregates, the transposed plan)
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
+#include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
 struct Plan {
@@ -7190,6 +7191,202 @@ bool anofox_hip_select_batch(const double *const *values, const size_t *lengths,
             out_n_rows[p] = k;
         }
     return true;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Bootstrap sample paths and their quantiles (DESIGN.md section 3 "Sample paths"; paths.hip, host_paths_plan.hpp)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+bool paths_plan_report(PathsPlanResult r, const std::string &message, AnofoxError *err)
+{
+    if (r == PATHS_PLAN_OK) return true;
+    if (r == PATHS_PLAN_NULL) set_error(err, NULL_POINTER, "Null pointer argument");
+    else set_error(err, INVALID_INPUT, message);
+    return false;
+}
+
+bool paths_options_ok(const AnofoxHipPathsOptions *o, size_t struct_size, AnofoxError *err)
+{
+    std::string message;
+    // (the fields are read only once the size has been found right)
+    const bool readable = o && struct_size == sizeof(AnofoxHipPathsOptions);
+    return paths_plan_report(paths_options_check(o != nullptr, struct_size, sizeof(AnofoxHipPathsOptions), readable ? o->mode : 0,
+                                                 readable ? o->joint : 0, readable ? o->route : 0, &message), message, err);
+}
+
+} // namespace
+
+extern "C" {
+
+static_assert(sizeof(AnofoxHipPathsOptions) == 24 && offsetof(AnofoxHipPathsOptions, seed) == 16, "AnofoxHipPathsOptions layout");
+static_assert(PATHS_PLAN_MAX_PATHS == (size_t)PATHS_MAX_PATHS && PATHS_PLAN_MAX_LEVELS == (size_t)PATHS_MAX_LEVELS &&
+              PATHS_PLAN_MAX_POOL_ROWS == PATHS_MAX_POOL_ROWS && PATHS_PLAN_MAX_ROWS == PATHS_MAX_ROWS &&
+              PATHS_MAX_PATHS == ANOFOX_HIP_PATHS_MAX_PATHS && PATHS_MAX_LEVELS == ANOFOX_HIP_PATHS_MAX_LEVELS &&
+              PATHS_MAX_POOL_ROWS == ANOFOX_HIP_PATHS_MAX_POOL_ROWS && PATHS_MAX_ROWS == (size_t)HIER_SPAN_MAX, "the limits of the sample-path entries");
+
+bool anofox_hip_paths_device(const double *point, size_t point_stride_s, size_t point_stride_t, const double *pool, size_t pool_stride_s,
+                             size_t pool_stride_t, const int32_t *pool_lengths, size_t pool_rows, size_t n_series, size_t horizon, size_t n_paths,
+                             const AnofoxHipPathsOptions *options, size_t struct_size, double *paths_out, size_t ld_out, int32_t *status,
+                             void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!paths_options_ok(options, struct_size, out_error)) return false;
+    if (!point || !paths_out || !status || (pool_rows > 0 && !pool)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_pool_check(pool_rows, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld_out, n_series, "ld_out", "n_series", &message), message, out_error)) return false;
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    PathsArgs a{};
+    a.point = point; a.point_stride_s = point_stride_s; a.point_stride_t = point_stride_t;
+    a.pool = pool; a.pool_stride_s = pool_stride_s; a.pool_stride_t = pool_stride_t; a.pool_len = pool_lengths;
+    a.pool_rows = (int)pool_rows; a.n_series = (int)n_series; a.horizon = (int)horizon; a.n_paths = (int)n_paths;
+    a.mode = options->mode; a.joint = options->joint;
+    a.key0 = (uint32_t)(options->seed & 0xffffffffull); a.key1 = (uint32_t)(options->seed >> 32);
+    a.paths = paths_out; a.ld_out = ld_out; a.status = status;
+    try {
+        (void)hipGetLastError();
+        launch_paths(a, (hipStream_t)stream);
+        LAUNCHCHECK("paths");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_path_quantiles_device(const double *paths, size_t ld, size_t n_cols, size_t horizon, size_t n_paths, const double *levels,
+                                      size_t n_levels, double *out, int32_t *status, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!paths || !out || !status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_levels_check(levels, n_levels, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld, n_cols, "ld", "n_cols", &message), message, out_error)) return false;
+    if (n_cols == 0) return true;
+    if (!device_ready(out_error)) return false;
+    PathQuantilesArgs a{};
+    a.paths = paths; a.ld = ld; a.n_cols = (int)n_cols; a.horizon = (int)horizon; a.n_paths = (int)n_paths;
+    a.n_levels = (int)n_levels;
+    for (size_t k = 0; k < n_levels; k++) a.levels[k] = levels[k];
+    a.out = out; a.status = status;
+    try {
+        (void)hipGetLastError();
+        launch_path_quantiles(a, (hipStream_t)stream);
+        LAUNCHCHECK("path quantiles");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_paths_batch(const double *points, const double *const *pools, const size_t *pool_lengths, size_t n_series, size_t horizon,
+                            size_t n_paths, const AnofoxHipPathsOptions *options, size_t struct_size, const double *levels, size_t n_levels,
+                            const int32_t *column_of, size_t n_groupings, size_t ld, double *out_quantiles, int32_t *out_status,
+                            int32_t *out_series_status, double *out_paths, size_t *out_n_out, size_t *out_ld, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!paths_options_ok(options, struct_size, out_error)) return false;
+    if (n_series > 0 && (!points || !pools || !pool_lengths)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_levels_check(levels, n_levels, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(SIZE_MAX, n_series, "ld", "n_series", &message), message, out_error)) return false;
+    size_t pool_rows = 0;
+    if (!paths_plan_report(paths_batch_pools(pool_lengths, n_series, &pool_rows, &message), message, out_error)) return false;
+    for (size_t s = 0; s < n_series; s++)
+        if (pool_lengths[s] > 0 && !pools[s]) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const bool planned = column_of != nullptr && n_groupings > 0;
+    size_t n_out = n_series, nnz = 0;
+    std::vector<int32_t> offs, memb;
+    if (planned) {
+        if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, nullptr, nullptr, out_error)) return false;
+        offs.resize(n_out + 1);
+        memb.resize(std::max<size_t>(nnz, 1));
+        if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, offs.data(), memb.data(), out_error)) return false;
+    }
+    const size_t need_ld = paths_ld(n_out);
+    if (out_n_out) *out_n_out = n_out;
+    if (out_ld) *out_ld = need_ld;
+    if (!out_quantiles) return true;
+    if (ld != need_ld) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is not what the sizing call returns"); return false; }
+    if (!out_status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_series == 0 || n_out == 0) return true;
+    if (!device_ready(out_error)) return false;
+
+    const size_t ld_s = paths_ld(n_series), rows = n_paths * horizon, pool_t = std::max<size_t>(pool_rows, 1);
+    const size_t leaf_cells = rows * ld_s, out_cells = planned ? rows * need_ld : 0, q_cells = n_levels * n_out * horizon;
+    Scratch scratch;
+    bool ok = true;
+    try {
+        std::vector<double> pool_block(pool_t * ld_s, 0.0);
+        const std::vector<int32_t> len = block_lengths(pool_lengths, n_series, ld_s);
+        pack_time_major(pool_block.data(), ld_s, pools, pool_lengths, n_series);
+        double *d_paths = nullptr, *d_agg = nullptr;
+        try {
+            d_paths = scratch.get<double>(leaf_cells);
+            if (planned) d_agg = scratch.get<double>(out_cells);
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the path block of " + std::to_string(rows) + " x " + std::to_string(ld_s) +
+                      " values" + (planned ? " and its aggregate of " + std::to_string(rows) + " x " + std::to_string(need_ld) + " values" : std::string()) +
+                      " need " + std::to_string((leaf_cells + out_cells) * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            double *d_point = scratch.get<double>(n_series * horizon);
+            double *d_pool = scratch.get<double>(pool_t * ld_s);
+            int32_t *d_len = scratch.get<int32_t>(ld_s);
+            int32_t *d_status = scratch.get<int32_t>(ld_s);
+            double *d_q = scratch.get<double>(q_cells);
+            int32_t *d_qstatus = scratch.get<int32_t>(need_ld);
+            HIPCHECK(hipMemcpy(d_point, points, n_series * horizon * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_pool, pool_block.data(), pool_t * ld_s * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemset(d_paths, 0, leaf_cells * sizeof(double)));          // the padding columns
+            ok = anofox_hip_paths_device(d_point, horizon, 1, d_pool, 1, ld_s, d_len, pool_rows, n_series, horizon, n_paths, options, struct_size,
+                                         d_paths, ld_s, d_status, nullptr, out_error);
+            const double *d_block = d_paths;
+            size_t ld_block = ld_s;
+            if (ok && planned) {
+                AnofoxHipHierarchyOptions ho{};
+                std::vector<int32_t> full(ld_s, 0);
+                for (size_t s = 0; s < n_series; s++) full[s] = (int32_t)rows;
+                int32_t *d_rows = scratch.get<int32_t>(ld_s);
+                int32_t *d_plan = scratch.get<int32_t>(n_out + 1 + nnz);
+                int32_t *d_len_out = scratch.get<int32_t>(need_ld);
+                int64_t *d_first_out = scratch.get<int64_t>(need_ld);
+                HIPCHECK(hipMemcpy(d_rows, full.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(d_plan, offs.data(), (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+                if (nnz) HIPCHECK(hipMemcpy(d_plan + n_out + 1, memb.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemset(d_agg, 0, out_cells * sizeof(double)));
+                ok = anofox_hip_hierarchy_device(d_paths, nullptr, nullptr, ld_s, d_rows, nullptr, n_series, rows, d_plan, d_plan + n_out + 1, n_out,
+                                                 nnz, &ho, sizeof ho, rows, d_agg, nullptr, need_ld, d_len_out, d_first_out, nullptr, out_error);
+                d_block = d_agg;
+                ld_block = need_ld;
+            }
+            if (ok)
+                ok = anofox_hip_path_quantiles_device(d_block, ld_block, n_out, horizon, n_paths, levels, n_levels, d_q, d_qstatus, nullptr,
+                                                      out_error);
+            if (ok) {
+                HIPCHECK(hipMemcpy(out_quantiles, d_q, q_cells * sizeof(double), hipMemcpyDeviceToHost));      // waits for the null stream
+                HIPCHECK(hipMemcpy(out_status, d_qstatus, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_series_status) HIPCHECK(hipMemcpy(out_series_status, d_status, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_paths) HIPCHECK(hipMemcpy(out_paths, d_block, rows * ld_block * sizeof(double), hipMemcpyDeviceToHost));
+            } else HIPCHECK(hipDeviceSynchronize());
+        }
+        scratch.settled();                                                 // (either way the device has been waited for)
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return ok;
 }
 
 } // extern "C"

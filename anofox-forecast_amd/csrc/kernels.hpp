@@ -695,6 +695,36 @@ int launch_arima(const ArimaArgs &, hipStream_t);   // returns the number of ker
 // whose quotients differ (0 is the claim), ~0 when the device could not run it; *first_bad: one of them
 unsigned long long recip_selftest(unsigned long long n, unsigned long long seed, double *first_bad, hipStream_t stream);
 
+// Bootstrap sample paths and their quantiles (DESIGN.md section 3 "Sample paths"; paths.hip).  Element (series s, row t) of the
+// point block and of the pool is at s * stride_s + t * stride_t, as for the metrics entries.
+enum { PATHS_CUMULATIVE = 0, PATHS_INDEPENDENT = 1 };
+enum { PATHS_ROUTE_AUTO = 0, PATHS_ROUTE_LANE = 1 };
+constexpr int PATHS_MAX_PATHS = 2048;                  // paths per call: one column of keys is 16 KiB of LDS
+constexpr int PATHS_MAX_LEVELS = 16;                   // quantile levels per call
+constexpr size_t PATHS_MAX_POOL_ROWS = (size_t)1 << 20; // the index rule has no rejection step: its bias is at most n / 2^32
+constexpr size_t PATHS_MAX_ROWS = (size_t)1 << 30;      // n_paths * horizon: the row limit of the hierarchy entry
+constexpr int32_t PATHS_OK = 0, PATHS_EMPTY = 1, PATHS_NAN = 2, PATHS_RAGGED = 3;
+struct PathsArgs {
+    const double *point; size_t point_stride_s, point_stride_t;      // [n_series x horizon]
+    const double *pool; size_t pool_stride_s, pool_stride_t;         // [n_series x pool_rows]
+    const int32_t *pool_len;                     // [n_series], null: every pool has pool_rows rows; cut to [0, pool_rows]
+    int pool_rows, n_series, horizon, n_paths;
+    int mode, joint;                             // PATHS_*; joint: one pool row per (path, step) for all series
+    uint32_t key0, key1;                         // the seed's low and high word
+    double *paths; size_t ld_out;                // [n_paths * horizon x ld_out], row p * horizon + k
+    int32_t *status;                             // [n_series]
+    int path_groups;                             // set by launch_paths: groups of 4 paths a tile of 64 series is cut into
+};
+struct PathQuantilesArgs {
+    const double *paths; size_t ld;              // [n_paths * horizon x ld]
+    int n_cols, horizon, n_paths;
+    int n_levels; double levels[PATHS_MAX_LEVELS];
+    double *out;                                 // [n_levels x n_cols x horizon]
+    int32_t *status;                             // [n_cols]
+};
+void launch_paths(const PathsArgs &, hipStream_t);                     // the statuses, then the paths
+void launch_path_quantiles(const PathQuantilesArgs &, hipStream_t);
+
 void launch_prep(const PrepArgs &, hipStream_t);
 void launch_select(const SelectArgs &, hipStream_t);
 void launch_classic(int kind, const ClassicArgs &, hipStream_t);

@@ -518,6 +518,122 @@ def aggregate_block(y: torch.Tensor, lengths: torch.Tensor, column_of, *, first:
     return {"y": yo, "present": po, "lengths": len_out, "first": first_out, "t_out": t_out, "n_out": n_out}
 
 
+def _paths_failed(entry: str, err) -> Exception:
+    text = f"{entry} failed: [{err.code}] {err.message.decode()}"
+    return ValueError(text) if err.code in (_lib.INVALID_INPUT, _lib.NULL_POINTER) else RuntimeError(text)
+
+
+def _paths_rows(n_paths: int, horizon: int) -> None:
+    # (the library checks the same before it touches the device; here the check comes before the output block is allocated)
+    if not 1 <= n_paths <= _lib.PATHS_MAX_PATHS:
+        raise ValueError(f"n_paths {n_paths} is outside [1, {_lib.PATHS_MAX_PATHS}], the limit of paths per call")
+    if horizon < 1:
+        raise ValueError("horizon must be at least 1")
+
+
+def paths_block(point: torch.Tensor, pool: torch.Tensor, *, pool_lengths: torch.Tensor | None = None, n_paths: int = 1000,
+                mode: str | int = "cumulative", joint: bool = False, seed: int = 0, series_major: bool = False,
+                pool_series_major: bool = False, n_series: int | None = None, route: str | int = "auto",
+                out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_paths_device on torch tensors: residual-bootstrap sample paths around a block of point forecasts, no host copy.
+
+    point: time-major [h, ld], or with series_major=True the [n_series, h] layout of DeviceBatch.results()["yhat"].  pool: the
+    residuals the paths draw from, time-major [pool_rows, ld], or with pool_series_major=True [n_series, pool_rows] -- the "error"
+    block of backtest_block viewed as [n_series, n_folds * h] is taken as it lies.  pool_lengths int32 [>= n_series] on the device:
+    the rows of every pool (None: all pool_rows).  mode "cumulative" (the errors add up along a path, so the band grows with the
+    horizon) or "independent"; joint=True draws ONE pool row per (path, step) for all series -- the same date, which keeps the
+    dependence between the series in their sums -- and needs every pool to have pool_rows rows.  The draws are Philox4x32-10 on the
+    counter (path, series, step): the same seed gives the same bits whatever the launch shape.
+
+    Returns {"paths": fp64 [n_paths * h, ld_out] time-major, row p * h + k of column s (`out`, or a new zero-filled block with
+    ld_out = n_series rounded up to 64), "status": int32 [n_series] (lib.PATHS_OK / _EMPTY / _NAN / _RAGGED; the paths of a series
+    whose status is not 0 are NaN), "n_series", "horizon", "n_paths"}.  The block is what aggregate_block takes with lengths
+    n_paths * h; path_quantiles_block reads the quantiles off it or off its aggregate."""
+    L = _lib.load()
+    for t in (point, pool):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 2
+    if series_major:
+        n_f, h = int(point.shape[0]), int(point.shape[1])
+        fs, ft = h, 1
+    else:
+        h, n_f = int(point.shape[0]), int(point.shape[1])
+        fs, ft = 1, n_f
+    if pool_series_major:
+        n_p, pool_rows = int(pool.shape[0]), int(pool.shape[1])
+        es, et = pool_rows, 1
+    else:
+        pool_rows, n_p = int(pool.shape[0]), int(pool.shape[1])
+        es, et = 1, n_p
+    n = min(n_f, n_p) if n_series is None else int(n_series)
+    assert 0 < n <= n_f and n <= n_p
+    n_paths = int(n_paths)
+    _paths_rows(n_paths, h)
+    dev = point.device
+    if pool_lengths is not None:
+        assert pool_lengths.dtype == torch.int32 and pool_lengths.is_cuda and pool_lengths.is_contiguous() and pool_lengths.numel() >= n
+    opts = _lib.make_paths_options(mode, joint, seed, route)
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    if out is None:
+        ld_out = (n + 63) // 64 * 64
+        try:
+            out = torch.zeros((n_paths * h, ld_out), dtype=torch.float64, device=dev)
+        except torch.cuda.OutOfMemoryError as e:
+            raise RuntimeError(f"the path block of {n_paths * h} x {ld_out} values needs {n_paths * h * ld_out * 8} bytes of device "
+                               "memory") from e
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.dim() == 2 and int(out.shape[0]) == n_paths * h
+    ld_out = int(out.shape[1])
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_paths_device(point.data_ptr(), fs, ft, pool.data_ptr(), es, et, pool_lengths.data_ptr() if pool_lengths is not None else None,
+                                   pool_rows, n, h, n_paths, C.byref(opts), C.sizeof(opts), out.data_ptr(), ld_out, status.data_ptr(),
+                                   C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_paths_device", err)
+    return {"paths": out, "status": status, "n_series": n, "horizon": h, "n_paths": n_paths}
+
+
+def path_quantiles_block(paths: torch.Tensor, levels, *, horizon: int, n_paths: int, n_cols: int | None = None,
+                         stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_path_quantiles_device on torch tensors: the quantiles of a block of sample paths, no host copy.
+
+    paths [n_paths * horizon, ld] fp64 time-major as paths_block or aggregate_block wrote it; levels: up to 16 values in [0, 1].
+    The n_paths values of a (column, step) are sorted by the total order of the bits (-0.0 below +0.0) and level q is
+    s[lo] * (1 - frac) + s[up] * frac at index q * (n_paths - 1).
+
+    Returns {"quantiles": fp64 [n_levels, n_cols, horizon] -- the shape of conformal_block's "lower" / "upper" for a series-major
+    forecast --, "status": int32 [n_cols]: 0, or lib.PATHS_NAN when a path of the column holds a NaN; every quantile of it is NaN}.
+
+    The chain for the band of an aggregate -- the quantile of a sum is not the sum of the quantiles, so the paths are added up, not
+    the bands:
+        g = paths_block(yhat, errors, n_paths=1000, joint=True, series_major=True, pool_series_major=True)
+        rows = torch.full((g["n_series"],), 1000 * h, dtype=torch.int32, device=yhat.device)
+        a = aggregate_block(g["paths"], rows, column_of, n_series=g["n_series"], t_out=1000 * h)
+        q = path_quantiles_block(a["y"], [0.05, 0.5, 0.95], horizon=h, n_paths=1000, n_cols=a["n_out"])"""
+    L = _lib.load()
+    assert paths.dtype == torch.float64 and paths.is_cuda and paths.is_contiguous() and paths.dim() == 2
+    horizon, n_paths = int(horizon), int(n_paths)
+    _paths_rows(n_paths, horizon)
+    ld = int(paths.shape[1])
+    n = ld if n_cols is None else int(n_cols)
+    assert int(paths.shape[0]) >= n_paths * horizon and 0 < n <= ld
+    al = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    k = len(al)
+    dev = paths.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    q = torch.full((max(min(k, _lib.PATHS_MAX_LEVELS), 1), n, horizon), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_path_quantiles_device(paths.data_ptr(), ld, n, horizon, n_paths, al.ctypes.data, k, q.data_ptr(), status.data_ptr(),
+                                            C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_path_quantiles_device", err)
+    return {"quantiles": q, "status": status}
+
+
 _RECONCILE_PLAN_KEYS = ("col_offsets", "members", "bottom_col", "agg_cols", "leaf_offsets", "leaf_aggs")
 
 

@@ -423,7 +423,24 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_reconcile_plan", "anofox_hip_reconcile_factor_device", "anofox_hip_reconcile_apply_device", "anofox_hip_reconcile_batch",
     "anofox_hip_select_winner_device", "anofox_hip_select_gather_device", "anofox_hip_select_scatter_device",
     "anofox_hip_select_combine_device", "anofox_hip_select_batch",
+    "anofox_hip_paths_device", "anofox_hip_path_quantiles_device", "anofox_hip_paths_batch",
 ]
+
+# include/anofox_fcst_hip.h block 9: bootstrap sample paths and their quantiles
+PATHS_MODES = {"cumulative": 0, "independent": 1}      # ANOFOX_PATHS_*
+PATHS_ROUTES = {"auto": 0, "lane": 1}                  # ANOFOX_PATHS_ROUTE_*
+PATHS_MAX_PATHS = 2048                                 # ANOFOX_HIP_PATHS_MAX_PATHS
+PATHS_MAX_LEVELS = 16                                  # ANOFOX_HIP_PATHS_MAX_LEVELS
+PATHS_MAX_POOL_ROWS = 1 << 20                          # ANOFOX_HIP_PATHS_MAX_POOL_ROWS
+PATHS_OK, PATHS_EMPTY, PATHS_NAN, PATHS_RAGGED = 0, 1, 2, 3
+
+
+class AnofoxHipPathsOptions(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipPathsOptions: mode, joint, route and the seed (24 bytes)."""
+    _fields_ = [("mode", C.c_int32), ("joint", C.c_int32), ("route", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+assert C.sizeof(AnofoxHipPathsOptions) == 24
 
 # include/anofox_fcst_hip.h block 8: the choice of a method per series
 SELECT_MAX_METHODS = 16
@@ -761,6 +778,18 @@ def load():
     L.anofox_hip_select_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_char_p, C.c_char_p,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    # block 9: bootstrap sample paths and their quantiles
+    L.anofox_hip_paths_device.restype = C.c_bool
+    L.anofox_hip_paths_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_size_t, C.c_size_t, C.c_size_t, P(AnofoxHipPathsOptions), C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_path_quantiles_device.restype = C.c_bool
+    L.anofox_hip_path_quantiles_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_paths_batch.restype = C.c_bool
+    L.anofox_hip_paths_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, P(AnofoxHipPathsOptions),
+                                         C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -856,6 +885,21 @@ def make_hierarchy_options(route="auto", tile_min_members=0):
     o = AnofoxHipHierarchyOptions()
     o.route = HIERARCHY_ROUTES[route] if isinstance(route, str) else int(route)
     o.tile_min_members = int(tile_min_members)
+    return o
+
+
+def make_paths_options(mode="cumulative", joint=False, seed=0, route="auto"):
+    """AnofoxHipPathsOptions: mode in PATHS_MODES and route in PATHS_ROUTES (or their codes; an unknown name raises ValueError, an
+    unknown code is the library's to refuse), seed a uint64."""
+    o = AnofoxHipPathsOptions()
+    for name, value, table in (("mode", mode, PATHS_MODES), ("route", route, PATHS_ROUTES)):
+        if isinstance(value, str):
+            if value not in table:
+                raise ValueError(f"unknown {name} {value!r}: one of {sorted(table)}")
+            value = table[value]
+        setattr(o, name, int(value))
+    o.joint = int(joint)
+    o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     return o
 
 

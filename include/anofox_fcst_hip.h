@@ -2369,6 +2369,123 @@ bool anofox_hip_select_batch(const double *const *values,
                              int32_t *out_n_rows,
                              struct AnofoxError *out_batch_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 9: bootstrap sample paths and their quantiles                         */
+/* ------------------------------------------------------------------------- */
+/*
+ * Residual bootstrap with cumulative resampling, per series or jointly across series (Panagiotelis et al. 2023), and the quantiles
+ * of a block of paths.  The names are this package's own; tests/paths_ref.py is the definition, bit for bit:
+ *   - the draw of series s, path p, step k is output word k & 3 of Philox4x32-10 with counter {p, joint ? 0 : s, k >> 2, joint ? 1 : 0}
+ *     and key {seed & 0xffffffff, seed >> 32}; the pool row is j = (u * n) >> 32 on 64-bit integers, n the pool length of the
+ *     series (joint: pool_rows -- every series of a path takes the same row at a step); no rejection step, bias at most n / 2^32;
+ *   - cumulative: acc = acc + e[j_k] from 0.0, path[k] = point[k] + acc; independent: path[k] = point[k] + e[j_k]; plain fp64
+ *     additions in step order;
+ *   - level q of n_paths values sorted by the total-order key (-0.0 below +0.0): s[lo] * (1 - frac) + s[up] * frac at index
+ *     q * (n_paths - 1); q <= 0 the first value, q >= 1 the last.
+ * Status per series (int32): 0 done; 1 empty pool; 2 a NaN among the pool's first `length` rows or in the point row; 3 joint mode
+ * and a pool length other than pool_rows (in that order of precedence: 3, 1, 2).  Paths of a series whose status is not 0 are NaN.
+ * +-inf are ordinary values.  Status per column of the quantile entry: 0, or 2 when any of its paths is NaN -- every quantile of
+ * that column is then NaN.
+ */
+#define ANOFOX_HIP_PATHS_MAX_PATHS 2048
+#define ANOFOX_HIP_PATHS_MAX_LEVELS 16
+#define ANOFOX_HIP_PATHS_MAX_POOL_ROWS 1048576
+enum { ANOFOX_PATHS_CUMULATIVE = 0, ANOFOX_PATHS_INDEPENDENT = 1 };
+enum { ANOFOX_PATHS_ROUTE_AUTO = 0, ANOFOX_PATHS_ROUTE_LANE = 1 };
+typedef struct AnofoxHipPathsOptions {
+    int32_t mode;                /* ANOFOX_PATHS_CUMULATIVE or ANOFOX_PATHS_INDEPENDENT */
+    int32_t joint;               /* 0: every series draws its own rows; 1: one row per path and step for all series */
+    int32_t route;               /* 0: automatic; 1: lanes over series (the one route there is) */
+    int32_t reserved;            /* 0 */
+    uint64_t seed;
+} AnofoxHipPathsOptions;
+
+/*
+ * Sample paths of a device-resident block.  Element (series s, row t) of `point` [n_series x horizon] is at s * point_stride_s +
+ * t * point_stride_t, of `pool` [n_series x pool_rows] at s * pool_stride_s + t * pool_stride_t: stride_s = 1 is a time-major block,
+ * stride_t = 1 a series-major one (the batch results' yhat; the error block of a backtest viewed as [n_series x n_folds * horizon]).
+ * pool_lengths int32 [n_series] in device memory, cut to [0, pool_rows]; NULL: every pool has pool_rows rows.
+ * Outputs, in device memory: paths_out fp64 [n_paths * horizon x ld_out] time-major, row p * horizon + k of column s -- what
+ * anofox_hip_hierarchy_device takes as it lies with t_rows = n_paths * horizon; columns >= n_series are not touched; status int32
+ * [n_series].  The call only enqueues on `stream` (NULL: the null stream) and does NOT wait on the host.
+ * INVALID_INPUT, each naming its limit, before the device is touched: struct_size, an unknown mode or route, n_paths 0 or above
+ * 2,048, horizon 0, n_paths * horizon above 2^30, pool_rows above 2^20, ld_out < n_series.
+ */
+bool anofox_hip_paths_device(const double *point,
+                             size_t point_stride_s,
+                             size_t point_stride_t,
+                             const double *pool,
+                             size_t pool_stride_s,
+                             size_t pool_stride_t,
+                             const int32_t *pool_lengths,
+                             size_t pool_rows,
+                             size_t n_series,
+                             size_t horizon,
+                             size_t n_paths,
+                             const AnofoxHipPathsOptions *options,
+                             size_t struct_size,
+                             double *paths_out,
+                             size_t ld_out,
+                             int32_t *status,
+                             void *stream,
+                             struct AnofoxError *out_error);
+
+/*
+ * Quantiles of a device-resident block of paths [n_paths * horizon x ld] as anofox_hip_paths_device or the hierarchy entry wrote
+ * it.  levels fp64 [n_levels] on the HOST, each in [0, 1].  Outputs, in device memory: out fp64 [n_levels x n_cols x horizon] (level
+ * l of column c at step k at (l * n_cols + c) * horizon + k), status int32 [n_cols].  The call only enqueues on `stream`.
+ * INVALID_INPUT, each naming its limit: n_paths 0 or above 2,048, horizon 0, n_paths * horizon above 2^30, n_levels 0 or above 16,
+ * a level outside [0, 1] or NaN, ld < n_cols.
+ */
+bool anofox_hip_path_quantiles_device(const double *paths,
+                                      size_t ld,
+                                      size_t n_cols,
+                                      size_t horizon,
+                                      size_t n_paths,
+                                      const double *levels,
+                                      size_t n_levels,
+                                      double *out,
+                                      int32_t *status,
+                                      void *stream,
+                                      struct AnofoxError *out_error);
+
+/*
+ * The chain for host buffers: points fp64 [n_series x horizon] series-major, pools[s] points to pool_lengths[s] residuals (NULL
+ * only where the length is 0); pool_rows is the longest pool.  column_of / n_groupings as for anofox_hip_hierarchy_plan; NULL (or
+ * 0 groupings): the leaves only.  The call packs once, generates the paths, aggregates them up the plan with
+ * anofox_hip_hierarchy_device when there is one -- every cell of an aggregated path is the serial sum of its members' paths in
+ * plan order -- and takes the quantiles of the leaf block or of the aggregated block.
+ *
+ * *out_n_out (n_series, or the plan's columns) and *out_ld (n_out rounded up to 64, at least 64) are always written.  With
+ * out_quantiles NULL that is all: the sizing call, which needs no device.  Otherwise ld must be what the sizing call returned and
+ * the caller's arrays receive out_quantiles fp64 [n_levels x n_out x horizon], out_status int32 [n_out] (per output column),
+ * out_series_status int32 [n_series] (may be NULL) and out_paths fp64 [n_paths * horizon x ld] (may be NULL): the block the
+ * quantiles were taken of.
+ *
+ * INVALID_INPUT as for the two device entries and for the plan, all before the device is touched.  A failed device allocation is
+ * a COMPUTATION_ERROR that names the size.  One device (the calling thread's current one); fp64 only.
+ */
+bool anofox_hip_paths_batch(const double *points,
+                            const double *const *pools,
+                            const size_t *pool_lengths,
+                            size_t n_series,
+                            size_t horizon,
+                            size_t n_paths,
+                            const AnofoxHipPathsOptions *options,
+                            size_t struct_size,
+                            const double *levels,
+                            size_t n_levels,
+                            const int32_t *column_of,
+                            size_t n_groupings,
+                            size_t ld,
+                            double *out_quantiles,
+                            int32_t *out_status,
+                            int32_t *out_series_status,
+                            double *out_paths,
+                            size_t *out_n_out,
+                            size_t *out_ld,
+                            struct AnofoxError *out_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
