@@ -2161,6 +2161,124 @@ def ts_detect_periods(date, value, params=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# Period search: SSA and STL strength, through entries of their own (method := 'ssa' | 'stl' of ts_detect_periods* stays an error)
+# ------------------------------------------------------------------------------------------------------------------------------
+def _period_search_call(series):
+    n = len(series)
+    ys = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    lens = np.array([len(y) for y in ys], dtype=np.uint64)
+    vals = (C.c_void_p * max(n, 1))(*[y.ctypes.data if len(y) else _EMPTY_SERIES_ADDR for y in ys])
+    return n, ys, lens, vals, (_lib.AnofoxError * max(n, 1))(), _lib.AnofoxError()
+
+
+def ssa_period_batch(series, window_size=None, n_components=None):
+    """anofox_hip_ssa_period_batch over a list of 1-D arrays with one parameter set; None or 0 means the source's default (window
+    n / 3 of each series, 10 components).  Per series a dict: ok, code, message, period, variance_explained, n_eigenvalues (int),
+    eigenvalues and detected_periods (lists, as long as the source's vectors), method."""
+    L = _lib.load()
+    n, ys, lens, vals, errs, berr = _period_search_call(series)
+    comps = _lib.ssa_components(_size_t(n_components))
+    fig = np.full((3, max(n, 1)), np.nan)
+    eig = np.full((min(comps, _lib.SSA_MAX_COMPONENTS), max(n, 1)), np.nan)
+    det = np.full((_lib.SSA_N_DETECTED, max(n, 1)), np.nan)
+    ok = L.anofox_hip_ssa_period_batch(vals, lens.ctypes.data, n, _size_t(window_size), _size_t(n_components), fig.ctypes.data,
+                                       eig.ctypes.data, det.ctypes.data, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    for i in range(n):
+        good = errs[i].code == _lib.SUCCESS
+        r = {"ok": good, "code": int(errs[i].code), "message": errs[i].message.decode(errors="replace"), "method": "ssa",
+             "period": float(fig[0, i]), "variance_explained": float(fig[1, i]), "n_eigenvalues": int(fig[2, i]) if good else 0}
+        r["eigenvalues"] = [float(x) for x in eig[:r["n_eigenvalues"], i]]
+        det_i = [float(x) for x in det[:, i]]
+        r["detected_periods"] = [x for x in det_i if x == x]
+        out.append(r)
+    return out
+
+
+def stl_period_batch(series, min_period=None, max_period=None, n_candidates=None):
+    """anofox_hip_stl_period_batch over a list of 1-D arrays with one parameter set; None or 0 means the source's default (min_period
+    4, max_period n / 3 of each series, 20 candidates).  Per series a dict: ok, code, message, period, seasonal_strength,
+    trend_strength, index (the winner's place among the candidates; -1: a constant series or a failure), candidates and
+    candidate_strengths (lists), method."""
+    L = _lib.load()
+    n, ys, lens, vals, errs, berr = _period_search_call(series)
+    k = min(_lib.stl_candidate_count(_size_t(n_candidates)), _lib.STL_MAX_CANDIDATES)
+    fig = np.full((3, max(n, 1)), np.nan)
+    idx = np.full(max(n, 1), -1, dtype=np.int32)
+    cand = np.full((k, max(n, 1)), -1, dtype=np.int32)
+    strength = np.full((k, max(n, 1)), np.nan)
+    ok = L.anofox_hip_stl_period_batch(vals, lens.ctypes.data, n, _size_t(min_period), _size_t(max_period), _size_t(n_candidates),
+                                       fig.ctypes.data, idx.ctypes.data, cand.ctypes.data, strength.ctypes.data, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    for i in range(n):
+        m = int((cand[:, i] >= 0).sum())
+        out.append({"ok": errs[i].code == _lib.SUCCESS, "code": int(errs[i].code), "message": errs[i].message.decode(errors="replace"),
+                    "method": "stl", "period": float(fig[0, i]), "seasonal_strength": float(fig[1, i]), "trend_strength": float(fig[2, i]),
+                    "index": int(idx[i]), "candidates": [int(x) for x in cand[:m, i]], "candidate_strengths": [float(x) for x in strength[:m, i]]})
+    return out
+
+
+_SSA_STRUCT = ("period", "variance_explained", "n_eigenvalues", "method")
+_STL_STRUCT = ("period", "seasonal_strength", "trend_strength", "method")
+
+
+def _period_search_many(lists, batch, fields, args):
+    """The scalar over many lists with one parameter set: every list with at least 16 non-NULL values goes to the GPU in ONE batch
+    call; None for a NULL list, a shorter one and a failed call."""
+    rows, series = [], []
+    for v in lists:
+        vals = None if v is None else _list_values(v)
+        if vals is None or len(vals) < 16:
+            rows.append(None)
+            continue
+        rows.append(len(series))
+        series.append(vals)
+    res = batch(series, *args) if series else []
+    return [None if k is None or not res[k]["ok"] else {f: res[k][f] for f in fields} for k in rows]
+
+
+def ts_ssa_period(values, window_size=None, n_components=None):
+    """The scalar ts_ssa_period(values[, window_size[, n_components]]) (ts_periods.cpp:1270-1365; BIGINT arguments): None for a NULL
+    list, for fewer than 16 non-NULL values (NULL elements are dropped) and when the call fails.  Else STRUCT(period,
+    variance_explained, n_eigenvalues, method) as a dict."""
+    return _period_search_many([values], ssa_period_batch, _SSA_STRUCT, (window_size, n_components))[0]
+
+
+def ts_stl_period(values, min_period=None, max_period=None, n_candidates=None):
+    """The scalar ts_stl_period(values[, min_period[, max_period[, n_candidates]]]) (ts_periods.cpp:1380-1475; BIGINT arguments): None
+    for a NULL list, for fewer than 16 non-NULL values and when the call fails (an empty candidate range included).  Else
+    STRUCT(period, seasonal_strength, trend_strength, method) as a dict."""
+    return _period_search_many([values], stl_period_batch, _STL_STRUCT, (min_period, max_period, n_candidates))[0]
+
+
+def ts_ssa_period_by(group, date, value, window_size=None, n_components=None, group_name="id"):
+    """This package's table form of ts_ssa_period: per group the values ordered by date, ALL groups in ONE anofox_hip_ssa_period_batch
+    call.  Returns a dict of columns: <group_name>, period, variance_explained, n_eigenvalues, method (None = NULL, the row of a group
+    whose detection failed)."""
+    keys, lists = _ordered_lists(group, date, value)
+    res = _period_search_many(lists, ssa_period_batch, _SSA_STRUCT, (window_size, n_components))
+    cols = {group_name: keys}
+    for f in _SSA_STRUCT:
+        cols[f] = [None if r is None else r[f] for r in res]
+    return cols
+
+
+def ts_stl_period_by(group, date, value, min_period=None, max_period=None, n_candidates=None, group_name="id"):
+    """This package's table form of ts_stl_period: ALL groups in ONE anofox_hip_stl_period_batch call.  Returns a dict of columns:
+    <group_name>, period, seasonal_strength, trend_strength, method (None = NULL)."""
+    keys, lists = _ordered_lists(group, date, value)
+    res = _period_search_many(lists, stl_period_batch, _STL_STRUCT, (min_period, max_period, n_candidates))
+    cols = {group_name: keys}
+    for f in _STL_STRUCT:
+        cols[f] = [None if r is None else r[f] for r in res]
+    return cols
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # Conformal prediction intervals: learn -> apply for every group in ONE call
 # ------------------------------------------------------------------------------------------------------------------------------
 def conformal_batch(residuals, forecasts=None, alphas=(0.1,), method="symmetric", strategy="split", difficulty=None, valids=None,

@@ -43,6 +43,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_reconcile_plan.hpp" // the host-only planner of the reconciliation entries (bottom columns, aggregates, the transposed plan)
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
+#include "host_period_search.hpp" // the host-only logic of the SSA / STL period entries (defaults, window, candidate list, checks naming their limits)
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
 struct Plan {
@@ -4773,6 +4774,265 @@ void anofox_free_flat_multi_period_result(FlatMultiPeriodResult *result)
     result->iteration_values = nullptr;
     result->matches_expected_values = nullptr;
     result->n_periods = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Period search: SSA and STL strength (periods.rs ssa_period, stl_period behind lib.rs:1755-1878; period_search.hip).  Entries of
+// their own: the dispatch by method name above keeps its not-implemented error for 'ssa' and 'stl' (DESIGN.md section 7).
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(SsaPeriodResultFFI) == 56 && offsetof(SsaPeriodResultFFI, n_eigenvalues) == 16 && offsetof(SsaPeriodResultFFI, method) == 24,
+              "SsaPeriodResultFFI layout");
+static_assert(sizeof(StlPeriodResultFFI) == 56 && offsetof(StlPeriodResultFFI, trend_strength) == 16 && offsetof(StlPeriodResultFFI, method) == 24,
+              "StlPeriodResultFFI layout");
+
+extern "C++" {
+namespace {
+
+bool psearch_check(PSearchCheck c, const std::string &text, AnofoxError *err)
+{
+    if (c == PSEARCH_CHECK_OK) return true;
+    if (c == PSEARCH_CHECK_NULL) set_error(err, NULL_POINTER, "Null pointer argument");
+    else set_error(err, INVALID_INPUT, text);
+    return false;
+}
+
+// a batch of host series on the device: the block, the lengths and the status column every period-search batch entry needs
+struct PSearchBlock {
+    size_t ld = 0, T = 1;
+    double *d_y = nullptr;
+    int32_t *d_len = nullptr, *d_st = nullptr;
+};
+
+PSearchBlock psearch_upload(Scratch &scratch, const BlockShape &shape, const double *const *values, const size_t *lengths, size_t n_series)
+{
+    PSearchBlock b;
+    b.ld = shape.ld; b.T = shape.T;
+    std::vector<double> yb(b.T * b.ld, 0.0);
+    const std::vector<int32_t> len = block_lengths(lengths, n_series, b.ld);
+    pack_time_major(yb.data(), b.ld, values, lengths, n_series);
+    b.d_y = scratch.get<double>(b.T * b.ld);
+    b.d_len = scratch.get<int32_t>(b.ld);
+    b.d_st = scratch.get<int32_t>(b.ld);
+    HIPCHECK(hipMemcpy(b.d_y, yb.data(), b.T * b.ld * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(b.d_len, len.data(), b.ld * sizeof(int32_t), hipMemcpyHostToDevice));
+    return b;
+}
+
+template <class T> std::vector<T> psearch_fetch(const T *d, size_t count)
+{
+    std::vector<T> h(count);
+    if (count) HIPCHECK(hipMemcpy(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost));
+    return h;
+}
+
+} // namespace
+} // extern "C++"
+
+bool anofox_hip_ssa_period_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, size_t window_size,
+                                  size_t n_components, int route, double *figures, double *eigenvalues, double *detected, int32_t *status,
+                                  void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!y || !lengths || !figures || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    std::string text;
+    if (!psearch_check(ssa_args_check(t_rows, n_components, &text), text, out_error)) return false;
+    if (route < SSA_ROUTE_AUTO || route > SSA_ROUTE_GROUP) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: route " + std::to_string(route) + " is unknown: 0 (automatic) or 1 (256 lanes for every window)");
+        return false;
+    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, PSEARCH_MAX_ROWS, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    SsaArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.window = psearch_arg(window_size); a.n_components = ssa_components(n_components); a.route = route;
+    a.out_fp = figures; a.out_eig = eigenvalues; a.out_det = detected; a.status = status;
+    a.work_stride = ssa_work_stride(t_rows, a.window);
+    a.work_blocks = ssa_work_blocks(a.work_stride, (int)n_series);
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const bool ok = launch_and_wait("ssa_period", st, out_error, [&] {
+        if (a.work_stride && a.work_blocks > 0) a.work = scratch.get<double>(a.work_stride * (size_t)a.work_blocks);
+        launch_ssa_period(a, st);
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_stl_period_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, size_t min_period,
+                                  size_t max_period, size_t n_candidates, double *figures, int32_t *index, int32_t *candidates,
+                                  double *candidate_strengths, int32_t *status, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!y || !lengths || !figures || !index || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    std::string text;
+    if (!psearch_check(stl_args_check(t_rows, n_candidates, &text), text, out_error)) return false;
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, PSEARCH_MAX_ROWS, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    StlPeriodArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.min_period = psearch_arg(min_period); a.max_period = psearch_arg(max_period); a.n_cand = stl_candidate_count(n_candidates);
+    a.out_fp = figures; a.out_index = index; a.status = status; a.out_cand = candidates; a.out_strength = candidate_strengths;
+    a.work_stride = stl_period_work_stride(t_rows);
+    a.work_blocks = stl_period_work_blocks(a.work_stride, (int)n_series);
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const bool ok = launch_and_wait("stl_period", st, out_error, [&] {
+        if (a.work_stride && a.work_blocks > 0) a.work = scratch.get<double>(a.work_stride * (size_t)a.work_blocks);
+        launch_stl_period(a, st);
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_ssa_period_batch(const double *const *values, const size_t *lengths, size_t n_series, size_t window_size, size_t n_components,
+                                 double *out_figures, double *out_eigenvalues, double *out_detected, AnofoxError *out_errors,
+                                 AnofoxError *out_batch_error)
+{
+    clear_error(out_batch_error);
+    if (n_series > 0 && (!values || !lengths || !out_figures)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    std::string text;
+    size_t longest = 0;
+    if (!psearch_check(ssa_args_check(0, n_components, &text), text, out_batch_error)) return false;
+    if (!psearch_check(psearch_batch_rows(lengths, n_series, &longest, &text), text, out_batch_error)) return false;
+    BlockShape shape;
+    if (!series_shape(values, nullptr, lengths, n_series, PSEARCH_MAX_ROWS, &shape, out_batch_error)) return false;
+    if (n_series == 0) return true;
+    const size_t ld = shape.ld, C = (size_t)ssa_components(n_components);
+    std::vector<double> fp, eig, det;
+    std::vector<int32_t> status;
+    Scratch scratch;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        const PSearchBlock b = psearch_upload(scratch, shape, values, lengths, n_series);
+        double *d_fp = scratch.get<double>(SSA_N_FIG * ld);
+        double *d_eig = out_eigenvalues ? scratch.get<double>(C * ld) : nullptr;
+        double *d_det = out_detected ? scratch.get<double>(SSA_N_DETECTED * ld) : nullptr;
+        if (!anofox_hip_ssa_period_device(b.d_y, ld, b.d_len, n_series, b.T, window_size, n_components, SSA_ROUTE_AUTO, d_fp, d_eig, d_det, b.d_st,
+                                          nullptr, out_batch_error))
+            return false;
+        fp = psearch_fetch(d_fp, SSA_N_FIG * ld);
+        if (d_eig) eig = psearch_fetch(d_eig, C * ld);
+        if (d_det) det = psearch_fetch(d_det, SSA_N_DETECTED * ld);
+        status = psearch_fetch(b.d_st, n_series);
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t s = 0; s < n_series; s++) {
+        const bool ok = status[s] == PSEARCH_OK;
+        if (out_errors) clear_error(&out_errors[s]);
+        if (!ok && out_errors) set_error(&out_errors[s], COMPUTATION_ERROR, psearch_series_error(status[s], lengths[s], psearch_arg(window_size)));
+        for (size_t j = 0; j < (size_t)SSA_N_FIG; j++) out_figures[j * n_series + s] = ok ? fp[j * ld + s] : nan;
+        if (out_eigenvalues)
+            for (size_t j = 0; j < C; j++) out_eigenvalues[j * n_series + s] = ok ? eig[j * ld + s] : nan;
+        if (out_detected)
+            for (size_t j = 0; j < (size_t)SSA_N_DETECTED; j++) out_detected[j * n_series + s] = ok ? det[j * ld + s] : nan;
+    }
+    return true;
+}
+
+bool anofox_hip_stl_period_batch(const double *const *values, const size_t *lengths, size_t n_series, size_t min_period, size_t max_period,
+                                 size_t n_candidates, double *out_figures, int32_t *out_index, int32_t *out_candidates,
+                                 double *out_candidate_strengths, AnofoxError *out_errors, AnofoxError *out_batch_error)
+{
+    clear_error(out_batch_error);
+    if (n_series > 0 && (!values || !lengths || !out_figures)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    std::string text;
+    size_t longest = 0;
+    if (!psearch_check(stl_args_check(0, n_candidates, &text), text, out_batch_error)) return false;
+    if (!psearch_check(psearch_batch_rows(lengths, n_series, &longest, &text), text, out_batch_error)) return false;
+    BlockShape shape;
+    if (!series_shape(values, nullptr, lengths, n_series, PSEARCH_MAX_ROWS, &shape, out_batch_error)) return false;
+    if (n_series == 0) return true;
+    const size_t ld = shape.ld, K = (size_t)stl_candidate_count(n_candidates);
+    std::vector<double> fp, strength;
+    std::vector<int32_t> status, idx, cand;
+    Scratch scratch;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        const PSearchBlock b = psearch_upload(scratch, shape, values, lengths, n_series);
+        double *d_fp = scratch.get<double>(STL_N_FIG * ld);
+        int32_t *d_idx = scratch.get<int32_t>(ld);
+        int32_t *d_cand = out_candidates ? scratch.get<int32_t>(K * ld) : nullptr;
+        double *d_str = out_candidate_strengths ? scratch.get<double>(K * ld) : nullptr;
+        if (!anofox_hip_stl_period_device(b.d_y, ld, b.d_len, n_series, b.T, min_period, max_period, n_candidates, d_fp, d_idx, d_cand, d_str, b.d_st,
+                                          nullptr, out_batch_error))
+            return false;
+        fp = psearch_fetch(d_fp, STL_N_FIG * ld);
+        idx = psearch_fetch(d_idx, n_series);
+        if (d_cand) cand = psearch_fetch(d_cand, K * ld);
+        if (d_str) strength = psearch_fetch(d_str, K * ld);
+        status = psearch_fetch(b.d_st, n_series);
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t s = 0; s < n_series; s++) {
+        const bool ok = status[s] == PSEARCH_OK;
+        if (out_errors) clear_error(&out_errors[s]);
+        if (!ok && out_errors) set_error(&out_errors[s], COMPUTATION_ERROR, psearch_series_error(status[s], lengths[s], 0));
+        for (size_t j = 0; j < (size_t)STL_N_FIG; j++) out_figures[j * n_series + s] = ok ? fp[j * ld + s] : nan;
+        if (out_index) out_index[s] = ok ? idx[s] : -1;
+        if (out_candidates)
+            for (size_t j = 0; j < K; j++) out_candidates[j * n_series + s] = ok ? cand[j * ld + s] : -1;
+        if (out_candidate_strengths)
+            for (size_t j = 0; j < K; j++) out_candidate_strengths[j * n_series + s] = ok ? strength[j * ld + s] : nan;
+    }
+    return true;
+}
+
+bool anofox_ts_ssa_period(const double *values, size_t length, size_t window_size, size_t n_components, SsaPeriodResultFFI *out_result,
+                          AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxError serr, berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    double fig[SSA_N_FIG];
+    if (!anofox_hip_ssa_period_batch(v, len, 1, window_size, n_components, fig, nullptr, nullptr, &serr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
+    out_result->period = fig[0]; out_result->variance_explained = fig[1]; out_result->n_eigenvalues = (size_t)fig[2];
+    copy_method(out_result->method, "ssa");
+    return true;
+}
+
+bool anofox_ts_stl_period(const double *values, size_t length, size_t min_period, size_t max_period, size_t n_candidates,
+                          StlPeriodResultFFI *out_result, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxError serr, berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    double fig[STL_N_FIG];
+    if (!anofox_hip_stl_period_batch(v, len, 1, min_period, max_period, n_candidates, fig, nullptr, nullptr, nullptr, &serr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
+    out_result->period = fig[0]; out_result->seasonal_strength = fig[1]; out_result->trend_strength = fig[2];
+    copy_method(out_result->method, "stl");
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -305,6 +305,52 @@ size_t periods_work_stride(size_t t_rows, int64_t s_pad);   // doubles per works
 int periods_work_blocks(size_t work_stride, int n_series);
 void launch_periods(const PeriodsArgs &, hipStream_t);
 
+// Period search (periods.rs ssa_period :800-937 and stl_period :952-1120; period_search.hip).  Bit for bit the source's arithmetic.
+constexpr int PSEARCH_TILE = 2048;           // rows of a series staged in LDS; a longer series is read from global memory
+constexpr size_t PSEARCH_MAX_ROWS = 65536;   // t_rows of a call
+constexpr int PSEARCH_LDS_DOUBLES = 7936;    // the LDS pool of a workgroup (62 KiB): vectors, the staged series and what else fits
+constexpr int32_t PSEARCH_OK = 0, PSEARCH_TOO_SHORT = 1, PSEARCH_OVER_LIMIT = 2, PSEARCH_STL_RANGE = 3, PSEARCH_STL_NO_CANDIDATE = 4;
+constexpr int SSA_MAX_WINDOW = 2048;         // a series whose effective window is larger fails alone (PSEARCH_OVER_LIMIT)
+constexpr int SSA_MAX_COMPONENTS = 32;
+constexpr int SSA_WAVE_WINDOW = 64;          // windows up to this run with one wavefront per series (matrix always in LDS)
+constexpr int SSA_N_FIG = 3, SSA_N_DETECTED = 4;
+constexpr int SSA_ROUTE_AUTO = 0, SSA_ROUTE_GROUP = 1;     // _AUTO: one wavefront where the window allows; _GROUP: 256 lanes for every window
+constexpr size_t SSA_WORK_BYTES = (size_t)1 << 30;      // upper bound of the matrix workspace, whatever n_series is (one slice if a slice is larger)
+constexpr int STL_MAX_CANDIDATES = 64;
+constexpr int STL_WAVES = 4;                 // waves of a workgroup, one candidate at a time each
+constexpr int STL_N_FIG = 3;
+constexpr size_t STL_WORK_BYTES = (size_t)256 << 20;
+struct SsaArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    int64_t window;              // 0: n / 3 of each series
+    int n_components;            // resolved: 10 by default, <= SSA_MAX_COMPONENTS
+    int route;
+    double *out_fp;              // [SSA_N_FIG x ld] period, variance_explained, n_eigenvalues
+    double *out_eig;             // [n_components x ld] or null: the eigenvalues, NaN beyond n_eigenvalues
+    double *out_det;             // [SSA_N_DETECTED x ld] or null: detected_periods, NaN beyond what exists
+    int32_t *status;             // [n_series] PSEARCH_OK / _TOO_SHORT / _OVER_LIMIT (nothing else written unless OK)
+    double *work; size_t work_stride; int work_blocks;     // matrices that do not fit in LDS: [work_blocks x work_stride]
+};
+size_t ssa_work_stride(size_t t_rows, int64_t window);      // doubles per workspace slice: the square of the largest window of the call
+int ssa_work_blocks(size_t work_stride, int n_series);
+void launch_ssa_period(const SsaArgs &, hipStream_t);
+struct StlPeriodArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;
+    int64_t min_period, max_period;      // 0: 4 and n / 3 of each series
+    int n_cand;                  // resolved: max(n_candidates or 20, 5), <= STL_MAX_CANDIDATES
+    double *out_fp;              // [STL_N_FIG x ld] period, seasonal_strength, trend_strength
+    int32_t *out_index;          // [n_series] the winning candidate, -1 for the constant-series return
+    int32_t *status;             // [n_series] PSEARCH_OK / _TOO_SHORT / _STL_RANGE / _STL_NO_CANDIDATE
+    int32_t *out_cand;           // [n_cand x ld] or null: the candidate periods, -1 beyond the list
+    double *out_strength;        // [n_cand x ld] or null: their seasonal strengths, NaN beyond the list
+    double *work; size_t work_stride; int work_blocks;     // rows that do not fit in LDS: [work_blocks x work_stride]
+};
+size_t stl_period_work_stride(size_t t_rows);
+int stl_period_work_blocks(size_t work_stride, int n_series);
+void launch_stl_period(const StlPeriodArgs &, hipStream_t);
+
 // Forecast accuracy metrics per group (metrics.rs mae .. coverage; metrics.hip)
 constexpr int METRICS_N_FIG = 12;        // rows of `figures`, in this order:
 enum { MF_MAE = 0, MF_MSE, MF_RMSE, MF_MAPE, MF_SMAPE, MF_R2, MF_BIAS, MF_RMAE, MF_MASE, MF_QUANTILE_LOSS, MF_MQLOSS, MF_COVERAGE };

@@ -234,6 +234,79 @@ def seasonality_block(y: torch.Tensor, lengths: torch.Tensor, valid: torch.Tenso
             "is_seasonal": values[10] > 0.1, "figures": figures, "values": values}
 
 
+def _period_search_block(y, lengths, n_series):
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    return t_rows, ld, n
+
+
+def ssa_period_block(y: torch.Tensor, lengths: torch.Tensor, window_size: int = 0, n_components: int = 0, *, route: str = "auto",
+                     n_series: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_ssa_period_device on torch tensors: the reference's ssa_period for every series of a block, nothing read back.
+
+    y [t_rows, ld] fp64 (t_rows <= 65,536), lengths int32 [>= n_series], on one HIP device, contiguous.  window_size / n_components
+    0: n / 3 of each series and 10.  route 'auto' | 'group' (lib.SSA_ROUTES) chooses the lanes per series, never the bits.
+
+    Returns device tensors: {"period", "variance_explained", "n_eigenvalues" (fp64 [ld] views of "figures" [3, ld]), "eigenvalues"
+    fp64 [C, ld] with C = lib.ssa_components(n_components), "detected_periods" fp64 [4, ld] (both NaN beyond what exists), "status"
+    int32 [ld]: lib.PSEARCH_OK, _TOO_SHORT (fewer than 16 rows) or _OVER_LIMIT (window above 2,048)}.  Columns s >= n_series and
+    failed series hold NaN; status is -1 in columns s >= n_series."""
+    L = _lib.load()
+    t_rows, ld, n = _period_search_block(y, lengths, n_series)
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    comps = _lib.ssa_components(n_components)
+    figures = torch.full((3, ld), float("nan"), dtype=torch.float64, device=dev)
+    eig = torch.full((comps, ld), float("nan"), dtype=torch.float64, device=dev)
+    det = torch.full((_lib.SSA_N_DETECTED, ld), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.full((ld,), -1, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_ssa_period_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, int(window_size or 0), int(n_components or 0),
+                                        _lib.SSA_ROUTES[route], figures.data_ptr(), eig.data_ptr(), det.data_ptr(), status.data_ptr(),
+                                        C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_ssa_period_device failed: [{err.code}] {err.message.decode()}")
+    return {"period": figures[0], "variance_explained": figures[1], "n_eigenvalues": figures[2], "figures": figures, "eigenvalues": eig,
+            "detected_periods": det, "status": status}
+
+
+def stl_period_block(y: torch.Tensor, lengths: torch.Tensor, min_period: int = 0, max_period: int = 0, n_candidates: int = 0, *,
+                     n_series: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_stl_period_device on torch tensors: the reference's stl_period for every series of a block, nothing read back.
+
+    y [t_rows, ld] fp64 (t_rows <= 65,536), lengths int32 [>= n_series], on one HIP device, contiguous.  0 means the source's default:
+    min_period 4, max_period n / 3 of each series, 20 candidates.
+
+    Returns device tensors: {"period", "seasonal_strength", "trend_strength" (fp64 [ld] views of "figures" [3, ld]), "index" int32 [ld]
+    (the winning candidate's place in its list; -1 for a constant series), "candidates" int32 [K, ld] (-1 beyond a series' list) and
+    "candidate_strengths" fp64 [K, ld] (NaN beyond it) with K = lib.stl_candidate_count(n_candidates), "status" int32 [ld]:
+    lib.PSEARCH_OK, _TOO_SHORT, _STL_RANGE or _STL_NO_CANDIDATE}.  Columns s >= n_series and failed series keep NaN / -1."""
+    L = _lib.load()
+    t_rows, ld, n = _period_search_block(y, lengths, n_series)
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    k = _lib.stl_candidate_count(n_candidates)
+    figures = torch.full((3, ld), float("nan"), dtype=torch.float64, device=dev)
+    index = torch.full((ld,), -1, dtype=torch.int32, device=dev)
+    cands = torch.full((k, ld), -1, dtype=torch.int32, device=dev)
+    strengths = torch.full((k, ld), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.full((ld,), -1, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_stl_period_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, int(min_period or 0), int(max_period or 0),
+                                        int(n_candidates or 0), figures.data_ptr(), index.data_ptr(), cands.data_ptr(), strengths.data_ptr(),
+                                        status.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_stl_period_device failed: [{err.code}] {err.message.decode()}")
+    return {"period": figures[0], "seasonal_strength": figures[1], "trend_strength": figures[2], "figures": figures, "index": index,
+            "candidates": cands, "candidate_strengths": strengths, "status": status}
+
+
 def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | None = None, actual: torch.Tensor | None = None,
                     calibration_forecast: torch.Tensor | None = None, valid: torch.Tensor | None = None,
                     lengths: torch.Tensor | None = None, n_groups: int | None = None, method: str = "symmetric",

@@ -217,6 +217,33 @@ PERIOD_FIGURES = {"lomb_scargle": ("period", "frequency", "power", "false_alarm_
 PERIODS_N_FP = 5
 
 
+class SsaPeriodResultFFI(C.Structure):
+    _fields_ = [("period", C.c_double), ("variance_explained", C.c_double), ("n_eigenvalues", C.c_size_t), ("method", C.c_char * 32)]
+
+
+class StlPeriodResultFFI(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("period", "seasonal_strength", "trend_strength")] + [("method", C.c_char * 32)]
+
+
+assert (C.sizeof(SsaPeriodResultFFI), C.sizeof(StlPeriodResultFFI)) == (56, 56)
+# include/anofox_fcst_hip.h: the figure rows of anofox_hip_ssa_period_* / anofox_hip_stl_period_*, their status codes and limits
+SSA_FIGURES = ("period", "variance_explained", "n_eigenvalues")
+STL_FIGURES = ("period", "seasonal_strength", "trend_strength")
+PSEARCH_OK, PSEARCH_TOO_SHORT, PSEARCH_OVER_LIMIT, PSEARCH_STL_RANGE, PSEARCH_STL_NO_CANDIDATE = 0, 1, 2, 3, 4
+SSA_N_DETECTED, SSA_MAX_WINDOW, SSA_MAX_COMPONENTS, STL_MAX_CANDIDATES, PSEARCH_MAX_ROWS = 4, 2048, 32, 64, 65536
+SSA_ROUTES = {"auto": 0, "group": 1}
+
+
+def ssa_components(n_components=None) -> int:
+    """Rows of the eigenvalue output: n_components, or the source's 10 for None / 0."""
+    return int(n_components) if n_components else 10
+
+
+def stl_candidate_count(n_candidates=None) -> int:
+    """Rows of the candidate outputs: max(n_candidates or 20, 5), as the source resolves it."""
+    return max(int(n_candidates) if n_candidates else 20, 5)
+
+
 # include/anofox_fcst_hip.h: bit k of the figure mask of anofox_hip_metrics_batch / _device and row k of their output
 METRIC_FIGURES = ("mae", "mse", "rmse", "mape", "smape", "r2", "bias", "rmae", "mase", "quantile_loss", "mqloss", "coverage")
 METRICS_MAX_LEVELS = 16
@@ -405,6 +432,8 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_seasonality_batch", "anofox_hip_seasonality_device",
     "anofox_ts_lomb_scargle", "anofox_ts_aic_period", "anofox_ts_sazed_period", "anofox_ts_detect_periods_flat",
     "anofox_free_flat_multi_period_result", "anofox_hip_periods_batch", "anofox_hip_periods_device",
+    "anofox_ts_ssa_period", "anofox_ts_stl_period", "anofox_hip_ssa_period_batch", "anofox_hip_stl_period_batch",
+    "anofox_hip_ssa_period_device", "anofox_hip_stl_period_device",
     "anofox_ts_mae", "anofox_ts_mse", "anofox_ts_rmse", "anofox_ts_mape", "anofox_ts_smape", "anofox_ts_r2", "anofox_ts_bias",
     "anofox_ts_rmae", "anofox_ts_mase", "anofox_ts_quantile_loss", "anofox_ts_mqloss", "anofox_ts_coverage",
     "anofox_hip_metrics_batch", "anofox_hip_metrics_device",
@@ -629,6 +658,22 @@ def load():
     L.anofox_hip_periods_device.restype = C.c_bool
     L.anofox_hip_periods_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_double,
                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_ssa_period.restype = C.c_bool
+    L.anofox_ts_ssa_period.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, P(SsaPeriodResultFFI), P(AnofoxError)]
+    L.anofox_ts_stl_period.restype = C.c_bool
+    L.anofox_ts_stl_period.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, P(StlPeriodResultFFI), P(AnofoxError)]
+    L.anofox_hip_ssa_period_batch.restype = C.c_bool
+    L.anofox_hip_ssa_period_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_stl_period_batch.restype = C.c_bool
+    L.anofox_hip_stl_period_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_ssa_period_device.restype = C.c_bool
+    L.anofox_hip_ssa_period_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_stl_period_device.restype = C.c_bool
+    L.anofox_hip_stl_period_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     for name in ("mae", "mse", "rmse", "mape", "smape", "r2", "bias"):
         f = getattr(L, "anofox_ts_" + name)
         f.restype = C.c_bool

@@ -237,6 +237,50 @@ bool anofox_ts_detect_periods_flat(const double *values,
 void anofox_free_flat_multi_period_result(struct FlatMultiPeriodResult *result);
 
 /*
+ * Period detection by SSA and by STL strength (layouts of the reference's anofox_fcst_ffi.h: SsaPeriodResultFFI and
+ * StlPeriodResultFFI, 56 bytes each; the eigenvalue and candidate vectors are dropped there, the batch and device entries return them).
+ */
+typedef struct SsaPeriodResultFFI {
+    double period;            /* from the zero crossings of the first qualifying eigenvector; NaN when none qualifies */
+    double variance_explained;
+    size_t n_eigenvalues;
+    char method[32];          /* "ssa" */
+} SsaPeriodResultFFI;
+
+typedef struct StlPeriodResultFFI {
+    double period;            /* the candidate with the largest seasonal strength; NaN for a constant series */
+    double seasonal_strength;
+    double trend_strength;
+    char method[32];          /* "stl" */
+} StlPeriodResultFFI;
+
+/*
+ * ONE series through the reference's ssa_period / stl_period (periods.rs) behind its FFI wrappers: an argument of zero means the
+ * source's default -- window_size n / 3 (then at most n / 2, at least 4), 10 components; min_period 4, max_period n / 3 (at most
+ * n / 2), 20 candidates (at least 5).  NULL `values` or `out_result`: NULL_POINTER "Null pointer argument".  COMPUTATION_ERROR:
+ * "Insufficient data: need at least 16 observations, got N", "Invalid input: min_period must be less than max_period", "Invalid
+ * input: No valid candidate periods found", and an SSA window above 2,048 rows, naming that limit of this backend.  More than 32
+ * components, more than 64 candidates or more than 65,536 observations: INVALID_INPUT naming the limit.  Each runs on the GPU as
+ * a batch of one, and every figure equals the source's arithmetic bit for bit (sequential sums in index order, no fused
+ * multiply-add), except for the sign of a zero result and NaN payloads.  The method dispatch by name (anofox_ts_detect_periods_flat
+ * with "ssa" or "stl") keeps its not-implemented error.
+ */
+bool anofox_ts_ssa_period(const double *values,
+                          size_t length,
+                          size_t window_size,
+                          size_t n_components,
+                          struct SsaPeriodResultFFI *out_result,
+                          struct AnofoxError *out_error);
+
+bool anofox_ts_stl_period(const double *values,
+                          size_t length,
+                          size_t min_period,
+                          size_t max_period,
+                          size_t n_candidates,
+                          struct StlPeriodResultFFI *out_result,
+                          struct AnofoxError *out_error);
+
+/*
  * Result of the Bayesian online changepoint detection (layout of the reference's anofox_fcst_ffi.h).  The arrays are malloc()ed
  * by the callee and released by anofox_free_bocpd_result; changepoint_indices is NULL when no point is flagged.
  */
@@ -1112,6 +1156,86 @@ bool anofox_hip_periods_device(const double *y,
                                int32_t *status,
                                void *stream,
                                struct AnofoxError *out_error);
+
+/*
+ * SSA and STL period detection of `n_series` series with one parameter set, in one GPU pass (the arguments of the single entries;
+ * zero means the source's default).  Figure j of series i is at out_figures[j * n_series + i], fp64 [3 x n_series]: SSA period,
+ * variance_explained, n_eigenvalues (as a double); STL period, seasonal_strength, trend_strength.  Optional outputs (may be NULL):
+ * SSA out_eigenvalues fp64 [C x n_series] with C = n_components, or 10 for 0, and out_detected fp64 [4 x n_series] (the source's
+ * detected_periods), both NaN beyond what exists; STL out_index int32 [n_series] (the winning candidate's place in the list, -1
+ * for the constant-series return and for a failed series), out_candidates int32 [K x n_series] (-1 beyond the list) and
+ * out_candidate_strengths fp64 [K x n_series] (NaN beyond it) with K = max(n_candidates or 20, 5).  A series that is too short,
+ * whose SSA window exceeds 2,048 rows or whose STL candidate range is empty fails alone: out_errors[i] (may be NULL) gets the single
+ * entry's COMPUTATION_ERROR and its outputs are NaN / -1.  More than 32 components, more than 64 candidates or a series above 65,536
+ * rows: INVALID_INPUT naming the limit, for the whole call.  The return value is false only for batch-level failures, also reported
+ * through `out_batch_error`.  Runs on the calling thread's current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_ssa_period_batch(const double *const *values,
+                                 const size_t *lengths,
+                                 size_t n_series,
+                                 size_t window_size,
+                                 size_t n_components,
+                                 double *out_figures,
+                                 double *out_eigenvalues,
+                                 double *out_detected,
+                                 struct AnofoxError *out_errors,
+                                 struct AnofoxError *out_batch_error);
+
+bool anofox_hip_stl_period_batch(const double *const *values,
+                                 const size_t *lengths,
+                                 size_t n_series,
+                                 size_t min_period,
+                                 size_t max_period,
+                                 size_t n_candidates,
+                                 double *out_figures,
+                                 int32_t *out_index,
+                                 int32_t *out_candidates,
+                                 double *out_candidate_strengths,
+                                 struct AnofoxError *out_errors,
+                                 struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows <= 65,536), lengths[n_series] (int32; a length
+ * above t_rows is cut to it) and the outputs are device pointers with row stride ld (figure j of series s at j * ld + s);
+ * eigenvalues, detected, candidates and candidate_strengths may be NULL.  status is int32 [n_series]: 0 done, 1 too short, 2 SSA
+ * window above 2,048, 3 STL "min_period must be less than max_period", 4 STL "No valid candidate periods found"; nothing else is
+ * written for a series whose status is not 0.  One workgroup per series, persistent over the batch.  SSA keeps the L x L matrix in
+ * LDS while it fits and otherwise in a workspace of at most 1 GiB whatever n_series is (one 32 MiB slice at the window limit, 330
+ * slices of 3.25 MB at n = 1,913); `route` is 0 (windows up to 64 on one wavefront per series, the rest on 256 lanes) or
+ * 1 (256 lanes for every window) and does not change a bit of the results.  STL keeps its rows in LDS up to 721
+ * observations and otherwise in a workspace of at most 256 MiB.  The same bits on every run and through every entry.  Runs on
+ * `stream` (NULL: the null stream) and returns after it has finished.
+ */
+bool anofox_hip_ssa_period_device(const double *y,
+                                  size_t ld,
+                                  const int32_t *lengths,
+                                  size_t n_series,
+                                  size_t t_rows,
+                                  size_t window_size,
+                                  size_t n_components,
+                                  int route,
+                                  double *figures,
+                                  double *eigenvalues,
+                                  double *detected,
+                                  int32_t *status,
+                                  void *stream,
+                                  struct AnofoxError *out_error);
+
+bool anofox_hip_stl_period_device(const double *y,
+                                  size_t ld,
+                                  const int32_t *lengths,
+                                  size_t n_series,
+                                  size_t t_rows,
+                                  size_t min_period,
+                                  size_t max_period,
+                                  size_t n_candidates,
+                                  double *figures,
+                                  int32_t *index,
+                                  int32_t *candidates,
+                                  double *candidate_strengths,
+                                  int32_t *status,
+                                  void *stream,
+                                  struct AnofoxError *out_error);
 
 /*
  * Forecast accuracy metrics, the reference's twelve functions of metrics.rs behind their FFI wrappers, with its signatures.  Each
