@@ -3945,6 +3945,37 @@ def reconcile_batch(column_of, forecast, method="ols", weights=None):
     return out, {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
 
 
+def reconcile_mint_batch(column_of, forecast, residuals, shrinkage=None):
+    """anofox_hip_reconcile_mint_batch: MinT with the shrinkage covariance (DESIGN.md section 3 "MinT-shrink").  column_of and forecast
+    as for reconcile_batch; residuals fp64 series-major [n_out, n_res]: the base-forecast errors of every output column (the rows of
+    empty columns are never read); shrinkage None estimates the intensity, a value in [0, 1] is taken as it is.
+
+    Returns ({"y": fp64 [n_out, h]; "row_status": int32 [h]; "shrinkage": the intensity used; "variances": fp64 [n_out]}, error)."""
+    L = _lib.load()
+    co = np.ascontiguousarray(column_of, dtype=np.int32)
+    co = co.reshape(1, -1) if co.ndim == 1 else co
+    G, n = co.shape
+    f = np.ascontiguousarray(forecast, dtype=np.float64)
+    f = f.reshape(len(f), -1) if f.ndim != 2 else f
+    n_out, h = f.shape
+    planned = int(co.max()) + 1 if co.size and co.max() >= 0 else 0
+    if n_out != planned:
+        raise ValueError(f"reconcile_mint_batch: the forecast block has {n_out} rows, the plan has {planned} output columns")
+    r = np.ascontiguousarray(residuals, dtype=np.float64)
+    r = r.reshape(len(r), -1) if r.ndim != 2 else r
+    if r.shape[0] != n_out:
+        raise ValueError(f"reconcile_mint_batch: the residual block has {r.shape[0]} rows, the plan has {n_out} output columns")
+    lam = C.c_double(float("nan") if shrinkage is None else float(shrinkage))
+    out = {"y": np.full((n_out, h), np.nan), "row_status": np.zeros(h, dtype=np.int32), "shrinkage": float("nan"),
+           "variances": np.full(n_out, np.nan)}
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_reconcile_mint_batch(co.ctypes.data, G, n, f.ctypes.data, h, r.ctypes.data, r.shape[1], C.byref(lam), out["y"].ctypes.data,
+                                           out["row_status"].ctypes.data, out["variances"].ctypes.data, C.byref(err))
+    if ok:
+        out["shrinkage"] = float(lam.value)
+    return out, {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+
+
 def _reconcile_level(parts, keyword):
     """The level of a key of BuildUniqueId: the number of leading parts that are kept -- the keyword stands from there on."""
     level = len(parts)
@@ -3980,8 +4011,11 @@ def ts_reconcile_hierarchy(unique_id, date, forecast, params=None, date_name="da
     """Makes the forecasts of a key hierarchy coherent: the rows that ts_aggregate_hierarchy -> ts_forecast_by produce, one forecast
     per (unique_id, date).  The reference has no such function; the name and the contract are this package's.
 
-    params: method ("bottom_up", "ols" -- the default --, "wls_struct", "wls_var"), separator and aggregate_keyword as for
-    ts_aggregate_hierarchy, weights (wls_var: a mapping unique_id -> positive weight, e.g. the error variance of that id's model).
+    params: method ("bottom_up", "ols" -- the default --, "wls_struct", "wls_var", "mint_shrink"), separator and aggregate_keyword as
+    for ts_aggregate_hierarchy, weights (wls_var: a mapping unique_id -> positive weight, e.g. the error variance of that id's model),
+    residuals (mint_shrink: a table (unique_id, date, residual) of base-forecast errors, the same dates for every id, e.g. the
+    backtest's errors) and optionally shrinkage (mint_shrink: an intensity in [0, 1] instead of the estimate; the one used comes
+    back as info["shrinkage"]).
     Membership is read from the keys: an id with the keyword from part L on holds every leaf whose first L parts match.  The leaves,
     in byte order of their ids, are the series; every aggregate comes back as the serial sum of its leaves' reconciled forecasts in
     that order.  Returns unique_id, <date_name>, <forecast_name>, sorted by (unique_id bytes, date).  InvalidInputException, naming the
@@ -3989,8 +4023,8 @@ def ts_reconcile_hierarchy(unique_id, date, forecast, params=None, date_name="da
     p = params or {}
     sep, keyword = _hierarchy_params(p)
     method = str(p["method"]) if p.get("method") is not None else "ols"
-    if method not in _lib.RECONCILE_METHODS:
-        raise InvalidInputException(f"ts_reconcile_hierarchy: unknown method {method!r}; one of {sorted(_lib.RECONCILE_METHODS)}")
+    if method not in _lib.RECONCILE_METHODS and method != "mint_shrink":
+        raise InvalidInputException(f"ts_reconcile_hierarchy: unknown method {method!r}; one of {sorted(list(_lib.RECONCILE_METHODS) + ['mint_shrink'])}")
     dates = np.asarray(date)
     kind = _date_kind(dates)
     us = _to_micros(dates, kind)
@@ -4018,14 +4052,45 @@ def ts_reconcile_hierarchy(unique_id, date, forecast, params=None, date_name="da
         if lacking:
             raise InvalidInputException(f"ts_reconcile_hierarchy: wls_var needs a weight for the ids {lacking[:5]}")
         weights = np.array([float(given[u]) for u in names])
+    residuals = None
+    if method == "mint_shrink":
+        if p.get("residuals") is None:
+            raise InvalidInputException("ts_reconcile_hierarchy: mint_shrink needs residuals, a table (unique_id, date, residual)")
+        r_uid, r_date, r_val = p["residuals"]
+        r_dates = np.asarray(r_date)
+        r_us = _to_micros(r_dates, _date_kind(r_dates))
+        r_uids = _hierarchy_strings(r_uid, len(r_dates))
+        r_vals = np.asarray(r_val, dtype=np.float64)
+        if len(r_vals) != len(r_dates):
+            raise InvalidInputException("every column of the residual table must have the same number of rows")
+        r_by = {u: {} for u in names}
+        for u, d, v in zip(r_uids, r_us, r_vals):
+            if u in r_by:
+                r_by[u][int(d)] = float(v)
+        lacking = [u for u in names if not r_by[u]]
+        if lacking:
+            raise InvalidInputException(f"ts_reconcile_hierarchy: mint_shrink needs residuals for the ids {lacking[:5]}")
+        r_grid = sorted(r_by[names[0]]) if names else []
+        differ = [u for u in names if sorted(r_by[u]) != r_grid]
+        if differ:
+            raise InvalidInputException(f"ts_reconcile_hierarchy: the residual dates of the ids {differ[:5]} differ from those of {names[0]!r}")
+        residuals = np.array([[r_by[u][d] for d in r_grid] for u in names], dtype=np.float64).reshape(len(names), len(r_grid))
     if len(names) and len(grid):
-        res, err = reconcile_batch(column_of, block, method, weights)
+        if method == "mint_shrink":
+            entry = "anofox_hip_reconcile_mint_batch"
+            res, err = reconcile_mint_batch(column_of, block, residuals, p.get("shrinkage"))
+        else:
+            entry = "anofox_hip_reconcile_batch"
+            res, err = reconcile_batch(column_of, block, method, weights)
         if not err["ok"]:
             if err["code"] == 2:
                 raise InvalidInputException(f"ts_reconcile_hierarchy: {err['message']}")
-            raise RuntimeError(f"anofox_hip_reconcile_batch failed: [{err['code']}] {err['message']}")
+            raise RuntimeError(f"{entry} failed: [{err['code']}] {err['message']}")
         block = res["y"]
         if info is not None:
+            if method == "mint_shrink":
+                info["shrinkage"] = res["shrinkage"]
+                info["variances"] = res["variances"]
             info["row_status"] = res["row_status"]
             info["column_of"] = column_of
     return {"unique_id": np.array([u for u in names for _ in grid], dtype=object),

@@ -41,6 +41,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_scratch.hpp"       // Scratch (a call's device blocks), the shape and packing of a batch of series, the _device entry's checks and launch
 #include "host_parts.hpp"         // how an auto-detected batch is cut into device batches (PartPlan), and how a batch's results reach the caller's arrays
 #include "host_reconcile_plan.hpp" // the host-only planner of the reconciliation entries (bottom columns, aggregates, the transposed plan)
+#include "host_reconcile_mint.hpp" // the host-only checks and workspace sizes of the MinT-shrink entries
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
 #include "host_period_search.hpp" // the host-only logic of the SSA / STL period entries (defaults, window, candidate list, checks naming their limits)
@@ -6968,7 +6969,7 @@ bool anofox_hip_reconcile_apply_device(const double *base, size_t stride_s, size
     if (n_rows == 0) return true;
     if (!device_ready(out_error)) return false;
     a.method = method; a.base = base; a.out = out; a.stride_s = stride_s; a.stride_t = stride_t; a.n_rows = n_rows;
-    a.L = factor; a.ld_a = ld_a; a.work = work; a.row_status = row_status;
+    a.L = factor; a.ld_a = ld_a; a.work = work; a.ld_work = n_agg; a.row_status = row_status;
     try {
         (void)hipGetLastError();
         launch_reconcile_apply(a, (hipStream_t)stream);
@@ -7049,6 +7050,234 @@ bool anofox_hip_reconcile_batch(const int32_t *column_of, size_t n_groupings, si
             if (ok) {
                 HIPCHECK(hipMemcpy(out, d_out, cells * sizeof(double), hipMemcpyDeviceToHost));          // waits for the null stream
                 HIPCHECK(hipMemcpy(out_row_status, d_status, h * sizeof(int32_t), hipMemcpyDeviceToHost));
+            } else {
+                HIPCHECK(hipDeviceSynchronize());
+            }
+        }
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return ok;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// MinT with the shrinkage covariance (DESIGN.md section 3 "MinT-shrink"; reconcile_mint.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(RECONCILE_MINT_MAX_RESIDUAL_ROWS == (size_t)ANOFOX_HIP_RECONCILE_MAX_RESIDUAL_ROWS, "the limit of residual rows");
+static_assert(RECONCILE_MINT_TILE == (size_t)64, "the Gram tile of reconcile_mint.hip");
+
+bool reconcile_mint_report(ReconcileMintResult r, const std::string &message, AnofoxError *err)
+{
+    if (r == RECONCILE_MINT_NULL) set_error(err, NULL_POINTER, "Null pointer argument");
+    else if (r == RECONCILE_MINT_INVALID) set_error(err, INVALID_INPUT, message);
+    return r == RECONCILE_MINT_OK;
+}
+
+// developer knob `name` of ANOFOX_HIP_TUNE: 0 plain FMA tile, anything else (and the default) MFMA
+int reconcile_tile_variant(const char *name)
+{
+    const std::map<std::string, std::string> kv = Tunables::tune_map();
+    auto it = kv.find(name);
+    return (it != kv.end() && std::atoi(it->second.c_str()) == 0) ? RECONCILE_TRAILING_FMA : RECONCILE_TRAILING_MFMA;
+}
+
+} // namespace
+
+extern "C" {
+
+bool anofox_hip_reconcile_mint_sizes(size_t n_res, size_t n_agg, size_t n_rows, size_t *gram_elems, size_t *e_elems, size_t *factor_elems,
+                                     size_t *work_elems, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    return reconcile_mint_report(reconcile_mint_sizes_host(n_res, n_agg, n_rows, (size_t)ANOFOX_HIP_RECONCILE_MAX_AGG, gram_elems, e_elems,
+                                                           factor_elems, work_elems, &message), message, out_error);
+}
+
+bool anofox_hip_reconcile_mint_factor_device(const double *residuals, size_t res_stride_s, size_t res_stride_t, size_t n_res,
+                                             const int32_t *col_offsets, const int32_t *members, size_t n_out, size_t nnz, size_t n_series,
+                                             const int32_t *bottom_col, const int32_t *agg_cols, size_t n_agg, const int32_t *leaf_offsets,
+                                             const int32_t *leaf_aggs, size_t n_leaf, double shrinkage, double *variances, double *e, size_t ld_e,
+                                             double *factor, size_t ld_a, double *gram_work, double *out_shrinkage, void *stream,
+                                             AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    bool estimate = false;
+    if (!reconcile_mint_report(reconcile_mint_rows_check(n_res, &message), message, out_error)) return false;
+    if (!reconcile_mint_report(reconcile_mint_lambda_check(shrinkage, true, &estimate, &message), message, out_error)) return false;
+    ReconcileMintArgs a{};
+    if (!reconcile_plan_args(col_offsets, members, n_out, nnz, n_series, bottom_col, agg_cols, n_agg, leaf_offsets, leaf_aggs, n_leaf, nullptr, &a.p,
+                             out_error))
+        return false;
+    if (!reconcile_mint_report(reconcile_mint_dims_check(n_series, n_agg, (size_t)ANOFOX_HIP_RECONCILE_MAX_AGG, ld_e, ld_a, &message), message, out_error))
+        return false;
+    if (!out_shrinkage || (n_out > 0 && (!residuals || !variances)) || (n_agg > 0 && (!factor || !e)) || (estimate && n_out > 0 && !gram_work)) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!device_ready(out_error)) return false;
+    a.res = residuals; a.res_stride_s = res_stride_s; a.res_stride_t = res_stride_t; a.n_res = (int)n_res;
+    a.var = variances; a.E = e; a.ld_e = ld_e; a.L = factor; a.ld_a = ld_a;
+    a.gram = estimate ? gram_work : nullptr; a.gram_splits = (int)reconcile_mint_gram_splits(n_res); a.lambda_in = shrinkage;
+    a.trailing = reconcile_tile_variant("reconcile_trailing");
+    a.ete = reconcile_tile_variant("reconcile_mint_ete");
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    int32_t info[4] = {RECONCILE_NONE, RECONCILE_NONE, RECONCILE_NONE, RECONCILE_NONE};
+    double lam = shrinkage;
+    const bool ok = launch_and_wait("reconcile mint factor", st, out_error, [&] {
+        a.info = scratch.get<int32_t>(4);
+        double *d = scratch.get<double>(2 * std::max<size_t>(n_out, 1) + 1);
+        a.rsd = d; a.f4col = d + std::max<size_t>(n_out, 1); a.lambda = d + 2 * std::max<size_t>(n_out, 1);
+        launch_reconcile_mint_factor(a, st);
+        HIPCHECK(hipMemcpyAsync(info, a.info, sizeof(info), hipMemcpyDeviceToHost, st));
+        if (n_out > 0) HIPCHECK(hipMemcpyAsync(&lam, a.lambda, sizeof(double), hipMemcpyDeviceToHost, st));
+    });
+    if (!ok) return false;
+    scratch.settled();
+    if (info[MINT_INFO_RESIDUAL] != RECONCILE_NONE) {
+        set_error(out_error, COMPUTATION_ERROR, "Computation error: a residual of column " + std::to_string(info[MINT_INFO_RESIDUAL]) + " is not finite");
+        return false;
+    }
+    if (info[MINT_INFO_VARIANCE] != RECONCILE_NONE) {
+        set_error(out_error, COMPUTATION_ERROR, "Computation error: the residual variance of column " + std::to_string(info[MINT_INFO_VARIANCE]) +
+                  " is not finite and positive");
+        return false;
+    }
+    if (info[MINT_INFO_PIVOT] != RECONCILE_NONE) {
+        set_error(out_error, COMPUTATION_ERROR, "Computation error: the pivot of row " + std::to_string(info[MINT_INFO_PIVOT]) +
+                  " of the reconciliation system is not positive");
+        return false;
+    }
+    if (estimate && n_out == 0) lam = 1.0;                          // (no column at all: nothing to estimate from)
+    *out_shrinkage = lam;
+    return true;
+}
+
+bool anofox_hip_reconcile_mint_apply_device(const double *base, size_t stride_s, size_t stride_t, size_t n_rows, const double *residuals,
+                                            size_t res_stride_s, size_t res_stride_t, size_t n_res, const int32_t *col_offsets,
+                                            const int32_t *members, size_t n_out, size_t nnz, size_t n_series, const int32_t *bottom_col,
+                                            const int32_t *agg_cols, size_t n_agg, const int32_t *leaf_offsets, const int32_t *leaf_aggs,
+                                            size_t n_leaf, const double *variances, const double *e, size_t ld_e, double shrinkage,
+                                            const double *factor, size_t ld_a, double *work, double *out, int32_t *row_status, void *stream,
+                                            AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!reconcile_mint_report(reconcile_mint_rows_check(n_res, &message), message, out_error)) return false;
+    if (!reconcile_mint_report(reconcile_mint_lambda_check(shrinkage, false, nullptr, &message), message, out_error)) return false;
+    ReconcileMintApplyArgs m{};
+    if (!reconcile_plan_args(col_offsets, members, n_out, nnz, n_series, bottom_col, agg_cols, n_agg, leaf_offsets, leaf_aggs, n_leaf, nullptr, &m.a.p,
+                             out_error))
+        return false;
+    if (!reconcile_mint_report(reconcile_mint_dims_check(n_series, n_agg, (size_t)ANOFOX_HIP_RECONCILE_MAX_AGG, ld_e, ld_a, &message), message, out_error))
+        return false;
+    if (n_rows > (size_t)INT32_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: n_rows is limited to 2^31 - 1"); return false; }
+    if (n_rows > 0 && (!row_status || (n_out > 0 && (!base || !out)))) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_agg > 0 && !factor) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the apply needs the factor of anofox_hip_reconcile_mint_factor_device");
+        return false;
+    }
+    if (n_agg > 0 && n_rows > 0 && (!work || !residuals || !variances || !e)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_rows == 0) return true;
+    if (!device_ready(out_error)) return false;
+    ReconcileApplyArgs &a = m.a;
+    a.method = RECONCILE_WLS_VAR; a.base = base; a.out = out; a.stride_s = stride_s; a.stride_t = stride_t; a.n_rows = n_rows;
+    a.L = factor; a.ld_a = ld_a; a.work = work; a.ld_work = n_agg; a.row_status = row_status;
+    m.res = residuals; m.res_stride_s = res_stride_s; m.res_stride_t = res_stride_t; m.n_res = (int)n_res;
+    m.var = variances; m.E = e; m.ld_e = ld_e; m.lambda = shrinkage; m.g = work ? work + n_rows * n_agg : nullptr;
+    try {
+        (void)hipGetLastError();
+        launch_reconcile_mint_apply(m, (hipStream_t)stream);
+        LAUNCHCHECK("reconcile mint apply");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_reconcile_mint_batch(const int32_t *column_of, size_t n_groupings, size_t n_series, const double *forecast, size_t h,
+                                     const double *residuals, size_t n_res, double *shrinkage, double *out, int32_t *out_row_status,
+                                     double *out_variances, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    bool estimate = false;
+    if (!shrinkage) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!reconcile_mint_report(reconcile_mint_rows_check(n_res, &message), message, out_error)) return false;
+    if (!reconcile_mint_report(reconcile_mint_lambda_check(*shrinkage, true, &estimate, &message), message, out_error)) return false;
+    size_t n_out = 0, nnz = 0, n_agg = 0, n_leaf = 0;
+    if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, nullptr, nullptr, out_error)) return false;
+    std::vector<int32_t> offs(n_out + 1), memb(std::max<size_t>(nnz, 1));
+    if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, offs.data(), memb.data(), out_error)) return false;
+    if (!anofox_hip_reconcile_plan(offs.data(), memb.data(), n_out, n_series, &n_agg, &n_leaf, nullptr, nullptr, nullptr, nullptr, nullptr, out_error))
+        return false;
+    std::vector<int32_t> bottom(std::max<size_t>(n_series, 1)), aggs(std::max<size_t>(n_agg, 1)), loffs(n_series + 1), laggs(std::max<size_t>(n_leaf, 1));
+    if (!anofox_hip_reconcile_plan(offs.data(), memb.data(), n_out, n_series, &n_agg, &n_leaf, bottom.data(), aggs.data(), loffs.data(), laggs.data(),
+                                   nullptr, out_error))
+        return false;
+    if (n_out > 0 && (!residuals || (h > 0 && (!forecast || !out || !out_row_status)))) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n_out == 0) return true;
+    if (!device_ready(out_error)) return false;
+    size_t gram_elems = 0, e_elems = 0, factor_elems = 0, work_elems = 0;
+    if (!anofox_hip_reconcile_mint_sizes(n_res, n_agg, h, &gram_elems, &e_elems, &factor_elems, &work_elems, out_error)) return false;
+    if (!estimate) gram_elems = 0;
+    const size_t n_int = (n_out + 1) + nnz + n_series + n_agg + (n_series + 1) + n_leaf, cells = n_out * h, rcells = n_out * n_res;
+    const size_t n_dbl = 2 * cells + rcells + n_out + gram_elems + e_elems + factor_elems + work_elems;
+    Scratch scratch;
+    bool ok = true;
+    try {
+        int32_t *d_int = nullptr, *d_status = nullptr;
+        double *d_all = nullptr;
+        try {
+            d_int = scratch.get<int32_t>(n_int);
+            d_status = scratch.get<int32_t>(std::max<size_t>(h, 1));
+            d_all = scratch.get<double>(std::max<size_t>(n_dbl, 1));
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the plan, two blocks of " + std::to_string(n_out) + " x " + std::to_string(h) +
+                      " values, the residual block of " + std::to_string(n_out) + " x " + std::to_string(n_res) + " values, the factor of " +
+                      std::to_string(n_agg) + " x " + std::to_string(n_agg) + " values and the workspaces need " +
+                      std::to_string(n_int * 4 + h * 4 + n_dbl * 8) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            std::vector<int32_t> plan;
+            plan.reserve(n_int);
+            plan.insert(plan.end(), offs.begin(), offs.end());
+            plan.insert(plan.end(), memb.begin(), memb.begin() + nnz);
+            plan.insert(plan.end(), bottom.begin(), bottom.begin() + n_series);
+            plan.insert(plan.end(), aggs.begin(), aggs.begin() + n_agg);
+            plan.insert(plan.end(), loffs.begin(), loffs.end());
+            plan.insert(plan.end(), laggs.begin(), laggs.begin() + n_leaf);
+            const int32_t *d_offs = d_int, *d_memb = d_offs + n_out + 1, *d_bottom = d_memb + nnz, *d_aggs = d_bottom + n_series,
+                          *d_loffs = d_aggs + n_agg, *d_laggs = d_loffs + n_series + 1;
+            double *d_base = d_all, *d_out = d_base + cells, *d_res = d_out + cells, *d_var = d_res + rcells, *d_gram = d_var + n_out,
+                   *d_e = d_gram + gram_elems, *d_L = d_e + e_elems, *d_work = d_L + factor_elems;
+            HIPCHECK(hipMemcpy(d_int, plan.data(), n_int * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (cells) HIPCHECK(hipMemcpy(d_base, forecast, cells * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_res, residuals, rcells * sizeof(double), hipMemcpyHostToDevice));
+            double lam = *shrinkage;
+            ok = anofox_hip_reconcile_mint_factor_device(d_res, n_res, 1, n_res, d_offs, d_memb, n_out, nnz, n_series, d_bottom, d_aggs, n_agg, d_loffs,
+                                                         d_laggs, n_leaf, lam, d_var, d_e, n_agg, d_L, n_agg, estimate ? d_gram : nullptr, &lam, nullptr,
+                                                         out_error);
+            if (ok && h > 0)
+                ok = anofox_hip_reconcile_mint_apply_device(d_base, h, 1, h, d_res, n_res, 1, n_res, d_offs, d_memb, n_out, nnz, n_series, d_bottom, d_aggs,
+                                                            n_agg, d_loffs, d_laggs, n_leaf, d_var, d_e, n_agg, lam, d_L, n_agg, d_work, d_out, d_status,
+                                                            nullptr, out_error);
+            if (ok) {
+                if (cells) HIPCHECK(hipMemcpy(out, d_out, cells * sizeof(double), hipMemcpyDeviceToHost));     // waits for the null stream
+                if (h) HIPCHECK(hipMemcpy(out_row_status, d_status, h * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_variances) HIPCHECK(hipMemcpy(out_variances, d_var, n_out * sizeof(double), hipMemcpyDeviceToHost));
+                *shrinkage = lam;
             } else {
                 HIPCHECK(hipDeviceSynchronize());
             }

@@ -559,11 +559,44 @@ struct ReconcileApplyArgs {
     int method;
     const double *base; double *out; size_t stride_s, stride_t, n_rows;  // element (column c, row t) at c * stride_s + t * stride_t
     const double *L; size_t ld_a;
-    double *work;                                      // [n_rows x n_agg]: the residuals, then lambda
+    double *work; size_t ld_work;                      // [n_rows x ld_work], ld_work >= n_agg: the residuals, then lambda
     int32_t *row_status;                               // [n_rows]
 };
 void launch_reconcile_factor(const ReconcileFactorArgs &, hipStream_t);
 void launch_reconcile_apply(const ReconcileApplyArgs &, hipStream_t);
+// the steps of the two launches above, one by one, for reconcile_mint.hip: M = diag(w_a) + A diag(w_b) A^T into the lower triangle;
+// the panels of the Cholesky factor (info[1]: the first pivot that is not positive); row_status; work = base_a - chain(base_b);
+// the two substitutions on work; the aggregates of out as the chain over out's own bottoms
+void launch_reconcile_assemble(const ReconcileFactorArgs &, hipStream_t);
+void launch_reconcile_panels(const ReconcileFactorArgs &, hipStream_t);
+void launch_reconcile_status(const ReconcileApplyArgs &, hipStream_t);
+void launch_reconcile_incoherence(const ReconcileApplyArgs &, hipStream_t);
+void launch_reconcile_substitute(const ReconcileApplyArgs &, hipStream_t);
+void launch_reconcile_aggregates(const ReconcileApplyArgs &, hipStream_t);
+
+// MinT with the shrinkage covariance (DESIGN.md section 3 "MinT-shrink"; reconcile_mint.hip)
+enum { MINT_INFO_RESIDUAL = 0, MINT_INFO_VARIANCE = 1, MINT_INFO_WEIGHT = 2, MINT_INFO_PIVOT = 3 };    // ReconcileMintArgs::info
+struct ReconcileMintArgs {
+    ReconcilePlan p;                                   // (p.weights is not read: the variances stand in their place)
+    const double *res; size_t res_stride_s, res_stride_t; int n_res;     // residual (column c, row t) at c * res_stride_s + t * res_stride_t
+    double *var;                                       // [n_out] v_c of every column with members, 0.0 for an empty one
+    double *rsd, *f4col;                               // [n_out] scratch: 1 / sqrt(v_c); the column sums of xs^4 (estimating only)
+    double *E; size_t ld_e;                            // [n_res x ld_e] the residuals' incoherence
+    double *gram; int gram_splits;                     // [gram_splits x n_res x n_res] partial Gram matrices, then [2 x tiles] partial sums (host_reconcile_mint.hpp sizes both); null: lambda is given
+    double *lambda; double lambda_in;                  // [1] device: where the estimate goes, or (gram null) lambda_in is written
+    double *L; size_t ld_a;
+    int32_t *info;                                     // [4] MINT_INFO_*
+    int trailing, ete;                                 // RECONCILE_TRAILING_* of the factor's trailing update and of the E^T E update
+};
+struct ReconcileMintApplyArgs {
+    ReconcileApplyArgs a;                              // forecast block, factor, work [n_rows x ld_work] (r, then mu), out, row_status
+    const double *res; size_t res_stride_s, res_stride_t; int n_res;
+    const double *var, *E; size_t ld_e;
+    double lambda;
+    double *g;                                         // [n_rows x n_res] scratch: g = E mu
+};
+void launch_reconcile_mint_factor(const ReconcileMintArgs &, hipStream_t);
+void launch_reconcile_mint_apply(const ReconcileMintApplyArgs &, hipStream_t);
 
 // The choice of a method per series from backtest scores (DESIGN.md section 3 "Selection"; select.hip)
 constexpr int SELECT_MAX_METHODS = 16;                 // the median's values and the partition's counters live in registers / LDS rows of 16

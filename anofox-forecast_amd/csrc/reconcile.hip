@@ -26,49 +26,14 @@
 //                         and workgroup 0 then solves its block, the next panel, in LDS.  Forward with L, then backward with L^T.
 //   rec_bottom_kernel     every column: an empty one is copied, a bottom column gets yhat + w * chain(lambda); aggregates wait for
 //   rec_chain_kernel<1>   the member chain over the OUTPUT's bottoms -> the aggregate columns
-#include "kernels.hpp"
+#include "reconcile_device.hpp"               // the tile sizes and the guarded plan reads, shared with reconcile_mint.hip
 
 namespace anofox {
 
 namespace {
 
-constexpr int RB = 64;                       // panel width of the factor and of the substitution
-constexpr int RP = RB + 1;                   // pitch of a 64 x 64 LDS tile read down a column
-constexpr int RC = 32;                       // right-hand sides per workgroup of the substitution
-constexpr int ZP = RC + 1;                   // pitch of its panel of right-hand sides (stored with lanes along the unknowns)
+constexpr int ZP = RC + 1;                   // pitch of the substitution's panel of right-hand sides (stored with lanes along the unknowns)
 constexpr int RA_CHUNK = 4096;               // columns of M that the assembly accumulates per pass (32 KiB of LDS)
-constexpr int RK = 32;                       // K of one staging step of the trailing update
-constexpr int KP = RK + 1;                   // pitch of its staged tiles [row][k]: the stores run along k, the reads down the rows
-constexpr unsigned REC_MAX_GRID_Y = 65535u;
-
-typedef double rec_double4 __attribute__((ext_vector_type(4)));
-
-// the member range of column c; an empty range when the offsets do not lie inside the plan
-__device__ __forceinline__ void rec_column(const ReconcilePlan &p, int c, int &o0, int &o1)
-{
-    o0 = o1 = 0;
-    if (c < 0 || c >= p.n_out) return;
-    const int a = p.col_offsets[c], b = p.col_offsets[c + 1];
-    if (a < 0 || b < a || b > p.nnz) return;
-    o0 = a; o1 = b;
-}
-
-// the bottom column of member s, -1 when the plan is not what the planner wrote
-__device__ __forceinline__ int rec_bottom_of(const ReconcilePlan &p, int s)
-{
-    if (s < 0 || s >= p.n_series) return -1;
-    const int c = p.bottom_col[s];
-    return (c < 0 || c >= p.n_out) ? -1 : c;
-}
-
-__device__ __forceinline__ void rec_leaf_range(const ReconcilePlan &p, int s, int &e0, int &e1)
-{
-    e0 = e1 = 0;
-    if (s < 0 || s >= p.n_series) return;
-    const int a = p.leaf_offsets[s], b = p.leaf_offsets[s + 1];
-    if (a < 0 || b < a || b > p.n_leaf) return;
-    e0 = a; e1 = b;
-}
 
 __global__ void rec_init_kernel(int32_t *info)
 {
@@ -323,7 +288,7 @@ template <int MODE> __global__ __launch_bounds__(64) void rec_chain_kernel(const
         }
         const size_t r = r0 + (size_t)lane;
         if (lane < nr && c >= 0 && c < a.p.n_out) {
-            if (MODE == 0) a.work[r * (size_t)a.p.n_agg + (size_t)i] = a.base[rec_at(a, c, r)] - sum;
+            if (MODE == 0) a.work[r * a.ld_work + (size_t)i] = a.base[rec_at(a, c, r)] - sum;
             else a.out[rec_at(a, c, r)] = a.row_status[r] ? __builtin_nan("") : sum;
         }
     }
@@ -361,13 +326,13 @@ template <bool BACK> __global__ __launch_bounds__(256) void rec_subst_kernel(con
             }
             for (int e = tid; e < RB * RC; e += 256) {
                 const int c = e / RB, r = e % RB;                        // (lanes along the unknowns: work is [row t][unknown])
-                Z[r * ZP + c] = (r < kn && c < nc) ? a.work[(t0 + (size_t)c) * (size_t)na + (size_t)(k0 + r)] : 0.0;
+                Z[r * ZP + c] = (r < kn && c < nc) ? a.work[(t0 + (size_t)c) * a.ld_work + (size_t)(k0 + r)] : 0.0;
             }
             __syncthreads();
             const int r = tid & 63, c0 = (tid >> 6) * (RC / 4);
             if (r < qn) {
                 for (int c = c0; c < c0 + RC / 4 && c < nc; c++) {
-                    double *at = a.work + (t0 + (size_t)c) * (size_t)na + (size_t)(q0 + r);
+                    double *at = a.work + (t0 + (size_t)c) * a.ld_work + (size_t)(q0 + r);
                     double s = *at;
                     for (int k = 0; k < kn; k++) s = __builtin_fma(-Lt[r * RP + k], Z[k * ZP + c], s);
                     *at = s;
@@ -382,7 +347,7 @@ template <bool BACK> __global__ __launch_bounds__(256) void rec_subst_kernel(con
         }
         for (int e = tid; e < RB * RC; e += 256) {
             const int c = e / RB, r = e % RB;
-            Z[r * ZP + c] = (r < qn && c < nc) ? a.work[(t0 + (size_t)c) * (size_t)na + (size_t)(q0 + r)] : 0.0;
+            Z[r * ZP + c] = (r < qn && c < nc) ? a.work[(t0 + (size_t)c) * a.ld_work + (size_t)(q0 + r)] : 0.0;
         }
         __syncthreads();
         // right-looking in LDS, all 256 threads: once unknown k is final, thread (r, cg) takes it out of equation r for its 8
@@ -402,7 +367,7 @@ template <bool BACK> __global__ __launch_bounds__(256) void rec_subst_kernel(con
         }
         for (int e = tid; e < RB * RC; e += 256) {
             const int c = e / RB, r = e % RB;
-            if (r < qn && c < nc) a.work[(t0 + (size_t)c) * (size_t)na + (size_t)(q0 + r)] = Z[r * ZP + c];
+            if (r < qn && c < nc) a.work[(t0 + (size_t)c) * a.ld_work + (size_t)(q0 + r)] = Z[r * ZP + c];
         }
         __syncthreads();                                                 // (Z is read to the end before a next chunk overwrites it)
     }
@@ -436,7 +401,7 @@ __global__ __launch_bounds__(256) void rec_bottom_kernel(const ReconcileApplyArg
                 double acc = 0.0;
                 for (int e = e0; e < e1; e++) {
                     const int i = a.p.leaf_aggs[e];
-                    if (i >= 0 && i < a.p.n_agg) acc += a.work[t * (size_t)a.p.n_agg + (size_t)i];
+                    if (i >= 0 && i < a.p.n_agg) acc += a.work[t * a.ld_work + (size_t)i];
                 }
                 v = v + w * acc;
             }
@@ -448,13 +413,15 @@ __global__ __launch_bounds__(256) void rec_bottom_kernel(const ReconcileApplyArg
 
 } // namespace
 
-void launch_reconcile_factor(const ReconcileFactorArgs &a, hipStream_t stream)
+void launch_reconcile_assemble(const ReconcileFactorArgs &a, hipStream_t stream)
 {
-    hipLaunchKernelGGL(rec_init_kernel, dim3(1), dim3(64), 0, stream, a.info);
-    if (a.p.n_out > 0) hipLaunchKernelGGL(rec_weights_kernel, dim3((unsigned)(((size_t)a.p.n_out + 255) / 256)), dim3(256), 0, stream, a);
+    if (a.p.n_agg > 0) hipLaunchKernelGGL(rec_assemble_kernel, dim3((unsigned)a.p.n_agg), dim3(64), 0, stream, a);
+}
+
+void launch_reconcile_panels(const ReconcileFactorArgs &a, hipStream_t stream)
+{
     const int na = a.p.n_agg;
     if (na <= 0) return;
-    hipLaunchKernelGGL(rec_assemble_kernel, dim3((unsigned)na), dim3(64), 0, stream, a);
     const int nb = (na + RB - 1) / RB;
     for (int p = 0; p < nb; p++) {
         hipLaunchKernelGGL(rec_potrf_kernel, dim3(1), dim3(64), 0, stream, a, p);
@@ -468,26 +435,56 @@ void launch_reconcile_factor(const ReconcileFactorArgs &a, hipStream_t stream)
     }
 }
 
+void launch_reconcile_factor(const ReconcileFactorArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(rec_init_kernel, dim3(1), dim3(64), 0, stream, a.info);
+    if (a.p.n_out > 0) hipLaunchKernelGGL(rec_weights_kernel, dim3((unsigned)(((size_t)a.p.n_out + 255) / 256)), dim3(256), 0, stream, a);
+    launch_reconcile_assemble(a, stream);
+    launch_reconcile_panels(a, stream);
+}
+
+// the grid's y extent over n units of work, walked with a stride past the limit
+static unsigned rec_grid_y(size_t n) { return (unsigned)(n > REC_MAX_GRID_Y ? REC_MAX_GRID_Y : n); }
+
+void launch_reconcile_status(const ReconcileApplyArgs &a, hipStream_t stream)
+{
+    if (a.n_rows > 0) hipLaunchKernelGGL(rec_status_kernel, dim3(rec_grid_y(a.n_rows)), dim3(256), 0, stream, a);
+}
+
+void launch_reconcile_incoherence(const ReconcileApplyArgs &a, hipStream_t stream)
+{
+    if (a.n_rows == 0 || a.p.n_agg <= 0) return;
+    hipLaunchKernelGGL(rec_chain_kernel<0>, dim3((unsigned)a.p.n_agg, rec_grid_y((a.n_rows + RB - 1) / RB)), dim3(64), 0, stream, a);
+}
+
+void launch_reconcile_substitute(const ReconcileApplyArgs &a, hipStream_t stream)
+{
+    if (a.n_rows == 0 || a.p.n_agg <= 0) return;
+    const unsigned gy_chunks = rec_grid_y((a.n_rows + RC - 1) / RC);
+    const int nb = (a.p.n_agg + RB - 1) / RB;
+    for (int prev = -1; prev < nb - 1; prev++)               // step: take panel `prev` out of the blocks below it, solve panel prev + 1
+        hipLaunchKernelGGL(rec_subst_kernel<false>, dim3((unsigned)(prev < 0 ? 1 : nb - 1 - prev), gy_chunks), dim3(256), 0, stream, a, prev, nb);
+    for (int prev = nb; prev > 0; prev--)                    // the same upwards with L^T
+        hipLaunchKernelGGL(rec_subst_kernel<true>, dim3((unsigned)(prev == nb ? 1 : prev), gy_chunks), dim3(256), 0, stream, a, prev, nb);
+}
+
+void launch_reconcile_aggregates(const ReconcileApplyArgs &a, hipStream_t stream)
+{
+    if (a.n_rows == 0 || a.p.n_agg <= 0) return;
+    hipLaunchKernelGGL(rec_chain_kernel<1>, dim3((unsigned)a.p.n_agg, rec_grid_y((a.n_rows + RB - 1) / RB)), dim3(64), 0, stream, a);
+}
+
 void launch_reconcile_apply(const ReconcileApplyArgs &a, hipStream_t stream)
 {
     if (a.n_rows == 0) return;
-    const unsigned gt = (unsigned)(a.n_rows > REC_MAX_GRID_Y ? REC_MAX_GRID_Y : a.n_rows);
-    hipLaunchKernelGGL(rec_status_kernel, dim3(gt), dim3(256), 0, stream, a);
+    launch_reconcile_status(a, stream);
     if (a.p.n_out <= 0) return;
-    const int na = a.p.n_agg;
-    const size_t n_tiles = (a.n_rows + RB - 1) / RB, n_chunks = (a.n_rows + RC - 1) / RC;
-    const unsigned gy_tiles = (unsigned)(n_tiles > REC_MAX_GRID_Y ? REC_MAX_GRID_Y : n_tiles);
-    const unsigned gy_chunks = (unsigned)(n_chunks > REC_MAX_GRID_Y ? REC_MAX_GRID_Y : n_chunks);
-    if (a.method != RECONCILE_BOTTOM_UP && na > 0) {
-        hipLaunchKernelGGL(rec_chain_kernel<0>, dim3((unsigned)na, gy_tiles), dim3(64), 0, stream, a);
-        const int nb = (na + RB - 1) / RB;
-        for (int prev = -1; prev < nb - 1; prev++)               // step: take panel `prev` out of the blocks below it, solve panel prev + 1
-            hipLaunchKernelGGL(rec_subst_kernel<false>, dim3((unsigned)(prev < 0 ? 1 : nb - 1 - prev), gy_chunks), dim3(256), 0, stream, a, prev, nb);
-        for (int prev = nb; prev > 0; prev--)                    // the same upwards with L^T
-            hipLaunchKernelGGL(rec_subst_kernel<true>, dim3((unsigned)(prev == nb ? 1 : prev), gy_chunks), dim3(256), 0, stream, a, prev, nb);
+    if (a.method != RECONCILE_BOTTOM_UP) {
+        launch_reconcile_incoherence(a, stream);
+        launch_reconcile_substitute(a, stream);
     }
-    hipLaunchKernelGGL(rec_bottom_kernel, dim3((unsigned)(((size_t)a.p.n_out + 255) / 256), gt), dim3(256), 0, stream, a);
-    if (na > 0) hipLaunchKernelGGL(rec_chain_kernel<1>, dim3((unsigned)na, gy_tiles), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(rec_bottom_kernel, dim3((unsigned)(((size_t)a.p.n_out + 255) / 256), rec_grid_y(a.n_rows)), dim3(256), 0, stream, a);
+    launch_reconcile_aggregates(a, stream);
 }
 
 } // namespace anofox

@@ -813,6 +813,90 @@ def reconcile_block(forecast: torch.Tensor, column_of, method: str | int = "ols"
     return {"y": out, "row_status": row_status[:n_rows], "factor": factor, "plan": plan}
 
 
+def reconcile_mint_block(forecast: torch.Tensor, residuals: torch.Tensor, column_of, shrinkage: float | None = None,
+                         series_major: bool = True, residuals_series_major: bool = True, factor: dict | None = None,
+                         out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None, *, n_series: int | None = None) -> dict:
+    """anofox_hip_reconcile_mint_factor_device + anofox_hip_reconcile_mint_apply_device on torch tensors: MinT with the shrinkage
+    covariance (DESIGN.md section 3 "MinT-shrink"), the forecasts made coherent where they lie.
+
+    forecast as for reconcile_block.  residuals fp64, contiguous, on the same device: residuals_series_major [>= n_out, n_res] -- the
+    `error` block of backtest_block over the aggregated block as it lies -- or time-major [n_res, ld >= n_out].  column_of: an int
+    array / tensor or a plan of reconcile_plan_device.  shrinkage: None estimates the intensity (Schaefer and Strimmer), a value in
+    [0, 1] is taken as it is.  factor: the "factor" bundle an earlier call with the same plan and residuals returned; it holds the
+    intensity, so `shrinkage` is not read then.  out: a tensor of forecast's shape (not forecast itself).
+
+    Returns {"y", "row_status", "shrinkage" (float), "variances" fp64 [n_out], "factor" (the bundle: variances, e, factor, shrinkage),
+    "plan"}.  The factor call waits for the device; the apply only enqueues.  A size or an intensity the entries refuse raises
+    ValueError, a residual that is not finite or a column without variance RuntimeError, each with the entry's message."""
+    L = _lib.load()
+    assert forecast.dtype == torch.float64 and forecast.is_cuda and forecast.is_contiguous() and forecast.dim() == 2
+    assert residuals.dtype == torch.float64 and residuals.is_cuda and residuals.is_contiguous() and residuals.dim() == 2
+    dev = forecast.device
+    assert residuals.device == dev
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    plan = column_of if isinstance(column_of, dict) and "bottom_col" in column_of else reconcile_plan_device(column_of, n_series, dev)
+    n_out, n_agg = int(plan["n_out"]), int(plan["n_agg"])
+    for k in _RECONCILE_PLAN_KEYS:
+        assert plan[k].dtype == torch.int32 and plan[k].is_cuda and plan[k].is_contiguous(), k
+    if series_major:
+        n_rows, stride_s, stride_t = int(forecast.shape[1]), int(forecast.shape[1]), 1
+        assert int(forecast.shape[0]) >= n_out, "a series-major block has one row per output column"
+    else:
+        n_rows, stride_s, stride_t = int(forecast.shape[0]), 1, int(forecast.shape[1])
+        assert int(forecast.shape[1]) >= n_out, "a time-major block has one column per output column"
+    if residuals_series_major:
+        n_res, res_s, res_t = int(residuals.shape[1]), int(residuals.shape[1]), 1
+        assert int(residuals.shape[0]) >= n_out, "a series-major residual block has one row per output column"
+    else:
+        n_res, res_s, res_t = int(residuals.shape[0]), 1, int(residuals.shape[1])
+        assert int(residuals.shape[1]) >= n_out, "a time-major residual block has one column per output column"
+    if out is None:
+        out = forecast.clone()
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == tuple(forecast.shape)
+    assert out.data_ptr() != forecast.data_ptr(), "the input may not alias the output"
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    plan_args = (plan["col_offsets"].data_ptr(), plan["members"].data_ptr(), n_out, int(plan["nnz"]), int(plan["n_series"]),
+                 plan["bottom_col"].data_ptr(), plan["agg_cols"].data_ptr(), n_agg, plan["leaf_offsets"].data_ptr(),
+                 plan["leaf_aggs"].data_ptr(), int(plan["n_leaf"]))
+    res_args = (residuals.data_ptr(), res_s, res_t, n_res)
+    err = _lib.AnofoxError()
+    sizes = _lib.reconcile_mint_sizes(n_res, n_agg, n_rows)
+    if factor is None:
+        estimate = shrinkage is None
+        variances = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
+        e = torch.zeros((n_res, max(n_agg, 1)), dtype=torch.float64, device=dev)
+        fac = torch.zeros((max(n_agg, 1), max(n_agg, 1)), dtype=torch.float64, device=dev)
+        gram = torch.empty(sizes["gram"], dtype=torch.float64, device=dev) if estimate else None
+        lam = C.c_double(float("nan"))
+        st.wait_stream(torch.cuda.current_stream(dev))
+        ok = L.anofox_hip_reconcile_mint_factor_device(*res_args, *plan_args, float("nan") if estimate else float(shrinkage), variances.data_ptr(),
+                                                       e.data_ptr(), int(e.shape[1]), fac.data_ptr(), int(fac.shape[1]),
+                                                       gram.data_ptr() if gram is not None else None, C.byref(lam), C.c_void_p(st.cuda_stream),
+                                                       C.byref(err))
+        if not ok:
+            exc = ValueError if err.code == 2 else RuntimeError
+            raise exc(f"anofox_hip_reconcile_mint_factor_device failed: [{err.code}] {err.message.decode()}")
+        factor = {"variances": variances, "e": e, "factor": fac, "shrinkage": float(lam.value)}
+    for k in ("variances", "e", "factor"):
+        t = factor[k]
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous(), k
+    assert factor["variances"].numel() >= n_out and int(factor["e"].shape[0]) >= n_res
+    assert int(factor["e"].shape[1]) >= n_agg and int(factor["factor"].shape[0]) >= n_agg and int(factor["factor"].shape[1]) >= n_agg
+    work = torch.empty(max(sizes["work"], 1), dtype=torch.float64, device=dev)
+    row_status = torch.zeros(max(n_rows, 1), dtype=torch.int32, device=dev)
+    ok = L.anofox_hip_reconcile_mint_apply_device(forecast.data_ptr(), stride_s, stride_t, n_rows, *res_args, *plan_args,
+                                                  factor["variances"].data_ptr(), factor["e"].data_ptr(), int(factor["e"].shape[1]),
+                                                  float(factor["shrinkage"]), factor["factor"].data_ptr(), int(factor["factor"].shape[1]),
+                                                  work.data_ptr(), out.data_ptr(), row_status.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        exc = ValueError if err.code == 2 else RuntimeError
+        raise exc(f"anofox_hip_reconcile_mint_apply_device failed: [{err.code}] {err.message.decode()}")
+    work.record_stream(st)
+    return {"y": out, "row_status": row_status[:n_rows], "shrinkage": float(factor["shrinkage"]), "variances": factor["variances"][:n_out],
+            "factor": factor, "plan": plan}
+
+
 def _check_methods(methods) -> int:
     """The method table of the selection entries: 1 .. lib.SELECT_MAX_METHODS option blocks that share one horizon >= 1."""
     M = len(methods)

@@ -382,6 +382,7 @@ assert C.sizeof(AnofoxHipHierarchyOptions) == 16
 HIERARCHY_ROUTES = {"auto": 0, "lane": 1, "tile": 2}      # include/anofox_fcst_hip.h ANOFOX_HIERARCHY_ROUTE_*
 RECONCILE_METHODS = {"bottom_up": 0, "ols": 1, "wls_struct": 2, "wls_var": 3}      # include/anofox_fcst_hip.h ANOFOX_RECONCILE_*
 RECONCILE_MAX_AGG = 16384                                 # ANOFOX_HIP_RECONCILE_MAX_AGG
+RECONCILE_MAX_RESIDUAL_ROWS = 8192                        # ANOFOX_HIP_RECONCILE_MAX_RESIDUAL_ROWS (the MinT-shrink entries)
 
 
 assert C.sizeof(ExogenousRegressor) == 32 and C.sizeof(ExogenousData) == 16 and C.sizeof(ForecastOptionsExog) == 192
@@ -450,6 +451,8 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_backtest_batch",
     "anofox_hip_hierarchy_plan", "anofox_hip_hierarchy_device", "anofox_hip_hierarchy_batch",
     "anofox_hip_reconcile_plan", "anofox_hip_reconcile_factor_device", "anofox_hip_reconcile_apply_device", "anofox_hip_reconcile_batch",
+    "anofox_hip_reconcile_mint_sizes", "anofox_hip_reconcile_mint_factor_device", "anofox_hip_reconcile_mint_apply_device",
+    "anofox_hip_reconcile_mint_batch",
     "anofox_hip_select_winner_device", "anofox_hip_select_gather_device", "anofox_hip_select_scatter_device",
     "anofox_hip_select_combine_device", "anofox_hip_select_batch",
     "anofox_hip_paths_device", "anofox_hip_path_quantiles_device", "anofox_hip_paths_batch",
@@ -805,6 +808,19 @@ def load():
     L.anofox_hip_reconcile_batch.restype = C.c_bool
     L.anofox_hip_reconcile_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_reconcile_mint_sizes.restype = C.c_bool
+    L.anofox_hip_reconcile_mint_sizes.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, P(C.c_size_t), P(C.c_size_t), P(C.c_size_t), P(C.c_size_t),
+                                                  P(AnofoxError)]
+    res_args = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]            # the residual block: pointer, stride_s, stride_t, n_res
+    L.anofox_hip_reconcile_mint_factor_device.restype = C.c_bool
+    L.anofox_hip_reconcile_mint_factor_device.argtypes = res_args + plan_args + \
+        [C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_double), C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_reconcile_mint_apply_device.restype = C.c_bool
+    L.anofox_hip_reconcile_mint_apply_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + res_args + plan_args + \
+        [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_reconcile_mint_batch.restype = C.c_bool
+    L.anofox_hip_reconcile_mint_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_double),
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     # block 8: the choice of a method per series
     L.anofox_hip_select_winner_device.restype = C.c_bool
     L.anofox_hip_select_winner_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
@@ -975,6 +991,17 @@ def reconcile_method(method):
             raise ValueError(f"unknown reconciliation method {method!r}: one of {sorted(RECONCILE_METHODS)}")
         return RECONCILE_METHODS[method]
     return int(method)
+
+
+def reconcile_mint_sizes(n_res, n_agg, n_rows):
+    """anofox_hip_reconcile_mint_sizes: the element counts {"gram", "e", "factor", "work"} of the workspaces of the MinT-shrink device
+    entries.  A size the entry refuses raises ValueError with its message."""
+    L = load()
+    vals = [C.c_size_t(0) for _ in range(4)]
+    err = AnofoxError()
+    if not L.anofox_hip_reconcile_mint_sizes(int(n_res), int(n_agg), int(n_rows), *[C.byref(v) for v in vals], C.byref(err)):
+        raise ValueError(f"anofox_hip_reconcile_mint_sizes failed: [{err.code}] {err.message.decode()}")
+    return dict(zip(("gram", "e", "factor", "work"), (int(v.value) for v in vals)))
 
 
 def reconcile_plan(col_offsets, members, n_series):

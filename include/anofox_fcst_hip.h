@@ -441,6 +441,8 @@ typedef struct FeaturesResult {
 #define ANOFOX_HIP_N_FEATURES 117
 #define ANOFOX_HIP_FEATURES_MAX_ROWS 65536
 #define ANOFOX_HIP_RECONCILE_MAX_AGG 16384      /* aggregate columns of a reconciliation plan: bounds the factor at 2 GiB */
+#define ANOFOX_HIP_RECONCILE_MAX_RESIDUAL_ROWS 8192     /* residual rows of a MinT-shrink call: one n_res x n_res Gram plane is 512 MiB,
+                                                           and the whole Gram workspace stays under 1 GiB for every n_res */
 
 /*
  * The features of ONE series, the reference's extract_features (features.rs) behind its FFI wrapper: only the features the source
@@ -2329,6 +2331,138 @@ bool anofox_hip_reconcile_batch(const int32_t *column_of,
                                 double *out,
                                 int32_t *out_row_status,
                                 struct AnofoxError *out_error);
+
+/*
+ * MinT with the shrinkage covariance estimator (Wickramasuriya et al. 2019; Schaefer and Strimmer 2005), in the same constraint form.
+ * These are entries of their own: the method enum above is not extended.  The residual block holds n_res rows of base-forecast
+ * errors for every column of the plan, element (column c, row t) at c * res_stride_s + t * res_stride_t in both layouts that
+ * anofox_hip_metrics_device takes (the `error` block of anofox_hip_backtest is series-major: res_stride_s = its row length,
+ * res_stride_t = 1).  P = every bottom and every aggregate column, n_p = n_series + n_agg; an empty column is never read.
+ *   1. v_c = ((((0.0 + x_0c^2) + x_1c^2) + ...) / n_res) for c in P: serial in row order, no fused multiply-add, no centring (the
+ *      shrink.estim of the hts package).  Contract: equality of bits with that restatement.
+ *   2. xs_tc = x_tc * (1 / sqrt(v_c)), G = Xs Xs^T (n_res x n_res, inner dimension over P: the bottoms in series order, then the
+ *      aggregates), fro = sum G_tu^2, q = sum G_tt^2, f4 = sum xs_tc^4, each in one fixed order.
+ *   3. T = n_res; sum_v = ((q - f4) - (fro - n_p T^2) / T) / (T (T - 1)); sum_d = fro / T^2 - n_p; shrinkage = min(max(sum_v / sum_d,
+ *      0), 1), and 1 when sum_d is not finite and positive.  These are the sums of shrink.estim over all n_p^2 pairs of columns; no
+ *      array of size n_p x n_p is formed.  A caller may pass its own intensity in [0, 1]; steps 2 and 3 are skipped then.
+ *   4. E[t][i] = x_t,agg(i) - (((0.0 + x_t,b(m0)) + x_t,b(m1)) + ...): the residuals' own incoherence.
+ *   5. M = shrinkage (diag(v_a) + A diag(v_b) A^T) + ((1 - shrinkage) / n_res) E^T E; every element takes its t terms in ascending
+ *      order (fused multiply-adds); M = L L^T by the factor kernels of anofox_hip_reconcile_factor_device.
+ *   6. For a forecast row: r and mu = M^-1 r as above; g_t = sum_i E[t][i] mu_i; btilde_s = (yhat_b(s) + (shrinkage v_b(s)) *
+ *      chain(mu over the aggregates that hold s)) - ((1 - shrinkage) / n_res) * sum_t x_t,b(s) g_t.  Both sums are chains of fused
+ *      multiply-adds from 0.0 in ascending index order.
+ *   7. As step 4 above: the aggregates are the chain over the output's own bottoms, the output is coherent to the bit; empty columns
+ *      are copied; row_status as anofox_hip_reconcile_apply_device.
+ * No floating-point atomics: the same bits on every run, through every entry, in both layouts of the forecast block and both
+ * layouts of the residual block.  With shrinkage 1 the result is that of method 3 with the variances as weights.
+ *
+ * The element counts (doubles) of what the caller of the device entries allocates.  Host only.  gram_elems: the workspace of the
+ * estimate (a function of n_res alone; not needed when an intensity is passed in); e_elems = n_res * n_agg; factor_elems = n_agg *
+ * n_agg; work_elems = n_rows * (n_agg + n_res), the work area of the apply.
+ * INVALID_INPUT: n_res < 2 or above ANOFOX_HIP_RECONCILE_MAX_RESIDUAL_ROWS, n_agg above ANOFOX_HIP_RECONCILE_MAX_AGG.
+ */
+bool anofox_hip_reconcile_mint_sizes(size_t n_res,
+                                     size_t n_agg,
+                                     size_t n_rows,
+                                     size_t *gram_elems,
+                                     size_t *e_elems,
+                                     size_t *factor_elems,
+                                     size_t *work_elems,
+                                     struct AnofoxError *out_error);
+
+/*
+ * Steps 1 to 5.  All arrays in device memory; the plan arrays as for anofox_hip_reconcile_factor_device.  shrinkage: NaN asks for the
+ * estimate, a value in [0, 1] is taken as it is.  Outputs: variances fp64 [n_out] (0.0 in an empty column); e fp64 [n_res x ld_e],
+ * ld_e >= n_agg -- a value the caller keeps beside the factor; factor fp64 [n_agg x ld_a]: only the lower triangle is written, and
+ * only the first n_agg columns of e; *out_shrinkage (host memory) the intensity used.  gram_work fp64 [gram_elems] is scratch (may
+ * be NULL when an intensity is passed in).  The call returns after everything is finished.
+ * INVALID_INPUT: n_res outside [2, ANOFOX_HIP_RECONCILE_MAX_RESIDUAL_ROWS], an intensity outside [0, 1], ld_e or ld_a < n_agg, the
+ * plan and size limits of the entries above.  COMPUTATION_ERROR, each naming the column or row: a residual of a participating
+ * column that is not finite; a participating column whose variance is not finite and positive; a pivot that is not positive
+ * (reachable with shrinkage 0 and n_res < n_agg).
+ */
+bool anofox_hip_reconcile_mint_factor_device(const double *residuals,
+                                             size_t res_stride_s,
+                                             size_t res_stride_t,
+                                             size_t n_res,
+                                             const int32_t *col_offsets,
+                                             const int32_t *members,
+                                             size_t n_out,
+                                             size_t nnz,
+                                             size_t n_series,
+                                             const int32_t *bottom_col,
+                                             const int32_t *agg_cols,
+                                             size_t n_agg,
+                                             const int32_t *leaf_offsets,
+                                             const int32_t *leaf_aggs,
+                                             size_t n_leaf,
+                                             double shrinkage,
+                                             double *variances,
+                                             double *e,
+                                             size_t ld_e,
+                                             double *factor,
+                                             size_t ld_a,
+                                             double *gram_work,
+                                             double *out_shrinkage,
+                                             void *stream,
+                                             struct AnofoxError *out_error);
+
+/*
+ * Steps 6 and 7 for n_rows rows of a device-resident forecast block (base, out, strides, row_status as for
+ * anofox_hip_reconcile_apply_device).  residuals, variances, e, shrinkage and factor as the factor call took and returned them;
+ * work fp64 [n_rows x (n_agg + n_res)] is the caller's scratch (NULL without aggregates).  The call only enqueues on `stream`.
+ * INVALID_INPUT: as above, a NaN intensity, a factor missing.
+ */
+bool anofox_hip_reconcile_mint_apply_device(const double *base,
+                                            size_t stride_s,
+                                            size_t stride_t,
+                                            size_t n_rows,
+                                            const double *residuals,
+                                            size_t res_stride_s,
+                                            size_t res_stride_t,
+                                            size_t n_res,
+                                            const int32_t *col_offsets,
+                                            const int32_t *members,
+                                            size_t n_out,
+                                            size_t nnz,
+                                            size_t n_series,
+                                            const int32_t *bottom_col,
+                                            const int32_t *agg_cols,
+                                            size_t n_agg,
+                                            const int32_t *leaf_offsets,
+                                            const int32_t *leaf_aggs,
+                                            size_t n_leaf,
+                                            const double *variances,
+                                            const double *e,
+                                            size_t ld_e,
+                                            double shrinkage,
+                                            const double *factor,
+                                            size_t ld_a,
+                                            double *work,
+                                            double *out,
+                                            int32_t *row_status,
+                                            void *stream,
+                                            struct AnofoxError *out_error);
+
+/*
+ * The same for host buffers: column_of as for anofox_hip_hierarchy_plan, forecast and out fp64 series-major [n_out x h], residuals
+ * fp64 series-major [n_out x n_res], *shrinkage NaN (estimate) or a value in [0, 1] on entry and the intensity used on return,
+ * out_row_status int32 [h], out_variances fp64 [n_out] (may be NULL).  The call plans, uploads, factors, applies and reads back
+ * once.  The planner's errors and the limits come first and need no device.  A failed device allocation is a COMPUTATION_ERROR that
+ * names the size.  One device; fp64 only.
+ */
+bool anofox_hip_reconcile_mint_batch(const int32_t *column_of,
+                                     size_t n_groupings,
+                                     size_t n_series,
+                                     const double *forecast,
+                                     size_t h,
+                                     const double *residuals,
+                                     size_t n_res,
+                                     double *shrinkage,
+                                     double *out,
+                                     int32_t *out_row_status,
+                                     double *out_variances,
+                                     struct AnofoxError *out_error);
 
 /* ------------------------------------------------------------------------- */
 /* Block 8: the choice of a forecast method per series from backtest scores    */
