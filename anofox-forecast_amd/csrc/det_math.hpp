@@ -126,6 +126,10 @@ __device__ __forceinline__ double dm_exp(double x)
 // two degree-6 polynomials in Estrin form (5 dependent fused multiply-adds each), the tables (tools/gen_pow_tables.py,
 // 2.5 KB) in LDS.  oracle/det_math.h (det_pow_step) states the identical sequence of operations on the identical
 // tables.   ln x = e ln2 + LOG_C[j] + log1p(m INV_C[j] - 1);   e^t = 2^(n >> 6) EXP2_T[n & 63] (1 + p(t - n ln2/64)).
+// Accuracy against the exact power (tests/math_cases.py): within 2.7 (1 + |y ln x|) ulp over the domain -- t = y ln x is rounded once,
+// as one double, so the error grows with |t|: 2.13 ulp at worst on [1/2, 2], 1426 ulp at 2^776.  It does not matter where growth rates
+// live: b is near 1 (|b - 1| > 1/16 in 0.1 % of the steps, else dm_pow_near1 below, which is under one ulp), so |y ln x| << 1 and the
+// bound is a few ulps; what the parity contract needs is the same bits as the checker, which tests/test_gpu_math.py compares directly.
 #include "pow_tables.inc"
 static __device__ const double dm_pow_inv_c_src[ANOFOX_POW_INV_C_N] = { ANOFOX_POW_INV_C_VALUES };
 static __device__ const double dm_pow_log_c_src[ANOFOX_POW_LOG_C_N] = { ANOFOX_POW_LOG_C_VALUES };
@@ -252,7 +256,8 @@ __device__ __forceinline__ double dm_pow_near1(double r, const DmPowNear1 &o)
 // matter for operands whose reciprocal or residual leaves the normal range: on this domain no operand is scaled (v_div_scale
 // returns it unchanged and leaves VCC clear, so v_div_fmas IS the fma below) and v_div_fixup returns its first operand, so the
 // result is bit for bit the hardware's correctly rounded quotient, which is the CPU's 1.0 / d.  7 instructions instead of 12.
-// (anofox_hip_selftest compares it with the compiled division on 2^28 operands per call.)
+// (anofox_hip_selftest_recip compares it with the compiled division on the caller's number of generated operands,
+// tests/test_gpu_parity.py: 2^28 per seed.)
 __device__ __forceinline__ double dm_recip(double d)
 {
     const double x0 = __builtin_amdgcn_rcp(d);

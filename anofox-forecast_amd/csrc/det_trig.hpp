@@ -1,6 +1,10 @@
 // det_trig.hpp -- sin and cos for the kernels that evaluate a phase (periods.hip, features.hip): a two-term Cody-Waite reduction by
-// fused multiply-adds, exact in its first step, then fdlibm's kernels on [-pi/4, pi/4].  Below one ulp for every argument a series
-// that fits in memory can produce; the same bits on every run.
+// fused multiply-adds, exact in its first step, then fdlibm's kernels on [-pi/4, pi/4].  The same bits on every run, and the bits of
+// oracle/det_trig.h (det_sincos) at every argument.  Accuracy (tests/math_cases.py, measured against an extended-precision reference):
+// the ABSOLUTE error is below 2^-53 for every accepted argument, and for |x| < 2^24 the error is below one ulp of the result wherever
+// |result| >= 2^-26.  It is NOT below one ulp of a result next to a zero of sin or cos (up to 1.5e5 ulp of a result of 1e-16 at the
+// nearest double to 1082091 pi/2; 640 ulp among the DFT phases -2 pi k t / n, n <= 2049): see the tail line below.  The sums that
+// use these values (periodograms, DFT coefficients) care about the absolute error only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,8 +13,12 @@ namespace anofox {
 namespace {
 
 // sin and cos of x.  k = nearest integer to x 2/pi; x - k p1 is exact (both are multiples of ulp(p1) and the difference is below 1),
-// the second step leaves a head and a tail for the kernels.  |k| <= 2^52 is accepted; pi/2 - p1 - p2 = 1.5e-33, so the reduction
-// error k 1.5e-33 stays below 1e-17 for every |x| < 1e16.
+// the second step leaves a head y0 and a tail y1 for the kernels.  |x| < 2^52 is accepted; pi/2 - p1 - p2 = p3 = -1.5e-33 goes into
+// the tail.  What limits the accuracy is the tail's r0 - y0: when x is next to a multiple of pi/2, y0 cancels far below r0 ~ k p2 and the
+// difference is rounded at the scale of r0, an absolute error of up to 2^-53 k p2 (below 2^-84 for |x| < 2^24, 2^-55 at |x| ~ 2^52) that is
+// the whole relative error of a tiny result.  Taking k p2 as an exact two-product would repair it and move bits of periods.hip and
+// features.hip at the 1e-26 level, for about nine more fp64 operations per call; tests/test_math_cpu.py asserts the present behaviour
+// so that such a repair shows.  sin(-0) is +0 (r0 adds +0 to -0): a sum of phases does not see the sign of a zero term.
 __device__ __forceinline__ void per_sincos(double x, double &s, double &c)
 {
     const double two_over_pi = 6.36619772367581382433e-01;

@@ -2073,6 +2073,22 @@ bool anofox_hip_selftest_recip(uint64_t n_operands, uint64_t seed, uint64_t *out
     return true;
 }
 
+bool anofox_hip_selftest_math(int fn, const double *x, const double *y, uint64_t n, int block_threads, double *out, double *out2, AnofoxError *err)
+{
+    static_assert(anofox::NM_BLOCK == 64, "the header names 64 as the fit kernels' workgroup size");
+    if (fn < 0 || fn >= ANOFOX_HIP_MATH_FN_COUNT) { set_error(err, INVALID_INPUT, "Invalid input: fn is not an AnofoxHipMathFn"); return false; }
+    if (block_threads != anofox::NM_BLOCK && block_threads != 256) { set_error(err, INVALID_INPUT, "Invalid input: block_threads must be 64 or 256"); return false; }
+    if (n > ((uint64_t)1 << 28)) { set_error(err, INVALID_INPUT, "Invalid input: more than 2^28 operands"); return false; }
+    const bool needs_y = fn == ANOFOX_HIP_MATH_SCALBN || fn == ANOFOX_HIP_MATH_POW_STEP || fn == ANOFOX_HIP_MATH_POW_NEAR1 || fn == ANOFOX_HIP_MATH_POW_POS;
+    if (n > 0 && (!x || !out || (needs_y && !y) || (fn == ANOFOX_HIP_MATH_SINCOS && !out2))) { set_error(err, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!device_ready(err)) return false;
+    if (!anofox::math_selftest(fn, x, needs_y ? y : nullptr, n, block_threads, out, out2, nullptr)) {
+        set_error(err, INTERNAL_ERROR, "Internal error: the device could not run the math self test");
+        return false;
+    }
+    return true;
+}
+
 bool anofox_hip_batch_lane_stats(AnofoxHipBatch *b, AnofoxHipLaneStats *out, size_t struct_size)
 {
     if (!b || !out || !b->ran || struct_size < sizeof(uint64_t)) return false;

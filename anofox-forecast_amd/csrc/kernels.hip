@@ -5,6 +5,8 @@
 #include "classic_device.hpp"
 #include "fit_units.hpp"
 #include "kernels.hpp"
+#include "det_trig.hpp"
+#include "../../include/anofox_fcst_hip.h"   // AnofoxHipMathFn of the math self test
 
 namespace anofox {
 
@@ -574,6 +576,49 @@ unsigned long long recip_selftest(unsigned long long n, unsigned long long seed,
     (void)hipFree(d_cnt); (void)hipFree(d_bad);
     if (first_bad_out) *first_bad_out = hb;
     return h[0];
+}
+
+// ---- self test of the elementary functions (det_math.hpp, det_trig.hpp): function `fn` at the caller's operands -------------------
+// One thread per operand, the workgroup size is the launch's (64 or 256).  The functions are the product's own inline ones.  POW_STEP
+// lives under the rule of the fit kernels: every thread of the workgroup, those past n included, fills the LDS tables before any leaves.
+__global__ __launch_bounds__(256) void math_selftest_kernel(int fn, const double *__restrict__ x, const double *__restrict__ y, unsigned long long n,
+                                                            double *__restrict__ out, double *__restrict__ out2)
+{
+    if (fn == ANOFOX_HIP_MATH_POW_STEP) dm_pow_tab_init();           // fn is the same for the whole grid: the barrier inside is uniform
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double xi = x[i], yi = y ? y[i] : 0.0;
+    double r = 0.0;
+    switch (fn) {
+    case ANOFOX_HIP_MATH_LOG: r = dm_log(xi); break;
+    case ANOFOX_HIP_MATH_EXP: r = dm_exp(xi); break;
+    case ANOFOX_HIP_MATH_SCALBN: r = dm_scalbn(xi, (int)yi); break;
+    case ANOFOX_HIP_MATH_POW_STEP: r = dm_pow_step(xi, yi, dm_pow_lane()); break;
+    case ANOFOX_HIP_MATH_POW_NEAR1: { DmPowNear1 c; dm_pow_near1_coef(yi, c); r = dm_pow_near1(xi, c); break; }
+    case ANOFOX_HIP_MATH_POW_POS: r = dm_pow_pos(xi, yi); break;
+    default: { double sn, cs; per_sincos(xi, sn, cs); r = sn; out2[i] = cs; break; }      // ANOFOX_HIP_MATH_SINCOS (the host entry checks fn)
+    }
+    out[i] = r;
+}
+
+bool math_selftest(int fn, const double *x, const double *y, unsigned long long n, int block_threads, double *out, double *out2, hipStream_t stream)
+{
+    if (n == 0) return true;
+    const size_t bytes = (size_t)n * sizeof(double);
+    const bool two = fn == ANOFOX_HIP_MATH_SINCOS;
+    double *d_x = nullptr, *d_y = nullptr, *d_out = nullptr, *d_out2 = nullptr;
+    bool ok = hipMalloc(&d_x, bytes) == hipSuccess && hipMalloc(&d_out, bytes) == hipSuccess && (!y || hipMalloc(&d_y, bytes) == hipSuccess) &&
+              (!two || hipMalloc(&d_out2, bytes) == hipSuccess);
+    ok = ok && hipMemcpyAsync(d_x, x, bytes, hipMemcpyHostToDevice, stream) == hipSuccess &&
+         (!y || hipMemcpyAsync(d_y, y, bytes, hipMemcpyHostToDevice, stream) == hipSuccess);
+    if (ok) {
+        const unsigned long long blocks = (n + (unsigned long long)block_threads - 1) / (unsigned long long)block_threads;
+        hipLaunchKernelGGL(math_selftest_kernel, dim3((unsigned)blocks), dim3((unsigned)block_threads), 0, stream, fn, d_x, d_y, n, d_out, d_out2);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) == hipSuccess &&
+             (!two || hipMemcpy(out2, d_out2, bytes, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    (void)hipFree(d_x); (void)hipFree(d_y); (void)hipFree(d_out); (void)hipFree(d_out2);
+    return ok;
 }
 
 } // namespace anofox

@@ -774,6 +774,10 @@ int launch_arima(const ArimaArgs &, hipStream_t);   // returns the number of ker
 // whose quotients differ (0 is the claim), ~0 when the device could not run it; *first_bad: one of them
 unsigned long long recip_selftest(unsigned long long n, unsigned long long seed, double *first_bad, hipStream_t stream);
 
+// the elementary functions of det_math.hpp / det_trig.hpp at the caller's operands (host arrays of n doubles; y may be NULL, out2 is
+// SINCOS's cosine): fn is an AnofoxHipMathFn, block_threads 64 or 256 (the host entry checks both).  False when the device could not run it
+bool math_selftest(int fn, const double *x, const double *y, unsigned long long n, int block_threads, double *out, double *out2, hipStream_t stream);
+
 // Bootstrap sample paths and their quantiles (DESIGN.md section 3 "Sample paths"; paths.hip).  Element (series s, row t) of the
 // point block and of the pool is at s * stride_s + t * stride_t, as for the metrics entries.
 enum { PATHS_CUMULATIVE = 0, PATHS_INDEPENDENT = 1 };

@@ -9,12 +9,12 @@
 // the source's sequential sums as well (every lane adds them redundantly from LDS).
 //
 // What differs from the source is the evaluation of the elementary functions only: sin / cos are per_sincos of det_trig.hpp (two-term
-// Cody-Waite reduction by fused multiply-adds, exact in its first step, then fdlibm's kernels on [-pi/4, pi/4]: below one ulp for
-// every argument a series that fits in memory can produce), ln / exp are det_math.hpp's, the power (1 - p)^M of the false-alarm
-// probability is exp(M ln(1 - p)), atan2 is the device library's.  SAZED evaluates the phase exactly: the padded length L is a
-// power of two, so (k t) mod L is an integer operation and the angle -2 pi ((k t) mod L) / L is rounded once.  The inner sum of
-// the DFT stops at n: the padded tail holds exact zeros.  The contract is therefore a tolerance on the figures plus equality of
-// every decision (tests/periods_ref.py).
+// Cody-Waite reduction by fused multiply-adds, exact in its first step, then fdlibm's kernels on [-pi/4, pi/4]: absolute error below
+// 2^-53, which is what these sums need; not below one ulp of a result next to a zero, see det_trig.hpp), ln / exp are det_math.hpp's,
+// the power (1 - p)^M of the false-alarm probability is exp(M ln(1 - p)), atan2 is the device library's.  SAZED evaluates the phase
+// exactly: the padded length L is a power of two, so (k t) mod L is an integer operation and the angle -2 pi ((k t) mod L) / L is
+// rounded once.  The inner sum of the DFT stops at n: the padded tail holds exact zeros.  The contract is therefore a tolerance on
+// the figures plus equality of every decision (tests/periods_ref.py).
 //
 // Decisions: the first strict maximum of the power in frequency order (Lomb-Scargle), the first strict minimum of the AIC, the
 // largest peak with ties to the lower bin (the source's stable sort).  A lane keeps the first strict extreme of its own ascending

@@ -419,7 +419,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_batch_n_series", "anofox_hip_batch_periods", "anofox_hip_batch_set_fixed_params",
     "anofox_hip_set_devices", "anofox_hip_get_devices", "anofox_hip_set_min_series_per_device", "anofox_hip_shard_range",
     "anofox_hip_set_default_arima_method", "anofox_hip_batch_set_arima_method", "anofox_hip_release_caches",
-    "anofox_hip_batch_run_many", "anofox_hip_batch_lane_stats", "anofox_hip_selftest_recip",
+    "anofox_hip_batch_run_many", "anofox_hip_batch_lane_stats", "anofox_hip_selftest_recip", "anofox_hip_selftest_math",
     "anofox_ts_mstl_decomposition", "anofox_free_mstl_result", "anofox_hip_mstl_decompose_batch", "anofox_hip_mstl_decompose_device",
     "anofox_ts_forecast_exog", "anofox_ts_forecast_exog_batch", "anofox_hip_batch_set_exog_device", "anofox_hip_batch_exog_coefficients",
     "anofox_ts_detect_changepoints_bocpd", "anofox_free_bocpd_result", "anofox_hip_changepoints_batch", "anofox_hip_changepoints_device",
@@ -484,6 +484,10 @@ ARIMA_CSS, ARIMA_CSS_ML = 0, 1     # include/anofox_fcst_hip.h: ANOFOX_ARIMA_CSS
 _lib = None
 
 
+MATH_FNS = {"log": 0, "exp": 1, "scalbn": 2, "pow_step": 3, "pow_near1": 4, "pow_pos": 5, "sincos": 6}      # AnofoxHipMathFn
+NM_BLOCK = 64                                          # csrc/nm.hpp: the fit kernels' workgroup; anofox_hip_selftest_math takes it or 256
+
+
 def load():
     """Load the HIP library; raises if it has not been built (no fallback)."""
     global _lib
@@ -531,6 +535,8 @@ def load():
     L.anofox_hip_batch_stats.argtypes = [C.c_void_p, P(AnofoxHipStats)]
     L.anofox_hip_selftest_recip.restype = C.c_bool
     L.anofox_hip_selftest_recip.argtypes = [C.c_uint64, C.c_uint64, P(C.c_uint64), P(C.c_double)]
+    L.anofox_hip_selftest_math.restype = C.c_bool
+    L.anofox_hip_selftest_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, P(AnofoxError)]
     L.anofox_hip_batch_lane_stats.restype = C.c_bool
     L.anofox_hip_batch_lane_stats.argtypes = [C.c_void_p, P(AnofoxHipLaneStats), C.c_size_t]
     L.anofox_hip_batch_device_results.restype = C.c_bool

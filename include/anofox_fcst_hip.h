@@ -1829,6 +1829,34 @@ bool anofox_hip_batch_periods(const AnofoxHipBatch *batch, int32_t *out_periods)
  */
 bool anofox_hip_selftest_recip(uint64_t n_operands, uint64_t seed, uint64_t *out_mismatches, double *out_first_bad);
 
+/*
+ * Self test of the kernels' elementary functions (csrc/det_math.hpp, csrc/det_trig.hpp): evaluates function `fn` on the device
+ * at the caller's operands, one thread per operand, through the very inline functions the fit kernels call.  x, y, out, out2 are
+ * HOST arrays of n doubles; y may be NULL where the function takes one operand, out2 is written by SINCOS only (NULL otherwise).
+ *   LOG        out = dm_log(x)
+ *   EXP        out = dm_exp(x)
+ *   SCALBN     out = dm_scalbn(x, (int)y)
+ *   POW_STEP   out = dm_pow_step(x, y)            x in [2^-1000, 2^1000], 0 < y <= 1; the tables are the workgroup's LDS copy
+ *   POW_NEAR1  out = dm_pow_near1(x, coef(y))     x = r = b - 1, |r| <= 2^-4; the coefficients are dm_pow_near1_coef(y) on the device
+ *   POW_POS    out = dm_pow_pos(x, y)
+ *   SINCOS     out = sin x, out2 = cos x          per_sincos
+ * block_threads is the workgroup size of the launch: 64 (the fit kernels' NM_BLOCK) or 256; anything else is refused.  The parity
+ * contract: every result has the bits of oracle/det_math.h / oracle/det_trig.h at the same operand, whatever the workgroup size and n.
+ * False with *err set for a bad argument, and when no device could run it.  Takes no environment switch, keeps no state.
+ */
+typedef enum AnofoxHipMathFn {
+    ANOFOX_HIP_MATH_LOG = 0,
+    ANOFOX_HIP_MATH_EXP = 1,
+    ANOFOX_HIP_MATH_SCALBN = 2,
+    ANOFOX_HIP_MATH_POW_STEP = 3,
+    ANOFOX_HIP_MATH_POW_NEAR1 = 4,
+    ANOFOX_HIP_MATH_POW_POS = 5,
+    ANOFOX_HIP_MATH_SINCOS = 6,
+    ANOFOX_HIP_MATH_FN_COUNT = 7,
+} AnofoxHipMathFn;
+bool anofox_hip_selftest_math(int fn, const double *x, const double *y, uint64_t n, int block_threads,
+                              double *out, double *out2, struct AnofoxError *err);
+
 /* Lane-level efficiency counters of the last run (waits for it); false before a run. */
 bool anofox_hip_batch_lane_stats(AnofoxHipBatch *batch, AnofoxHipLaneStats *out, size_t struct_size);
 

@@ -150,7 +150,11 @@ static inline double det_pow_pos(double x, double y) { return det_exp(y * det_lo
  *           p(s)     = s + s^2 (1/2 + s/6 + s^2 (1/24 + s/120 + s^2/720))             (remainder s^7/5040 < 3e-20)
  * Every operation is an IEEE-754 binary64 +, *, fma or an exact integer step, in a fixed order: csrc/det_math.hpp
  * (dm_pow_step) states the identical sequence and reads the identical tables, so kernel and checker agree bit for bit.
- * Accuracy against the exact power: < 1.5 ulp over the domain (tests/test_host_logic.py).
+ * Accuracy against the exact power (tests/math_cases.py, tests/test_math_cpu.py): within 2.7 (1 + |y ln x|) ulp over the domain.  t = y * lg
+ * is rounded once, as one double, so the error grows with |t|: 2.13 ulp at worst on [1/2, 2] (x = 0x1.ef5efcfd85d72p+0,
+ * y = 0x1.ff53967c7cdd5p-1), 1426 ulp at x = 0x1.8659eb9cfcda2p+776.  It does not matter where growth rates live: b is near 1 (99.9 % of the
+ * steps take det_pow_near1 below, which is under one ulp), there |y ln x| << 1 and the bound is a few ulps; the likelihood compares
+ * trial points that all went through this same function, and what parity needs is the same bits on both sides.
  */
 #include "pow_tables.inc"
 static const double det_pow_inv_c[ANOFOX_POW_INV_C_N] = { ANOFOX_POW_INV_C_VALUES };
@@ -222,7 +226,7 @@ static inline double det_pow_near1(double r, const double *c)
  * the DOMAIN: a denominator outside [2^-1000, 2^1000] in magnitude (or not a number) makes the trial point inadmissible -- the
  * kernels then compute the quotient with v_rcp_f64 + two Newton steps + one correction, the compiler's own division expansion
  * without its range scaling and special-case fix-up (7 instructions instead of 12), which is the correctly rounded quotient
- * exactly on that domain (csrc/det_math.hpp dm_recip; checked against the hardware division by anofox_hip_selftest).
+ * exactly on that domain (csrc/det_math.hpp dm_recip; checked against the hardware division by anofox_hip_selftest_recip).
  */
 static inline int det_recip_ok(double d) { double a = fabs(d); return a >= 0x1p-1000 && a <= 0x1p+1000; }
 /*

@@ -22,6 +22,7 @@
 #include "../include/anofox_fcst_hip.h"
 #include "arima.h"
 #include "det_math.h"
+#include "det_trig.h"
 #include "ets.h"
 
 #include <ctype.h>
@@ -876,3 +877,23 @@ int oracle_ets_fixed_batch(const double *values, const int64_t *offsets, size_t 
 double oracle_det_log(double x) { return det_log(x); }
 double oracle_det_exp(double x) { return det_exp(x); }
 double oracle_det_pow_step(double x, double y) { return det_pow_step(x, y); }
+
+/* The checker's elementary functions at given operands: the CPU side of anofox_hip_selftest_math (same enum, same meaning of x, y,
+ * out, out2; y may be NULL where the function takes one operand, out2 is written by SINCOS only).  Returns 0, or -1 for an unknown fn. */
+int oracle_det_eval(int fn, const double *x, const double *y, uint64_t n, double *out, double *out2)
+{
+    if (fn < 0 || fn >= ANOFOX_HIP_MATH_FN_COUNT) return -1;
+    for (uint64_t i = 0; i < n; i++) {
+        const double xi = x[i], yi = y ? y[i] : 0.0;
+        switch (fn) {
+        case ANOFOX_HIP_MATH_LOG: out[i] = det_log(xi); break;
+        case ANOFOX_HIP_MATH_EXP: out[i] = det_exp(xi); break;
+        case ANOFOX_HIP_MATH_SCALBN: out[i] = det_scalbn(xi, (int)yi); break;
+        case ANOFOX_HIP_MATH_POW_STEP: out[i] = det_pow_step(xi, yi); break;
+        case ANOFOX_HIP_MATH_POW_NEAR1: { double c[DET_POW_NEAR1_DEG + 1]; det_pow_near1_coef(yi, c); out[i] = det_pow_near1(xi, c); break; }
+        case ANOFOX_HIP_MATH_POW_POS: out[i] = det_pow_pos(xi, yi); break;
+        default: det_sincos(xi, &out[i], &out2[i]); break;
+        }
+    }
+    return 0;
+}

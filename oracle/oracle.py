@@ -104,6 +104,8 @@ def lib():
         _lib.oracle_det_log.argtypes = [C.c_double]
         _lib.oracle_det_exp.restype = C.c_double
         _lib.oracle_det_exp.argtypes = [C.c_double]
+        _lib.oracle_det_eval.restype = C.c_int
+        _lib.oracle_det_eval.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         _lib.oracle_detect_seasonality_first.restype = C.c_int
         _lib.oracle_detect_seasonality_first.argtypes = [C.c_void_p, C.c_size_t]
         _lib.oracle_fill_nulls_interpolate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -111,6 +113,24 @@ def lib():
         _lib.oracle_auto_ets_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     return _lib
+
+
+# the functions of oracle_det_eval / anofox_hip_selftest_math (AnofoxHipMathFn, include/anofox_fcst_hip.h)
+MATH_FNS = {"log": 0, "exp": 1, "scalbn": 2, "pow_step": 3, "pow_near1": 4, "pow_pos": 5, "sincos": 6}
+
+
+def det_eval(fn, x, y=None):
+    """The checker's det_log / det_exp / det_scalbn / det_pow_step / det_pow_near1 / det_pow_pos / det_sincos at the operands x (and y):
+    an array of results, for "sincos" the pair (sin, cos)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    assert y is None or y.shape == x.shape
+    out = np.full(x.shape, np.nan)
+    out2 = np.full(x.shape, np.nan) if fn == "sincos" else None
+    rc = lib().oracle_det_eval(MATH_FNS[fn], x.ctypes.data, None if y is None else y.ctypes.data, x.size, out.ctypes.data,
+                               None if out2 is None else out2.ctypes.data)
+    assert rc == 0, rc
+    return (out, out2) if fn == "sincos" else out
 
 
 def validity_mask(valid):
