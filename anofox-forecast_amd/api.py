@@ -4410,6 +4410,155 @@ def ts_forecast_quantiles_by(group, date, target, method, horizon, frequency, le
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# scores of sample paths: CRPS, pinball, ranks and energy score (include/anofox_fcst_hip.h block 10)
+# --------------------------------------------------------------------------------------------
+def path_scores_batch(points, pools, actuals, levels=(), n_paths=1000, mode="cumulative", joint=False, seed=0, column_of=None):
+    """anofox_hip_path_scores_batch: what paths_batch takes, plus `actuals` [n_series, h] with NaN for a row that does not exist.
+    One pack, the sample paths, then -- with column_of -- paths AND actuals added up the hierarchy (the actual of an aggregate is the
+    serial sum of its members' actuals), then the scores of every output column and the energy score of every grouping's column
+    range and of the whole.
+
+    Returns ({"crps": fp64 [n_out, h]; "below", "equal": int32 [n_out, h]; "quantiles": fp64 [n_levels, n_out, h]; "crps_mean",
+    "n_steps": fp64 [n_out]; "pinball": fp64 [n_levels, n_out]; "status": int32 [n_out] (lib.PATH_SCORES_*); "series_status": int32
+    [n_series] (lib.PATHS_*); "energy": fp64 [n_ranges, h], "energy_mean", "energy_steps": fp64 [n_ranges]; "ranges": int32
+    [n_ranges, 2] -- one range per grouping, the whole last; without column_of the whole alone; "n_out", "ld"}, error)."""
+    L = _lib.load()
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim == 1:
+        pts = pts.reshape(len(pools), -1) if len(pools) else pts.reshape(0, 0)
+    n, h = int(pts.shape[0]), int(pts.shape[1])
+    act = np.ascontiguousarray(actuals, dtype=np.float64).reshape(n, h)
+    arrs = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1) for p in pools]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else None for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+    al = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    k = len(al)
+    opts = _lib.make_paths_options(mode, joint, seed)
+    co, G = None, 0
+    if column_of is not None:
+        co = np.ascontiguousarray(column_of, dtype=np.int32).reshape(-1, n) if n else np.zeros((0, 0), dtype=np.int32)
+        G = int(co.shape[0])
+    planned = co is not None and co.size > 0
+    R = (G if planned else 0) + 1
+    n_out, ld = C.c_size_t(), C.c_size_t()
+    err = _lib.AnofoxError()
+    out = {"n_out": 0, "ld": 0}
+    report = lambda ok: {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+    args = (pts.ctypes.data, ptrs, lens, n, h, int(n_paths), C.byref(opts), C.sizeof(opts), al.ctypes.data if k else None, k,
+            co.ctypes.data if planned else None, G, act.ctypes.data)
+    if not L.anofox_hip_path_scores_batch(*args, 0, *([None] * 9), C.byref(n_out), C.byref(ld), C.byref(err)):
+        return out, report(False)
+    m, w = int(n_out.value), int(ld.value)
+    crps = np.full((m, h), np.nan)
+    below, equal = np.full((m, h), -1, dtype=np.int32), np.full((m, h), -1, dtype=np.int32)
+    quant = np.full((k, m, h), np.nan)
+    column = np.full((2 + k, w), np.nan)
+    status = np.full(m, _lib.INTERNAL_ERROR, dtype=np.int32)
+    series_status = np.zeros(n, dtype=np.int32)
+    energy = np.full((R, h + 2), np.nan)
+    ranges = np.zeros((R, 2), dtype=np.int32)
+    ok = L.anofox_hip_path_scores_batch(*args, w, crps.ctypes.data, below.ctypes.data, equal.ctypes.data, quant.ctypes.data if k else None,
+                                        column.ctypes.data, status.ctypes.data, series_status.ctypes.data, energy.ctypes.data, ranges.ctypes.data,
+                                        C.byref(n_out), C.byref(ld), C.byref(err))
+    out.update({"n_out": m, "ld": w, "crps": crps, "below": below, "equal": equal, "quantiles": quant, "crps_mean": column[0, :m],
+                "n_steps": column[1, :m], "pinball": column[2:, :m], "status": status, "series_status": series_status,
+                "energy": energy[:, :h], "energy_mean": energy[:, h], "energy_steps": energy[:, h + 1], "ranges": ranges})
+    return out, report(ok)
+
+
+def ts_evaluate_quantiles_by(group, date, target, method, horizon, frequency, levels, residual_folds=10, n_paths=1000, mode="cumulative",
+                             joint=True, seed=0, params=None, group_name="id", info=None):
+    """How good the probabilistic forecasts of ts_forecast_quantiles_by are on the table's own last `horizon` rows, all of it on the
+    device.
+
+    The last `horizon` rows of every series are held out.  The chain of ts_forecast_quantiles_by runs on the rest -- the one-step
+    backtest errors over `residual_folds` folds as the pool, the fit on the shortened block, paths_block -- and path_scores_block
+    scores the paths against the held-out rows; path_energy_block takes the energy score of the leaves.  Every series needs more than
+    `horizon` rows.
+
+    One row per group, in the order of ts_forecast_by (a group whose fit fails yields no row): model_name, crps (the mean CRPS over
+    the held-out steps), one column "pinball_q<level>" per level, n_steps and paths_status (lib.PATHS_* of the generating step; a
+    group whose pool is empty or holds a NaN has NaN scores and says so there).  `info` (a dict) receives "crps" (per step, numpy
+    [n_groups, horizon]), "below", "equal" (the ranks of the actuals, for PIT histograms), "quantiles", "actual", "status"
+    (lib.PATH_SCORES_*), "series_status", "energy" (fp64 [horizon], of the leaves), "energy_mean", "energy_steps", "yhat" (the point
+    forecasts the paths were drawn around, [n_groups, horizon]), "errors", "folds", "groups"."""
+    order, series, last, kind, us, kept, dtype = _select_groups(group, date, target, "ts_evaluate_quantiles_by")
+    h = int(horizon)
+    b = bind(method, horizon, frequency, params)
+    opts = options_from_bind(b)
+    opts1 = options_from_bind(bind(method, 1, frequency, params))
+    al = [float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1)]
+    names = ["pinball_q%g" % v for v in al]
+    out = {group_name: [], "model_name": [], "crps": []}
+    out.update({c: [] for c in names})
+    out.update({"n_steps": [], "paths_status": []})
+    for s, k in enumerate(order):
+        if len(series[s]) <= h:
+            raise InvalidInputException(f"Invalid input: group {k!r} has {len(series[s])} rows, ts_evaluate_quantiles_by holds out {h} and "
+                                        "needs at least one more")
+    if series:
+        import torch
+        from . import device as _device
+        if not torch.cuda.is_available():
+            raise RuntimeError("ts_evaluate_quantiles_by needs a HIP device (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        train = [np.asarray(s[:-h], dtype=np.float64) for s in series]
+        held = np.stack([np.asarray(s[-h:], dtype=np.float64) for s in series])
+        n, T = len(train), max(len(s) for s in train)
+        block = _device.pack_time_major(np.stack([np.pad(s, (0, T - len(s))) for s in train]))
+        y = torch.from_numpy(block).to(dev)
+        lens = torch.zeros(block.shape[1], dtype=torch.int32)
+        lens[:n] = torch.tensor([len(s) for s in train], dtype=torch.int32)
+        lens = lens.to(dev)
+        actual = torch.from_numpy(held).to(dev)                          # [n, h] series-major
+        bounds = _lib.backtest_folds(T, 1, int(residual_folds), "expanding")
+        F = len(bounds)
+        try:
+            if F:
+                bt = _device.backtest_block(y, lens, opts1, bounds, n_series=n)
+                pool = bt["error"].view(n, F)
+            else:
+                pool = torch.zeros((n, 0), dtype=torch.float64, device=dev)
+            batch = _device.DeviceBatch(n, T, opts, dev)
+            batch.set_block(y, lens)
+            batch.run()
+            res = batch.results()
+            g = _device.paths_block(res["yhat"], pool, n_paths=int(n_paths), mode=mode, joint=joint, seed=seed, series_major=True,
+                                    pool_series_major=True, n_series=n)
+            sc = _device.path_scores_block(g["paths"], actual, al, horizon=h, n_paths=int(n_paths), n_cols=n, actual_series_major=True)
+            en = _device.path_energy_block(g["paths"], actual, horizon=h, n_paths=int(n_paths), col_begin=0, col_end=n,
+                                           actual_series_major=True)
+        except ValueError as e:
+            raise InvalidInputException(str(e)) from e
+        crps_mean, n_steps = sc["crps_mean"].cpu().numpy(), sc["n_steps"].cpu().numpy()
+        pinball = sc["pinball"].cpu().numpy()
+        series_status = g["status"].cpu().numpy()
+        fit_status, codes = res["status"].cpu().numpy(), res["model_code"].cpu().numpy()
+        if info is not None:
+            summary = en["summary"].cpu().numpy()
+            info.update({"crps": sc["crps"].cpu().numpy(), "below": sc["below"].cpu().numpy(), "equal": sc["equal"].cpu().numpy(),
+                         "quantiles": sc["quantiles"].cpu().numpy() if sc["quantiles"] is not None else np.zeros((0, n, h)),
+                         "actual": held, "status": sc["status"].cpu().numpy(), "series_status": series_status,
+                         "energy": en["es"].cpu().numpy(), "energy_mean": float(summary[0]), "energy_steps": int(summary[1]),
+                         "errors": pool.cpu().numpy(), "folds": bounds, "groups": list(order), "yhat": res["yhat"].cpu().numpy()})
+        for s, k in enumerate(order):
+            if fit_status[s] != 0:
+                continue                      # the group yields no row, as in ts_forecast_by
+            out[group_name].append(None if k == "__NULL__" else k)
+            out["model_name"].append(batch.model_name(int(codes[s]), s))
+            out["crps"].append(crps_mean[s])
+            for l, c in enumerate(names):
+                out[c].append(pinball[l, s])
+            out["n_steps"].append(int(n_steps[s]) if n_steps[s] == n_steps[s] else 0)
+            out["paths_status"].append(int(series_status[s]))
+    for c in ["crps"] + names:
+        out[c] = np.array(out[c], dtype=np.float64)
+    out["n_steps"] = np.array(out["n_steps"], dtype=np.int32)
+    out["paths_status"] = np.array(out["paths_status"], dtype=np.int32)
+    return out
+
+
 anofox_fcst_ts_aggregate_hierarchy = ts_aggregate_hierarchy
 anofox_fcst_ts_combine_keys = ts_combine_keys
 anofox_fcst_ts_split_keys = ts_split_keys

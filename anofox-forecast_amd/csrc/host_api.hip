@@ -44,6 +44,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_reconcile_mint.hpp" // the host-only checks and workspace sizes of the MinT-shrink entries
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
+#include "host_path_scores_plan.hpp" // the host-only checks of the path-score entries, the energy workspace and a plan's column ranges
 #include "host_period_search.hpp" // the host-only logic of the SSA / STL period entries (defaults, window, candidate list, checks naming their limits)
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
@@ -7884,6 +7885,232 @@ bool anofox_hip_paths_batch(const double *points, const double *const *pools, co
                 HIPCHECK(hipMemcpy(out_status, d_qstatus, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
                 if (out_series_status) HIPCHECK(hipMemcpy(out_series_status, d_status, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
                 if (out_paths) HIPCHECK(hipMemcpy(out_paths, d_block, rows * ld_block * sizeof(double), hipMemcpyDeviceToHost));
+            } else HIPCHECK(hipDeviceSynchronize());
+        }
+        scratch.settled();                                                 // (either way the device has been waited for)
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return ok;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Scores of sample paths: CRPS, pinball, ranks and energy score (DESIGN.md section 3 "Path scores"; path_scores.hip,
+// host_path_scores_plan.hpp)
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+static_assert(PATH_SCORES_OK == ANOFOX_PATH_SCORES_OK && PATH_SCORES_NO_ACTUAL == ANOFOX_PATH_SCORES_NO_ACTUAL &&
+              PATH_SCORES_NAN == ANOFOX_PATH_SCORES_NAN, "the statuses of the path-score entries");
+
+bool anofox_hip_path_scores_device(const double *paths, size_t ld, size_t n_cols, size_t horizon, size_t n_paths, const double *actual,
+                                   size_t actual_stride_c, size_t actual_stride_k, const double *levels, size_t n_levels, double *out_crps,
+                                   int32_t *out_below, int32_t *out_equal, double *out_quantiles, double *out_column, size_t ld_out,
+                                   int32_t *status, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!paths || !actual || !status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(path_scores_levels_check(levels, n_levels, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld, n_cols, "ld", "n_cols", &message), message, out_error)) return false;
+    if (out_column && !paths_plan_report(paths_block_check(ld_out, n_cols, "ld_out", "n_cols", &message), message, out_error)) return false;
+    if (n_cols == 0) return true;
+    if (!device_ready(out_error)) return false;
+    PathScoresArgs a{};
+    a.paths = paths; a.ld = ld; a.n_cols = (int)n_cols; a.horizon = (int)horizon; a.n_paths = (int)n_paths;
+    a.actual = actual; a.actual_stride_c = actual_stride_c; a.actual_stride_k = actual_stride_k;
+    a.n_levels = (int)n_levels;
+    for (size_t k = 0; k < n_levels; k++) a.levels[k] = levels[k];
+    a.crps = out_crps; a.below = out_below; a.equal = out_equal; a.quantiles = n_levels ? out_quantiles : nullptr;
+    a.column = out_column; a.ld_column = ld_out; a.status = status;
+    try {
+        (void)hipGetLastError();
+        launch_path_scores(a, (hipStream_t)stream);
+        LAUNCHCHECK("path scores");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_path_scores_sizes(size_t horizon, size_t n_paths, size_t *out_workspace_doubles, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!out_workspace_doubles) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    *out_workspace_doubles = path_energy_workspace(horizon, n_paths);
+    return true;
+}
+
+bool anofox_hip_path_energy_device(const double *paths, size_t ld, size_t col_begin, size_t col_end, size_t horizon, size_t n_paths,
+                                   const double *actual, size_t actual_stride_c, size_t actual_stride_k, double *workspace, double *out_es,
+                                   double *out_summary, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!paths || !actual || !workspace || !out_es || !out_summary) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(path_energy_range_check(ld, col_begin, col_end, &message), message, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    PathEnergyArgs a{};
+    a.paths = paths; a.ld = ld; a.col_begin = (int)col_begin; a.col_end = (int)col_end; a.horizon = (int)horizon; a.n_paths = (int)n_paths;
+    a.actual = actual; a.actual_stride_c = actual_stride_c; a.actual_stride_k = actual_stride_k;
+    a.workspace = workspace; a.es = out_es; a.summary = out_summary;
+    try {
+        (void)hipGetLastError();
+        launch_path_energy(a, (hipStream_t)stream);
+        LAUNCHCHECK("path energy");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_path_scores_batch(const double *points, const double *const *pools, const size_t *pool_lengths, size_t n_series, size_t horizon,
+                                  size_t n_paths, const AnofoxHipPathsOptions *options, size_t struct_size, const double *levels, size_t n_levels,
+                                  const int32_t *column_of, size_t n_groupings, const double *actuals, size_t ld, double *out_crps,
+                                  int32_t *out_below, int32_t *out_equal, double *out_quantiles, double *out_column, int32_t *out_status,
+                                  int32_t *out_series_status, double *out_energy, int32_t *out_ranges, size_t *out_n_out, size_t *out_ld,
+                                  AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!paths_options_ok(options, struct_size, out_error)) return false;
+    if (n_series > 0 && (!points || !pools || !pool_lengths || !actuals)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(path_scores_levels_check(levels, n_levels, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(SIZE_MAX, n_series, "ld", "n_series", &message), message, out_error)) return false;
+    size_t pool_rows = 0;
+    if (!paths_plan_report(paths_batch_pools(pool_lengths, n_series, &pool_rows, &message), message, out_error)) return false;
+    for (size_t s = 0; s < n_series; s++)
+        if (pool_lengths[s] > 0 && !pools[s]) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    const bool planned = column_of != nullptr && n_groupings > 0;
+    size_t n_out = n_series, nnz = 0;
+    std::vector<int32_t> offs, memb;
+    if (planned) {
+        if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, nullptr, nullptr, out_error)) return false;
+        offs.resize(n_out + 1);
+        memb.resize(std::max<size_t>(nnz, 1));
+        if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, offs.data(), memb.data(), out_error)) return false;
+    }
+    const size_t need_ld = paths_ld(n_out);
+    if (out_n_out) *out_n_out = n_out;
+    if (out_ld) *out_ld = need_ld;
+    if (!out_status) return true;
+    if (ld != need_ld) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is not what the sizing call returns"); return false; }
+    const size_t n_ranges = (planned ? n_groupings : 0) + 1, e_row = horizon + 2;
+    std::vector<size_t> ranges(2 * n_ranges);
+    path_scores_ranges(planned ? column_of : nullptr, n_groupings, n_series, n_out, ranges.data());
+    if (out_ranges)
+        for (size_t r = 0; r < 2 * n_ranges; r++) out_ranges[r] = (int32_t)ranges[r];
+    if (out_energy)
+        for (size_t r = 0; r < n_ranges * e_row; r++) out_energy[r] = std::numeric_limits<double>::quiet_NaN();
+    if (n_series == 0 || n_out == 0) return true;
+    if (!device_ready(out_error)) return false;
+
+    const size_t ld_s = paths_ld(n_series), rows = n_paths * horizon, pool_t = std::max<size_t>(pool_rows, 1);
+    const size_t leaf_cells = rows * ld_s, out_cells = planned ? rows * need_ld : 0, cells = n_out * horizon, q_cells = n_levels * cells;
+    Scratch scratch;
+    bool ok = true;
+    try {
+        std::vector<double> pool_block(pool_t * ld_s, 0.0);
+        const std::vector<int32_t> len = block_lengths(pool_lengths, n_series, ld_s);
+        pack_time_major(pool_block.data(), ld_s, pools, pool_lengths, n_series);
+        double *d_paths = nullptr, *d_agg = nullptr;
+        try {
+            d_paths = scratch.get<double>(leaf_cells);
+            if (planned) d_agg = scratch.get<double>(out_cells);
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the path block of " + std::to_string(rows) + " x " + std::to_string(ld_s) +
+                      " values" + (planned ? " and its aggregate of " + std::to_string(rows) + " x " + std::to_string(need_ld) + " values" : std::string()) +
+                      " need " + std::to_string((leaf_cells + out_cells) * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            double *d_point = scratch.get<double>(n_series * horizon);
+            double *d_pool = scratch.get<double>(pool_t * ld_s);
+            int32_t *d_len = scratch.get<int32_t>(ld_s);
+            int32_t *d_status = scratch.get<int32_t>(ld_s);
+            double *d_crps = scratch.get<double>(cells);
+            int32_t *d_below = scratch.get<int32_t>(cells), *d_equal = scratch.get<int32_t>(cells);
+            double *d_q = scratch.get<double>(std::max<size_t>(q_cells, 1));
+            double *d_column = scratch.get<double>((2 + n_levels) * need_ld);
+            int32_t *d_cstatus = scratch.get<int32_t>(need_ld);
+            double *d_work = scratch.get<double>(path_energy_workspace(horizon, n_paths));
+            double *d_energy = scratch.get<double>(n_ranges * e_row);
+            HIPCHECK(hipMemcpy(d_point, points, n_series * horizon * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_pool, pool_block.data(), pool_t * ld_s * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemset(d_paths, 0, leaf_cells * sizeof(double)));          // the padding columns
+            HIPCHECK(hipMemset(d_column, 0, (2 + n_levels) * need_ld * sizeof(double)));
+            ok = anofox_hip_paths_device(d_point, horizon, 1, d_pool, 1, ld_s, d_len, pool_rows, n_series, horizon, n_paths, options, struct_size,
+                                         d_paths, ld_s, d_status, nullptr, out_error);
+            const double *d_block = d_paths, *d_actual = nullptr;
+            size_t ld_block = ld_s, stride_c = horizon, stride_k = 1;
+            if (ok && !planned) {
+                double *d_act = scratch.get<double>(n_series * horizon);
+                HIPCHECK(hipMemcpy(d_act, actuals, n_series * horizon * sizeof(double), hipMemcpyHostToDevice));
+                d_actual = d_act;
+            }
+            if (ok && planned) {
+                AnofoxHipHierarchyOptions ho{};
+                std::vector<int32_t> full(ld_s, 0), steps(ld_s, 0);
+                for (size_t s = 0; s < n_series; s++) { full[s] = (int32_t)rows; steps[s] = (int32_t)horizon; }
+                std::vector<double> act_block(horizon * ld_s, 0.0);              // the actuals, time-major as the path block is
+                for (size_t s = 0; s < n_series; s++)
+                    for (size_t k = 0; k < horizon; k++) act_block[k * ld_s + s] = actuals[s * horizon + k];
+                int32_t *d_rows = scratch.get<int32_t>(ld_s), *d_steps = scratch.get<int32_t>(ld_s);
+                int32_t *d_plan = scratch.get<int32_t>(n_out + 1 + nnz);
+                int32_t *d_len_out = scratch.get<int32_t>(need_ld);
+                int64_t *d_first_out = scratch.get<int64_t>(need_ld);
+                double *d_act = scratch.get<double>(horizon * ld_s), *d_act_agg = scratch.get<double>(horizon * need_ld);
+                HIPCHECK(hipMemcpy(d_rows, full.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(d_steps, steps.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(d_act, act_block.data(), horizon * ld_s * sizeof(double), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(d_plan, offs.data(), (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+                if (nnz) HIPCHECK(hipMemcpy(d_plan + n_out + 1, memb.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemset(d_agg, 0, out_cells * sizeof(double)));
+                HIPCHECK(hipMemset(d_act_agg, 0, horizon * need_ld * sizeof(double)));
+                ok = anofox_hip_hierarchy_device(d_paths, nullptr, nullptr, ld_s, d_rows, nullptr, n_series, rows, d_plan, d_plan + n_out + 1, n_out,
+                                                 nnz, &ho, sizeof ho, rows, d_agg, nullptr, need_ld, d_len_out, d_first_out, nullptr, out_error);
+                if (ok)
+                    ok = anofox_hip_hierarchy_device(d_act, nullptr, nullptr, ld_s, d_steps, nullptr, n_series, horizon, d_plan, d_plan + n_out + 1,
+                                                     n_out, nnz, &ho, sizeof ho, horizon, d_act_agg, nullptr, need_ld, d_len_out, d_first_out, nullptr,
+                                                     out_error);
+                d_block = d_agg;
+                ld_block = need_ld;
+                d_actual = d_act_agg;
+                stride_c = 1;
+                stride_k = need_ld;
+            }
+            if (ok)
+                ok = anofox_hip_path_scores_device(d_block, ld_block, n_out, horizon, n_paths, d_actual, stride_c, stride_k, levels, n_levels, d_crps,
+                                                   d_below, d_equal, d_q, d_column, need_ld, d_cstatus, nullptr, out_error);
+            for (size_t r = 0; ok && out_energy && r < n_ranges; r++) {
+                if (ranges[2 * r + 1] <= ranges[2 * r]) continue;                 // a grouping that maps no series: NaN
+                ok = anofox_hip_path_energy_device(d_block, ld_block, ranges[2 * r], ranges[2 * r + 1], horizon, n_paths, d_actual, stride_c, stride_k,
+                                                   d_work, d_energy + r * e_row, d_energy + r * e_row + horizon, nullptr, out_error);
+            }
+            if (ok) {
+                if (out_crps) HIPCHECK(hipMemcpy(out_crps, d_crps, cells * sizeof(double), hipMemcpyDeviceToHost));      // waits for the null stream
+                if (out_below) HIPCHECK(hipMemcpy(out_below, d_below, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_equal) HIPCHECK(hipMemcpy(out_equal, d_equal, cells * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_quantiles && q_cells) HIPCHECK(hipMemcpy(out_quantiles, d_q, q_cells * sizeof(double), hipMemcpyDeviceToHost));
+                if (out_column) HIPCHECK(hipMemcpy(out_column, d_column, (2 + n_levels) * need_ld * sizeof(double), hipMemcpyDeviceToHost));
+                HIPCHECK(hipMemcpy(out_status, d_cstatus, n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_series_status) HIPCHECK(hipMemcpy(out_series_status, d_status, n_series * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_energy)
+                    for (size_t r = 0; r < n_ranges; r++)
+                        if (ranges[2 * r + 1] > ranges[2 * r])
+                            HIPCHECK(hipMemcpy(out_energy + r * e_row, d_energy + r * e_row, e_row * sizeof(double), hipMemcpyDeviceToHost));
             } else HIPCHECK(hipDeviceSynchronize());
         }
         scratch.settled();                                                 // (either way the device has been waited for)

@@ -808,6 +808,31 @@ struct PathQuantilesArgs {
 void launch_paths(const PathsArgs &, hipStream_t);                     // the statuses, then the paths
 void launch_path_quantiles(const PathQuantilesArgs &, hipStream_t);
 
+// Scores of a block of sample paths (DESIGN.md section 3 "Path scores"; path_scores.hip).  Element (column c, step k) of `actual` is
+// at c * actual_stride_c + k * actual_stride_k; a NaN there drops the step.
+constexpr int32_t PATH_SCORES_OK = 0, PATH_SCORES_NO_ACTUAL = 1, PATH_SCORES_NAN = 2;
+struct PathScoresArgs {
+    const double *paths; size_t ld;              // [n_paths * horizon x ld]
+    int n_cols, horizon, n_paths;
+    const double *actual; size_t actual_stride_c, actual_stride_k;
+    int n_levels; double levels[PATHS_MAX_LEVELS];
+    double *crps;                                // [n_cols x horizon] or null
+    int32_t *below, *equal;                      // [n_cols x horizon] or null
+    double *quantiles;                           // [n_levels x n_cols x horizon] or null
+    double *column; size_t ld_column;            // [(2 + n_levels) x ld_column]: crps_mean, n_steps, pinball_l; or null
+    int32_t *status;                             // [n_cols]
+};
+struct PathEnergyArgs {
+    const double *paths; size_t ld;              // [n_paths * horizon x ld]
+    int col_begin, col_end, horizon, n_paths;
+    const double *actual; size_t actual_stride_c, actual_stride_k;
+    double *workspace;                           // [2 x n_paths x horizon]: D1, D2
+    double *es;                                  // [horizon]
+    double *summary;                             // [2]: es_mean, es_steps
+};
+void launch_path_scores(const PathScoresArgs &, hipStream_t);
+void launch_path_energy(const PathEnergyArgs &, hipStream_t);   // the rows, the steps, the mean
+
 void launch_prep(const PrepArgs &, hipStream_t);
 void launch_select(const SelectArgs &, hipStream_t);
 void launch_classic(int kind, const ClassicArgs &, hipStream_t);

@@ -707,6 +707,112 @@ def path_quantiles_block(paths: torch.Tensor, levels, *, horizon: int, n_paths: 
     return {"quantiles": q, "status": status}
 
 
+PATH_SCORES_WANT = ("crps", "ranks", "quantiles", "column")
+
+
+def _path_scores_actual(actual: torch.Tensor, horizon: int, n: int, series_major: bool):
+    """-> (stride_c, stride_k) of the actual block: time-major [>= h, ld_a >= n], or series-major [>= n, h]."""
+    assert actual.dtype == torch.float64 and actual.is_cuda and actual.is_contiguous() and actual.dim() == 2
+    if series_major:
+        assert int(actual.shape[0]) >= n and int(actual.shape[1]) == horizon
+        return horizon, 1
+    assert int(actual.shape[0]) >= horizon and int(actual.shape[1]) >= n
+    return 1, int(actual.shape[1])
+
+
+def path_scores_block(paths: torch.Tensor, actual: torch.Tensor, levels=(), *, horizon: int, n_paths: int, n_cols: int | None = None,
+                      actual_series_major: bool = False, want=PATH_SCORES_WANT, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_path_scores_device on torch tensors: the CRPS, the ranks and the pinball losses of a block of sample paths against
+    the actuals, no host copy.
+
+    paths [n_paths * horizon, ld] fp64 time-major as paths_block or aggregate_block wrote it.  actual: time-major [horizon, >= n_cols]
+    (the "y" of aggregate_block on the actuals), or with actual_series_major=True [>= n_cols, horizon] -- a backtest's "actual" block
+    as it lies; a NaN there drops the step.  levels: none or up to 16 values in [0, 1].  One sort per (column, step) serves every
+    output; `want` names the outputs to compute: "crps" (per step), "ranks", "quantiles", "column".
+
+    Returns {"crps": fp64 [n_cols, horizon]; "below", "equal": int32 [n_cols, horizon], the paths below the actual and equal to it
+    (-1 where there is no actual); "quantiles": fp64 [n_levels, n_cols, horizon], the bits of path_quantiles_block; "crps_mean",
+    "n_steps": fp64 [n_cols]; "pinball": fp64 [n_levels, n_cols] (views of "column" fp64 [2 + n_levels, ld_out]); "status": int32
+    [n_cols]: lib.PATH_SCORES_OK, _NO_ACTUAL (every mean NaN) or _NAN (a NaN among the column's paths: every figure NaN)}; an output
+    that was not wanted is None."""
+    L = _lib.load()
+    assert paths.dtype == torch.float64 and paths.is_cuda and paths.is_contiguous() and paths.dim() == 2
+    horizon, n_paths = int(horizon), int(n_paths)
+    _paths_rows(n_paths, horizon)
+    ld = int(paths.shape[1])
+    n = ld if n_cols is None else int(n_cols)
+    assert int(paths.shape[0]) >= n_paths * horizon and 0 < n <= ld
+    unknown = [w for w in want if w not in PATH_SCORES_WANT]
+    if unknown:
+        raise ValueError(f"path_scores_block: unknown outputs {unknown}; the outputs are {list(PATH_SCORES_WANT)}")
+    sc, sk = _path_scores_actual(actual, horizon, n, actual_series_major)
+    al = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    k = len(al)
+    kk = min(k, _lib.PATHS_MAX_LEVELS)
+    dev = paths.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    ld_out = (n + 63) // 64 * 64
+    nan = float("nan")
+    crps = torch.full((n, horizon), nan, dtype=torch.float64, device=dev) if "crps" in want else None
+    below = torch.full((n, horizon), -1, dtype=torch.int32, device=dev) if "ranks" in want else None
+    equal = torch.full((n, horizon), -1, dtype=torch.int32, device=dev) if "ranks" in want else None
+    q = torch.full((kk, n, horizon), nan, dtype=torch.float64, device=dev) if "quantiles" in want and kk else None
+    column = torch.full((2 + kk, ld_out), nan, dtype=torch.float64, device=dev) if "column" in want else None
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_path_scores_device(paths.data_ptr(), ld, n, horizon, n_paths, actual.data_ptr(), sc, sk, al.ctypes.data if k else None, k,
+                                         ptr(crps), ptr(below), ptr(equal), ptr(q), ptr(column), ld_out, status.data_ptr(),
+                                         C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_path_scores_device", err)
+    out = {"crps": crps, "below": below, "equal": equal, "quantiles": q, "column": column, "status": status,
+           "crps_mean": None, "n_steps": None, "pinball": None}
+    if column is not None:
+        out.update({"crps_mean": column[0, :n], "n_steps": column[1, :n], "pinball": column[2:, :n]})
+    return out
+
+
+def path_energy_block(paths: torch.Tensor, actual: torch.Tensor, *, horizon: int, n_paths: int, col_begin: int = 0, col_end: int | None = None,
+                      actual_series_major: bool = False, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_path_energy_device on torch tensors: the energy score of the columns [col_begin, col_end) of a block of sample
+    paths -- a level of a hierarchy, the leaves alone or the whole plan -- in the estimator that takes consecutive paths as the
+    independent copy: es[k] = mean_p |x_p - y| - sum_p |x_p - x_{p+1}| / (2 (P - 1)), Euclidean norms over the columns of the range.
+    paths and actual as for path_scores_block; a NaN in the range propagates into es[k].
+
+    Returns {"es": fp64 [horizon]; "summary": fp64 [2], es_mean (over the non-NaN steps) and es_steps; "workspace": fp64
+    [2, n_paths, horizon], the distances D1 and D2 the sums run over}."""
+    L = _lib.load()
+    assert paths.dtype == torch.float64 and paths.is_cuda and paths.is_contiguous() and paths.dim() == 2
+    horizon, n_paths = int(horizon), int(n_paths)
+    _paths_rows(n_paths, horizon)
+    ld = int(paths.shape[1])
+    cb, ce = int(col_begin), ld if col_end is None else int(col_end)
+    assert int(paths.shape[0]) >= n_paths * horizon
+    err = _lib.AnofoxError()
+    sc, sk = 1, 1
+    if 0 <= cb < ce <= ld:                                    # (any other range is refused by the library, with its text)
+        sc, sk = _path_scores_actual(actual, horizon, ce, actual_series_major)
+    dev = paths.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    words = C.c_size_t()
+    if not L.anofox_hip_path_scores_sizes(horizon, n_paths, C.byref(words), C.byref(err)):
+        raise _paths_failed("anofox_hip_path_scores_sizes", err)
+    assert int(words.value) == 2 * n_paths * horizon
+    work = torch.zeros((2, n_paths, horizon), dtype=torch.float64, device=dev)
+    es = torch.full((horizon,), float("nan"), dtype=torch.float64, device=dev)
+    summary = torch.full((2,), float("nan"), dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    ok = L.anofox_hip_path_energy_device(paths.data_ptr(), ld, cb, ce, horizon, n_paths, actual.data_ptr(), sc, sk, work.data_ptr(), es.data_ptr(),
+                                         summary.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_path_energy_device", err)
+    return {"es": es, "summary": summary, "workspace": work}
+
+
 _RECONCILE_PLAN_KEYS = ("col_offsets", "members", "bottom_col", "agg_cols", "leaf_offsets", "leaf_aggs")
 
 

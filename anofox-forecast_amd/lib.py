@@ -456,6 +456,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_select_winner_device", "anofox_hip_select_gather_device", "anofox_hip_select_scatter_device",
     "anofox_hip_select_combine_device", "anofox_hip_select_batch",
     "anofox_hip_paths_device", "anofox_hip_path_quantiles_device", "anofox_hip_paths_batch",
+    "anofox_hip_path_scores_device", "anofox_hip_path_scores_sizes", "anofox_hip_path_energy_device", "anofox_hip_path_scores_batch",
 ]
 
 # include/anofox_fcst_hip.h block 9: bootstrap sample paths and their quantiles
@@ -465,6 +466,8 @@ PATHS_MAX_PATHS = 2048                                 # ANOFOX_HIP_PATHS_MAX_PA
 PATHS_MAX_LEVELS = 16                                  # ANOFOX_HIP_PATHS_MAX_LEVELS
 PATHS_MAX_POOL_ROWS = 1 << 20                          # ANOFOX_HIP_PATHS_MAX_POOL_ROWS
 PATHS_OK, PATHS_EMPTY, PATHS_NAN, PATHS_RAGGED = 0, 1, 2, 3
+# block 10: scores of sample paths (ANOFOX_PATH_SCORES_*): done; no step with an actual; a NaN among the column's paths
+PATH_SCORES_OK, PATH_SCORES_NO_ACTUAL, PATH_SCORES_NAN = 0, 1, 2
 
 
 class AnofoxHipPathsOptions(C.Structure):
@@ -857,6 +860,21 @@ def load():
     L.anofox_hip_paths_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, P(AnofoxHipPathsOptions),
                                          C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
+    # block 10: scores of sample paths
+    L.anofox_hip_path_scores_device.restype = C.c_bool
+    L.anofox_hip_path_scores_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_path_scores_sizes.restype = C.c_bool
+    L.anofox_hip_path_scores_sizes.argtypes = [C.c_size_t, C.c_size_t, P(C.c_size_t), P(AnofoxError)]
+    L.anofox_hip_path_energy_device.restype = C.c_bool
+    L.anofox_hip_path_energy_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_path_scores_batch.restype = C.c_bool
+    L.anofox_hip_path_scores_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, P(AnofoxHipPathsOptions),
+                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

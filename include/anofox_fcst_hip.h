@@ -2772,6 +2772,140 @@ bool anofox_hip_paths_batch(const double *points,
                             size_t *out_ld,
                             struct AnofoxError *out_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 10: scores of sample paths: CRPS, pinball, ranks and energy score     */
+/* ------------------------------------------------------------------------- */
+/*
+ * How good a block of sample paths is, judged against the actuals where the paths lie.  The names are this package's own;
+ * tests/path_scores_ref.py is the definition, bit for bit.  Plain fp64, one rounding per operation, nothing fused.
+ *   - the wave sum W(t_0 .. t_{n-1}), the one order of addition of every sum over paths or over columns: a_l is the serial sum from
+ *     0.0 of t_i with i = l (mod 64), ascending in i (an empty class gives 0.0); W = ((a_0 + a_1) + a_2) + ... + a_63;
+ *   - per (column c, step k), y = actual[c, k], x_(0) <= ... <= x_(P-1) the P = n_paths values sorted by the total-order key of the
+ *     quantile entry (-0.0 below +0.0), d_i = x_(i) - y:
+ *       crps  = W(|d_i|) / P - W((2i - P + 1) * d_i) / (P * P)       -- the sorted form of E|X - y| - 1/2 E|X - X'|; P = 1: |x - y|
+ *       below = the paths with x < y, equal = the paths with x == y (IEEE comparisons): the rank of the actual, ties kept apart
+ *       quantile l = what anofox_hip_path_quantiles_device returns, the same bits; its pinball term is tau * e if e >= 0.0 else
+ *       (tau - 1.0) * e with e = y - quantile;
+ *   - per column: crps_mean and pinball_l are the serial sums from 0.0 over the steps that have an actual, in step order, divided by
+ *     their count n_steps.  A NaN actual drops the step: its crps is NaN, its below and equal are -1 (its quantiles are computed);
+ *   - status per column (int32): 0 done; 1 no step with an actual -- every mean is NaN; 2 a NaN among the column's paths -- every
+ *     figure of the column is NaN, below and equal are -1; 2 takes precedence.  +-inf are ordinary values;
+ *   - the energy score of the columns [col_begin, col_end) at step k, consecutive paths as the independent copy (Panagiotelis et al.
+ *     2023): D1[p] = sqrt(W_c((x[p,k,c] - y[k,c])^2)), D2[p] = sqrt(W_c((x[p,k,c] - x[p+1,k,c])^2)) for p < P - 1, the terms indexed by
+ *     c - col_begin, each square one rounded product, sqrt correctly rounded; S1, S2 the serial sums over p from 0.0;
+ *     es[k] = S1 / P - S2 / (2 * (P - 1)), for P = 1 es[k] = S1.  A NaN (a path or an actual of the range) propagates by arithmetic
+ *     into es[k].  es_mean is the serial sum of the non-NaN es[k] in step order over their count es_steps; NaN when that is 0.
+ * Element (column c, step k) of `actual` is at c * actual_stride_c + k * actual_stride_k: stride_c = 1 is a time-major [horizon x ld]
+ * block (what anofox_hip_hierarchy_device writes for aggregated actuals), stride_k = 1 a series-major one (a backtest's actual block).
+ */
+enum { ANOFOX_PATH_SCORES_OK = 0, ANOFOX_PATH_SCORES_NO_ACTUAL = 1, ANOFOX_PATH_SCORES_NAN = 2 };
+
+/*
+ * Scores of a device-resident block of paths [n_paths * horizon x ld].  levels fp64 [n_levels] on the HOST, each in [0, 1];
+ * n_levels may be 0 (levels may then be NULL).  Outputs, in device memory, each but `status` may be NULL and is then skipped:
+ * out_crps fp64 [n_cols x horizon] (column c, step k at c * horizon + k), out_below and out_equal int32 [n_cols x horizon],
+ * out_quantiles fp64 [n_levels x n_cols x horizon] as the quantile entry writes them, out_column fp64 [(2 + n_levels) x ld_out] in
+ * the rows crps_mean, n_steps (as double), pinball_l (row r of column c at r * ld_out + c), status int32 [n_cols].  One sort per
+ * (column, step) serves every output.  The call only enqueues on `stream` (NULL: the null stream) and does NOT wait on the host.
+ * INVALID_INPUT, each naming its limit, before the device is touched: n_paths 0 or above 2,048, horizon 0, n_paths * horizon above
+ * 2^30, n_levels above 16, a level outside [0, 1] or NaN, ld < n_cols, out_column with ld_out < n_cols.
+ */
+bool anofox_hip_path_scores_device(const double *paths,
+                                   size_t ld,
+                                   size_t n_cols,
+                                   size_t horizon,
+                                   size_t n_paths,
+                                   const double *actual,
+                                   size_t actual_stride_c,
+                                   size_t actual_stride_k,
+                                   const double *levels,
+                                   size_t n_levels,
+                                   double *out_crps,
+                                   int32_t *out_below,
+                                   int32_t *out_equal,
+                                   double *out_quantiles,
+                                   double *out_column,
+                                   size_t ld_out,
+                                   int32_t *status,
+                                   void *stream,
+                                   struct AnofoxError *out_error);
+
+/*
+ * The doubles of the energy entry's workspace (2 * n_paths * horizon).  Host only; the limits of n_paths and horizon as above.
+ */
+bool anofox_hip_path_scores_sizes(size_t horizon,
+                                  size_t n_paths,
+                                  size_t *out_workspace_doubles,
+                                  struct AnofoxError *out_error);
+
+/*
+ * The energy score of the columns [col_begin, col_end) of a device-resident block of paths.  workspace fp64
+ * [anofox_hip_path_scores_sizes] in device memory receives D1 [n_paths x horizon] and D2 [n_paths x horizon] (row p, step k at
+ * p * horizon + k; D2 of the last path is 0).  Outputs, in device memory: out_es fp64 [horizon], out_summary fp64 [2]: es_mean and
+ * es_steps.  The path block is streamed once; the call only enqueues on `stream`.
+ * INVALID_INPUT, each naming its limit: the limits of n_paths and horizon, an empty or reversed range, a range beyond ld.
+ */
+bool anofox_hip_path_energy_device(const double *paths,
+                                   size_t ld,
+                                   size_t col_begin,
+                                   size_t col_end,
+                                   size_t horizon,
+                                   size_t n_paths,
+                                   const double *actual,
+                                   size_t actual_stride_c,
+                                   size_t actual_stride_k,
+                                   double *workspace,
+                                   double *out_es,
+                                   double *out_summary,
+                                   void *stream,
+                                   struct AnofoxError *out_error);
+
+/*
+ * The chain for host buffers: what anofox_hip_paths_batch takes, plus actuals fp64 [n_series x horizon] series-major with NaN for a
+ * row that does not exist.  The call packs once, generates the paths and aggregates paths AND actuals up the plan when there is
+ * one -- the actual of an aggregate is the serial sum of its members' actuals by the same anofox_hip_hierarchy_device, so a member's
+ * NaN drops the step of the aggregate --, scores every output column and takes the energy score of every grouping's column range
+ * -- [the smallest column the grouping maps a series to, the largest + 1): a plan's columns lie grouping by grouping -- and of the
+ * whole [0, n_out).
+ *
+ * *out_n_out and *out_ld as for anofox_hip_paths_batch, always written.  With out_status NULL that is all: the sizing call, which
+ * needs no device.  Otherwise ld must be what the sizing call returned and the caller's arrays receive, each but out_status optional
+ * (NULL): out_crps fp64 [n_out x horizon], out_below and out_equal int32 [n_out x horizon], out_quantiles fp64 [n_levels x n_out x
+ * horizon], out_column fp64 [(2 + n_levels) x ld], out_status int32 [n_out], out_series_status int32 [n_series] (of the generating
+ * entry), out_energy fp64 [(n_groupings + 1) x (horizon + 2)] -- per range es[0 .. horizon), es_mean, es_steps; the whole is the
+ * last row; without a plan there is that row alone; a grouping that maps no series has NaN -- and out_ranges int32 [(n_groupings +
+ * 1) x 2], the ranges themselves.
+ *
+ * INVALID_INPUT as for the device entries and for the plan, all before the device is touched.  A failed device allocation is a
+ * COMPUTATION_ERROR that names the size.  One device (the calling thread's current one); fp64 only.
+ */
+bool anofox_hip_path_scores_batch(const double *points,
+                                  const double *const *pools,
+                                  const size_t *pool_lengths,
+                                  size_t n_series,
+                                  size_t horizon,
+                                  size_t n_paths,
+                                  const AnofoxHipPathsOptions *options,
+                                  size_t struct_size,
+                                  const double *levels,
+                                  size_t n_levels,
+                                  const int32_t *column_of,
+                                  size_t n_groupings,
+                                  const double *actuals,
+                                  size_t ld,
+                                  double *out_crps,
+                                  int32_t *out_below,
+                                  int32_t *out_equal,
+                                  double *out_quantiles,
+                                  double *out_column,
+                                  int32_t *out_status,
+                                  int32_t *out_series_status,
+                                  double *out_energy,
+                                  int32_t *out_ranges,
+                                  size_t *out_n_out,
+                                  size_t *out_ld,
+                                  struct AnofoxError *out_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
