@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import calendar
 import ctypes as C
+import math
 import re
 from dataclasses import dataclass
 
@@ -4557,6 +4558,354 @@ def ts_evaluate_quantiles_by(group, date, target, method, horizon, frequency, le
     out["n_steps"] = np.array(out["n_steps"], dtype=np.int32)
     out["paths_status"] = np.array(out["paths_status"], dtype=np.int32)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# scaled, weighted scores of a hierarchy: RMSSE, SPL, WRMSSE, WSPL (include/anofox_fcst_hip.h block 11)
+# --------------------------------------------------------------------------------------------
+def scale_batch(series, w_series=None, lag=1, trim_leading_zeros=True, tail_rows=28):
+    """The in-sample scale and the weight mass of host series: one upload, device.scale_block, one download.  series: a list of 1-d
+    arrays (left-aligned, any lengths); w_series: the arrays the tail is summed over (None: the series themselves; else one per
+    series, of its length).
+
+    Returns {"msd", "mad", "n_terms", "tail": fp64 [n]; "first", "status": int32 [n] (lib.SCALE_*)}."""
+    import torch
+    from . import device as _device
+    if not torch.cuda.is_available():
+        raise RuntimeError("scale_batch needs a HIP device (no CPU fallback)")
+    arrs = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in series]
+    n = len(arrs)
+    if n == 0:
+        return {k: np.zeros(0) for k in _lib.SCALE_ROWS} | {"first": np.zeros(0, dtype=np.int32), "status": np.zeros(0, dtype=np.int32)}
+    T = max(1, max(len(a) for a in arrs))
+    ld = (n + 63) // 64 * 64
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def pack(rows):
+        block = np.zeros((T, ld))
+        for s, a in enumerate(rows):
+            block[:len(a), s] = a
+        return torch.from_numpy(block).to(dev)
+    w = None
+    if w_series is not None:
+        ws = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in w_series]
+        if len(ws) != n or any(len(a) != len(b) for a, b in zip(ws, arrs)):
+            raise InvalidInputException("Invalid input: w_series must hold one array per series, of the series' length")
+        w = pack(ws)
+    lens = torch.zeros(ld, dtype=torch.int32)
+    lens[:n] = torch.tensor([len(a) for a in arrs], dtype=torch.int32)
+    try:
+        r = _device.scale_block(pack(arrs), lens.to(dev), w_src=w, lag=int(lag), trim_leading_zeros=bool(trim_leading_zeros),
+                                tail_rows=int(tail_rows), n_cols=n)
+    except ValueError as e:
+        raise InvalidInputException(str(e)) from e
+    return {k: r[k].cpu().numpy() for k in ("msd", "mad", "n_terms", "tail", "first", "status")}
+
+
+def wrmsse_batch(train, forecast, actual, column_of=None, prices=None, lag=1, trim_leading_zeros=True, tail_rows=28):
+    """anofox_hip_wrmsse_batch: the WRMSSE of a set of forecasts.  train: a list of 1-d training series that end on the same date;
+    forecast, actual: [n_series, h], NaN for a row that does not exist; column_of int32 [n_groupings, n_series] as for hierarchy_batch
+    (None: the leaves alone, one range); prices: None (weights from the units) or one array per series, of its length (an entry may
+    be None).  One pack; training values, revenue, forecasts and actuals added up the plan; mse per column; the scales; the weighted
+    mean of the RMSSE per grouping; one readback.
+
+    Returns ({"scale": fp64 [4, ld] (rows lib.SCALE_ROWS); "msd", "tail": fp64 [n_out]; "rmsse": fp64 [n_out] (NaN: left out);
+    "status": int32 [n_out] (lib.SCALE_*); "score": fp64 [n_ranges], "left": int32 [n_ranges], "ranges": int32 [n_ranges, 2] -- one
+    range per grouping, without column_of the whole; "wrmsse": the mean of the scores; "n_out", "ld"}, error)."""
+    L = _lib.load()
+    arrs = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in train]
+    n = len(arrs)
+    fc = np.ascontiguousarray(forecast, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 1))
+    h = int(fc.shape[1])
+    act = np.ascontiguousarray(actual, dtype=np.float64).reshape(n, h) if n else np.zeros((0, 1))
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else None for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+    pr, pptr = None, None
+    if prices is not None:
+        pr = [None if p is None else np.ascontiguousarray(p, dtype=np.float64).reshape(-1) for p in prices]
+        if len(pr) != n or any(p is not None and len(p) != len(a) for p, a in zip(pr, arrs)):
+            raise InvalidInputException("Invalid input: prices must hold one array per series, of the series' length")
+        pptr = (C.c_void_p * max(n, 1))(*[None if p is None or not len(p) else p.ctypes.data for p in pr])
+    co, G = None, 0
+    if column_of is not None:
+        co = np.ascontiguousarray(column_of, dtype=np.int32).reshape(-1, n) if n else np.zeros((0, 0), dtype=np.int32)
+        G = int(co.shape[0])
+    planned = co is not None and co.size > 0
+    R = G if planned else 1
+    n_out, ld = C.c_size_t(), C.c_size_t()
+    err = _lib.AnofoxError()
+    out = {"n_out": 0, "ld": 0}
+    report = lambda ok: {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+    args = (ptrs, lens, pptr, n, fc.ctypes.data, act.ctypes.data, h, co.ctypes.data if planned else None, G, int(lag), bool(trim_leading_zeros),
+            int(tail_rows))
+    if not L.anofox_hip_wrmsse_batch(*args, 0, *([None] * 7), C.byref(n_out), C.byref(ld), C.byref(err)):
+        return out, report(False)
+    m, w = int(n_out.value), int(ld.value)
+    scale = np.full((4, w), np.nan)
+    rmsse = np.full(w, np.nan)
+    status = np.full(m, _lib.INTERNAL_ERROR, dtype=np.int32)
+    score = np.full(R, np.nan)
+    left = np.full(R, -1, dtype=np.int32)
+    ranges = np.zeros((R, 2), dtype=np.int32)
+    total = np.full(1, np.nan)
+    ok = L.anofox_hip_wrmsse_batch(*args, w, scale.ctypes.data, rmsse.ctypes.data, status.ctypes.data, score.ctypes.data, left.ctypes.data,
+                                   ranges.ctypes.data, total.ctypes.data, C.byref(n_out), C.byref(ld), C.byref(err))
+    out.update({"n_out": m, "ld": w, "scale": scale, "msd": scale[0, :m], "tail": scale[3, :m], "rmsse": rmsse[:m], "status": status,
+                "score": score, "left": left, "ranges": ranges, "wrmsse": float(total[0])})
+    return out, report(ok)
+
+
+def wspl_block(paths, actual, levels, train, train_lengths, ranges, *, horizon, n_paths, n_cols=None, w_src=None, lag=1,
+               trim_leading_zeros=True, tail_rows=28, actual_series_major=False):
+    """The weighted scaled pinball loss of a block of sample paths, all of it on the device: the pinball rows of
+    device.path_scores_block as they lie, device.scale_block on the (aggregated) training block `train` [t_rows, ld] with
+    `train_lengths`, then device.weighted_scores_block(transform="ratio") with the mad row as the scale and the tail row as the
+    weight over `ranges` [n_ranges, 2] -- for a plan, one range per level.  paths, actual, levels, horizon, n_paths as for
+    path_scores_block; w_src, lag, trim_leading_zeros, tail_rows as for scale_block.
+
+    Returns {"score": fp64 [n_ranges, n_levels] (the SPL of every range at every level); "left": int32 [n_ranges, n_levels];
+    "weight_sum"; "total": fp64 [n_levels]; "wspl": fp64 [1], the mean over the levels of the mean over the ranges; "scaled": fp64
+    [n_levels, ld], the SPL per column; "scale": scale_block's result; "scores": path_scores_block's} -- device tensors."""
+    from . import device as _device
+    sc = _device.path_scores_block(paths, actual, levels, horizon=int(horizon), n_paths=int(n_paths), n_cols=n_cols,
+                                   actual_series_major=actual_series_major, want=("column",))
+    n = int(sc["status"].numel())
+    k = int(sc["column"].shape[0]) - 2
+    if k < 1:
+        raise ValueError("wspl_block needs at least one level")
+    scale = _device.scale_block(train, train_lengths, w_src=w_src, lag=lag, trim_leading_zeros=trim_leading_zeros, tail_rows=tail_rows, n_cols=n)
+    # (a column whose paths hold a NaN, or that has no actual, has NaN pinball rows: the scaled loss leaves it out)
+    ws = _device.weighted_scores_block(sc["column"][2:], scale["scale"][1], scale["scale"][3], ranges, transform="ratio",
+                                       col_status=scale["status"], n_cols=n)
+    return {"score": ws["score"], "left": ws["left"], "weight_sum": ws["weight_sum"], "total": ws["total"], "wspl": ws["total_mean"],
+            "scaled": ws["scaled"], "scale": scale, "scores": sc}
+
+
+def _wrmsse_host(train_cols, w_cols, fc_cols, act_cols, ranges, lag, trim, tail_rows):
+    """The restatement of include/anofox_fcst_hip.h block 11 on host columns, in Python floats: columns are lists of floats (the
+    aggregates already formed).  -> (rmsse per column, score per range, left per range, wrmsse)."""
+    nan = math.nan
+    m = len(train_cols)
+    msd, tail, status = [nan] * m, [nan] * m, [0] * m
+    for c in range(m):
+        y, w = train_cols[c], w_cols[c]
+        n = len(y)
+        t0 = 0
+        if trim:
+            t0 = n
+            for t in range(n):
+                if y[t] != 0.0:
+                    t0 = t
+                    break
+        sq = 0.0
+        for t in range(t0 + lag, n):
+            d = y[t] - y[t - lag]
+            sq = sq + d * d
+        tl = 0.0
+        for t in range(max(0, n - tail_rows), n):
+            tl = tl + w[t]
+        terms = n - t0 - lag
+        bad = any(v != v for v in y) or any(w[t] != w[t] for t in range(max(0, n - tail_rows), n))
+        if bad:
+            status[c] = _lib.SCALE_NAN
+        elif terms <= 0:
+            status[c], tail[c] = _lib.SCALE_SHORT, tl
+        else:
+            msd[c], tail[c] = sq / float(terms), tl
+            status[c] = _lib.SCALE_CONSTANT if msd[c] == 0.0 else _lib.SCALE_OK
+    rmsse = [nan] * m
+    for c in range(m):
+        total, count = 0.0, 0
+        for f, a in zip(fc_cols[c], act_cols[c]):
+            if f != f or a != a:
+                continue
+            e = a - f
+            total = total + e * e
+            count += 1
+        if count == 0 or status[c] != 0 or not (msd[c] > 0.0 and msd[c] < math.inf) or not tail[c] >= 0.0:
+            continue
+        q = (total / float(count)) / msd[c]
+        s = math.sqrt(q) if q >= 0.0 else nan
+        if s == s and s < math.inf:
+            rmsse[c] = s
+    score, left = [], []
+    for b, e in ranges:
+        if b < 0 or e <= b or e > m:
+            score.append(nan)
+            left.append(-1)
+            continue
+        num, den, out = [0.0] * 64, [0.0] * 64, 0
+        for i, c in enumerate(range(b, e)):
+            keep = rmsse[c] == rmsse[c]
+            out += 0 if keep else 1
+            num[i % 64] = num[i % 64] + (tail[c] * rmsse[c] if keep else 0.0)
+            den[i % 64] = den[i % 64] + (tail[c] if keep else 0.0)
+        N, D = num[0], den[0]
+        for l in range(1, 64):
+            N, D = N + num[l], D + den[l]
+        score.append(N / D if D > 0.0 else nan)
+        left.append(out)
+    total, count = 0.0, 0
+    for v in score:
+        if v == v:
+            total, count = total + v, count + 1
+    return rmsse, score, left, (total / float(count) if count else nan)
+
+
+def ts_wrmsse_by(date, value, ids, forecast_table, params=None, info=None):
+    """The WRMSSE of a forecast table against a training table, level by level of the key hierarchy of ts_aggregate_hierarchy.
+
+    date, value, ids: the training table, `ids` the list of id columns (a NULL id is "NULL"); rows with a NULL date are dropped.
+    forecast_table: {"unique_id": the leaf's ids joined by the separator, "date", "forecast", "actual"} -- a leaf step that has no
+    row, or a NULL forecast or actual, is NaN and drops that step of every aggregate above it.  params: "price" (a column of the
+    training table: the weights are then the sums of value * price over the last tail_rows rows; default: of the values),
+    "tail_rows" (28), "lag" (1), "trim_leading_zeros" (True), "separator" ("|"), "aggregate_keyword" ("AGGREGATED").  Level L = 0 .. N
+    keeps the first L ids; every level weighs its series by their weight mass and the WRMSSE is the mean of the levels' scores.
+
+    Returns {"level": int32 [N + 2] (0 .. N, then -1 for the total), "n_series", "left_out": int32, "score": fp64} -- the last row is
+    the WRMSSE.  The GPU route (api.wrmsse_batch) runs under the table-order rule of ts_aggregate_hierarchy -- one series order
+    reproduces the row order of every date, no (leaf, date) twice -- and when every leaf's rows are consecutive dates of the grid that
+    end on its last date, without a NULL value; any other table runs the host restatement of the same definition.  `info` receives
+    {"route": "gpu" | "host", "rmsse", "unique_id", "status"}."""
+    ids = list(ids)
+    if len(ids) < 1:
+        raise InvalidInputException("ts_wrmsse_by requires at least one id column")
+    p = dict(params or {})
+    sep, keyword = _hierarchy_params(p)
+    lag, tail_rows = int(p.get("lag", 1)), int(p.get("tail_rows", 28))
+    trim = bool(p.get("trim_leading_zeros", True))
+    if lag < 1 or tail_rows < 1:
+        raise InvalidInputException("Invalid input: lag and tail_rows must be at least 1")
+    price = p.get("price")
+    masked_date = np.ma.getmaskarray(date) if np.ma.isMaskedArray(date) else None
+    dates = np.ma.getdata(date) if masked_date is not None else np.asarray(date)
+    kind = _date_kind(dates)
+    us_all = _to_micros(dates, kind)
+    null_date = np.isnat(dates) if np.issubdtype(dates.dtype, np.datetime64) else np.zeros(len(dates), bool)
+    if masked_date is not None:
+        null_date = null_date | masked_date
+
+    def floats(col, what):
+        a = np.ma.filled(np.ma.asarray(col, dtype=object), None) if np.ma.isMaskedArray(col) else np.asarray(col, dtype=object)
+        if len(a) != len(dates):
+            raise InvalidInputException(f"every column of the input table must have the same number of rows ({what})")
+        return a
+    val = floats(value, "value")
+    prc = floats(price, "price") if price is not None else None
+    id_cols = [_hierarchy_strings(c, len(dates)) for c in ids]
+    keep = np.nonzero(~null_date)[0]
+    N = len(ids)
+    # the leaves, in order of first appearance, and their rows
+    leaf_index, leaf_keys, rows_of = {}, [], []
+    us = np.array([int(us_all[i]) for i in keep], dtype=np.int64)
+    grid, rank_of_row = np.unique(us, return_inverse=True) if len(keep) else (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+    leaf_of_row = np.empty(len(keep), dtype=np.int64)
+    has_null = False
+    for r, i in enumerate(keep):
+        parts = tuple(c[i] for c in id_cols)
+        k = leaf_index.get(parts)
+        if k is None:
+            k = leaf_index[parts] = len(leaf_keys)
+            leaf_keys.append(parts)
+            rows_of.append([])
+        leaf_of_row[r] = k
+        rows_of[k].append(r)
+        has_null = has_null or val[i] is None or (prc is not None and prc[i] is None)
+    n_leaf = len(leaf_keys)
+    # the forecast table: steps = the ranks of its distinct dates
+    f_uid = _hierarchy_strings(forecast_table["unique_id"], len(forecast_table["unique_id"]))
+    f_dates = np.asarray(np.ma.getdata(forecast_table["date"]))
+    f_us = _to_micros(f_dates, _date_kind(f_dates))
+    f_grid, f_rank = np.unique(np.array([int(v) for v in f_us], dtype=np.int64), return_inverse=True)
+    h = max(len(f_grid), 1)
+    f_fc, f_act = _floats_or_nan(forecast_table["forecast"]), _floats_or_nan(forecast_table["actual"])
+    leaf_uid = {sep.join(parts): k for k, parts in enumerate(leaf_keys)}
+    fc = np.full((n_leaf, h), np.nan)
+    act = np.full((n_leaf, h), np.nan)
+    for r, u in enumerate(f_uid):
+        k = leaf_uid.get(u)
+        if k is None:
+            raise InvalidInputException(f"Invalid input: the forecast table's unique_id {u!r} is not a leaf of the training table")
+        fc[k, int(f_rank[r])] = f_fc[r]
+        act[k, int(f_rank[r])] = f_act[r]
+    # the levels: columns numbered level by level, within a level by the byte order of the unique_id
+    uid = [[_hierarchy_unique_id(parts, level, sep, keyword) for parts in leaf_keys] for level in range(N + 1)]
+    column_of = np.zeros((N + 1, n_leaf), dtype=np.int32)
+    names, base = [], 0
+    for level in range(N + 1):
+        distinct = sorted(set(uid[level]), key=lambda u: u.encode("utf-8"))
+        at = {u: base + c for c, u in enumerate(distinct)}
+        column_of[level] = [at[u] for u in uid[level]]
+        names.extend(distinct)
+        base += len(distinct)
+    n_out = base
+    numbering = _hierarchy_leaf_order(leaf_of_row, rank_of_row, leaf_keys) if n_leaf else None
+    def dense_to_the_end(rows):                                        # consecutive positions of the grid, the last one included
+        ranks = rank_of_row[rows]
+        return int(ranks.max()) == len(grid) - 1 and len(rows) == int(ranks.max() - ranks.min()) + 1
+    dense = n_leaf > 0 and not has_null and all(dense_to_the_end(rows_of[k]) for k in range(n_leaf))
+    route = "gpu" if (numbering is not None and dense) else "host"
+    nan = math.nan
+    if route == "gpu":
+        order = np.argsort(numbering, kind="stable")                   # series s of the batch = leaf order[s]
+        train, prices = [], ([] if prc is not None else None)
+        for k in order:
+            rs = sorted(rows_of[k], key=lambda r: rank_of_row[r])
+            train.append(np.array([float(val[keep[r]]) for r in rs]))
+            if prc is not None:
+                prices.append(np.array([float(prc[keep[r]]) for r in rs]))
+        res, err = wrmsse_batch(train, fc[order], act[order], column_of=column_of[:, order], prices=prices, lag=lag, trim_leading_zeros=trim,
+                                tail_rows=tail_rows)
+        if not err["ok"]:
+            if err["code"] in (_lib.INVALID_INPUT, _lib.NULL_POINTER):
+                raise InvalidInputException(err["message"])
+            raise RuntimeError(f"anofox_hip_wrmsse_batch failed: [{err['code']}] {err['message']}")
+        rmsse, score, left, total, status = res["rmsse"], res["score"], res["left"], res["wrmsse"], res["status"]
+        ranges = res["ranges"]
+    else:
+        # the operator's map of maps: every row is added to its cell of every level in row order
+        T = len(grid)
+        cells = [[None] * T for _ in range(n_out)]
+        wcells = [[None] * T for _ in range(n_out)]
+        for r, i in enumerate(keep):
+            v = 0.0 if val[i] is None else float(val[i])
+            w = v if prc is None else v * (0.0 if prc[i] is None else float(prc[i]))
+            t = int(rank_of_row[r])
+            for level in range(N + 1):
+                c = int(column_of[level, leaf_of_row[r]])
+                cells[c][t] = (0.0 if cells[c][t] is None else cells[c][t]) + v
+                wcells[c][t] = (0.0 if wcells[c][t] is None else wcells[c][t]) + w
+        train_cols, w_cols = [], []
+        for c in range(n_out):
+            have = [t for t in range(T) if cells[c][t] is not None]
+            lo, hi = (have[0], have[-1]) if have else (0, -1)
+            train_cols.append([0.0 if cells[c][t] is None else cells[c][t] for t in range(lo, hi + 1)])
+            w_cols.append([0.0 if wcells[c][t] is None else wcells[c][t] for t in range(lo, hi + 1)])
+        fc_cols = [[0.0] * h for _ in range(n_out)]
+        act_cols = [[0.0] * h for _ in range(n_out)]
+        for k in range(n_leaf):                                        # leaves in order of first appearance: the row order of a date
+            for level in range(N + 1):
+                c = int(column_of[level, k])
+                for s in range(h):
+                    fc_cols[c][s] = fc_cols[c][s] + float(fc[k, s])
+                    act_cols[c][s] = act_cols[c][s] + float(act[k, s])
+        ranges = [(int(column_of[level].min()), int(column_of[level].max()) + 1) if n_leaf else (0, 0) for level in range(N + 1)]
+        rmsse, score, left, total = _wrmsse_host(train_cols, w_cols, fc_cols, act_cols, ranges, lag, trim, tail_rows)
+        status = None
+    if info is not None:
+        info.update({"route": route, "rmsse": np.array(rmsse, dtype=np.float64), "unique_id": np.array(names, dtype=object), "status": status})
+    widths = [int(b) - int(a) for a, b in ranges]
+    lefts = [int(v) for v in left]
+    return {"level": np.array(list(range(N + 1)) + [-1], dtype=np.int32),
+            "n_series": np.array(widths + [n_out], dtype=np.int32),
+            "left_out": np.array(lefts + [sum(v for v in lefts if v > 0)], dtype=np.int32),
+            "score": np.array([float(v) for v in score] + [float(total) if total == total else nan], dtype=np.float64)}
+
+
+def _floats_or_nan(col):
+    """A numeric column with NULLs (None, masked) -> fp64 with NaN."""
+    a = np.ma.filled(np.ma.asarray(col, dtype=object), None) if np.ma.isMaskedArray(col) else np.asarray(col, dtype=object)
+    return np.array([np.nan if v is None else float(v) for v in a], dtype=np.float64)
 
 
 anofox_fcst_ts_aggregate_hierarchy = ts_aggregate_hierarchy

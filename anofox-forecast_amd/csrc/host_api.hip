@@ -45,6 +45,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
 #include "host_path_scores_plan.hpp" // the host-only checks of the path-score entries, the energy workspace and a plan's column ranges
+#include "host_scaled_scores_plan.hpp" // the host-only checks of the scaled-score entries and the ranges of the WRMSSE chain
 #include "host_period_search.hpp" // the host-only logic of the SSA / STL period entries (defaults, window, candidate list, checks naming their limits)
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
@@ -8119,6 +8120,232 @@ bool anofox_hip_path_scores_batch(const double *points, const double *const *poo
         return false;
     }
     return ok;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Scaled, weighted scores of a hierarchy: the in-sample scale, RMSSE / MASE / SPL and their weighted means, WRMSSE and WSPL
+// (DESIGN.md section 3 "Scaled scores"; scaled_scores.hip, host_scaled_scores_plan.hpp)
+// ------------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+static_assert(SCALE_OK == ANOFOX_SCALE_OK && SCALE_SHORT == ANOFOX_SCALE_SHORT && SCALE_NAN == ANOFOX_SCALE_NAN &&
+              SCALE_CONSTANT == ANOFOX_SCALE_CONSTANT && SCALED_MAX_LOSS == ANOFOX_HIP_SCALED_MAX_LOSS, "the constants of the scaled-score entries");
+
+bool anofox_hip_scale_device(const double *y, size_t ld, const int32_t *lengths, size_t n_cols, size_t t_rows, const double *w_src, size_t lag,
+                             bool trim_leading_zeros, size_t tail_rows, double *out_scale, size_t ld_out, int32_t *out_first, int32_t *status,
+                             void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!y || !lengths || !out_scale || !out_first || !status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(scale_check(ld, n_cols, t_rows, lag, tail_rows, ld_out, &message), message, out_error)) return false;
+    if (n_cols == 0) return true;
+    if (!device_ready(out_error)) return false;
+    ScaleArgs a{};
+    a.y = y; a.ld = ld; a.w_src = w_src ? w_src : y; a.len = lengths; a.n_cols = (int)n_cols; a.t_rows = (int)t_rows; a.lag = (int)lag;
+    a.tail_rows = (int)tail_rows; a.trim = trim_leading_zeros ? 1 : 0; a.out = out_scale; a.ld_out = ld_out; a.first = out_first; a.status = status;
+    try {
+        (void)hipGetLastError();
+        launch_scale(a, (hipStream_t)stream);
+        LAUNCHCHECK("scale");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_weighted_scores_device(const double *loss, size_t ld, size_t n_cols, size_t n_loss, const double *scale, const double *weight,
+                                       const int32_t *col_status, const int32_t *ranges, size_t n_ranges, int32_t transform, double *out_scaled,
+                                       double *out_score, double *out_weight_sum, int32_t *out_left, double *out_total, void *stream,
+                                       AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!loss || !scale || !weight || !ranges || !out_score || !out_weight_sum || !out_left || !out_total) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!paths_plan_report(weighted_scores_check(ld, n_cols, n_loss, n_ranges, transform, &message), message, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    WeightedScoresArgs a{};
+    a.loss = loss; a.ld = ld; a.scale = scale; a.weight = weight; a.col_status = col_status; a.ranges = ranges; a.n_cols = (int)n_cols;
+    a.n_loss = (int)n_loss; a.n_ranges = (int)n_ranges; a.transform = transform; a.scaled = out_scaled; a.score = out_score;
+    a.weight_sum = out_weight_sum; a.left = out_left; a.total = out_total;
+    try {
+        (void)hipGetLastError();
+        launch_weighted_scores(a, (hipStream_t)stream);
+        LAUNCHCHECK("weighted scores");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_wrmsse_batch(const double *const *values, const size_t *lengths, const double *const *prices, size_t n_series,
+                             const double *forecast, const double *actual, size_t horizon, const int32_t *column_of, size_t n_groupings,
+                             size_t lag, bool trim_leading_zeros, size_t tail_rows, size_t ld, double *out_scale, double *out_rmsse,
+                             int32_t *out_status, double *out_score, int32_t *out_left, int32_t *out_ranges, double *out_total,
+                             size_t *out_n_out, size_t *out_ld, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (n_series > 0 && (!values || !lengths || !forecast || !actual)) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (horizon < 1) { set_error(out_error, INVALID_INPUT, "Invalid input: horizon must be at least 1"); return false; }
+    if (horizon > SCALED_PLAN_MAX_ROWS) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: horizon " + std::to_string(horizon) + " exceeds the limit of 2^30 rows");
+        return false;
+    }
+    if (!paths_plan_report(scale_check(SIZE_MAX, n_series, 0, lag, tail_rows, SIZE_MAX, &message), message, out_error)) return false;
+    size_t T = 1;
+    for (size_t s = 0; s < n_series; s++) {
+        if (lengths[s] > 0 && !values[s]) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (lengths[s] > SCALED_PLAN_MAX_ROWS) {
+            set_error(out_error, INVALID_INPUT, "Invalid input: series " + std::to_string(s) + " is longer than the limit of 2^30 rows");
+            return false;
+        }
+        T = std::max(T, lengths[s]);
+    }
+    const bool planned = column_of != nullptr && n_groupings > 0;
+    size_t n_out = n_series, nnz = 0;
+    std::vector<int32_t> offs, memb;
+    if (planned) {
+        if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, nullptr, nullptr, out_error)) return false;
+        offs.resize(n_out + 1);
+        memb.resize(std::max<size_t>(nnz, 1));
+        if (!anofox_hip_hierarchy_plan(column_of, n_groupings, n_series, &n_out, &nnz, offs.data(), memb.data(), out_error)) return false;
+    }
+    const size_t need_ld = paths_ld(n_out);
+    if (out_n_out) *out_n_out = n_out;
+    if (out_ld) *out_ld = need_ld;
+    if (!out_status) return true;
+    if (ld != need_ld) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is not what the sizing call returns"); return false; }
+    const size_t R = wrmsse_n_ranges(planned, n_groupings);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<int32_t> ranges(2 * R);
+    wrmsse_ranges(planned ? column_of : nullptr, n_groupings, n_series, n_out, ranges.data());
+    if (out_ranges) std::memcpy(out_ranges, ranges.data(), 2 * R * sizeof(int32_t));
+    if (out_total) *out_total = nan;
+    for (size_t r = 0; r < R; r++) {
+        if (out_score) out_score[r] = nan;
+        if (out_left) out_left[r] = -1;
+    }
+    if (n_series == 0 || n_out == 0) return true;
+    if (!device_ready(out_error)) return false;
+
+    const size_t ld_s = paths_ld(n_series);
+    // ONE arena of results, so that one copy brings them back: scale [4 x ld], rmsse [ld], score [R], total [2], then status [ld], left [R]
+    const size_t back_doubles = 5 * need_ld + R + 2, back_bytes = back_doubles * 8 + (need_ld + R) * 4;
+    std::vector<uint8_t> back(back_bytes);
+    Scratch scratch;
+    bool ok = true;
+    try {
+        std::vector<double> yb(T * ld_s, 0.0), rb(prices ? T * ld_s : 0, 0.0), fb(horizon * ld_s, 0.0), ab(horizon * ld_s, 0.0);
+        const std::vector<int32_t> len = block_lengths(lengths, n_series, ld_s);
+        std::vector<int32_t> steps(ld_s, 0);
+        std::vector<int64_t> fst(ld_s, 0);                                     // the series end on the same date
+        pack_time_major(yb.data(), ld_s, values, lengths, n_series);
+        for (size_t s = 0; s < n_series; s++) {
+            steps[s] = (int32_t)horizon;
+            fst[s] = (int64_t)(T - std::max<size_t>(lengths[s], lengths[s] ? 0 : T));
+            for (size_t k = 0; k < horizon; k++) { fb[k * ld_s + s] = forecast[s * horizon + k]; ab[k * ld_s + s] = actual[s * horizon + k]; }
+            if (prices)
+                for (size_t t = 0; t < lengths[s]; t++) rb[t * ld_s + s] = prices[s] ? values[s][t] * prices[s][t] : values[s][t];
+        }
+        const size_t n_blocks = planned ? (prices ? 2 : 1) : 0;
+        double *d_y = nullptr, *d_rev = nullptr, *d_agg = nullptr;
+        try {
+            d_y = scratch.get<double>(T * ld_s);
+            if (prices) d_rev = scratch.get<double>(T * ld_s);
+            if (n_blocks) d_agg = scratch.get<double>(n_blocks * T * need_ld);
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the training block" + std::string(prices ? "s" : "") + " of " + std::to_string(T) +
+                      " x " + std::to_string(ld_s) + " values" + (planned ? " and the aggregate of " + std::to_string(T) + " x " +
+                      std::to_string(need_ld) + " values" : std::string()) + " need " +
+                      std::to_string(((prices ? 2 : 1) * T * ld_s + n_blocks * T * need_ld) * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            double *d_f = scratch.get<double>(horizon * ld_s), *d_a = scratch.get<double>(horizon * ld_s);
+            int32_t *d_len = scratch.get<int32_t>(ld_s), *d_steps = scratch.get<int32_t>(ld_s);
+            double *d_fig = scratch.get<double>(12 * need_ld);
+            int32_t *d_mstatus = scratch.get<int32_t>(need_ld), *d_first = scratch.get<int32_t>(need_ld), *d_ranges = scratch.get<int32_t>(2 * R);
+            double *d_wsum = scratch.get<double>(R);
+            uint8_t *d_back = scratch.get<uint8_t>(back_bytes);
+            double *d_scale = (double *)d_back, *d_rmsse = d_scale + 4 * need_ld, *d_score = d_rmsse + need_ld, *d_total = d_score + R;
+            int32_t *d_status = (int32_t *)(d_back + back_doubles * 8), *d_left = d_status + need_ld;
+            HIPCHECK(hipMemcpy(d_y, yb.data(), T * ld_s * sizeof(double), hipMemcpyHostToDevice));
+            if (prices) HIPCHECK(hipMemcpy(d_rev, rb.data(), T * ld_s * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_f, fb.data(), horizon * ld_s * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_a, ab.data(), horizon * ld_s * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_len, len.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_steps, steps.data(), ld_s * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemcpy(d_ranges, ranges.data(), 2 * R * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMemset(d_back, 0xFF, back_doubles * 8));               // NaN in every figure of the padding columns
+            HIPCHECK(hipMemset(d_back + back_doubles * 8, 0, (need_ld + R) * 4));
+            const double *d_train = d_y, *d_weight = d_rev, *d_fc = d_f, *d_act = d_a;
+            const int32_t *d_tlen = d_len, *d_hlen = d_steps;
+            if (planned) {
+                AnofoxHipHierarchyOptions ho{};
+                int32_t *d_plan = scratch.get<int32_t>(n_out + 1 + nnz);
+                int64_t *d_fst = scratch.get<int64_t>(ld_s), *d_first_out = scratch.get<int64_t>(need_ld);
+                int32_t *d_len_agg = scratch.get<int32_t>(need_ld), *d_len_rev = scratch.get<int32_t>(need_ld), *d_len_h = scratch.get<int32_t>(need_ld);
+                double *d_fa = scratch.get<double>(2 * horizon * need_ld);
+                HIPCHECK(hipMemcpy(d_plan, offs.data(), (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+                if (nnz) HIPCHECK(hipMemcpy(d_plan + n_out + 1, memb.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(d_fst, fst.data(), ld_s * sizeof(int64_t), hipMemcpyHostToDevice));
+                HIPCHECK(hipMemset(d_agg, 0, n_blocks * T * need_ld * sizeof(double)));
+                HIPCHECK(hipMemset(d_fa, 0, 2 * horizon * need_ld * sizeof(double)));
+                HIPCHECK(hipMemset(d_len_agg, 0, need_ld * sizeof(int32_t)));
+                HIPCHECK(hipMemset(d_len_h, 0, need_ld * sizeof(int32_t)));
+                const int32_t *d_memb = d_plan + n_out + 1;
+                ok = anofox_hip_hierarchy_device(d_y, nullptr, nullptr, ld_s, d_len, d_fst, n_series, T, d_plan, d_memb, n_out, nnz, &ho, sizeof ho, T,
+                                                 d_agg, nullptr, need_ld, d_len_agg, d_first_out, nullptr, out_error);
+                if (ok && prices)
+                    ok = anofox_hip_hierarchy_device(d_rev, nullptr, nullptr, ld_s, d_len, d_fst, n_series, T, d_plan, d_memb, n_out, nnz, &ho, sizeof ho,
+                                                     T, d_agg + T * need_ld, nullptr, need_ld, d_len_rev, d_first_out, nullptr, out_error);
+                if (ok)
+                    ok = anofox_hip_hierarchy_device(d_f, nullptr, nullptr, ld_s, d_steps, nullptr, n_series, horizon, d_plan, d_memb, n_out, nnz, &ho,
+                                                     sizeof ho, horizon, d_fa, nullptr, need_ld, d_len_h, d_first_out, nullptr, out_error);
+                if (ok)
+                    ok = anofox_hip_hierarchy_device(d_a, nullptr, nullptr, ld_s, d_steps, nullptr, n_series, horizon, d_plan, d_memb, n_out, nnz, &ho,
+                                                     sizeof ho, horizon, d_fa + horizon * need_ld, nullptr, need_ld, d_len_h, d_first_out, nullptr,
+                                                     out_error);
+                d_train = d_agg; d_weight = prices ? d_agg + T * need_ld : nullptr; d_fc = d_fa; d_act = d_fa + horizon * need_ld;
+                d_tlen = d_len_agg; d_hlen = d_len_h;
+            }
+            const size_t ld_b = planned ? need_ld : ld_s;                       // (the same number without a plan)
+            if (ok)
+                ok = anofox_hip_metrics_device(d_act, d_fc, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 1, ld_b, d_hlen, n_out, horizon,
+                                               1u << MF_MSE, 0.5, true, d_fig, need_ld, d_mstatus, nullptr, out_error);
+            if (ok)
+                ok = anofox_hip_scale_device(d_train, ld_b, d_tlen, n_out, T, d_weight, lag, trim_leading_zeros, tail_rows, d_scale, need_ld, d_first,
+                                             d_status, nullptr, out_error);
+            if (ok)
+                ok = anofox_hip_weighted_scores_device(d_fig + (size_t)MF_MSE * need_ld, need_ld, n_out, 1, d_scale, d_scale + 3 * need_ld, d_status,
+                                                       d_ranges, R, 1, d_rmsse, d_score, d_wsum, d_left, d_total, nullptr, out_error);
+            if (ok) HIPCHECK(hipMemcpy(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost));          // waits for the null stream
+            else HIPCHECK(hipDeviceSynchronize());
+        }
+        scratch.settled();                                                 // (either way the device has been waited for)
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    if (!ok) return false;
+    const double *b_scale = (const double *)back.data(), *b_rmsse = b_scale + 4 * need_ld, *b_score = b_rmsse + need_ld, *b_total = b_score + R;
+    const int32_t *b_status = (const int32_t *)(back.data() + back_doubles * 8), *b_left = b_status + need_ld;
+    if (out_scale) std::memcpy(out_scale, b_scale, 4 * need_ld * sizeof(double));
+    if (out_rmsse) std::memcpy(out_rmsse, b_rmsse, need_ld * sizeof(double));
+    std::memcpy(out_status, b_status, n_out * sizeof(int32_t));
+    if (out_score) std::memcpy(out_score, b_score, R * sizeof(double));
+    if (out_left) std::memcpy(out_left, b_left, R * sizeof(int32_t));
+    if (out_total) *out_total = b_total[1];
+    return true;
 }
 
 } // extern "C"

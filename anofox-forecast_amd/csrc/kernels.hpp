@@ -833,6 +833,31 @@ struct PathEnergyArgs {
 void launch_path_scores(const PathScoresArgs &, hipStream_t);
 void launch_path_energy(const PathEnergyArgs &, hipStream_t);   // the rows, the steps, the mean
 
+// Scaled, weighted scores of a hierarchy (DESIGN.md section 3 "Scaled scores"; scaled_scores.hip)
+constexpr int32_t SCALE_OK = 0, SCALE_SHORT = 1, SCALE_NAN = 2, SCALE_CONSTANT = 3;
+constexpr int SCALED_MAX_LOSS = 16;                    // loss rows per call: the project's level limit
+struct ScaleArgs {
+    const double *y; size_t ld;                  // [t_rows x ld] time-major, left-aligned
+    const double *w_src;                         // the block the tail is summed over, laid out as y (never null: y itself by default)
+    const int32_t *len;                          // [n_cols], cut to [0, t_rows]
+    int n_cols, t_rows, lag, tail_rows, trim;
+    double *out; size_t ld_out;                  // [4 x ld_out]: msd, mad, n_terms, tail
+    int32_t *first, *status;                     // [n_cols]
+};
+struct WeightedScoresArgs {
+    const double *loss; size_t ld;               // [n_loss x ld]
+    const double *scale, *weight;                // [n_cols]
+    const int32_t *col_status;                   // [n_cols] or null
+    const int32_t *ranges;                       // [n_ranges x 2]
+    int n_cols, n_loss, n_ranges, transform;     // 0: loss / scale; 1: sqrt(loss / scale)
+    double *scaled;                              // [n_loss x ld] or null
+    double *score, *weight_sum;                  // [n_ranges x n_loss]
+    int32_t *left;                               // [n_ranges x n_loss]
+    double *total;                               // [n_loss + 1]
+};
+void launch_scale(const ScaleArgs &, hipStream_t);
+void launch_weighted_scores(const WeightedScoresArgs &, hipStream_t);   // the cells, the ranges, the totals
+
 void launch_prep(const PrepArgs &, hipStream_t);
 void launch_select(const SelectArgs &, hipStream_t);
 void launch_classic(int kind, const ClassicArgs &, hipStream_t);

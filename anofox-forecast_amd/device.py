@@ -813,6 +813,99 @@ def path_energy_block(paths: torch.Tensor, actual: torch.Tensor, *, horizon: int
     return {"es": es, "summary": summary, "workspace": work}
 
 
+def scale_block(y: torch.Tensor, lengths: torch.Tensor, *, w_src: torch.Tensor | None = None, lag: int = 1, trim_leading_zeros: bool = True,
+                tail_rows: int = 28, n_cols: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_scale_device on torch tensors: the in-sample scale and the weight mass of every column of a resident block, no
+    host copy.
+
+    y [t_rows, ld] fp64 time-major, left-aligned with lengths int32 [>= n_cols] -- the "y" and "lengths" of aggregate_block as they
+    lie.  Per column: t0 = its first non-zero row (0 without trim_leading_zeros), msd and mad = the mean squared and the mean absolute
+    difference y[t] - y[t - lag] over the rows t0 + lag .. n - 1 (what RMSSE, and MASE and the scaled pinball loss, divide by), and
+    tail = the sum of the last tail_rows rows of w_src (a block laid out as y; None: y itself -- for M5 the aggregated units x price).
+
+    Returns {"scale": fp64 [4, ld_out] in the rows lib.SCALE_ROWS; "msd", "mad", "n_terms", "tail": fp64 [n_cols], its views;
+    "first": int32 [n_cols], t0; "status": int32 [n_cols]: lib.SCALE_OK, _SHORT (no difference: the scales NaN), _NAN (a NaN in the
+    column or its tail: every figure NaN), _CONSTANT (msd == 0: the scales 0.0)}."""
+    L = _lib.load()
+    assert y.dtype == torch.float64 and y.is_cuda and y.is_contiguous() and y.dim() == 2
+    t_rows, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_cols is None else int(n_cols)
+    assert 0 < n <= ld
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    if w_src is not None:
+        assert w_src.dtype == torch.float64 and w_src.is_cuda and w_src.is_contiguous() and tuple(w_src.shape) == tuple(y.shape)
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    ld_out = (n + 63) // 64 * 64
+    scale = torch.full((4, ld_out), float("nan"), dtype=torch.float64, device=dev)
+    first = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_scale_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, w_src.data_ptr() if w_src is not None else None, int(lag),
+                                   bool(trim_leading_zeros), int(tail_rows), scale.data_ptr(), ld_out, first.data_ptr(), status.data_ptr(),
+                                   C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_scale_device", err)
+    return {"scale": scale, "msd": scale[0, :n], "mad": scale[1, :n], "n_terms": scale[2, :n], "tail": scale[3, :n], "first": first,
+            "status": status}
+
+
+def weighted_scores_block(loss: torch.Tensor, scale: torch.Tensor, weight: torch.Tensor, ranges, *, transform: str | int,
+                          col_status: torch.Tensor | None = None, n_cols: int | None = None, want_scaled: bool = True,
+                          stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_weighted_scores_device on torch tensors: the scaled losses and their weighted mean over column ranges, no host copy.
+
+    loss fp64 [n_loss, ld] (or [ld]: one row) -- rows of metrics figures or of path_scores_block's "column" as they lie (a view of
+    whole rows is taken as it is); scale and weight fp64 [>= n_cols] -- one row of scale_block's "scale" each, usually "msd" or "mad"
+    and "tail"; col_status int32 [>= n_cols] or None; ranges: an int array or tensor [n_ranges, 2] of [begin, end).  transform "ratio"
+    (loss / scale: SPL, MASE) or "root" (its square root: RMSSE).  A column is left out when its status is not 0, its scale is not
+    finite or not positive, its weight is NaN or negative, or its scaled loss is not finite.
+
+    Returns {"scaled": fp64 [n_loss, ld] (NaN where left out or in no range; None without want_scaled); "score", "weight_sum": fp64
+    [n_ranges, n_loss]; "left": int32 [n_ranges, n_loss] (-1: a range that is empty, reversed or beyond n_cols; its score is NaN);
+    "total": fp64 [n_loss], the mean of the ranges' scores per loss row; "total_mean": fp64 [1], the mean of those (the WSPL of nine
+    pinball rows, the WRMSSE of one mse row)}."""
+    L = _lib.load()
+    code = _lib.SCALED_TRANSFORMS.get(transform, transform) if isinstance(transform, str) else int(transform)
+    if isinstance(code, str):
+        raise ValueError(f"weighted_scores_block: unknown transform {transform!r}; the transforms are {list(_lib.SCALED_TRANSFORMS)}")
+    if loss.dim() == 1:
+        loss = loss.view(1, -1)
+    assert loss.dtype == torch.float64 and loss.is_cuda and loss.is_contiguous() and loss.dim() == 2
+    n_loss, ld = int(loss.shape[0]), int(loss.shape[1])
+    n = ld if n_cols is None else int(n_cols)
+    assert 0 < n <= ld
+    for t in (scale, weight):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 1 and t.numel() >= n
+    if col_status is not None:
+        assert col_status.dtype == torch.int32 and col_status.is_cuda and col_status.is_contiguous() and col_status.numel() >= n
+    dev = loss.device
+    rg = torch.as_tensor(np.ascontiguousarray(ranges, dtype=np.int32) if not torch.is_tensor(ranges) else ranges).to(device=dev, dtype=torch.int32)
+    rg = rg.reshape(-1, 2).contiguous()
+    R = int(rg.shape[0])
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    nan = float("nan")
+    rows = max(min(n_loss, _lib.SCALED_MAX_LOSS), 1)
+    scaled = torch.full((rows, ld), nan, dtype=torch.float64, device=dev) if want_scaled and n_loss <= _lib.SCALED_MAX_LOSS else None
+    score = torch.full((max(R, 1), rows), nan, dtype=torch.float64, device=dev)
+    wsum = torch.full((max(R, 1), rows), nan, dtype=torch.float64, device=dev)
+    left = torch.full((max(R, 1), rows), -1, dtype=torch.int32, device=dev)
+    total = torch.full((rows + 1,), nan, dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_weighted_scores_device(loss.data_ptr(), ld, n, n_loss, scale.data_ptr(), weight.data_ptr(),
+                                             col_status.data_ptr() if col_status is not None else None, rg.data_ptr(), R, code,
+                                             scaled.data_ptr() if scaled is not None else None, score.data_ptr(), wsum.data_ptr(), left.data_ptr(),
+                                             total.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_weighted_scores_device", err)
+    return {"scaled": scaled, "score": score, "weight_sum": wsum, "left": left, "total": total[:n_loss], "total_mean": total[n_loss:],
+            "ranges": rg}
+
+
 _RECONCILE_PLAN_KEYS = ("col_offsets", "members", "bottom_col", "agg_cols", "leaf_offsets", "leaf_aggs")
 
 

@@ -457,6 +457,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_select_combine_device", "anofox_hip_select_batch",
     "anofox_hip_paths_device", "anofox_hip_path_quantiles_device", "anofox_hip_paths_batch",
     "anofox_hip_path_scores_device", "anofox_hip_path_scores_sizes", "anofox_hip_path_energy_device", "anofox_hip_path_scores_batch",
+    "anofox_hip_scale_device", "anofox_hip_weighted_scores_device", "anofox_hip_wrmsse_batch",
 ]
 
 # include/anofox_fcst_hip.h block 9: bootstrap sample paths and their quantiles
@@ -468,6 +469,11 @@ PATHS_MAX_POOL_ROWS = 1 << 20                          # ANOFOX_HIP_PATHS_MAX_PO
 PATHS_OK, PATHS_EMPTY, PATHS_NAN, PATHS_RAGGED = 0, 1, 2, 3
 # block 10: scores of sample paths (ANOFOX_PATH_SCORES_*): done; no step with an actual; a NaN among the column's paths
 PATH_SCORES_OK, PATH_SCORES_NO_ACTUAL, PATH_SCORES_NAN = 0, 1, 2
+# block 11: scaled, weighted scores (ANOFOX_SCALE_*): done; no lag difference; a NaN in the column or in its tail; constant after t0
+SCALE_OK, SCALE_SHORT, SCALE_NAN, SCALE_CONSTANT = 0, 1, 2, 3
+SCALED_TRANSFORMS = {"ratio": 0, "root": 1}            # ANOFOX_SCALED_RATIO (loss / scale), ANOFOX_SCALED_ROOT (its square root)
+SCALED_MAX_LOSS = 16                                   # ANOFOX_HIP_SCALED_MAX_LOSS
+SCALE_ROWS = ("msd", "mad", "n_terms", "tail")         # the rows of out_scale
 
 
 class AnofoxHipPathsOptions(C.Structure):
@@ -875,6 +881,18 @@ def load():
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
+    # block 11: scaled, weighted scores of a hierarchy
+    L.anofox_hip_scale_device.restype = C.c_bool
+    L.anofox_hip_scale_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_bool,
+                                          C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_weighted_scores_device.restype = C.c_bool
+    L.anofox_hip_weighted_scores_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_wrmsse_batch.restype = C.c_bool
+    L.anofox_hip_wrmsse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_size_t, C.c_size_t, C.c_bool, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]

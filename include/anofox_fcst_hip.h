@@ -2906,6 +2906,142 @@ bool anofox_hip_path_scores_batch(const double *points,
                                   size_t *out_ld,
                                   struct AnofoxError *out_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 11: scaled, weighted scores of a hierarchy: RMSSE, SPL, WRMSSE, WSPL  */
+/* ------------------------------------------------------------------------- */
+/*
+ * The scores a hierarchy such as M5 is judged by (Makridakis et al., The M5 competition, competitors' guide): a loss per column
+ * divided by the column's in-sample scale, and the weighted mean of the scaled losses over the columns of a level.  The reference
+ * has no such function; the names are this package's own and tests/scaled_scores_ref.py is the definition, bit for bit.  Plain
+ * fp64, one rounding per operation, nothing fused: a product is rounded, then added.
+ *   - the scale of a column y[0 .. n) (n = its length cut to t_rows): t0 = the first row with y != 0.0 when trim_leading_zeros
+ *     (+0.0 and -0.0 are both zero; t0 = n when every row is) and 0 otherwise; for t = t0 + lag .. n - 1 in row order,
+ *     d = y[t] - y[t - lag], sq = sq + d * d, ab = ab + |d|, both serial from 0.0; n_terms = n - t0 - lag, msd = sq / n_terms,
+ *     mad = ab / n_terms.  msd is what RMSSE divides the mse by, mad what MASE and the scaled pinball loss divide by;
+ *   - the weight mass: tail = the serial sum from 0.0 of w_src over the rows max(0, n - tail_rows) .. n - 1 in row order (w_src NULL:
+ *     y itself; for M5 the aggregated units x price block and tail_rows = 28);
+ *   - status per column (int32): 0 done; 1 n_terms <= 0 -- msd and mad are NaN, n_terms and tail are still written (tail is 0.0 for
+ *     n = 0); 2 a NaN among the rows [0, n) of y or among the tail rows of w_src -- all four figures are NaN; 2 takes precedence;
+ *     3 msd == 0.0 -- the series is constant after t0 and both scales are written as 0.0.  +-inf are ordinary values.  Rows >= n and
+ *     columns >= n_cols never enter a result;
+ *   - the scaled loss of (loss row r, column c): s = loss / scale (transform 0: SPL from a pinball row and mad, MASE from mae and
+ *     mad) or s = sqrt(loss / scale) (transform 1: RMSSE from mse and msd; the correctly rounded root).  A column is LEFT OUT when
+ *     col_status != 0, when its scale is not finite or is <= 0.0, when its weight is NaN or negative, or when s is not finite (that
+ *     one per loss row): its out_scaled cell is NaN, it adds 0.0 to both sums and it is counted in out_left;
+ *   - per (range g = [begin, end), loss row r): N = W_c(w_c * s_c), D = W_c(w_c), each product rounded once, W the wave sum of Block
+ *     10 with the terms indexed by c - begin; score[g, r] = N / D, NaN when D is not positive;
+ *   - total[r] = the serial sum from 0.0 of the non-NaN score[g, r] in range order, divided by their count (NaN when there is none):
+ *     with M5's twelve ranges the 1/12 per level; total_mean = the serial sum over r of total[r], divided by n_loss: with the nine
+ *     pinball rows the WSPL.
+ */
+enum { ANOFOX_SCALE_OK = 0, ANOFOX_SCALE_SHORT = 1, ANOFOX_SCALE_NAN = 2, ANOFOX_SCALE_CONSTANT = 3 };
+enum { ANOFOX_SCALED_RATIO = 0, ANOFOX_SCALED_ROOT = 1 };       /* transform */
+#define ANOFOX_HIP_SCALED_MAX_LOSS 16
+
+/*
+ * Scale and weight mass of every column of a device-resident block y[t * ld + c] (fp64, time-major, left-aligned, lengths int32
+ * [n_cols] on the device, a length above t_rows is cut to it) -- the y_out and lengths_out of anofox_hip_hierarchy_device as they
+ * lie.  w_src: a block in the same layout, or NULL for y itself.  Outputs, in device memory: out_scale fp64 [4 x ld_out] in the rows
+ * msd, mad, n_terms (as double), tail (row r of column c at r * ld_out + c), out_first int32 [n_cols] (t0), status int32 [n_cols].
+ * One lane per column; the loads of a block of rows are issued ahead of the serial chains that consume them.  The call only
+ * enqueues on `stream` (NULL: the null stream) and does NOT wait on the host.
+ * INVALID_INPUT, each naming its limit, before the device is touched: lag or tail_rows 0; lag, tail_rows or t_rows above 2^30;
+ * ld < n_cols; ld_out < n_cols; n_cols above 2^31 - 1.
+ */
+bool anofox_hip_scale_device(const double *y,
+                             size_t ld,
+                             const int32_t *lengths,
+                             size_t n_cols,
+                             size_t t_rows,
+                             const double *w_src,
+                             size_t lag,
+                             bool trim_leading_zeros,
+                             size_t tail_rows,
+                             double *out_scale,
+                             size_t ld_out,
+                             int32_t *out_first,
+                             int32_t *status,
+                             void *stream,
+                             struct AnofoxError *out_error);
+
+/*
+ * Scaled losses and their weighted mean per column range.  All arrays in device memory: loss fp64 [n_loss x ld] (row r of column c
+ * at r * ld + c) -- rows of `figures` of anofox_hip_metrics_device or of out_column of anofox_hip_path_scores_device are passed by
+ * pointer offset, as they lie --, scale fp64 [n_cols] (one row of out_scale), weight fp64 [n_cols] (the tail row, or any non-negative
+ * figure per column), col_status int32 [n_cols] or NULL, ranges int32 [n_ranges x 2], [begin, end) each.  Outputs: out_scaled fp64
+ * [n_loss x ld] or NULL (written for the columns of the valid ranges; a cell no range covers is not touched), out_score and
+ * out_weight_sum (D) fp64 [n_ranges x n_loss] (range g, row r at g * n_loss + r), out_left int32 [n_ranges x n_loss], out_total fp64
+ * [n_loss + 1]: total[r], then total_mean.  A range that is empty, reversed or ends beyond n_cols is seen only on the device: its
+ * out_left is -1, its score and weight sum are NaN -- never a cut sum -- and it does not enter the totals.  One wavefront per
+ * (range, loss row), one small launch for the totals, no atomics.  The call only enqueues on `stream`.
+ * INVALID_INPUT, each naming its limit: n_loss 0 or above 16, an unknown transform, ld < n_cols, n_ranges 0 or above 2^31 - 1,
+ * n_cols above 2^31 - 1.
+ */
+bool anofox_hip_weighted_scores_device(const double *loss,
+                                       size_t ld,
+                                       size_t n_cols,
+                                       size_t n_loss,
+                                       const double *scale,
+                                       const double *weight,
+                                       const int32_t *col_status,
+                                       const int32_t *ranges,
+                                       size_t n_ranges,
+                                       int32_t transform,
+                                       double *out_scaled,
+                                       double *out_score,
+                                       double *out_weight_sum,
+                                       int32_t *out_left,
+                                       double *out_total,
+                                       void *stream,
+                                       struct AnofoxError *out_error);
+
+/*
+ * The WRMSSE of a set of forecasts, for host buffers.  values[s] points to the lengths[s] training values of series s; the series end
+ * on the same date (a shorter one starts later).  prices: NULL (the weights come from the units) or one pointer per series to
+ * lengths[s] prices (an entry may be NULL: the units): the weight source is then the rounded product value * price per leaf row.
+ * forecast and actual fp64 [n_series x horizon] series-major, NaN for a row that does not exist.  column_of / n_groupings as for
+ * anofox_hip_hierarchy_plan; NULL (or 0 groupings): the leaves alone, one range.
+ *
+ * The call packs once; aggregates training values, revenue, forecasts and actuals up the plan with anofox_hip_hierarchy_device (a
+ * member's NaN forecast or actual drops that step of the aggregate); takes mse per column from anofox_hip_metrics_device with
+ * drop_nan; computes the scales with anofox_hip_scale_device; scores one range per grouping by the rule of
+ * anofox_hip_path_scores_batch -- [the smallest column the grouping maps a series to, the largest + 1) --, without a plan the whole;
+ * runs anofox_hip_weighted_scores_device with transform 1, the msd row, the tail row and the scale's status; and reads back once.
+ *
+ * *out_n_out and *out_ld (n_out rounded up to 64, at least 64) are always written.  With out_status NULL that is all: the sizing
+ * call, which needs no device.  Otherwise ld must be what the sizing call returned and the caller's arrays receive, each but
+ * out_status optional (NULL): out_scale fp64 [4 x ld], out_rmsse fp64 [ld] (NaN for a column left out), out_status int32 [n_out] (of
+ * the scale), out_score fp64 and out_left int32 [n_groupings, or 1 without a plan], out_ranges int32 [that many x 2], *out_total the
+ * WRMSSE: the mean of the levels' scores.
+ *
+ * INVALID_INPUT as for the device entries and for the plan, and horizon 0 or above 2^30, a series above 2^30 rows, all before the
+ * device is touched.  A failed device allocation is a COMPUTATION_ERROR that names the size.  One device (the calling thread's
+ * current one); fp64 only.
+ */
+bool anofox_hip_wrmsse_batch(const double *const *values,
+                             const size_t *lengths,
+                             const double *const *prices,
+                             size_t n_series,
+                             const double *forecast,
+                             const double *actual,
+                             size_t horizon,
+                             const int32_t *column_of,
+                             size_t n_groupings,
+                             size_t lag,
+                             bool trim_leading_zeros,
+                             size_t tail_rows,
+                             size_t ld,
+                             double *out_scale,
+                             double *out_rmsse,
+                             int32_t *out_status,
+                             double *out_score,
+                             int32_t *out_left,
+                             int32_t *out_ranges,
+                             double *out_total,
+                             size_t *out_n_out,
+                             size_t *out_ld,
+                             struct AnofoxError *out_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
