@@ -2280,6 +2280,76 @@ def ts_stl_period_by(group, date, value, min_period=None, max_period=None, n_can
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# Period by matrix profile, through entries of its own (method := 'matrix_profile' of ts_detect_periods* stays an error)
+# ------------------------------------------------------------------------------------------------------------------------------
+def matrix_profile_batch(series, subsequence_length=None, n_best=None, profile=True):
+    """anofox_hip_matrix_profile_batch over a list of 1-D arrays with one parameter set; None or 0 means the source's default
+    (subsequence length n / 10 of each series, at least 4 and at most n / 4; n_best is the EXCLUSION ZONE, as the reference's wrapper
+    passes it on: m / 4, at least 1).  Per series a dict: ok, code, message, period, confidence, n_motifs (int), subsequence_length
+    (int), best_count (int), n_tied (int: how many lags share the best count; the smallest is the period), method, and with
+    profile=True "profile" (fp64 array, the distance of every subsequence to its nearest neighbour) and "profile_index" (int32)."""
+    L = _lib.load()
+    n, ys, lens, vals, errs, berr = _period_search_call(series)
+    rows = _lib.matrix_profile_rows(int(lens.max()) if n else 0, _size_t(subsequence_length)) if n else 0
+    fig = np.full((len(_lib.MATRIX_PROFILE_FIGURES), max(n, 1)), np.nan)
+    prof = np.full((max(rows, 1), max(n, 1)), np.nan)
+    idx = np.full((max(rows, 1), max(n, 1)), -1, dtype=np.int32)
+    ok = L.anofox_hip_matrix_profile_batch(vals, lens.ctypes.data, n, _size_t(subsequence_length), _size_t(n_best), fig.ctypes.data,
+                                           prof.ctypes.data if profile else None, idx.ctypes.data if profile else None, errs, C.byref(berr))
+    if not ok:
+        raise InvalidInputException(berr.message.decode(errors="replace"))
+    out = []
+    for i in range(n):
+        good = errs[i].code == _lib.SUCCESS
+        r = {"ok": good, "code": int(errs[i].code), "message": errs[i].message.decode(errors="replace"), "method": "matrix_profile",
+             "period": float(fig[0, i]), "confidence": float(fig[1, i])}
+        for k, name in enumerate(_lib.MATRIX_PROFILE_FIGURES[2:], 2):
+            r[name] = int(fig[k, i]) if good else 0
+        if profile:
+            p = _lib.matrix_profile_rows(len(ys[i]), _size_t(subsequence_length)) if good else 0
+            r["profile"], r["profile_index"] = prof[:p, i].copy(), idx[:p, i].copy()
+        out.append(r)
+    return out
+
+
+_MATRIX_PROFILE_STRUCT = ("period", "confidence", "n_motifs", "subsequence_length", "method")
+
+
+def _matrix_profile_many(lists, args):
+    """The scalar over many lists with one parameter set: every list with at least 32 non-NULL values goes to the GPU in ONE batch
+    call; None for a NULL list, a shorter one and a failed call."""
+    rows, series = [], []
+    for v in lists:
+        vals = None if v is None else _list_values(v)
+        if vals is None or len(vals) < _lib.MPROF_MIN_ROWS:
+            rows.append(None)
+            continue
+        rows.append(len(series))
+        series.append(vals)
+    res = matrix_profile_batch(series, *args, profile=False) if series else []
+    return [None if k is None or not res[k]["ok"] else {f: res[k][f] for f in _MATRIX_PROFILE_STRUCT} for k in rows]
+
+
+def ts_matrix_profile_period(values, subsequence_length=None, n_best=None):
+    """The scalar ts_matrix_profile_period(values[, subsequence_length[, n_best]]) (BIGINT arguments; n_best acts as the exclusion
+    zone): None for a NULL list, for fewer than 32 non-NULL values (NULL elements are dropped) and when the call fails.  Else
+    STRUCT(period, confidence, n_motifs, subsequence_length, method) as a dict."""
+    return _matrix_profile_many([values], (subsequence_length, n_best))[0]
+
+
+def ts_matrix_profile_period_by(group, date, value, subsequence_length=None, n_best=None, group_name="id"):
+    """This package's table form of ts_matrix_profile_period: per group the values ordered by date, ALL groups in ONE
+    anofox_hip_matrix_profile_batch call.  Returns a dict of columns: <group_name>, period, confidence, n_motifs, subsequence_length,
+    method (None = NULL, the row of a group that is too short or whose detection failed)."""
+    keys, lists = _ordered_lists(group, date, value)
+    res = _matrix_profile_many(lists, (subsequence_length, n_best))
+    cols = {group_name: keys}
+    for f in _MATRIX_PROFILE_STRUCT:
+        cols[f] = [None if r is None else r[f] for r in res]
+    return cols
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # Conformal prediction intervals: learn -> apply for every group in ONE call
 # ------------------------------------------------------------------------------------------------------------------------------
 def conformal_batch(residuals, forecasts=None, alphas=(0.1,), method="symmetric", strategy="split", difficulty=None, valids=None,

@@ -47,6 +47,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_path_scores_plan.hpp" // the host-only checks of the path-score entries, the energy workspace and a plan's column ranges
 #include "host_scaled_scores_plan.hpp" // the host-only checks of the scaled-score entries and the ranges of the WRMSSE chain
 #include "host_period_search.hpp" // the host-only logic of the SSA / STL period entries (defaults, window, candidate list, checks naming their limits)
+#include "host_matrix_profile.hpp" // the host-only logic of the matrix-profile period entries (m and exclusion rule, homes, workspace, tile walk, checks)
 #include "host_fit_schedule.hpp"  // the schedule of an ETS / AutoETS fit, decided from plain values (plan_fit_schedule): launch_fit_slots walks it
 
 struct Plan {
@@ -5051,6 +5052,121 @@ bool anofox_ts_stl_period(const double *values, size_t length, size_t min_period
     if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
     out_result->period = fig[0]; out_result->seasonal_strength = fig[1]; out_result->trend_strength = fig[2];
     copy_method(out_result->method, "stl");
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Period by matrix profile (periods.rs matrix_profile_period behind lib.rs:1888; matrix_profile.hip).  Entries of its own: the
+// dispatch by method name above keeps its not-implemented error for 'matrix_profile' (DESIGN.md section 7).
+// ------------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(MatrixProfilePeriodResultFFI) == 64 && offsetof(MatrixProfilePeriodResultFFI, n_motifs) == 16 &&
+              offsetof(MatrixProfilePeriodResultFFI, method) == 32, "MatrixProfilePeriodResultFFI layout");
+
+bool anofox_hip_matrix_profile_device(const double *y, size_t ld, const int32_t *lengths, size_t n_series, size_t t_rows, size_t subsequence_length,
+                                      size_t n_best, double *figures, double *profile, int32_t *profile_index, int32_t *status, void *stream,
+                                      AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!y || !lengths || !figures || !status) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    std::string text;
+    if (mprof_args_check(t_rows, &text) != MPROF_CHECK_OK) {
+        set_error(out_error, INVALID_INPUT, text);
+        return false;
+    }
+    if (!block_args_ok(ld, n_series, "n_series", t_rows, MPROF_MAX_ROWS, out_error)) return false;
+    if (!device_ready(out_error)) return false;
+    MatrixProfileArgs a{};
+    a.y = y; a.ld = ld; a.len = lengths; a.n_series = (int)n_series; a.t_rows = t_rows;
+    a.subsequence = mprof_arg(subsequence_length); a.n_best = mprof_arg(n_best);
+    a.out_fp = figures; a.out_profile = profile; a.out_index = profile_index; a.status = status;
+    a.profile_rows = (int)mprof_profile_len((int64_t)t_rows, a.subsequence);
+    a.work_stride = matrix_profile_work_stride(t_rows, a.subsequence);
+    a.work_blocks = matrix_profile_work_blocks(a.work_stride, (int)n_series);
+    hipStream_t st = (hipStream_t)stream;
+    Scratch scratch;
+    const bool ok = launch_and_wait("matrix_profile", st, out_error, [&] {
+        if (a.work_stride && a.work_blocks > 0) a.work = scratch.get<double>(a.work_stride * (size_t)a.work_blocks);
+        launch_matrix_profile(a, st);
+    });
+    if (ok) scratch.settled();
+    return ok;
+}
+
+bool anofox_hip_matrix_profile_batch(const double *const *values, const size_t *lengths, size_t n_series, size_t subsequence_length, size_t n_best,
+                                     double *out_figures, double *out_profile, int32_t *out_profile_index, AnofoxError *out_errors,
+                                     AnofoxError *out_batch_error)
+{
+    clear_error(out_batch_error);
+    if (n_series > 0 && (!values || !lengths || !out_figures)) {
+        set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    std::string text;
+    size_t longest = 0;
+    const MProfCheck rows = mprof_batch_rows(lengths, n_series, &longest, &text);
+    if (rows != MPROF_CHECK_OK) {
+        if (rows == MPROF_CHECK_NULL) set_error(out_batch_error, NULL_POINTER, "Null pointer argument");
+        else set_error(out_batch_error, INVALID_INPUT, text);
+        return false;
+    }
+    BlockShape shape;
+    if (!series_shape(values, nullptr, lengths, n_series, MPROF_MAX_ROWS, &shape, out_batch_error)) return false;
+    if (n_series == 0) return true;
+    const size_t ld = shape.ld, P = (size_t)mprof_profile_len((int64_t)longest, mprof_arg(subsequence_length));
+    std::vector<double> fp, prof;
+    std::vector<int32_t> status, index;
+    Scratch scratch;
+    try {
+        if (!device_ready(out_batch_error)) return false;
+        const PSearchBlock b = psearch_upload(scratch, shape, values, lengths, n_series);
+        double *d_fp = scratch.get<double>(MPROF_N_FIG * ld);
+        double *d_prof = out_profile && P ? scratch.get<double>(P * ld) : nullptr;
+        int32_t *d_idx = out_profile_index && P ? scratch.get<int32_t>(P * ld) : nullptr;
+        if (!anofox_hip_matrix_profile_device(b.d_y, ld, b.d_len, n_series, b.T, subsequence_length, n_best, d_fp, d_prof, d_idx, b.d_st, nullptr,
+                                              out_batch_error))
+            return false;
+        fp = psearch_fetch(d_fp, MPROF_N_FIG * ld);
+        if (d_prof) prof = psearch_fetch(d_prof, P * ld);
+        if (d_idx) index = psearch_fetch(d_idx, P * ld);
+        status = psearch_fetch(b.d_st, n_series);
+        scratch.settled();
+    } catch (const HipFail &f) {
+        report_hip_failure(out_batch_error, f);
+        return false;
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t s = 0; s < n_series; s++) {
+        const bool ok = status[s] == MPROF_OK;
+        if (out_errors) clear_error(&out_errors[s]);
+        if (!ok && out_errors) set_error(&out_errors[s], COMPUTATION_ERROR, mprof_series_error(status[s], lengths[s], mprof_arg(subsequence_length)));
+        for (size_t j = 0; j < (size_t)MPROF_N_FIG; j++) out_figures[j * n_series + s] = ok ? fp[j * ld + s] : nan;
+        if (out_profile)
+            for (size_t j = 0; j < P; j++) out_profile[j * n_series + s] = ok ? prof[j * ld + s] : nan;
+        if (out_profile_index)
+            for (size_t j = 0; j < P; j++) out_profile_index[j * n_series + s] = ok ? index[j * ld + s] : -1;
+    }
+    return true;
+}
+
+bool anofox_ts_matrix_profile_period(const double *values, size_t length, size_t subsequence_length, size_t n_best,
+                                     MatrixProfilePeriodResultFFI *out_result, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!values || !out_result) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    AnofoxError serr, berr;
+    const double *v[1] = {values};
+    const size_t len[1] = {length};
+    double fig[MPROF_N_FIG];
+    if (!anofox_hip_matrix_profile_batch(v, len, 1, subsequence_length, n_best, fig, nullptr, nullptr, &serr, &berr)) {
+        if (out_error) *out_error = berr;
+        return false;
+    }
+    if (serr.code != SUCCESS) { if (out_error) *out_error = serr; return false; }
+    out_result->period = fig[0]; out_result->confidence = fig[1]; out_result->n_motifs = (size_t)fig[2]; out_result->subsequence_length = (size_t)fig[3];
+    copy_method(out_result->method, "matrix_profile");
     return true;
 }
 

@@ -351,6 +351,33 @@ size_t stl_period_work_stride(size_t t_rows);
 int stl_period_work_blocks(size_t work_stride, int n_series);
 void launch_stl_period(const StlPeriodArgs &, hipStream_t);
 
+// Matrix profile period (periods.rs matrix_profile_period :1134-1244; matrix_profile.hip).  Bit for bit the source's arithmetic; among
+// lags of equal best count the smallest wins (the source leaves that to its hash order).
+constexpr size_t MPROF_MAX_ROWS = 65536;     // t_rows of a call
+constexpr int MPROF_MIN_ROWS = 32;           // a shorter series fails alone (MPROF_TOO_SHORT)
+constexpr int MPROF_MAX_M = 2048;            // a series whose effective subsequence length is larger fails alone (MPROF_OVER_LIMIT)
+constexpr int MPROF_TILE = 64;               // rows and columns of a tile of pairs
+constexpr int MPROF_KCHUNK = 16;             // steps of k whose z values a tile holds in LDS at a time
+constexpr int MPROF_HOME_DOUBLES = 5504;     // the LDS a series, its profile and its index may take (43 KiB); else they live in the workspace
+constexpr int MPROF_N_FIG = 6;               // period, confidence, n_motifs, subsequence_length, best_count, n_tied
+constexpr int32_t MPROF_OK = 0, MPROF_TOO_SHORT = 1, MPROF_OVER_LIMIT = 2;
+constexpr size_t MPROF_WORK_BYTES = (size_t)256 << 20;      // upper bound of the workspace, whatever n_series is (one slice if a slice is larger)
+struct MatrixProfileArgs {
+    const double *y; size_t ld; const int32_t *len; int n_series;
+    size_t t_rows;               // a longer series is cut to it
+    int64_t subsequence;         // 0: n / 10 of each series
+    int64_t n_best;              // the exclusion zone (the reference's wrapper passes n_best on as that); 0: m / 4
+    double *out_fp;              // [MPROF_N_FIG x ld]
+    double *out_profile;         // [profile_rows x ld] or null: the nearest-neighbour distances, NaN beyond a series' P
+    int32_t *out_index;          // [profile_rows x ld] or null: their indices, -1 beyond a series' P
+    int profile_rows;            // P of a series of t_rows rows
+    int32_t *status;             // [n_series] MPROF_OK / _TOO_SHORT / _OVER_LIMIT (the figures are not written unless OK)
+    double *work; size_t work_stride; int work_blocks;     // means and stds, and what does not fit in LDS: [work_blocks x work_stride]
+};
+size_t matrix_profile_work_stride(size_t t_rows, int64_t subsequence);      // doubles per workspace slice
+int matrix_profile_work_blocks(size_t work_stride, int n_series);
+void launch_matrix_profile(const MatrixProfileArgs &, hipStream_t);
+
 // Forecast accuracy metrics per group (metrics.rs mae .. coverage; metrics.hip)
 constexpr int METRICS_N_FIG = 12;        // rows of `figures`, in this order:
 enum { MF_MAE = 0, MF_MSE, MF_RMSE, MF_MAPE, MF_SMAPE, MF_R2, MF_BIAS, MF_RMAE, MF_MASE, MF_QUANTILE_LOSS, MF_MQLOSS, MF_COVERAGE };

@@ -307,6 +307,45 @@ def stl_period_block(y: torch.Tensor, lengths: torch.Tensor, min_period: int = 0
             "candidates": cands, "candidate_strengths": strengths, "status": status}
 
 
+def matrix_profile_block(y: torch.Tensor, lengths: torch.Tensor, subsequence_length: int = 0, n_best: int = 0, *, profile: bool = True,
+                         n_series: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_matrix_profile_device on torch tensors: the reference's matrix_profile_period for every series of a block, and the
+    profile itself, nothing read back.
+
+    y [t_rows, ld] fp64 (t_rows <= 65,536), lengths int32 [>= n_series], on one HIP device, contiguous.  subsequence_length 0: n / 10
+    of each series (at least 4, at most n / 4); n_best is the exclusion zone, 0: m / 4 (at least 1).
+
+    Returns device tensors: {"period", "confidence", "n_motifs", "subsequence_length", "best_count", "n_tied" (fp64 [ld] views of
+    "figures" [6, ld]; among lags of equal best count the smallest is the period), "status" int32 [ld]: lib.MPROF_OK, _TOO_SHORT
+    (fewer than 32 rows) or _OVER_LIMIT (subsequence length above 2,048), and with profile=True "profile" fp64 and "profile_index"
+    int32 [lib.matrix_profile_rows(t_rows, subsequence_length), ld]: every subsequence's distance to its nearest neighbour outside
+    the exclusion zone and that neighbour's index, NaN / -1 beyond a series' own profile}.  Columns s >= n_series and failed series
+    hold NaN / -1; status is -1 in columns s >= n_series."""
+    L = _lib.load()
+    t_rows, ld, n = _period_search_block(y, lengths, n_series)
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    rows = _lib.matrix_profile_rows(t_rows, int(subsequence_length or 0))
+    figures = torch.full((len(_lib.MATRIX_PROFILE_FIGURES), ld), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.full((ld,), -1, dtype=torch.int32, device=dev)
+    prof = torch.full((rows, ld), float("nan"), dtype=torch.float64, device=dev) if profile else None
+    index = torch.full((rows, ld), -1, dtype=torch.int32, device=dev) if profile else None
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_matrix_profile_device(y.data_ptr(), ld, lengths.data_ptr(), n, t_rows, int(subsequence_length or 0), int(n_best or 0),
+                                            figures.data_ptr(), prof.data_ptr() if profile and rows else None,
+                                            index.data_ptr() if profile and rows else None, status.data_ptr(), C.c_void_p(st.cuda_stream),
+                                            C.byref(err))
+    if not ok:
+        raise RuntimeError(f"anofox_hip_matrix_profile_device failed: [{err.code}] {err.message.decode()}")
+    out = {name: figures[k] for k, name in enumerate(_lib.MATRIX_PROFILE_FIGURES)}
+    out.update({"figures": figures, "status": status})
+    if profile:
+        out.update({"profile": prof, "profile_index": index})
+    return out
+
+
 def conformal_block(forecast: torch.Tensor, alphas, *, residual: torch.Tensor | None = None, actual: torch.Tensor | None = None,
                     calibration_forecast: torch.Tensor | None = None, valid: torch.Tensor | None = None,
                     lengths: torch.Tensor | None = None, n_groups: int | None = None, method: str = "symmetric",

@@ -244,6 +244,29 @@ def stl_candidate_count(n_candidates=None) -> int:
     return max(int(n_candidates) if n_candidates else 20, 5)
 
 
+class MatrixProfilePeriodResultFFI(C.Structure):
+    _fields_ = [("period", C.c_double), ("confidence", C.c_double), ("n_motifs", C.c_size_t), ("subsequence_length", C.c_size_t),
+                ("method", C.c_char * 32)]
+
+
+assert C.sizeof(MatrixProfilePeriodResultFFI) == 64
+# include/anofox_fcst_hip.h: the figure rows of anofox_hip_matrix_profile_*, their status codes and limits
+MATRIX_PROFILE_FIGURES = ("period", "confidence", "n_motifs", "subsequence_length", "best_count", "n_tied")
+MPROF_OK, MPROF_TOO_SHORT, MPROF_OVER_LIMIT = 0, 1, 2
+MPROF_MIN_ROWS, MPROF_MAX_M, MPROF_MAX_ROWS = 32, 2048, 65536
+
+
+def matrix_profile_subsequence(n, subsequence_length=None) -> int:
+    """The effective subsequence length of a series of n rows: min(max(subsequence_length or n / 10, 4), n / 4)."""
+    return min(max(int(subsequence_length) if subsequence_length else n // 10, 4), n // 4)
+
+
+def matrix_profile_rows(t_rows, subsequence_length=None) -> int:
+    """Rows of the profile outputs: the profile length n - m + 1 of a series of t_rows rows (0 below 32 rows); no shorter series
+    has a longer profile."""
+    return 0 if t_rows < MPROF_MIN_ROWS else t_rows - matrix_profile_subsequence(t_rows, subsequence_length) + 1
+
+
 # include/anofox_fcst_hip.h: bit k of the figure mask of anofox_hip_metrics_batch / _device and row k of their output
 METRIC_FIGURES = ("mae", "mse", "rmse", "mape", "smape", "r2", "bias", "rmae", "mase", "quantile_loss", "mqloss", "coverage")
 METRICS_MAX_LEVELS = 16
@@ -435,6 +458,7 @@ EXPORTED_SYMBOLS = [
     "anofox_free_flat_multi_period_result", "anofox_hip_periods_batch", "anofox_hip_periods_device",
     "anofox_ts_ssa_period", "anofox_ts_stl_period", "anofox_hip_ssa_period_batch", "anofox_hip_stl_period_batch",
     "anofox_hip_ssa_period_device", "anofox_hip_stl_period_device",
+    "anofox_ts_matrix_profile_period", "anofox_hip_matrix_profile_batch", "anofox_hip_matrix_profile_device",
     "anofox_ts_mae", "anofox_ts_mse", "anofox_ts_rmse", "anofox_ts_mape", "anofox_ts_smape", "anofox_ts_r2", "anofox_ts_bias",
     "anofox_ts_rmae", "anofox_ts_mase", "anofox_ts_quantile_loss", "anofox_ts_mqloss", "anofox_ts_coverage",
     "anofox_hip_metrics_batch", "anofox_hip_metrics_device",
@@ -692,6 +716,14 @@ def load():
     L.anofox_hip_stl_period_device.restype = C.c_bool
     L.anofox_hip_stl_period_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_ts_matrix_profile_period.restype = C.c_bool
+    L.anofox_ts_matrix_profile_period.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, P(MatrixProfilePeriodResultFFI), P(AnofoxError)]
+    L.anofox_hip_matrix_profile_batch.restype = C.c_bool
+    L.anofox_hip_matrix_profile_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_matrix_profile_device.restype = C.c_bool
+    L.anofox_hip_matrix_profile_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
     for name in ("mae", "mse", "rmse", "mape", "smape", "r2", "bias"):
         f = getattr(L, "anofox_ts_" + name)
         f.restype = C.c_bool

@@ -281,6 +281,36 @@ bool anofox_ts_stl_period(const double *values,
                           struct AnofoxError *out_error);
 
 /*
+ * Period detection by matrix profile (layout of the reference's anofox_fcst_ffi.h: MatrixProfilePeriodResultFFI, 64 bytes).
+ */
+typedef struct MatrixProfilePeriodResultFFI {
+    double period;            /* the most frequent lag between a motif and its nearest neighbour; NaN when there is no motif */
+    double confidence;        /* the share of the motifs that have this lag; 0.0 without motifs */
+    size_t n_motifs;
+    size_t subsequence_length;
+    char method[32];          /* "matrix_profile" */
+} MatrixProfilePeriodResultFFI;
+
+/*
+ * ONE series through the reference's matrix_profile_period (periods.rs) behind its FFI wrapper: an argument of zero means the
+ * source's default -- subsequence_length m = n / 10 (then at least 4, at most n / 4), exclusion zone m / 4 (at least 1).  The
+ * wrapper passes `n_best` on as the EXCLUSION ZONE; that is kept.  NULL `values` or `out_result`: NULL_POINTER "Null pointer
+ * argument".  COMPUTATION_ERROR: "Insufficient data: need at least 32 observations, got N", and an effective subsequence length
+ * above 2,048, naming that limit of this backend.  More than 65,536 observations: INVALID_INPUT naming the limit.  Runs on the GPU as
+ * a batch of one.  confidence, n_motifs and subsequence_length equal the source's arithmetic bit for bit (every distance its own
+ * sequential sum over k, no fused multiply-add, compared after the square root).  Where several lags share the highest count the
+ * source returns one of them by the iteration order of a hash map; here the SMALLEST such lag is returned, always one of the
+ * source's possible answers.  The method dispatch by name (anofox_ts_detect_periods_flat with "matrix_profile", "matrixprofile" or
+ * "mp") keeps its not-implemented error.
+ */
+bool anofox_ts_matrix_profile_period(const double *values,
+                                     size_t length,
+                                     size_t subsequence_length,
+                                     size_t n_best,
+                                     struct MatrixProfilePeriodResultFFI *out_result,
+                                     struct AnofoxError *out_error);
+
+/*
  * Result of the Bayesian online changepoint detection (layout of the reference's anofox_fcst_ffi.h).  The arrays are malloc()ed
  * by the callee and released by anofox_free_bocpd_result; changepoint_indices is NULL when no point is flagged.
  */
@@ -1238,6 +1268,55 @@ bool anofox_hip_stl_period_device(const double *y,
                                   int32_t *status,
                                   void *stream,
                                   struct AnofoxError *out_error);
+
+/*
+ * Matrix-profile period detection of `n_series` series with one parameter set, in one GPU pass (the arguments of the single entry;
+ * zero means the source's default, `n_best` is the exclusion zone).  Figure j of series i is at out_figures[j * n_series + i], fp64
+ * [6 x n_series]: period, confidence, n_motifs, subsequence_length, best_count (the count of the winning lag) and n_tied (how many
+ * lags share it; the smallest is the period).  Optional outputs (may be NULL): out_profile fp64 and out_profile_index int32, both
+ * [P_max x n_series] with P_max the profile length n - m + 1 of the LONGEST series of the call (0 rows when that one has fewer than
+ * 32 observations): the distance of every subsequence to its nearest neighbour outside the exclusion zone (+inf where it has none)
+ * and that neighbour's index (the smallest among equal distances; 0 where there is none, as in the source), NaN / -1 beyond a
+ * series' own profile and for a failed series.  A series that is too short or whose subsequence length exceeds 2,048 fails alone:
+ * out_errors[i] (may be NULL) gets the single entry's COMPUTATION_ERROR and its figures are NaN.  A series above 65,536 rows:
+ * INVALID_INPUT naming the limit, for the whole call.  Non-finite values get no status: a NaN distance never updates a profile
+ * entry, and a profile without a finite value gives NaN / 0.0 / 0.  The return value is false only for batch-level failures, also
+ * reported through `out_batch_error`.  Runs on the calling thread's current device (anofox_hip_set_devices does not shard it).
+ */
+bool anofox_hip_matrix_profile_batch(const double *const *values,
+                                     const size_t *lengths,
+                                     size_t n_series,
+                                     size_t subsequence_length,
+                                     size_t n_best,
+                                     double *out_figures,
+                                     double *out_profile,
+                                     int32_t *out_profile_index,
+                                     struct AnofoxError *out_errors,
+                                     struct AnofoxError *out_batch_error);
+
+/*
+ * The same on a device-resident time-major block: y[t * ld + s] (fp64, t < t_rows <= 65,536), lengths[n_series] (int32; a length
+ * above t_rows is cut to it) and the outputs are device pointers with row stride ld (figure j of series s at j * ld + s).  profile
+ * and profile_index may be NULL; they have P_max rows, the profile length of a series of t_rows rows.  status is int32 [n_series]:
+ * 0 done, 1 too short, 2 subsequence length above 2,048; the figures are not written for a series whose status is not 0, its
+ * profile rows are NaN / -1.  One workgroup per series, persistent over the batch.  The series, its profile and its index live in
+ * LDS up to 2,341 rows at the default subsequence length (2,203 with a forced length of 4) and otherwise in a workspace of at most
+ * 256 MiB whatever n_series is.  The same bits on every run and through every entry.  Runs on `stream` (NULL: the null stream) on
+ * the calling thread's current device and returns after it has finished.
+ */
+bool anofox_hip_matrix_profile_device(const double *y,
+                                      size_t ld,
+                                      const int32_t *lengths,
+                                      size_t n_series,
+                                      size_t t_rows,
+                                      size_t subsequence_length,
+                                      size_t n_best,
+                                      double *figures,
+                                      double *profile,
+                                      int32_t *profile_index,
+                                      int32_t *status,
+                                      void *stream,
+                                      struct AnofoxError *out_error);
 
 /*
  * Forecast accuracy metrics, the reference's twelve functions of metrics.rs behind their FFI wrappers, with its signatures.  Each
