@@ -308,7 +308,7 @@ __global__ __launch_bounds__(NM_BLOCK) void ets_final_kernel(const FitArgs a)
     fin.var_out = want_sd ? &var : nullptr;
     fin.mean = (want_sd && active) ? a.mean[s] : 0.0;
     if (inspect) {
-        fin.fitted = a.insp_fitted + (valid ? s : 0); fin.fitted_ld = a.ld;
+        fin.fitted = a.insp_fitted ? a.insp_fitted + (valid ? s : 0) : nullptr; fin.fitted_ld = a.ld;      // (null: the caller wants no fitted values)
         fin.states = a.insp_states + (valid ? s : 0); fin.states_ld = a.ld;
         fin.sse_out = &sse;
         fin.h = 0;                                   // the forecasts of the run stay as they are

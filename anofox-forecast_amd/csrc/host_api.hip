@@ -44,6 +44,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_reconcile_mint.hpp" // the host-only checks and workspace sizes of the MinT-shrink entries
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
+#include "host_ets_paths_plan.hpp" // the host-only checks of the model-path entries (options, period and ring, pool), each naming its limit
 #include "host_path_scores_plan.hpp" // the host-only checks of the path-score entries, the energy workspace and a plan's column ranges
 #include "host_scaled_scores_plan.hpp" // the host-only checks of the scaled-score entries and the ranges of the WRMSSE chain
 #include "host_period_search.hpp" // the host-only logic of the SSA / STL period entries (defaults, window, candidate list, checks naming their limits)
@@ -2262,6 +2263,64 @@ void anofox_free_forecast_result(ForecastResult *r)
     if (r) free_result_arrays(*r);
 }
 
+namespace {
+
+// a batch whose fit state the inspection passes can re-read: AutoETS or ETS(spec), run, with its final-kernel arguments kept
+bool inspectable_ets(const AnofoxHipBatch *b)
+{
+    return (b->plan.model == M_AutoETS || (b->plan.model == M_ETS && b->plan.ets_spec_id >= 0)) && b->insp_ok;
+}
+
+// The inspection passes of an ETS batch, enqueued on the stream of its last run: d_info [8 x ld], d_states [(2 + max(m, 1)) x ld] and
+// d_fit [max(t_max, 1) x ld] (may be null) are filled with NaN, then the final kernel of every spec writes the series it was selected
+// for.  Nothing is copied and nothing is waited for.
+void inspect_ets_passes(AnofoxHipBatch *b, double *d_info, double *d_states, double *d_fit)
+{
+    for (size_t s = 1; s < b->n; s++)
+        if (b->h_period[s] != b->h_period[0]) throw HipFail{"inspection needs one seasonal period for the whole batch"};
+    const size_t ld = b->ld, T = std::max<size_t>(b->t_max, 1), rows = (size_t)(2 + std::max(b->insp_m, 1));
+    hipStream_t st = b->last_stream;
+    const double nan = std::nan("");
+    (void)hipGetLastError();
+    if (d_fit) launch_fill_f64(d_fit, T * ld, nan, st);
+    launch_fill_f64(d_states, rows * ld, nan, st);
+    launch_fill_f64(d_info, 8 * ld, nan, st);
+    LAUNCHCHECK("inspection fill");
+    for (size_t oi = 0; oi < b->insp_args.size(); oi++) {
+        FitArgs a = b->insp_args[oi];
+        a.insp_sel = b->d_model_code;
+        a.insp_code = b->plan.model == M_AutoETS ? 100 + b->insp_spec[oi] : 0;
+        a.insp_fitted = d_fit; a.insp_states = d_states; a.insp_info = d_info;
+        b->insp_fns[oi].final(a, st);
+    }
+}
+
+} // namespace
+
+bool anofox_hip_batch_inspect_device(AnofoxHipBatch *b, double *d_info, double *d_states, double *d_fitted, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!b || !d_info || !d_states) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!b->ran) { set_error(out_error, INVALID_INPUT, "Invalid input: the batch has not been run"); return false; }
+    if (!inspectable_ets(b)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: the device inspection needs an AutoETS or ETS(spec) batch");
+        return false;
+    }
+    DeviceGuard guard(b->dev);
+    try {
+        b->quiesced = false;
+        inspect_ets_passes(b, d_info, d_states, d_fitted);
+        HIPCHECK(hipStreamSynchronize(b->last_stream));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    } catch (const std::exception &e) {
+        set_error(out_error, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
+        return false;
+    }
+    return true;
+}
+
 bool anofox_hip_batch_inspect(AnofoxHipBatch *b, AnofoxHipInspection *out, double *fitted, double *seasonal, size_t seasonal_stride,
                               AnofoxError *out_error)
 {
@@ -2281,31 +2340,18 @@ bool anofox_hip_batch_inspect(AnofoxHipBatch *b, AnofoxHipInspection *out, doubl
             o.alpha = o.beta = o.gamma = o.phi = o.aic = o.aicc = o.bic = o.sse = o.level = o.trend = std::nan("");
         }
         if (fitted) for (size_t i = 0; i < n * T; i++) fitted[i] = std::nan("");
-        const bool ets = (b->plan.model == M_AutoETS || (b->plan.model == M_ETS && b->plan.ets_spec_id >= 0)) && b->insp_ok;
-        if (ets) {
-            for (size_t s = 1; s < n; s++)
-                if (b->h_period[s] != b->h_period[0]) throw HipFail{"inspection needs one seasonal period for the whole batch"};
+        if (inspectable_ets(b)) {
             const int m = b->insp_m;
             const size_t rows = (size_t)(2 + std::max(m, 1));
-            double *d_fit = dalloc<double>(T * ld), *d_states = dalloc<double>(rows * ld), *d_info = dalloc<double>(8 * ld);
-            std::vector<double> nanv(std::max(T, rows) * ld, std::nan(""));
-            HIPCHECK(hipMemcpy(d_fit, nanv.data(), T * ld * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(d_states, nanv.data(), rows * ld * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHECK(hipMemcpy(d_info, nanv.data(), 8 * ld * sizeof(double), hipMemcpyHostToDevice));
-            hipStream_t st = b->last_stream;
-            for (size_t oi = 0; oi < b->insp_args.size(); oi++) {
-                FitArgs a = b->insp_args[oi];
-                a.insp_sel = b->d_model_code;
-                a.insp_code = b->plan.model == M_AutoETS ? 100 + b->insp_spec[oi] : 0;
-                a.insp_fitted = d_fit; a.insp_states = d_states; a.insp_info = d_info;
-                b->insp_fns[oi].final(a, st);
-            }
-            HIPCHECK(hipStreamSynchronize(st));
+            Scratch scratch;
+            double *d_fit = fitted ? scratch.get<double>(T * ld) : nullptr, *d_states = scratch.get<double>(rows * ld), *d_info = scratch.get<double>(8 * ld);
+            inspect_ets_passes(b, d_info, d_states, d_fit);
+            HIPCHECK(hipStreamSynchronize(b->last_stream));
+            scratch.settled();
             std::vector<double> info(8 * ld), states(rows * ld), fit;
             HIPCHECK(hipMemcpy(info.data(), d_info, 8 * ld * sizeof(double), hipMemcpyDeviceToHost));
             HIPCHECK(hipMemcpy(states.data(), d_states, rows * ld * sizeof(double), hipMemcpyDeviceToHost));
             if (fitted) { fit.resize(T * ld); HIPCHECK(hipMemcpy(fit.data(), d_fit, T * ld * sizeof(double), hipMemcpyDeviceToHost)); }
-            dev_free(d_fit, true); dev_free(d_states, true); dev_free(d_info, true);       // the stream was synchronised above
             for (size_t s = 0; s < n; s++) {
                 AnofoxHipInspection &o = out[s];
                 o.alpha = info[0 * ld + s]; o.beta = info[1 * ld + s]; o.gamma = info[2 * ld + s]; o.phi = info[3 * ld + s];
@@ -8007,6 +8053,170 @@ bool anofox_hip_paths_batch(const double *points, const double *const *pools, co
         scratch.settled();                                                 // (either way the device has been waited for)
     } catch (const HipFail &f) {
         report_hip_failure(out_error, f);
+        return false;
+    }
+    return ok;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Sample paths simulated from the fitted ETS models (DESIGN.md section 3 "Model paths"; ets_paths.hip, host_ets_paths_plan.hpp)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+bool ets_paths_options_ok(const AnofoxHipEtsPathsOptions *o, size_t struct_size, AnofoxError *err)
+{
+    std::string message;
+    // (the fields are read only once the size has been found right)
+    const bool readable = o && struct_size == sizeof(AnofoxHipEtsPathsOptions);
+    return paths_plan_report(ets_paths_options_check(o != nullptr, struct_size, sizeof(AnofoxHipEtsPathsOptions), readable ? o->innovations : 0,
+                                                     readable ? o->joint : 0, &message), message, err);
+}
+
+} // namespace
+
+extern "C" {
+
+static_assert(sizeof(AnofoxHipEtsPathsOptions) == 24 && offsetof(AnofoxHipEtsPathsOptions, seed) == 16, "AnofoxHipEtsPathsOptions layout");
+static_assert(ETS_PATHS_PLAN_MAX_PERIOD == (size_t)ETS_PATHS_MAX_PERIOD && ETS_PATHS_PLAN_MAX_RING == (size_t)ETS_PATHS_MAX_RING &&
+              ETS_PATHS_MAX_PERIOD == ANOFOX_HIP_ETS_PATHS_MAX_PERIOD && ETS_PATHS_MAX_RING == ANOFOX_HIP_ETS_PATHS_MAX_RING &&
+              ETS_PATHS_GAUSSIAN == ANOFOX_ETS_PATHS_GAUSSIAN && ETS_PATHS_BOOTSTRAP == ANOFOX_ETS_PATHS_BOOTSTRAP &&
+              ETS_PATHS_NO_MODEL == ANOFOX_ETS_PATHS_NO_MODEL, "the limits and codes of the model-path entries");
+
+bool anofox_hip_ets_innovations_device(const double *y, const double *fitted, size_t ld, const int32_t *lengths, const int32_t *spec,
+                                       size_t n_series, size_t t_rows, double *pool, int32_t *pool_lengths, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!y || !fitted || !lengths || !spec || !pool || !pool_lengths) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_block_check(ld, n_series, "ld", "n_series", &message), message, out_error)) return false;
+    if (t_rows > (size_t)INT32_MAX) { set_error(out_error, INVALID_INPUT, "Invalid input: t_rows exceeds the limit of 2^31 - 1"); return false; }
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    try {
+        (void)hipGetLastError();
+        launch_ets_innovations(y, fitted, ld, lengths, spec, (int)n_series, (int)t_rows, pool, pool_lengths, (hipStream_t)stream);
+        LAUNCHCHECK("ets innovations");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_ets_paths_device(const int32_t *spec, const double *info, const double *states, size_t ld, size_t m, const int32_t *lengths,
+                                 const double *pool, size_t pool_stride_s, size_t pool_stride_t, const int32_t *pool_lengths, size_t pool_rows,
+                                 size_t n_series, size_t horizon, size_t n_paths, const AnofoxHipEtsPathsOptions *options, size_t struct_size,
+                                 double *paths_out, size_t ld_out, int32_t *status, int32_t *n_broken, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!ets_paths_options_ok(options, struct_size, out_error)) return false;
+    if (!spec || !info || !states || !lengths || !paths_out || !status || !n_broken) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld_out, n_series, "ld_out", "n_series", &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld, n_series, "ld", "n_series", &message), message, out_error)) return false;
+    if (!paths_plan_report(ets_paths_period_check(m, horizon, &message), message, out_error)) return false;
+    if (!paths_plan_report(ets_paths_pool_check(options->innovations, pool != nullptr, pool_rows, &message), message, out_error)) return false;
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    const bool boot = options->innovations == ETS_PATHS_BOOTSTRAP;
+    EtsPathsArgs a{};
+    a.spec = spec; a.info = info; a.states = states; a.ld = ld; a.m = (int)m; a.lengths = lengths;
+    a.innovations = options->innovations;
+    a.pool = boot ? pool : nullptr; a.pool_stride_s = pool_stride_s; a.pool_stride_t = pool_stride_t;
+    a.pool_len = boot ? pool_lengths : nullptr; a.pool_rows = boot ? (int)pool_rows : 0; a.joint = boot ? options->joint : 0;
+    a.n_series = (int)n_series; a.horizon = (int)horizon; a.n_paths = (int)n_paths;
+    a.key0 = (uint32_t)(options->seed & 0xffffffffull); a.key1 = (uint32_t)(options->seed >> 32);
+    a.paths = paths_out; a.ld_out = ld_out; a.status = status; a.n_broken = n_broken;
+    try {
+        (void)hipGetLastError();
+        launch_ets_paths(a, (hipStream_t)stream);
+        LAUNCHCHECK("ets paths");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_batch_ets_paths(AnofoxHipBatch *b, const AnofoxHipEtsPathsOptions *options, size_t struct_size, size_t n_paths, const double *levels,
+                                size_t n_levels, size_t ld, double *out_quantiles, int32_t *out_status, int32_t *out_series_status,
+                                int32_t *out_n_broken, double *out_paths, size_t *out_ld, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!ets_paths_options_ok(options, struct_size, out_error)) return false;
+    if (!paths_plan_report(paths_rows_check(1, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_levels_check(levels, n_levels, &message), message, out_error)) return false;
+    if (!b) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!b->ran) { set_error(out_error, INVALID_INPUT, "Invalid input: the batch has not been run"); return false; }
+    if (!inspectable_ets(b)) {
+        set_error(out_error, INVALID_INPUT, "Invalid input: model paths need an AutoETS or ETS(spec) batch");
+        return false;
+    }
+    const size_t n = b->n, horizon = (size_t)std::max(b->h, 0), m = (size_t)std::max(b->insp_m, 1), need_ld = b->ld;
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(ets_paths_period_check(m, horizon, &message), message, out_error)) return false;
+    if (out_ld) *out_ld = need_ld;
+    if (!out_quantiles) return true;
+    if (ld != need_ld) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is not what the sizing call returns"); return false; }
+    if (!out_status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (n == 0) return true;
+    DeviceGuard guard(b->dev);
+
+    const bool boot = options->innovations == ETS_PATHS_BOOTSTRAP;
+    const size_t T = std::max<size_t>(b->t_max, 1), rows = n_paths * horizon, cells = rows * need_ld, q_cells = n_levels * n * horizon;
+    Scratch scratch;
+    bool ok = true;
+    try {
+        double *d_paths = nullptr;
+        try {
+            d_paths = scratch.get<double>(cells);
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the path block of " + std::to_string(rows) + " x " + std::to_string(need_ld) +
+                      " values needs " + std::to_string(cells * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            double *d_info = scratch.get<double>(8 * need_ld), *d_states = scratch.get<double>((2 + m) * need_ld);
+            double *d_fit = boot ? scratch.get<double>(T * need_ld) : nullptr, *d_pool = boot ? scratch.get<double>(T * need_ld) : nullptr;
+            int32_t *d_spec = scratch.get<int32_t>(need_ld), *d_plen = scratch.get<int32_t>(need_ld), *d_status = scratch.get<int32_t>(need_ld);
+            int32_t *d_broken = scratch.get<int32_t>(need_ld), *d_qstatus = scratch.get<int32_t>(need_ld);
+            double *d_q = scratch.get<double>(q_cells);
+            b->quiesced = false;
+            inspect_ets_passes(b, d_info, d_states, d_fit);
+            HIPCHECK(hipStreamSynchronize(b->last_stream));
+            (void)hipGetLastError();
+            // (ETS(spec): the spec that was fitted -- a seasonal one without a usable period ran as its non-seasonal sibling)
+            launch_ets_spec_of(b->d_model_code, b->d_status, b->plan.model == M_AutoETS ? 1 : 0, b->insp_spec.empty() ? -1 : b->insp_spec[0], (int)n,
+                               d_spec, nullptr);
+            LAUNCHCHECK("ets spec");
+            HIPCHECK(hipMemset(d_paths, 0, cells * sizeof(double)));            // the padding columns
+            if (boot)
+                ok = anofox_hip_ets_innovations_device(b->d_y, d_fit, need_ld, b->d_len, d_spec, n, T, d_pool, d_plen, nullptr, out_error);
+            if (ok)
+                ok = anofox_hip_ets_paths_device(d_spec, d_info, d_states, need_ld, m, b->d_len, d_pool, 1, need_ld, boot ? d_plen : nullptr,
+                                                 boot ? T : 0, n, horizon, n_paths, options, struct_size, d_paths, need_ld, d_status, d_broken,
+                                                 nullptr, out_error);
+            if (ok)
+                ok = anofox_hip_path_quantiles_device(d_paths, need_ld, n, horizon, n_paths, levels, n_levels, d_q, d_qstatus, nullptr, out_error);
+            if (ok) {
+                HIPCHECK(hipMemcpy(out_quantiles, d_q, q_cells * sizeof(double), hipMemcpyDeviceToHost));      // waits for the null stream
+                HIPCHECK(hipMemcpy(out_status, d_qstatus, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_series_status) HIPCHECK(hipMemcpy(out_series_status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_n_broken) HIPCHECK(hipMemcpy(out_n_broken, d_broken, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_paths) HIPCHECK(hipMemcpy(out_paths, d_paths, cells * sizeof(double), hipMemcpyDeviceToHost));
+            } else HIPCHECK(hipDeviceSynchronize());
+        }
+        scratch.settled();                                                 // (either way the device has been waited for)
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    } catch (const std::exception &e) {
+        set_error(out_error, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
         return false;
     }
     return ok;

@@ -835,6 +835,37 @@ struct PathQuantilesArgs {
 void launch_paths(const PathsArgs &, hipStream_t);                     // the statuses, then the paths
 void launch_path_quantiles(const PathQuantilesArgs &, hipStream_t);
 
+// Sample paths simulated from fitted ETS models (DESIGN.md section 3 "Model paths"; ets_paths.hip).  `info` [8 x ld] and `states`
+// [(2 + max(m, 1)) x ld] are the blocks of the inspection pass (FitArgs::insp_info / insp_states); the pool is addressed as PathsArgs'.
+enum { ETS_PATHS_GAUSSIAN = 0, ETS_PATHS_BOOTSTRAP = 1 };
+constexpr int32_t ETS_PATHS_NO_MODEL = 4;              // beside PATHS_OK / _EMPTY / _NAN / _RAGGED
+constexpr int ETS_PATHS_MAX_PERIOD = 2048;
+constexpr int ETS_PATHS_MAX_RING = 128;                // R = min(m, horizon): 64 lanes x R x 8 bytes of LDS per wave within 64 KiB
+struct EtsPathsArgs {
+    const int32_t *spec;                         // [n_series] error * 15 + trend * 3 + season
+    const double *info, *states; size_t ld;      // rows alpha, beta, gamma, phi, -, -, -, sse; rows level, growth, seasonal state of phase j
+    int m;                                       // the batch's seasonal period
+    const int32_t *lengths;                      // [n_series] observations: step k has phase (n + k) % m
+    int innovations;                             // ETS_PATHS_*
+    const double *pool; size_t pool_stride_s, pool_stride_t;
+    const int32_t *pool_len;
+    int pool_rows, joint;
+    int n_series, horizon, n_paths;
+    uint32_t key0, key1;
+    double *paths; size_t ld_out;                // [n_paths * horizon x ld_out], row p * horizon + k
+    int32_t *status, *n_broken;                  // [n_series]
+    int path_groups, ring, waves;                // set by launch_ets_paths: groups of `waves` paths per tile, R, waves per workgroup
+};
+int ets_paths_waves(int ring);                                              // waves per workgroup of the simulation kernel at R = ring
+void launch_ets_paths(const EtsPathsArgs &, hipStream_t);                   // the statuses, the paths, then n_broken
+// pool[t * ld + s] = y - fitted (additive error) or (y - fitted) / fitted (multiplicative) for t < lengths[s]; pool_len[s] = lengths[s]
+// (0 for a spec that is none of the project's)
+void launch_ets_innovations(const double *y, const double *fitted, size_t ld, const int32_t *lengths, const int32_t *spec, int n_series,
+                            int t_rows, double *pool, int32_t *pool_len, hipStream_t);
+// spec[s] = status[s] == 0 ? (auto_ets ? model_code[s] - 100 : explicit_spec) : -1
+void launch_ets_spec_of(const int32_t *model_code, const int32_t *status, int auto_ets, int explicit_spec, int n_series, int32_t *spec, hipStream_t);
+void launch_fill_f64(double *p, size_t n, double value, hipStream_t);
+
 // Scores of a block of sample paths (DESIGN.md section 3 "Path scores"; path_scores.hip).  Element (column c, step k) of `actual` is
 // at c * actual_stride_c + k * actual_stride_k; a NaN there drops the step.
 constexpr int32_t PATH_SCORES_OK = 0, PATH_SCORES_NO_ACTUAL = 1, PATH_SCORES_NAN = 2;

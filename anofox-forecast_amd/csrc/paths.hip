@@ -30,6 +30,7 @@
 // No floating-point atomics, no atomic at all.
 #include "kernels.hpp"
 #include "det_math.hpp"
+#include "philox.hpp"
 #include "wave_sort.hpp"
 
 namespace anofox {
@@ -39,25 +40,6 @@ namespace {
 constexpr int PT_SLICES = 4;                              // row slices of the status kernel
 constexpr int PQ_MAX_WAVES = 16;                          // columns (wavefronts) per workgroup of the quantile kernel
 constexpr size_t PQ_LDS_BYTES = 64 * 1024;               // dynamic LDS a workgroup may ask for without raising the limit
-
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-// Philox4x32-10: ten rounds, the key bumped between them
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-        const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += PHILOX_W0;
-        k1 += PHILOX_W1;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // the rows of series s' pool that the draws index: pool_len cut to [0, pool_rows]
 __device__ __forceinline__ int pt_length(const PathsArgs &a, int s)

@@ -746,6 +746,116 @@ def path_quantiles_block(paths: torch.Tensor, levels, *, horizon: int, n_paths: 
     return {"quantiles": q, "status": status}
 
 
+def ets_innovations_block(y: torch.Tensor, fitted: torch.Tensor, lengths: torch.Tensor, spec: torch.Tensor, *, n_series: int | None = None,
+                          stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_ets_innovations_device on torch tensors: the in-sample innovations of a fitted block in the model's own terms.
+
+    y and fitted fp64 [T, ld] time-major (the series block of a DeviceBatch and the "fitted" block of its inspect_device), lengths and
+    spec int32 [>= n_series] on the device (spec: error * 15 + trend * 3 + season).  An additive error gives y - fitted, a
+    multiplicative one (y - fitted) / fitted.
+
+    Returns {"pool": fp64 [T, ld] time-major, NaN where nothing is written (past a series' length, the padding columns),
+    "pool_lengths": int32 [n_series], 0 for a spec that is none of the project's}: what ets_paths_block takes as its pool."""
+    L = _lib.load()
+    for t in (y, fitted):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 2
+    assert tuple(y.shape) == tuple(fitted.shape), (tuple(y.shape), tuple(fitted.shape))
+    T, ld = int(y.shape[0]), int(y.shape[1])
+    n = ld if n_series is None else int(n_series)
+    for t in (lengths, spec):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= n
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    pool = torch.full((T, ld), float("nan"), dtype=torch.float64, device=dev)
+    pool_lengths = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_ets_innovations_device(y.data_ptr(), fitted.data_ptr(), ld, lengths.data_ptr(), spec.data_ptr(), n, T, pool.data_ptr(),
+                                             pool_lengths.data_ptr(), C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_ets_innovations_device", err)
+    return {"pool": pool, "pool_lengths": pool_lengths}
+
+
+def ets_paths_block(batch=None, *, spec: torch.Tensor | None = None, info: torch.Tensor | None = None, states: torch.Tensor | None = None,
+                    lengths: torch.Tensor | None = None, m: int | None = None, horizon: int | None = None, n_paths: int = 1000,
+                    innovations: str | int = "gaussian", pool: torch.Tensor | None = None, pool_lengths: torch.Tensor | None = None,
+                    pool_series_major: bool = False, joint: bool = False, seed: int = 0, n_series: int | None = None,
+                    out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_ets_paths_device on torch tensors: sample paths simulated from fitted ETS models, no host copy.
+
+    Either a DeviceBatch that has been run (AutoETS or ETS(spec), one seasonal period): its inspect_device gives spec, info, states,
+    lengths, m and the horizon, and with innovations="bootstrap" and no `pool` the batch's own in-sample innovations
+    (ets_innovations_block) are the pool.  Or the tensors themselves: spec int32 [>= n], info fp64 [8, ld] (rows alpha, beta, gamma,
+    phi, -, -, -, sse), states fp64 [2 + max(m, 1), ld] (level, growth, seasonal state of phase j in row 2 + j), lengths int32 [>= n],
+    m and horizon.  innovations "gaussian" (sigma = sqrt(sse / n) per series) or "bootstrap" (pool fp64 [pool_rows, ld] time-major,
+    or [n, pool_rows] with pool_series_major=True; pool_lengths as for paths_block; joint=True: one pool row per path and step for
+    all series).  The draws are Philox4x32-10 on the counter (path, series, step): the same seed gives the same bits whatever the
+    launch shape.
+
+    Returns {"paths": fp64 [n_paths * h, ld_out] in the layout of paths_block, "status": int32 [n] (lib.PATHS_* and
+    lib.ETS_PATHS_NO_MODEL; the paths of a series whose status is not 0 are NaN), "n_broken": int32 [n], the paths of a series that
+    hold a NaN (a damped multiplicative trend whose growth left the positive numbers), "n_series", "horizon", "n_paths"}.
+    path_quantiles_block, path_scores_block and aggregate_block take the block as it lies."""
+    L = _lib.load()
+    if batch is not None:
+        insp = batch.inspect_device(fitted=(innovations in ("bootstrap", 1) and pool is None))
+        spec, info, states, lengths, m = insp["spec"], insp["info"], insp["states"], batch._len, insp["m"]
+        horizon = batch.h if horizon is None else horizon
+        n_series = batch.n if n_series is None else n_series
+        if insp["fitted"] is not None:
+            inn = ets_innovations_block(batch._y, insp["fitted"], lengths, spec, n_series=n_series, stream=stream)
+            pool, pool_lengths, pool_series_major = inn["pool"], inn["pool_lengths"], False
+    assert spec is not None and info is not None and states is not None and lengths is not None and m is not None and horizon is not None
+    m, h, n_paths = int(m), int(horizon), int(n_paths)
+    for t in (info, states):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 2
+    ld = int(info.shape[1])
+    assert int(info.shape[0]) >= 8 and int(states.shape[1]) == ld and int(states.shape[0]) >= 2 + max(m, 1)
+    n = ld if n_series is None else int(n_series)
+    assert 0 < n <= ld
+    for t in (spec, lengths):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= n
+    _paths_rows(n_paths, h)
+    dev = info.device
+    pool_rows, es, et = 0, 0, 0
+    if pool is not None:
+        assert pool.dtype == torch.float64 and pool.is_cuda and pool.is_contiguous() and pool.dim() == 2
+        if pool_series_major:
+            assert int(pool.shape[0]) >= n
+            pool_rows, es, et = int(pool.shape[1]), int(pool.shape[1]), 1
+        else:
+            assert int(pool.shape[1]) >= n
+            pool_rows, es, et = int(pool.shape[0]), 1, int(pool.shape[1])
+    if pool_lengths is not None:
+        assert pool_lengths.dtype == torch.int32 and pool_lengths.is_cuda and pool_lengths.is_contiguous() and pool_lengths.numel() >= n
+    opts = _lib.make_ets_paths_options(innovations, joint, seed)
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    if out is None:
+        ld_out = (n + 63) // 64 * 64
+        try:
+            out = torch.zeros((n_paths * h, ld_out), dtype=torch.float64, device=dev)
+        except torch.cuda.OutOfMemoryError as e:
+            raise RuntimeError(f"the path block of {n_paths * h} x {ld_out} values needs {n_paths * h * ld_out * 8} bytes of device "
+                               "memory") from e
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.dim() == 2 and int(out.shape[0]) == n_paths * h
+    ld_out = int(out.shape[1])
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    n_broken = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_ets_paths_device(spec.data_ptr(), info.data_ptr(), states.data_ptr(), ld, m, lengths.data_ptr(),
+                                       pool.data_ptr() if pool is not None else None, es, et,
+                                       pool_lengths.data_ptr() if pool_lengths is not None else None, pool_rows, n, h, n_paths,
+                                       C.byref(opts), C.sizeof(opts), out.data_ptr(), ld_out, status.data_ptr(), n_broken.data_ptr(),
+                                       C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_ets_paths_device", err)
+    return {"paths": out, "status": status, "n_broken": n_broken, "n_series": n, "horizon": h, "n_paths": n_paths}
+
+
 PATH_SCORES_WANT = ("crps", "ranks", "quantiles", "column")
 
 
@@ -1437,6 +1547,11 @@ def select_block(y: torch.Tensor, lengths: torch.Tensor, methods, folds, *, metr
             "backtests": backtests, "sub_batches": subs, "n_folds": F, "horizon": h}
 
 
+def _ets_notation_parts(notation: str) -> tuple:
+    """"AAdN" -> (0, 2, 0): the error, trend and season indices of spec id = error * 15 + trend * 3 + season."""
+    return "AM".index(notation[0]), ("N", "A", "Ad", "M", "Md").index(notation[1:-1]), "NAM".index(notation[-1])
+
+
 class DeviceBatch:
     """anofox_hip_batch_* over torch-owned HBM."""
 
@@ -1588,6 +1703,34 @@ class DeviceBatch:
             "model_code": view(ptrs[3], (self.n,), torch.int32, 4),
             "status": view(ptrs[4], (self.n,), torch.int32, 4),
         }
+
+    def inspect_device(self, fitted: bool = True) -> dict:
+        """anofox_hip_batch_inspect_device: the fit state of an AutoETS or ETS(spec) batch that has been run, left on the device.
+
+        Returns {"info": fp64 [8, ld] (rows alpha, beta, gamma, phi, aic, aicc, bic, sse), "states": fp64 [2 + max(m, 1), ld] (level,
+        growth, seasonal state of phase j in row 2 + j), "fitted": fp64 [max(t_max, 1), ld] time-major or None, "spec": int32 [n] --
+        error * 15 + trend * 3 + season of the model every series was fitted with, -1 where none was --, "m": the batch's period}:
+        what ets_innovations_block and ets_paths_block take.  NaN wherever a series or a spec has no value.  Waits for the passes."""
+        per = self.periods()
+        m = max(int(per[0]), 1) if self.n else 1
+        info = torch.empty((8, self.ld), dtype=torch.float64, device=self.device)
+        states = torch.empty((2 + m, self.ld), dtype=torch.float64, device=self.device)
+        fit = torch.empty((max(self.t_max, 1), self.ld), dtype=torch.float64, device=self.device) if fitted else None
+        torch.cuda.current_stream(self.device).synchronize()       # (the blocks exist before the batch's own stream writes them)
+        err = _lib.AnofoxError()
+        if not self.L.anofox_hip_batch_inspect_device(self.handle, info.data_ptr(), states.data_ptr(), fit.data_ptr() if fitted else None,
+                                                      C.byref(err)):
+            raise _paths_failed("anofox_hip_batch_inspect_device", err)
+        res = self.results()
+        if (self.opts.model or b"").decode() == "AutoETS":
+            spec = res["model_code"] - 100
+        else:
+            e, t, s = _ets_notation_parts(self.opts.ets_model.decode())
+            if s != 0 and int(per[0]) <= 1:
+                s = 0                                                # no usable period: the spec ran as its non-seasonal sibling
+            spec = torch.full((self.n,), e * 15 + t * 3 + s, dtype=torch.int32, device=self.device)
+        spec = torch.where(res["status"] == 0, spec, torch.full_like(spec, -1)).to(torch.int32).contiguous()
+        return {"info": info, "states": states, "fitted": fit, "spec": spec, "m": m}
 
     def model_name(self, code: int, series: int | None = None) -> str:
         """Name of a model code; with `series`, the name anofox_hip_batch_fetch gives that series (an AutoARIMA code carries the

@@ -482,6 +482,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_paths_device", "anofox_hip_path_quantiles_device", "anofox_hip_paths_batch",
     "anofox_hip_path_scores_device", "anofox_hip_path_scores_sizes", "anofox_hip_path_energy_device", "anofox_hip_path_scores_batch",
     "anofox_hip_scale_device", "anofox_hip_weighted_scores_device", "anofox_hip_wrmsse_batch",
+    "anofox_hip_batch_inspect_device", "anofox_hip_ets_innovations_device", "anofox_hip_ets_paths_device", "anofox_hip_batch_ets_paths",
 ]
 
 # include/anofox_fcst_hip.h block 9: bootstrap sample paths and their quantiles
@@ -498,6 +499,11 @@ SCALE_OK, SCALE_SHORT, SCALE_NAN, SCALE_CONSTANT = 0, 1, 2, 3
 SCALED_TRANSFORMS = {"ratio": 0, "root": 1}            # ANOFOX_SCALED_RATIO (loss / scale), ANOFOX_SCALED_ROOT (its square root)
 SCALED_MAX_LOSS = 16                                   # ANOFOX_HIP_SCALED_MAX_LOSS
 SCALE_ROWS = ("msd", "mad", "n_terms", "tail")         # the rows of out_scale
+# block 12: sample paths simulated from the fitted ETS models
+ETS_PATHS_INNOVATIONS = {"gaussian": 0, "bootstrap": 1}   # ANOFOX_ETS_PATHS_*
+ETS_PATHS_NO_MODEL = 4                                 # ANOFOX_ETS_PATHS_NO_MODEL, beside PATHS_OK / _EMPTY / _NAN / _RAGGED
+ETS_PATHS_MAX_PERIOD = 2048                            # ANOFOX_HIP_ETS_PATHS_MAX_PERIOD
+ETS_PATHS_MAX_RING = 128                               # ANOFOX_HIP_ETS_PATHS_MAX_RING: R = min(m, horizon)
 
 
 class AnofoxHipPathsOptions(C.Structure):
@@ -506,6 +512,14 @@ class AnofoxHipPathsOptions(C.Structure):
 
 
 assert C.sizeof(AnofoxHipPathsOptions) == 24
+
+
+class AnofoxHipEtsPathsOptions(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipEtsPathsOptions: innovations, joint and the seed (24 bytes)."""
+    _fields_ = [("innovations", C.c_int32), ("joint", C.c_int32), ("reserved", C.c_int32 * 2), ("seed", C.c_uint64)]
+
+
+assert C.sizeof(AnofoxHipEtsPathsOptions) == 24
 
 # include/anofox_fcst_hip.h block 8: the choice of a method per series
 SELECT_MAX_METHODS = 16
@@ -925,6 +939,21 @@ def load():
     L.anofox_hip_wrmsse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t, C.c_size_t, C.c_bool, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_size_t), P(C.c_size_t), P(AnofoxError)]
+    # block 12: sample paths simulated from the fitted ETS models
+    L.anofox_hip_batch_inspect_device.restype = C.c_bool
+    L.anofox_hip_batch_inspect_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_ets_innovations_device.restype = C.c_bool
+    L.anofox_hip_ets_innovations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_ets_paths_device.restype = C.c_bool
+    L.anofox_hip_ets_paths_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              P(AnofoxHipEtsPathsOptions), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_batch_ets_paths.restype = C.c_bool
+    L.anofox_hip_batch_ets_paths.argtypes = [C.c_void_p, P(AnofoxHipEtsPathsOptions), C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_size_t),
+                                             P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -1033,6 +1062,20 @@ def make_paths_options(mode="cumulative", joint=False, seed=0, route="auto"):
                 raise ValueError(f"unknown {name} {value!r}: one of {sorted(table)}")
             value = table[value]
         setattr(o, name, int(value))
+    o.joint = int(joint)
+    o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return o
+
+
+def make_ets_paths_options(innovations="gaussian", joint=False, seed=0):
+    """AnofoxHipEtsPathsOptions: innovations in ETS_PATHS_INNOVATIONS (or its code; an unknown name raises ValueError, an unknown code
+    is the library's to refuse), seed a uint64."""
+    o = AnofoxHipEtsPathsOptions()
+    if isinstance(innovations, str):
+        if innovations not in ETS_PATHS_INNOVATIONS:
+            raise ValueError(f"unknown innovations {innovations!r}: one of {sorted(ETS_PATHS_INNOVATIONS)}")
+        innovations = ETS_PATHS_INNOVATIONS[innovations]
+    o.innovations = int(innovations)
     o.joint = int(joint)
     o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     return o

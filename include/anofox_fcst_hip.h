@@ -3121,6 +3121,139 @@ bool anofox_hip_wrmsse_batch(const double *const *values,
                              size_t *out_ld,
                              struct AnofoxError *out_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 12: sample paths simulated from the fitted ETS models                 */
+/* ------------------------------------------------------------------------- */
+/*
+ * The state equations of the fitted spec run forward from the final states: h steps for each of n_paths paths per series, with
+ * innovations that are Gaussian or drawn from the model's own in-sample innovations (Hyndman, Koehler, Ord & Snyder 2008, section
+ * 6.1: the forecast distribution of the multiplicative-error and multiplicative-trend specs has no closed form).  The names and the
+ * contract are this package's own; tests/ets_paths_ref.py is the definition, bit for bit:
+ *   - spec int32 [n_series]: error * 15 + trend * 3 + season (error 0 A, 1 M; trend 0 N, 1 A, 2 Ad, 3 M, 4 Md; season 0 N, 1 A, 2 M),
+ *     the encoding of model_code - 100 of an AutoETS batch.  Anything that is not one of the 25 specs of the project (no
+ *     multiplicative error with an additive season), and a series with lengths[s] < 1, has status 4 (NO_MODEL) and NaN paths;
+ *   - info fp64 [8 x ld] (rows alpha, beta, gamma, phi, aic, aicc, bic, sse) and states fp64 [(2 + max(m, 1)) x ld] (rows level, growth,
+ *     then the seasonal state of phase j in row 2 + j) as anofox_hip_batch_inspect_device writes them; the phase of step k = 0 .. h - 1
+ *     is (lengths[s] + k) % m;
+ *   - Gaussian innovations: sigma = sqrt(sse / n), two IEEE operations.  The draw of (series s, path p) for steps 4j .. 4j + 3 is the
+ *     Philox4x32-10 block of counter {p, s, j, 2} under the key {seed & 0xffffffff, seed >> 32}: words (w0, w1) serve steps 4j and
+ *     4j + 1, (w2, w3) steps 4j + 2 and 4j + 3; u1 = (wa + 0.5) 2^-32, u2 = (wb + 0.5) 2^-32, r = sqrt(-2 log u1), theta =
+ *     6.283185307179586 u2; the even step takes z = r cos(theta), the odd one r sin(theta), e = sigma z (log, sin and cos are the
+ *     library's own, anofox_hip_selftest_math LOG and SINCOS).  The 32-bit uniform cuts the tails at |z| = 6.76.  No joint mode;
+ *   - bootstrap innovations: the index rule and the counters of block 9 unchanged (word k & 3 of counter {p, joint ? 0 : s, k >> 2,
+ *     joint ? 1 : 0}, row j = (u * n) >> 32), on a pool in the model's own terms (anofox_hip_ets_innovations_device);
+ *   - the step, with q = l, l + phi b, l b^phi, pt the trend's part of it (phi b, b^phi; phi = 1 undamped) and s the seasonal state of
+ *     the step's phase: mu = q, q + s or q s.  Additive error: y = mu + e, l' = q + alpha e [e / s with a multiplicative season],
+ *     b' = pt + beta e [e / s] (additive trend) or pt + beta e / l [e / (s l)] (multiplicative trend), s' = s + gamma e or
+ *     s + gamma e / q.  Multiplicative error: y = mu (1 + e), l' = q (1 + alpha e), b' = pt + beta q e or pt (1 + beta e), s' = s (1 +
+ *     gamma e).  Plain fp64, one rounding per operation, left to right, nothing fused.  b^phi of a damped multiplicative trend is
+ *     the library's POW_POS; where b is not a finite positive number at that point the path is broken: that step and every later one
+ *     are NaN.  Nothing else is clamped.
+ * Status per series (int32): 0; 4 NO_MODEL; then those of block 9 for the pool (3, 1, 2 in that precedence); 2 also for a NaN in a
+ * parameter or state the spec reads (Gaussian: in sigma).  n_broken int32 [n_series]: the paths of the series that hold a NaN.
+ * Parameter uncertainty is not simulated.  One seasonal period per call, one device, fp64.
+ */
+#define ANOFOX_HIP_ETS_PATHS_MAX_PERIOD 2048
+#define ANOFOX_HIP_ETS_PATHS_MAX_RING 128
+enum { ANOFOX_ETS_PATHS_GAUSSIAN = 0, ANOFOX_ETS_PATHS_BOOTSTRAP = 1 };
+enum { ANOFOX_ETS_PATHS_NO_MODEL = 4 };
+typedef struct AnofoxHipEtsPathsOptions {
+    int32_t innovations;         /* ANOFOX_ETS_PATHS_GAUSSIAN or ANOFOX_ETS_PATHS_BOOTSTRAP */
+    int32_t joint;               /* bootstrap only: 1 = one pool row per path and step for all series */
+    int32_t reserved[2];         /* 0 */
+    uint64_t seed;
+} AnofoxHipEtsPathsOptions;
+
+/*
+ * The fit state of an AutoETS or ETS(spec) batch that has been run, left on the device: the passes of anofox_hip_batch_inspect
+ * write d_info fp64 [8 x ld], d_states fp64 [(2 + max(m, 1)) x ld] and, unless NULL, d_fitted fp64 [max(t_max, 1) x ld], all
+ * time-major with ld = anofox_hip_batch_ld and NaN wherever a series or a spec has no value.  Nothing is copied to the host; the
+ * call returns when the blocks are written.  The batch must have one seasonal period; any other model is INVALID_INPUT.
+ */
+bool anofox_hip_batch_inspect_device(AnofoxHipBatch *batch,
+                                     double *d_info,
+                                     double *d_states,
+                                     double *d_fitted,
+                                     struct AnofoxError *out_error);
+
+/*
+ * The in-sample innovations of a fitted block: pool[t * ld + s] = y - fitted for an additive error and (y - fitted) / fitted for a
+ * multiplicative one, t < lengths[s]; rows past a series' length are not written.  pool_lengths[s] = lengths[s] cut to [0, t_rows],
+ * 0 for a spec that is none of the project's.  y, fitted and pool are fp64 [t_rows x ld] time-major in device memory.  The call only
+ * enqueues on `stream`.  INVALID_INPUT: ld < n_series, n_series or t_rows above 2^31 - 1.
+ */
+bool anofox_hip_ets_innovations_device(const double *y,
+                                       const double *fitted,
+                                       size_t ld,
+                                       const int32_t *lengths,
+                                       const int32_t *spec,
+                                       size_t n_series,
+                                       size_t t_rows,
+                                       double *pool,
+                                       int32_t *pool_lengths,
+                                       void *stream,
+                                       struct AnofoxError *out_error);
+
+/*
+ * The simulation.  All pointers but `options` are device memory.  The pool (bootstrap only) is addressed as in
+ * anofox_hip_paths_device: element (s, t) at s * pool_stride_s + t * pool_stride_t, pool_lengths NULL = every pool has pool_rows
+ * rows.  Outputs: paths_out fp64 [n_paths * horizon x ld_out], row p * horizon + k of column s, columns >= n_series not touched --
+ * what anofox_hip_hierarchy_device, anofox_hip_path_quantiles_device and anofox_hip_path_scores_device take as it lies; status and
+ * n_broken int32 [n_series].  The call only enqueues on `stream` (NULL: the null stream).
+ * INVALID_INPUT, each naming its limit, before the device is touched: struct_size, an unknown innovations mode, joint with the
+ * Gaussian mode, n_paths 0 or above 2,048, horizon 0, n_paths * horizon above 2^30, ld_out < n_series, ld < n_series, m < 1 or above
+ * 2,048, R = min(m, horizon) above 128 (the seasonal states of a path live in 64 KiB of LDS), the bootstrap without a pool,
+ * pool_rows above 2^20.
+ */
+bool anofox_hip_ets_paths_device(const int32_t *spec,
+                                 const double *info,
+                                 const double *states,
+                                 size_t ld,
+                                 size_t m,
+                                 const int32_t *lengths,
+                                 const double *pool,
+                                 size_t pool_stride_s,
+                                 size_t pool_stride_t,
+                                 const int32_t *pool_lengths,
+                                 size_t pool_rows,
+                                 size_t n_series,
+                                 size_t horizon,
+                                 size_t n_paths,
+                                 const AnofoxHipEtsPathsOptions *options,
+                                 size_t struct_size,
+                                 double *paths_out,
+                                 size_t ld_out,
+                                 int32_t *status,
+                                 int32_t *n_broken,
+                                 void *stream,
+                                 struct AnofoxError *out_error);
+
+/*
+ * The chain for a batch that has been run (AutoETS or ETS(spec), one seasonal period): the fit state stays on the device
+ * (anofox_hip_batch_inspect_device), the bootstrap takes the batch's own innovations (anofox_hip_ets_innovations_device), the
+ * paths of the batch's horizon are simulated and anofox_hip_path_quantiles_device reads `levels` (host, up to 16 in [0, 1]) off them.
+ * *out_ld (= anofox_hip_batch_ld) is always written.  With out_quantiles NULL that is all: the sizing call.  Otherwise ld must be
+ * that value and the caller's host arrays receive out_quantiles fp64 [n_levels x n_series x horizon], out_status int32 [n_series]
+ * (of the quantile entry: 2 where a path of the series holds a NaN), and, each optional (NULL), out_series_status int32 [n_series],
+ * out_n_broken int32 [n_series] and out_paths fp64 [n_paths * horizon x ld].
+ * The argument checks (options, n_paths, levels; then the batch; then horizon, period and R) come before the device is touched.  A
+ * failed device allocation is a COMPUTATION_ERROR that names the size.
+ */
+bool anofox_hip_batch_ets_paths(AnofoxHipBatch *batch,
+                                const AnofoxHipEtsPathsOptions *options,
+                                size_t struct_size,
+                                size_t n_paths,
+                                const double *levels,
+                                size_t n_levels,
+                                size_t ld,
+                                double *out_quantiles,
+                                int32_t *out_status,
+                                int32_t *out_series_status,
+                                int32_t *out_n_broken,
+                                double *out_paths,
+                                size_t *out_ld,
+                                struct AnofoxError *out_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
