@@ -4441,6 +4441,52 @@ def ets_paths_batch(series, opts, levels, n_paths=1000, innovations="gaussian", 
         L.anofox_hip_batch_destroy(hb)
 
 
+def arima_paths_batch(series, opts, levels, n_paths=1000, innovations="gaussian", joint=False, seed=0, want_paths=False, valids=None):
+    """anofox_hip_batch_arima_paths: fit the batch (AutoARIMA, one seasonal period; the horizon is the options'), then simulate
+    `n_paths` sample paths per series from the fitted models -- innovations "gaussian" (sigma = sqrt(css / nu)) or "bootstrap" (the
+    model's own residuals; joint=True: one residual row, counted from the end, per path and step for all series) -- and read `levels`
+    off them.
+
+    Returns ({"quantiles": fp64 [n_levels, n_series, h]; "status": int32 [n_series], 0 or lib.PATHS_NAN (a path of the series holds a
+    NaN); "series_status": int32 [n_series] (lib.PATHS_* and lib.ARIMA_PATHS_NO_MODEL); "n_broken": int32 [n_series]; "paths": fp64
+    [n_paths * h, ld] time-major, row p * h + k (want_paths, else None); "ld"}, error)."""
+    L = _lib.load()
+    n = len(series)
+    arrs = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+    t_max = max((len(a) for a in arrs), default=0)
+    h = int(opts.horizon)
+    al = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    k = len(al)
+    o = _lib.make_arima_paths_options(innovations, joint, seed)
+    err = _lib.AnofoxError()
+    out = {"quantiles": np.full((k, n, h), np.nan), "status": np.full(n, _lib.INTERNAL_ERROR, dtype=np.int32),
+           "series_status": np.zeros(n, dtype=np.int32), "n_broken": np.zeros(n, dtype=np.int32), "paths": None, "ld": 0}
+    report = lambda ok: {"ok": bool(ok), "code": int(err.code), "message": err.message.decode()}
+    hb = C.c_void_p()
+    if not L.anofox_hip_batch_create(n, t_max, C.byref(opts), C.byref(hb), C.byref(err)):
+        return out, report(False)
+    try:
+        masks = [validity_mask(v) for v in valids] if valids is not None else None
+        vptr = (C.c_void_p * max(n, 1))(*[a.ctypes.data if len(a) else _EMPTY_SERIES_ADDR for a in arrs])
+        mptr = (C.c_void_p * max(n, 1))(*[m.ctypes.data if len(m) else None for m in masks]) if masks is not None else None
+        lens = (C.c_size_t * max(n, 1))(*[len(a) for a in arrs])
+        if not L.anofox_hip_batch_pack_host(hb, vptr, mptr, lens, C.byref(err)) or not L.anofox_hip_batch_run(hb, None, C.byref(err)):
+            return out, report(False)
+        ld = C.c_size_t()
+        args = (hb, C.byref(o), C.sizeof(o), int(n_paths), al.ctypes.data, k)
+        if not L.anofox_hip_batch_arima_paths(*args, 0, None, None, None, None, None, C.byref(ld), C.byref(err)):
+            return out, report(False)
+        out["ld"] = int(ld.value)
+        if want_paths:
+            out["paths"] = np.full((int(n_paths) * h, out["ld"]), np.nan)
+        ok = L.anofox_hip_batch_arima_paths(*args, out["ld"], out["quantiles"].ctypes.data, out["status"].ctypes.data,
+                                            out["series_status"].ctypes.data, out["n_broken"].ctypes.data,
+                                            out["paths"].ctypes.data if want_paths else None, C.byref(ld), C.byref(err))
+        return out, report(ok)
+    finally:
+        L.anofox_hip_batch_destroy(hb)
+
+
 QUANTILE_PATHS = ("bootstrap", "model_gaussian", "model_bootstrap")
 
 
@@ -4448,9 +4494,10 @@ def ts_forecast_quantiles_by(group, date, target, method, horizon, frequency, le
                              joint=True, seed=0, params=None, group_name="id", date_name="ds", info=None, paths="bootstrap"):
     """ts_forecast_by with quantile forecasts at `levels` from bootstrap sample paths, all of it on the device.
 
-    paths="model_gaussian" | "model_bootstrap" (ETS and AutoETS only) simulates the paths from the fitted models instead
-    (device.ets_paths_block): no residual backtest, `mode` and `residual_folds` are not read, `joint` only by "model_bootstrap";
-    paths_status then also takes lib.ETS_PATHS_NO_MODEL and `info` receives "n_broken" in place of "errors" and "folds".  What
+    paths="model_gaussian" | "model_bootstrap" (ETS, AutoETS and AutoARIMA only) simulates the paths from the fitted models instead
+    (device.ets_paths_block, device.arima_paths_block): no residual backtest, `mode` and `residual_folds` are not read, `joint` only
+    by "model_bootstrap"; paths_status then also takes lib.ETS_PATHS_NO_MODEL (= lib.ARIMA_PATHS_NO_MODEL: an AutoARIMA series that
+    the fallback chain forecast has no model to simulate) and `info` receives "n_broken" in place of "errors" and "folds".  What
     follows describes the default, paths="bootstrap".
 
     The residuals are out-of-sample: a backtest with horizon 1 over `residual_folds` rolling folds of the resident block
@@ -4466,8 +4513,9 @@ def ts_forecast_quantiles_by(group, date, target, method, horizon, frequency, le
     if paths not in QUANTILE_PATHS:
         raise InvalidInputException(f"Invalid input: paths {paths!r} is unknown: one of {list(QUANTILE_PATHS)}")
     model_paths = paths != "bootstrap"
-    if model_paths and str(method) not in ("ETS", "AutoETS"):
-        raise InvalidInputException(f"Invalid input: paths={paths!r} simulates fitted ETS models: the method must be ETS or AutoETS, not {method!r}")
+    if model_paths and str(method) not in ("ETS", "AutoETS", "AutoARIMA"):
+        raise InvalidInputException(f"Invalid input: paths={paths!r} simulates the fitted models: the method must be ETS or AutoETS "
+                                    f"(or AutoARIMA), not {method!r}")
     order, series, last, kind, us, kept, dtype = _select_groups(group, date, target, "ts_forecast_quantiles_by")
     b = bind(method, horizon, frequency, params)
     opts = options_from_bind(b)
@@ -4505,8 +4553,9 @@ def ts_forecast_quantiles_by(group, date, target, method, horizon, frequency, le
             batch.run()
             res = batch.results()
             if model_paths:
-                g = _device.ets_paths_block(batch, n_paths=int(n_paths), innovations=paths[len("model_"):],
-                                            joint=bool(joint) and paths == "model_bootstrap", seed=seed)
+                simulate = _device.arima_paths_block if str(method) == "AutoARIMA" else _device.ets_paths_block
+                g = simulate(batch, n_paths=int(n_paths), innovations=paths[len("model_"):],
+                             joint=bool(joint) and paths == "model_bootstrap", seed=seed)
             else:
                 g = _device.paths_block(res["yhat"], pool, n_paths=int(n_paths), mode=mode, joint=joint, seed=seed, series_major=True,
                                         pool_series_major=True, n_series=n)

@@ -44,6 +44,7 @@ constexpr int TINY_BATCH_PROBLEMS = 1024;   // (series x specs) up to which ever
 #include "host_reconcile_mint.hpp" // the host-only checks and workspace sizes of the MinT-shrink entries
 #include "host_select_plan.hpp"   // the host-only logic of the selection entries (method table checks, criterion and mode names, sub-batch shapes)
 #include "host_paths_plan.hpp"    // the host-only checks of the sample-path entries, each naming its limit, and the batch entry's shapes
+#include "host_arima_paths_plan.hpp" // the host-only checks of the ARIMA model-path entries (options, period, the ring limit), each naming its limit
 #include "host_ets_paths_plan.hpp" // the host-only checks of the model-path entries (options, period and ring, pool), each naming its limit
 #include "host_path_scores_plan.hpp" // the host-only checks of the path-score entries, the energy workspace and a plan's column ranges
 #include "host_scaled_scores_plan.hpp" // the host-only checks of the scaled-score entries and the ranges of the WRMSSE chain
@@ -8201,6 +8202,220 @@ bool anofox_hip_batch_ets_paths(AnofoxHipBatch *b, const AnofoxHipEtsPathsOption
                 ok = anofox_hip_ets_paths_device(d_spec, d_info, d_states, need_ld, m, b->d_len, d_pool, 1, need_ld, boot ? d_plen : nullptr,
                                                  boot ? T : 0, n, horizon, n_paths, options, struct_size, d_paths, need_ld, d_status, d_broken,
                                                  nullptr, out_error);
+            if (ok)
+                ok = anofox_hip_path_quantiles_device(d_paths, need_ld, n, horizon, n_paths, levels, n_levels, d_q, d_qstatus, nullptr, out_error);
+            if (ok) {
+                HIPCHECK(hipMemcpy(out_quantiles, d_q, q_cells * sizeof(double), hipMemcpyDeviceToHost));      // waits for the null stream
+                HIPCHECK(hipMemcpy(out_status, d_qstatus, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_series_status) HIPCHECK(hipMemcpy(out_series_status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_n_broken) HIPCHECK(hipMemcpy(out_n_broken, d_broken, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                if (out_paths) HIPCHECK(hipMemcpy(out_paths, d_paths, cells * sizeof(double), hipMemcpyDeviceToHost));
+            } else HIPCHECK(hipDeviceSynchronize());
+        }
+        scratch.settled();                                                 // (either way the device has been waited for)
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    } catch (const std::exception &e) {
+        set_error(out_error, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
+        return false;
+    }
+    return ok;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Sample paths simulated from the fitted AutoARIMA models (DESIGN.md section 3 "ARIMA paths"; arima_paths.hip,
+// host_arima_paths_plan.hpp)
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+bool arima_paths_options_ok(const AnofoxHipArimaPathsOptions *o, size_t struct_size, AnofoxError *err)
+{
+    std::string message;
+    // (the fields are read only once the size has been found right)
+    const bool readable = o && struct_size == sizeof(AnofoxHipArimaPathsOptions);
+    return paths_plan_report(arima_paths_options_check(o != nullptr, struct_size, sizeof(AnofoxHipArimaPathsOptions), readable ? o->innovations : 0,
+                                                       readable ? o->joint : 0, &message), message, err);
+}
+
+// developer knob arima_paths_waves of ANOFOX_HIP_TUNE: waves per workgroup of the simulation kernel (0, the default: as many as the LDS takes)
+int arima_paths_waves_knob()
+{
+    const std::map<std::string, std::string> kv = Tunables::tune_map();
+    auto it = kv.find("arima_paths_waves");
+    const int w = it != kv.end() ? std::atoi(it->second.c_str()) : 0;
+    return w < 0 ? 0 : w;
+}
+
+// what anofox_hip_batch_arima_fit asks of a batch; throws HipFail for the cases that entry reports that way
+bool arima_fit_batch_ok(AnofoxHipBatch *b, const char *what, AnofoxError *out_error)
+{
+    if (!b->ran) { set_error(out_error, INVALID_INPUT, "Invalid input: the batch has not been run"); return false; }
+    if (b->plan.model != M_AutoARIMA) { set_error(out_error, INVALID_INPUT, std::string("Invalid input: ") + what + " needs an AutoARIMA batch"); return false; }
+    if (b->h_period.size() < b->n) throw HipFail{"the batch has no series block"};
+    for (size_t s = 1; s < b->n; s++)
+        if (b->h_period[s] != b->h_period[0]) throw HipFail{"the ARIMA fit readback needs one seasonal period for the whole batch"};
+    return true;
+}
+
+// enqueues the fit-state kernel behind the batch's run
+void arima_fit_state_pass(AnofoxHipBatch *b, int32_t *d_orders, double *d_coef)
+{
+    (void)hipGetLastError();
+    launch_arima_fit_state(b->d_status, b->d_model_code, b->ar_order, b->ar_d, b->ar_D, b->ar_wlen, b->ar_x, b->ar_aicc, b->ld, (int)b->n,
+                           d_orders, d_coef, b->last_stream);
+    LAUNCHCHECK("arima fit state");
+}
+
+} // namespace
+
+extern "C" {
+
+static_assert(sizeof(AnofoxHipArimaPathsOptions) == 24 && offsetof(AnofoxHipArimaPathsOptions, seed) == 16, "AnofoxHipArimaPathsOptions layout");
+static_assert(ARIMA_PATHS_PLAN_MAX_PERIOD == (size_t)ARIMA_PATHS_MAX_PERIOD && ARIMA_PATHS_PLAN_MAX_LDS_ROWS == (size_t)ARIMA_PATHS_MAX_LDS_ROWS &&
+              ARIMA_PATHS_MAX_PERIOD == ANOFOX_HIP_ARIMA_PATHS_MAX_PERIOD && ARIMA_PATHS_MAX_LDS_ROWS == ANOFOX_HIP_ARIMA_PATHS_MAX_LDS_ROWS &&
+              ARIMA_PATHS_GAUSSIAN == ANOFOX_ARIMA_PATHS_GAUSSIAN && ARIMA_PATHS_BOOTSTRAP == ANOFOX_ARIMA_PATHS_BOOTSTRAP &&
+              ARIMA_PATHS_NO_MODEL == ANOFOX_ARIMA_PATHS_NO_MODEL, "the limits and codes of the ARIMA model-path entries");
+
+bool anofox_hip_batch_arima_fit_device(AnofoxHipBatch *b, int32_t *d_orders, double *d_coef, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    if (!b || !d_orders || !d_coef) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    try {
+        if (!arima_fit_batch_ok(b, "the ARIMA fit readback", out_error)) return false;
+        if (b->n == 0) return true;
+        DeviceGuard guard(b->dev);
+        arima_fit_state_pass(b, d_orders, d_coef);
+        HIPCHECK(hipStreamSynchronize(b->last_stream));
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    } catch (const std::exception &e) {
+        set_error(out_error, INTERNAL_ERROR, std::string("Internal error: ") + e.what());
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_arima_innovations_device(const int32_t *orders, const double *coef, size_t ld, const double *y, const int32_t *lengths, size_t m,
+                                         size_t n_series, size_t t_rows, double *resid, int32_t *resid_lengths, double *sigma, void *stream,
+                                         AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!orders || !coef || !y || !lengths || !resid || !resid_lengths || !sigma) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    if (!paths_plan_report(paths_block_check(ld, n_series, "ld", "n_series", &message), message, out_error)) return false;
+    if (!paths_plan_report(arima_paths_rows_limit_check(t_rows, &message), message, out_error)) return false;
+    if (!paths_plan_report(arima_paths_period_check(m, &message), message, out_error)) return false;
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    try {
+        (void)hipGetLastError();
+        launch_arima_innovations(orders, coef, ld, y, lengths, (int)t_rows, (int)m, (int)n_series, resid, resid_lengths, sigma, (hipStream_t)stream);
+        LAUNCHCHECK("arima innovations");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_arima_paths_device(const int32_t *orders, const double *coef, size_t ld, const double *y, const int32_t *lengths, size_t t_rows,
+                                   const double *resid, const int32_t *resid_lengths, const double *sigma, size_t m, size_t pool_rows,
+                                   size_t n_series, size_t horizon, size_t n_paths, const AnofoxHipArimaPathsOptions *options, size_t struct_size,
+                                   double *paths_out, size_t ld_out, int32_t *status, int32_t *n_broken, void *stream, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!arima_paths_options_ok(options, struct_size, out_error)) return false;
+    if (!orders || !coef || !y || !lengths || !resid || !resid_lengths || !sigma || !paths_out || !status || !n_broken) {
+        set_error(out_error, NULL_POINTER, "Null pointer argument");
+        return false;
+    }
+    if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld_out, n_series, "ld_out", "n_series", &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_block_check(ld, n_series, "ld", "n_series", &message), message, out_error)) return false;
+    if (!paths_plan_report(arima_paths_rows_limit_check(t_rows, &message), message, out_error)) return false;
+    if (!paths_plan_report(arima_paths_ring_check(m, horizon, &message), message, out_error)) return false;
+    if (!paths_plan_report(arima_paths_pool_check(options->joint, pool_rows, &message), message, out_error)) return false;
+    if (n_series == 0) return true;
+    if (!device_ready(out_error)) return false;
+    const bool boot = options->innovations == ARIMA_PATHS_BOOTSTRAP;
+    ArimaPathsArgs a{};
+    a.orders = orders; a.coef = coef; a.ld = ld; a.y = y; a.lengths = lengths; a.t_rows = (int)t_rows;
+    a.resid = resid; a.resid_len = resid_lengths; a.sigma = sigma;
+    a.m = (int)m; a.innovations = options->innovations; a.joint = boot ? options->joint : 0; a.pool_rows = a.joint ? (int)pool_rows : 0;
+    a.n_series = (int)n_series; a.horizon = (int)horizon; a.n_paths = (int)n_paths;
+    a.key0 = (uint32_t)(options->seed & 0xffffffffull); a.key1 = (uint32_t)(options->seed >> 32);
+    a.paths = paths_out; a.ld_out = ld_out; a.status = status; a.n_broken = n_broken;
+    a.waves = arima_paths_waves_knob();
+    try {
+        (void)hipGetLastError();
+        launch_arima_paths(a, (hipStream_t)stream);
+        LAUNCHCHECK("arima paths");
+    } catch (const HipFail &f) {
+        report_hip_failure(out_error, f);
+        return false;
+    }
+    return true;
+}
+
+bool anofox_hip_batch_arima_paths(AnofoxHipBatch *b, const AnofoxHipArimaPathsOptions *options, size_t struct_size, size_t n_paths,
+                                  const double *levels, size_t n_levels, size_t ld, double *out_quantiles, int32_t *out_status,
+                                  int32_t *out_series_status, int32_t *out_n_broken, double *out_paths, size_t *out_ld, AnofoxError *out_error)
+{
+    clear_error(out_error);
+    std::string message;
+    if (!arima_paths_options_ok(options, struct_size, out_error)) return false;
+    if (!paths_plan_report(paths_rows_check(1, n_paths, &message), message, out_error)) return false;
+    if (!paths_plan_report(paths_levels_check(levels, n_levels, &message), message, out_error)) return false;
+    if (!b) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+    Scratch scratch;
+    bool ok = true;
+    try {
+        if (!arima_fit_batch_ok(b, "ARIMA model paths", out_error)) return false;
+        const size_t n = b->n, horizon = (size_t)std::max(b->h, 0), m = (size_t)std::max(n ? b->h_period[0] : 1, 1), need_ld = b->ld;
+        if (!paths_plan_report(paths_rows_check(horizon, n_paths, &message), message, out_error)) return false;
+        if (!paths_plan_report(arima_paths_ring_check(m, horizon, &message), message, out_error)) return false;
+        if (out_ld) *out_ld = need_ld;
+        if (!out_quantiles) return true;
+        if (ld != need_ld) { set_error(out_error, INVALID_INPUT, "Invalid input: ld is not what the sizing call returns"); return false; }
+        if (!out_status) { set_error(out_error, NULL_POINTER, "Null pointer argument"); return false; }
+        if (n == 0) return true;
+        DeviceGuard guard(b->dev);
+        const size_t T = std::max<size_t>(b->t_max, 1), rows = n_paths * horizon, cells = rows * need_ld, q_cells = n_levels * n * horizon;
+        double *d_paths = nullptr;
+        try {
+            d_paths = scratch.get<double>(cells);
+        } catch (const HipFail &f) {
+            if (!f.oom) throw;
+            set_error(out_error, COMPUTATION_ERROR, "Computation error: the path block of " + std::to_string(rows) + " x " + std::to_string(need_ld) +
+                      " values needs " + std::to_string(cells * sizeof(double)) + " bytes of device memory");
+            ok = false;
+        }
+        if (ok) {
+            int32_t *d_orders = scratch.get<int32_t>(8 * need_ld), *d_rlen = scratch.get<int32_t>(need_ld), *d_status = scratch.get<int32_t>(need_ld);
+            int32_t *d_broken = scratch.get<int32_t>(need_ld), *d_qstatus = scratch.get<int32_t>(need_ld);
+            double *d_coef = scratch.get<double>(16 * need_ld), *d_resid = scratch.get<double>(T * need_ld), *d_sigma = scratch.get<double>(need_ld);
+            double *d_q = scratch.get<double>(q_cells);
+            arima_fit_state_pass(b, d_orders, d_coef);
+            HIPCHECK(hipStreamSynchronize(b->last_stream));
+            HIPCHECK(hipMemset(d_paths, 0, cells * sizeof(double)));            // the padding columns
+            ok = anofox_hip_arima_innovations_device(d_orders, d_coef, need_ld, b->d_y, b->d_len, m, n, T, d_resid, d_rlen, d_sigma, nullptr, out_error);
+            size_t pool_rows = 0;
+            if (ok && options->joint) {                                        // the smallest nu among the fitted series
+                std::vector<int32_t> rlen(n);
+                HIPCHECK(hipMemcpy(rlen.data(), d_rlen, n * sizeof(int32_t), hipMemcpyDeviceToHost));      // waits for the null stream
+                int32_t least = 0;
+                for (size_t s = 0; s < n; s++)
+                    if (rlen[s] > 0 && (least == 0 || rlen[s] < least)) least = rlen[s];
+                pool_rows = (size_t)least;
+            }
+            if (ok)
+                ok = anofox_hip_arima_paths_device(d_orders, d_coef, need_ld, b->d_y, b->d_len, T, d_resid, d_rlen, d_sigma, m, pool_rows, n, horizon,
+                                                   n_paths, options, struct_size, d_paths, need_ld, d_status, d_broken, nullptr, out_error);
             if (ok)
                 ok = anofox_hip_path_quantiles_device(d_paths, need_ld, n, horizon, n_paths, levels, n_levels, d_q, d_qstatus, nullptr, out_error);
             if (ok) {

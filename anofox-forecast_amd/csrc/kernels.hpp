@@ -866,6 +866,35 @@ void launch_ets_innovations(const double *y, const double *fitted, size_t ld, co
 void launch_ets_spec_of(const int32_t *model_code, const int32_t *status, int auto_ets, int explicit_spec, int n_series, int32_t *spec, hipStream_t);
 void launch_fill_f64(double *p, size_t n, double value, hipStream_t);
 
+// Sample paths simulated from fitted ARIMA models (DESIGN.md section 3 "ARIMA paths"; arima_paths.hip).  `orders` int32 [8 x ld] (rows
+// p, d, q, P, D, Q, has_constant, n_diff) and `coef` fp64 [16 x ld] (rows phi 1..5, theta 1..5, Phi 1..2, Theta 1..2, constant, aicc)
+// are the fit blocks; `resid` [t_rows x ld] is compacted: row j of a column is the residual of differenced index p + m P + j.
+enum { ARIMA_PATHS_GAUSSIAN = 0, ARIMA_PATHS_BOOTSTRAP = 1 };
+constexpr int32_t ARIMA_PATHS_NO_MODEL = 4;            // beside PATHS_OK / _EMPTY / _NAN / _RAGGED
+constexpr int ARIMA_PATHS_MAX_PERIOD = 2048;
+constexpr int ARIMA_PATHS_MAX_LDS_ROWS = 128;          // 2 min(h, 2 m + 5) + (m < h ? m : 0) rows of 64 lanes x 8 bytes per wave within 64 KiB
+struct ArimaPathsArgs {
+    const int32_t *orders; const double *coef; size_t ld;
+    const double *y; const int32_t *lengths; int t_rows;      // the series block [t_rows x ld] and its lengths (cut to t_rows)
+    const double *resid; const int32_t *resid_len; const double *sigma;
+    int m, innovations, joint, pool_rows;        // ARIMA_PATHS_*; joint: draw j < pool_rows takes residual row nu - pool_rows + j of every series
+    int n_series, horizon, n_paths;
+    uint32_t key0, key1;
+    double *paths; size_t ld_out;                // [n_paths * horizon x ld_out], row p * horizon + k
+    int32_t *status, *n_broken;                  // [n_series]
+    int waves;                                   // developer knob: waves per workgroup of the simulation kernel, 0 = as many as the LDS takes
+    int path_groups, ring, yring;                // set by launch_arima_paths
+};
+int arima_paths_lds_rows(int m, int horizon);                              // the LDS rows of a wave
+int arima_paths_waves(int lds_rows);                                       // waves per workgroup of the simulation kernel
+void launch_arima_paths(const ArimaPathsArgs &, hipStream_t);              // the statuses, the paths, then n_broken
+void launch_arima_innovations(const int32_t *orders, const double *coef, size_t ld, const double *y, const int32_t *lengths, int t_rows, int m,
+                              int n_series, double *resid, int32_t *resid_len, double *sigma, hipStream_t);
+// the batch's search state (arima.hip ArimaArgs: order [5 x ld], d, D, wlen, xbest [6 x ld], aicc) -> the two fit blocks
+void launch_arima_fit_state(const int32_t *status, const int32_t *model_code, const int32_t *order, const int32_t *d, const int32_t *D,
+                            const int32_t *wlen, const double *x, const double *aicc, size_t ld, int n_series, int32_t *orders, double *coef,
+                            hipStream_t);
+
 // Scores of a block of sample paths (DESIGN.md section 3 "Path scores"; path_scores.hip).  Element (column c, step k) of `actual` is
 // at c * actual_stride_c + k * actual_stride_k; a NaN there drops the step.
 constexpr int32_t PATH_SCORES_OK = 0, PATH_SCORES_NO_ACTUAL = 1, PATH_SCORES_NAN = 2;

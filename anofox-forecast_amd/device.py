@@ -856,6 +856,118 @@ def ets_paths_block(batch=None, *, spec: torch.Tensor | None = None, info: torch
     return {"paths": out, "status": status, "n_broken": n_broken, "n_series": n, "horizon": h, "n_paths": n_paths}
 
 
+def arima_innovations_block(orders: torch.Tensor, coef: torch.Tensor, y: torch.Tensor, lengths: torch.Tensor, m: int, *,
+                            n_series: int | None = None, out: dict | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_arima_innovations_device on torch tensors: the in-sample innovations of fitted ARIMA models (the CSS recursion).
+
+    orders int32 [8, ld] and coef fp64 [16, ld] as DeviceBatch.arima_fit_device gives them, y fp64 [T, ld] time-major (the series block
+    of a DeviceBatch), lengths int32 [>= n_series] on the device, m the seasonal period.
+
+    Returns {"resid": fp64 [T, ld] compacted (row j of a column is the residual of differenced index p + m P + j; NaN where nothing
+    is written), "resid_lengths": int32 [n_series] (nu = n_diff - p - m P; 0 where the series has no model), "sigma": fp64 [n_series]
+    (sqrt(css / nu); NaN where the series has no model)}: what arima_paths_block takes.  `out`: such a dict from an earlier call of
+    the same shape, written again in place (nothing is allocated or filled: rows past a series' nu keep what they held)."""
+    L = _lib.load()
+    for t in (coef, y):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 2
+    assert orders.dtype == torch.int32 and orders.is_cuda and orders.is_contiguous() and orders.dim() == 2
+    T, ld = int(y.shape[0]), int(y.shape[1])
+    assert tuple(orders.shape) == (8, ld) and tuple(coef.shape) == (16, ld), (tuple(orders.shape), tuple(coef.shape), ld)
+    n = ld if n_series is None else int(n_series)
+    assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.is_contiguous() and lengths.numel() >= n
+    dev = y.device
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    if out is not None:
+        resid, resid_lengths, sigma = out["resid"], out["resid_lengths"], out["sigma"]
+        assert resid.dtype == torch.float64 and resid.is_cuda and resid.is_contiguous() and tuple(resid.shape) == (T, ld)
+        assert resid_lengths.dtype == torch.int32 and resid_lengths.is_cuda and resid_lengths.is_contiguous() and resid_lengths.numel() >= n
+        assert sigma.dtype == torch.float64 and sigma.is_cuda and sigma.is_contiguous() and sigma.numel() >= n
+    else:
+        resid = torch.full((T, ld), float("nan"), dtype=torch.float64, device=dev)
+        resid_lengths = torch.zeros(n, dtype=torch.int32, device=dev)
+        sigma = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_arima_innovations_device(orders.data_ptr(), coef.data_ptr(), ld, y.data_ptr(), lengths.data_ptr(), int(m), n, T,
+                                               resid.data_ptr(), resid_lengths.data_ptr(), sigma.data_ptr(), C.c_void_p(st.cuda_stream),
+                                               C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_arima_innovations_device", err)
+    return {"resid": resid, "resid_lengths": resid_lengths, "sigma": sigma}
+
+
+def arima_paths_block(batch=None, *, orders: torch.Tensor | None = None, coef: torch.Tensor | None = None, y: torch.Tensor | None = None,
+                      lengths: torch.Tensor | None = None, resid: torch.Tensor | None = None, resid_lengths: torch.Tensor | None = None,
+                      sigma: torch.Tensor | None = None, m: int | None = None, horizon: int | None = None, n_paths: int = 1000,
+                      innovations: str | int = "gaussian", joint: bool = False, pool_rows: int | None = None, seed: int = 0,
+                      n_series: int | None = None, out: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+    """anofox_hip_arima_paths_device on torch tensors: sample paths simulated from fitted ARIMA models, no host copy.
+
+    Either a DeviceBatch that has been run (AutoARIMA, one seasonal period): its arima_fit_device gives orders, coef and m, the batch
+    its series, lengths and horizon, arima_innovations_block the residuals and sigma.  Or the tensors themselves (see
+    arima_innovations_block).  innovations "gaussian" (e = sigma z) or "bootstrap" (the series' own residuals; joint=True: draw
+    j < pool_rows takes residual row nu - pool_rows + j of every series; pool_rows None: the smallest nu among the series that have
+    a model).  The draws are Philox4x32-10 on the counter (path, series, step): the same seed gives the same bits whatever the
+    launch shape.
+
+    Returns {"paths": fp64 [n_paths * h, ld_out] in the layout of paths_block, "status": int32 [n] (lib.PATHS_* and
+    lib.ARIMA_PATHS_NO_MODEL; the paths of a series whose status is not 0 are NaN), "n_broken": int32 [n], the paths of a series
+    that hold a NaN, "n_series", "horizon", "n_paths", "pool_rows"}.  path_quantiles_block, path_scores_block and aggregate_block
+    take the block as it lies."""
+    L = _lib.load()
+    if batch is not None:
+        fit = batch.arima_fit_device()
+        orders, coef, m, y, lengths = fit["orders"], fit["coef"], fit["m"], batch._y, batch._len
+        horizon = batch.h if horizon is None else horizon
+        n_series = batch.n if n_series is None else n_series
+        inn = arima_innovations_block(orders, coef, y, lengths, m, n_series=n_series, stream=stream)
+        resid, resid_lengths, sigma = inn["resid"], inn["resid_lengths"], inn["sigma"]
+    assert orders is not None and coef is not None and y is not None and lengths is not None and m is not None and horizon is not None
+    assert resid is not None and resid_lengths is not None and sigma is not None
+    m, h, n_paths = int(m), int(horizon), int(n_paths)
+    for t in (coef, y, resid):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.dim() == 2
+    assert orders.dtype == torch.int32 and orders.is_cuda and orders.is_contiguous()
+    T, ld = int(y.shape[0]), int(y.shape[1])
+    assert tuple(orders.shape) == (8, ld) and tuple(coef.shape) == (16, ld) and tuple(resid.shape) == (T, ld)
+    n = ld if n_series is None else int(n_series)
+    assert 0 < n <= ld
+    for t in (lengths, resid_lengths):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= n
+    assert sigma.dtype == torch.float64 and sigma.is_cuda and sigma.is_contiguous() and sigma.numel() >= n
+    _paths_rows(n_paths, h)
+    dev = y.device
+    opts = _lib.make_arima_paths_options(innovations, joint, seed)
+    if opts.joint and pool_rows is None:
+        nu = resid_lengths[:n]
+        fitted = nu[nu > 0]
+        pool_rows = int(fitted.min().item()) if fitted.numel() else 0
+    pool_rows = int(pool_rows) if (opts.joint and pool_rows is not None) else 0
+    if L.anofox_hip_set_device(dev.index or 0) != 0:
+        raise RuntimeError(f"hipSetDevice({dev.index or 0}) failed")
+    if out is None:
+        ld_out = (n + 63) // 64 * 64
+        try:
+            out = torch.zeros((n_paths * h, ld_out), dtype=torch.float64, device=dev)
+        except torch.cuda.OutOfMemoryError as e:
+            raise RuntimeError(f"the path block of {n_paths * h} x {ld_out} values needs {n_paths * h * ld_out * 8} bytes of device "
+                               "memory") from e
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.dim() == 2 and int(out.shape[0]) == n_paths * h
+    ld_out = int(out.shape[1])
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    n_broken = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    err = _lib.AnofoxError()
+    ok = L.anofox_hip_arima_paths_device(orders.data_ptr(), coef.data_ptr(), ld, y.data_ptr(), lengths.data_ptr(), T, resid.data_ptr(),
+                                         resid_lengths.data_ptr(), sigma.data_ptr(), m, pool_rows, n, h, n_paths, C.byref(opts),
+                                         C.sizeof(opts), out.data_ptr(), ld_out, status.data_ptr(), n_broken.data_ptr(),
+                                         C.c_void_p(st.cuda_stream), C.byref(err))
+    if not ok:
+        raise _paths_failed("anofox_hip_arima_paths_device", err)
+    return {"paths": out, "status": status, "n_broken": n_broken, "n_series": n, "horizon": h, "n_paths": n_paths, "pool_rows": pool_rows}
+
+
 PATH_SCORES_WANT = ("crps", "ranks", "quantiles", "column")
 
 
@@ -1731,6 +1843,22 @@ class DeviceBatch:
             spec = torch.full((self.n,), e * 15 + t * 3 + s, dtype=torch.int32, device=self.device)
         spec = torch.where(res["status"] == 0, spec, torch.full_like(spec, -1)).to(torch.int32).contiguous()
         return {"info": info, "states": states, "fitted": fit, "spec": spec, "m": m}
+
+    def arima_fit_device(self) -> dict:
+        """anofox_hip_batch_arima_fit_device: the fit of an AutoARIMA batch that has been run, left on the device.
+
+        Returns {"orders": int32 [8, ld] (rows lib.ARIMA_FIT_ORDER_ROWS), "coef": fp64 [16, ld] (rows phi 1..5, theta 1..5, Phi 1..2,
+        Theta 1..2, constant, aicc), "m": the batch's period}: what arima_innovations_block and arima_paths_block take.  A series
+        nothing was fitted to has zero orders and NaN coefficients.  Waits for the pass."""
+        per = self.periods()
+        m = max(int(per[0]), 1) if self.n else 1
+        orders = torch.zeros((8, self.ld), dtype=torch.int32, device=self.device)
+        coef = torch.full((16, self.ld), float("nan"), dtype=torch.float64, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()       # (the blocks exist before the batch's own stream writes them)
+        err = _lib.AnofoxError()
+        if not self.L.anofox_hip_batch_arima_fit_device(self.handle, orders.data_ptr(), coef.data_ptr(), C.byref(err)):
+            raise _paths_failed("anofox_hip_batch_arima_fit_device", err)
+        return {"orders": orders, "coef": coef, "m": m}
 
     def model_name(self, code: int, series: int | None = None) -> str:
         """Name of a model code; with `series`, the name anofox_hip_batch_fetch gives that series (an AutoARIMA code carries the

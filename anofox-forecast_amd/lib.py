@@ -483,6 +483,7 @@ EXPORTED_SYMBOLS = [
     "anofox_hip_path_scores_device", "anofox_hip_path_scores_sizes", "anofox_hip_path_energy_device", "anofox_hip_path_scores_batch",
     "anofox_hip_scale_device", "anofox_hip_weighted_scores_device", "anofox_hip_wrmsse_batch",
     "anofox_hip_batch_inspect_device", "anofox_hip_ets_innovations_device", "anofox_hip_ets_paths_device", "anofox_hip_batch_ets_paths",
+    "anofox_hip_batch_arima_fit_device", "anofox_hip_arima_innovations_device", "anofox_hip_arima_paths_device", "anofox_hip_batch_arima_paths",
 ]
 
 # include/anofox_fcst_hip.h block 9: bootstrap sample paths and their quantiles
@@ -520,6 +521,21 @@ class AnofoxHipEtsPathsOptions(C.Structure):
 
 
 assert C.sizeof(AnofoxHipEtsPathsOptions) == 24
+
+# include/anofox_fcst_hip.h block 13: sample paths simulated from the fitted AutoARIMA models
+ARIMA_PATHS_INNOVATIONS = {"gaussian": 0, "bootstrap": 1}  # ANOFOX_ARIMA_PATHS_*
+ARIMA_PATHS_NO_MODEL = 4                                # ANOFOX_ARIMA_PATHS_NO_MODEL, beside PATHS_OK / _EMPTY / _NAN / _RAGGED
+ARIMA_PATHS_MAX_PERIOD = 2048                           # ANOFOX_HIP_ARIMA_PATHS_MAX_PERIOD
+ARIMA_PATHS_MAX_LDS_ROWS = 128                          # ANOFOX_HIP_ARIMA_PATHS_MAX_LDS_ROWS: 2 min(h, 2 m + 5) + (m < h ? m : 0)
+ARIMA_FIT_ORDER_ROWS = ("p", "d", "q", "P", "D", "Q", "has_constant", "n_diff")      # rows of the orders block
+
+
+class AnofoxHipArimaPathsOptions(C.Structure):
+    """include/anofox_fcst_hip.h AnofoxHipArimaPathsOptions: innovations, joint and the seed (24 bytes)."""
+    _fields_ = [("innovations", C.c_int32), ("joint", C.c_int32), ("reserved", C.c_int32 * 2), ("seed", C.c_uint64)]
+
+
+assert C.sizeof(AnofoxHipArimaPathsOptions) == 24
 
 # include/anofox_fcst_hip.h block 8: the choice of a method per series
 SELECT_MAX_METHODS = 16
@@ -954,6 +970,21 @@ def load():
     L.anofox_hip_batch_ets_paths.argtypes = [C.c_void_p, P(AnofoxHipEtsPathsOptions), C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_size_t),
                                              P(AnofoxError)]
+    # block 13: sample paths simulated from the fitted AutoARIMA models
+    L.anofox_hip_batch_arima_fit_device.restype = C.c_bool
+    L.anofox_hip_batch_arima_fit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_arima_innovations_device.restype = C.c_bool
+    L.anofox_hip_arima_innovations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_arima_paths_device.restype = C.c_bool
+    L.anofox_hip_arima_paths_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                P(AnofoxHipArimaPathsOptions), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, P(AnofoxError)]
+    L.anofox_hip_batch_arima_paths.restype = C.c_bool
+    L.anofox_hip_batch_arima_paths.argtypes = [C.c_void_p, P(AnofoxHipArimaPathsOptions), C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_size_t),
+                                               P(AnofoxError)]
     # block 4: columnar ingest (host side only; usable without a GPU up to pack_ingest)
     L.anofox_hip_ingest_create.restype = C.c_void_p
     L.anofox_hip_ingest_destroy.argtypes = [C.c_void_p]
@@ -1075,6 +1106,20 @@ def make_ets_paths_options(innovations="gaussian", joint=False, seed=0):
         if innovations not in ETS_PATHS_INNOVATIONS:
             raise ValueError(f"unknown innovations {innovations!r}: one of {sorted(ETS_PATHS_INNOVATIONS)}")
         innovations = ETS_PATHS_INNOVATIONS[innovations]
+    o.innovations = int(innovations)
+    o.joint = int(joint)
+    o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return o
+
+
+def make_arima_paths_options(innovations="gaussian", joint=False, seed=0):
+    """AnofoxHipArimaPathsOptions: innovations in ARIMA_PATHS_INNOVATIONS (or its code; an unknown name raises ValueError, an unknown
+    code is the library's to refuse), seed a uint64."""
+    o = AnofoxHipArimaPathsOptions()
+    if isinstance(innovations, str):
+        if innovations not in ARIMA_PATHS_INNOVATIONS:
+            raise ValueError(f"unknown innovations {innovations!r}: one of {sorted(ARIMA_PATHS_INNOVATIONS)}")
+        innovations = ARIMA_PATHS_INNOVATIONS[innovations]
     o.innovations = int(innovations)
     o.joint = int(joint)
     o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF

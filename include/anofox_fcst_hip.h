@@ -3254,6 +3254,136 @@ bool anofox_hip_batch_ets_paths(AnofoxHipBatch *batch,
                                 size_t *out_ld,
                                 struct AnofoxError *out_error);
 
+/* ------------------------------------------------------------------------- */
+/* Block 13: sample paths simulated from the fitted AutoARIMA models           */
+/* ------------------------------------------------------------------------- */
+/*
+ * The fitted ARIMA recursion simulated forward from the tails of the differenced series and of its in-sample innovations, then the
+ * differences integrated: h steps for each of n_paths paths per series (Box & Jenkins; Hyndman & Athanasopoulos, Forecasting:
+ * Principles and Practice, "Prediction intervals from simulated paths").  The names and the contract are this package's own;
+ * tests/arima_paths_ref.py is the definition, bit for bit:
+ *   - the convention of AnofoxHipArimaFit, (1 - phi(B))(1 - Phi(B^m)) (w_t - c) = (1 - theta(B))(1 - Theta(B^m)) e_t on the differenced
+ *     series w (the seasonal difference first, then the d ordinary ones, each a single subtraction), c the constant or 0.0;
+ *   - the fit blocks, time-major with leading dimension ld: orders int32 [8 x ld] (rows p, d, q, P, D, Q, has_constant, n_diff) and
+ *     coef fp64 [16 x ld] (rows phi 1..5, theta 1..5, Phi 1..2, Theta 1..2, constant, aicc), as anofox_hip_batch_arima_fit_device
+ *     writes them;
+ *   - the lag polynomials are not multiplied out: a side is the sum over the terms (i, j), 0 <= i <= p, 0 <= j <= P, without (0, 0),
+ *     of coefficient x value at lag i + j m, the coefficient phi_i, Phi_j or -(phi_i Phi_j), added j-major and i-minor from 0.0; a
+ *     value before the differenced series is 0.0.  x_t = w_t - c; in sample e_t = 0 for t < La = p + m P and e_t = (x_t - ar) + ma
+ *     after; css = the serial sum of e_t^2, nu = n_diff - La, sigma = sqrt(css / nu).  A path: x_t = (ar + e_t) - ma, v = x_t + c,
+ *     then last_d1 += v (d = 2), last_d0 += v (d >= 1) and + y of m steps before (D = 1), from the history or the path itself.
+ *     Plain fp64, one rounding per operation, nothing fused, nothing clamped: a step whose value is not finite is NaN and so is
+ *     every later step of that path;
+ *   - Gaussian innovations: the rule of block 12 with the last counter word 3: counter {p, s, j, 3}, e = sigma z.  No joint mode;
+ *   - bootstrap innovations: the index rule and the counters of block 9 on the series' own nu residuals; joint: draw j < pool_rows
+ *     takes residual row nu - pool_rows + j of every series (the same date for series that end together).
+ * Status per series (int32): 0; 4 NO_MODEL (orders outside p, q <= 5, P, Q <= 2, d <= 2, D <= 1, has_constant 0 / 1; lengths[s] < 1;
+ * n_diff other than lengths[s] - d - D m, which includes the zero row of a series without a fit; nu < 1; resid_lengths[s] other
+ * than nu); then 3 (joint: nu < pool_rows), 1 (joint: pool_rows 0), 2: a NaN in a coefficient the orders read, in sigma (Gaussian),
+ * in the last La + d + D m observations, in the last min(nu, q + m Q) residuals or (bootstrap) in the rows of the pool.  The paths
+ * of a series whose status is not 0 are NaN.  n_broken int32 [n_series]: the paths of the series that hold a NaN.
+ * AutoARIMA only (the fixed-order ARIMA model has no fit readback); parameter uncertainty is not simulated.  One seasonal period
+ * per call, one device, fp64.  The simulated values a later step reads at a seasonal lag live in LDS: 2 min(h, 2 m + 5) +
+ * (m < h ? m : 0) rows of 512 bytes per wavefront, at most ANOFOX_HIP_ARIMA_PATHS_MAX_LDS_ROWS.
+ */
+#define ANOFOX_HIP_ARIMA_PATHS_MAX_PERIOD 2048
+#define ANOFOX_HIP_ARIMA_PATHS_MAX_LDS_ROWS 128
+enum { ANOFOX_ARIMA_PATHS_GAUSSIAN = 0, ANOFOX_ARIMA_PATHS_BOOTSTRAP = 1 };
+enum { ANOFOX_ARIMA_PATHS_NO_MODEL = 4 };
+typedef struct AnofoxHipArimaPathsOptions {
+    int32_t innovations;         /* ANOFOX_ARIMA_PATHS_GAUSSIAN or ANOFOX_ARIMA_PATHS_BOOTSTRAP */
+    int32_t joint;               /* bootstrap only: 1 = one residual row (counted from the end) per path and step for all series */
+    int32_t reserved[2];         /* 0 */
+    uint64_t seed;
+} AnofoxHipArimaPathsOptions;
+
+/*
+ * The fit of an AutoARIMA batch that has been run, left on the device: d_orders int32 [8 x ld] and d_coef fp64 [16 x ld] with
+ * ld = anofox_hip_batch_ld.  The coefficients are the ones the recursion reads (the box clip applied); zeros and NaN go exactly
+ * where anofox_hip_batch_arima_fit puts them: a series nothing was fitted to has zero orders and NaN in every double, slots beyond
+ * the orders are 0.0.  Nothing is copied to the host; the call returns when the blocks are written.  The error cases are those of
+ * anofox_hip_batch_arima_fit.
+ */
+bool anofox_hip_batch_arima_fit_device(AnofoxHipBatch *batch,
+                                       int32_t *d_orders,
+                                       double *d_coef,
+                                       struct AnofoxError *out_error);
+
+/*
+ * The in-sample innovations of the fitted models.  y fp64 [t_rows x ld] time-major, lengths int32 [n_series] (cut to [0, t_rows]).
+ * Outputs: resid fp64 [t_rows x ld], compacted -- row j of column s is the residual of differenced index La + j, rows from nu on are
+ * not written --, resid_lengths int32 [n_series] (nu; 0 where the series has no model) and sigma fp64 [n_series] (NaN there).  All
+ * pointers are device memory.  The call only enqueues on `stream`.  INVALID_INPUT, each naming its limit, before the device is
+ * touched: ld < n_series, n_series or t_rows above 2^31 - 1, m < 1 or above 2,048.
+ */
+bool anofox_hip_arima_innovations_device(const int32_t *orders,
+                                         const double *coef,
+                                         size_t ld,
+                                         const double *y,
+                                         const int32_t *lengths,
+                                         size_t m,
+                                         size_t n_series,
+                                         size_t t_rows,
+                                         double *resid,
+                                         int32_t *resid_lengths,
+                                         double *sigma,
+                                         void *stream,
+                                         struct AnofoxError *out_error);
+
+/*
+ * The simulation.  All pointers but `options` are device memory; y and resid are fp64 [t_rows x ld], sigma fp64 [n_series] (read by
+ * the Gaussian mode only), pool_rows is read in joint mode only.  Outputs: paths_out fp64 [n_paths * horizon x ld_out], row
+ * p * horizon + k of column s, columns >= n_series not touched -- what anofox_hip_hierarchy_device,
+ * anofox_hip_path_quantiles_device and anofox_hip_path_scores_device take as it lies; status and n_broken int32 [n_series].  The
+ * call only enqueues on `stream` (NULL: the null stream).
+ * INVALID_INPUT, each naming its limit, before the device is touched: struct_size, an unknown innovations mode, joint with the
+ * Gaussian mode, n_paths 0 or above 2,048, horizon 0, n_paths * horizon above 2^30, ld_out < n_series, ld < n_series, t_rows above
+ * 2^31 - 1, m < 1 or above 2,048, 2 min(horizon, 2 m + 5) + (m < horizon ? m : 0) above 128 LDS rows, pool_rows above 2^20.
+ */
+bool anofox_hip_arima_paths_device(const int32_t *orders,
+                                   const double *coef,
+                                   size_t ld,
+                                   const double *y,
+                                   const int32_t *lengths,
+                                   size_t t_rows,
+                                   const double *resid,
+                                   const int32_t *resid_lengths,
+                                   const double *sigma,
+                                   size_t m,
+                                   size_t pool_rows,
+                                   size_t n_series,
+                                   size_t horizon,
+                                   size_t n_paths,
+                                   const AnofoxHipArimaPathsOptions *options,
+                                   size_t struct_size,
+                                   double *paths_out,
+                                   size_t ld_out,
+                                   int32_t *status,
+                                   int32_t *n_broken,
+                                   void *stream,
+                                   struct AnofoxError *out_error);
+
+/*
+ * The chain for an AutoARIMA batch that has been run (one seasonal period): the fit stays on the device
+ * (anofox_hip_batch_arima_fit_device), anofox_hip_arima_innovations_device gives residuals and sigma, the paths of the batch's
+ * horizon are simulated (joint: pool_rows = the smallest nu among the fitted series) and anofox_hip_path_quantiles_device reads
+ * `levels` (host, up to 16 in [0, 1]) off them.  Sizing call, outputs and the order of the checks as for anofox_hip_batch_ets_paths.
+ */
+bool anofox_hip_batch_arima_paths(AnofoxHipBatch *batch,
+                                  const AnofoxHipArimaPathsOptions *options,
+                                  size_t struct_size,
+                                  size_t n_paths,
+                                  const double *levels,
+                                  size_t n_levels,
+                                  size_t ld,
+                                  double *out_quantiles,
+                                  int32_t *out_status,
+                                  int32_t *out_series_status,
+                                  int32_t *out_n_broken,
+                                  double *out_paths,
+                                  size_t *out_ld,
+                                  struct AnofoxError *out_error);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
